@@ -3,15 +3,20 @@
 12 kHz -> 48 kHz segments (BASELINE.json configs[1]: netG=global, ngf 64, 9 ResNet blocks, no attention,
 num_D 2, per-GPU batch 8, float32, T = 32512 = 128 frames x 256 bins).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode train|infer]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode train|infer|codec] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One step = one train.py:160-202 iteration (forward, 3 discriminator passes, G backward + Adam, D backward +
 Adam) through Pix2PixHDModel.optimize_parameters; inputs are resident in HBM before the timed region.
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline line (metric,
+value, unit, ms_per_step, ...).  --full adds everything else the line has carried (each still switched off by its --no-* flag):
   roofline     -- dominant kernel (by event-timed GPU time in the timed region): algorithmic FLOPs per launch /
-                  average launch duration (HIP events on the launch stream) vs the dense f32 MFMA peak.
+                  average launch duration (HIP events on the launch stream) vs the dense f32 MFMA peak, the per-symbol
+                  table and the live rocprofv3 PMC traffic passes.
   cpu_baseline -- the CPU oracle's train step (torch CPU, all host cores) on a bounded sample, N == 1 only.
+  also         -- the other BASELINE configurations as side lines (child processes, each run with --full).
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64; arrays larger
+than DUMP_MAX_ELEMS as a fixed seeded sample of their elements), for output-for-output comparison of two builds.
 """
 import argparse
 import json
@@ -31,6 +36,7 @@ import torch.distributed as dist  # noqa: E402
 PEAK_F32_MFMA_TFLOPS = 157.3      # /opt/skills/guides/MI355X_MICROARCH.md: dense f32-input MFMA peak
 PEAK_F16_MFMA_TFLOPS = 2500.0     # dense f16 MFMA peak (same guide); kernels named "..., 2>" / "..., 3>" compute on it
 T_SEG, BATCH = 32512, 8
+DUMP_MAX_ELEMS = 1 << 22       # per dumped array (16 MB in float32; at most three arrays this size: under 64 MB in all)
 
 
 def synth_batch(batch, seed, device, lr_rate=12000, hr_rate=48000):
@@ -196,7 +202,7 @@ def cpu_baseline_train_cfg2(max_threads):
 def _compact(d):
     """A side line as embedded in the headline: without the per-symbol table and the long definition / sample strings (the driver
     keeps the last 8 KB of stdout; round 4's configs[2] --fp16 value was pushed out of it).  The full line is what
-    `python bench.py --no-also <that configuration>` prints; the committed copies are under profiles/."""
+    `python bench.py --full --no-also <that configuration>` prints; the committed copies are under profiles/."""
     d = {k: v for k, v in d.items() if k != "roofline_symbols"}
     for key in ("roofline", "roofline_codec", "cpu_baseline"):
         sub = d.get(key)
@@ -245,7 +251,7 @@ def also_lines(args):
     for extra, env in ((["--config", "2", "--fp16"], None), (["--config", "4"], None), (["--mode", "codec"], None),
                        (["--config", "4", "--no-cpu-baseline"], {"MG_F32_SPLIT": "1"})):
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
-               "--no-also"] + extra
+               "--full", "--no-also"] + extra
         t0 = time.perf_counter()
         label = " ".join("%s=%s" % kv for kv in (env or {}).items())
         label = (label + " " if label else "") + "python bench.py " + " ".join(cmd[2:])
@@ -399,9 +405,11 @@ def bench_codec(args, dev, rank, world):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(ev[i])
+        y = step(ev[i])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"audio": y})
     k1 = sum(e[0].elapsed_time(e[1]) for e in ev) / args.steps * 1e-3
     k2 = sum(e[1].elapsed_time(e[2]) for e in ev) / args.steps * 1e-3
     bytes_k = 261120.0 * B
@@ -456,8 +464,7 @@ def bench_codec(args, dev, rank, world):
                 "HBM bytes per launch = (2 * FETCH_SIZE + WRITE_SIZE) * 1024 from separate rocprofv3 --pmc passes over this bench "
                 "mode at 4096 clips (%s), scaled by clips / 4096" % table.get("_source"))
     if rank == 0 and world == 1 and not args.no_roofline:
-        child = [os.path.abspath(__file__), "--mode", "codec", "--codec-batch", str(B), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                 "--no-roofline"]
+        child = [os.path.abspath(__file__), "--mode", "codec", "--codec-batch", str(B), "--steps", "3", "--warmup", "1"]
         live = live_traffic(child, ["mdct4_", "imdct4_"])
         if len(live) == 2:
             out["roofline"]["traffic"], out["roofline"]["k2_traffic"] = live["mdct4_"], live["imdct4_"]
@@ -498,15 +505,34 @@ def _wire_bytes(r):
     return int(total)
 
 
+def dump_outputs(out_dir, arrays):
+    """arrays: {name: tensor} -> out_dir/<name>.npy in float32 (float64 stays float64).  An array of more than DUMP_MAX_ELEMS
+    elements is written as the elements at DUMP_MAX_ELEMS sorted indices drawn with numpy's default_rng(0) (same size, same
+    indices on every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        t = t if t.dtype == torch.float64 else t.float()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--mode", default="train", choices=["train", "infer", "codec"],
                     help="train: G+D step (the headline).  infer: generate_audio path (inference + segment stitching). "
                          "codec: K1+K2 only (to_spectro + to_audio) on --codec-batch clips, reported against the HBM roofline")
     ap.add_argument("--codec-batch", type=int, default=4096)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline / per-kernel figures, the CPU baseline and the other configurations' side lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-also", action="store_true", help="headline line only (no configs[2] --fp16 / configs[4] side lines)")
     ap.add_argument("--no-roofline", action="store_true")
@@ -521,6 +547,11 @@ def main():
                     help="torch.distributed backend of the data-parallel run: nccl = RCCL over xGMI (the product path); gloo "
                          "exists so that the N > 1 launch path can be tested with several ranks sharing one GPU")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    # a plain run measures the headline only: the probes, baselines and side lines run with --full
+    if not args.full:
+        args.no_roofline = args.no_cpu_baseline = args.no_also = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)          # plain `python bench.py --gpus N`: start the N ranks ourselves
@@ -587,9 +618,8 @@ def main():
 
     def eager_step():
         if args.mode == "train":
-            model.optimize_parameters(lr, hr)
-        else:
-            generate(model, lr, batch_size=batch, gen_overlap=0)
+            return model.optimize_parameters(lr, hr)
+        return generate(model, lr, batch_size=batch, gen_overlap=0)
     step = eager_step
     # data parallel: eager unless MDCTGAN_DDP_GRAPH=1 | auto (auto: every rank tries the capture, all fall back together: Pix2PixHDModel.make_step)
     use_graph = (not args.no_graph) and (not use_ddp or os.environ.get("MDCTGAN_DDP_GRAPH", "0") in ("1", "auto"))
@@ -665,10 +695,23 @@ def main():
         ops.PROFILER = timer      # eager: the dominant kernel's launches are event-bracketed inside the timed region
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        result = step()
     fence()
     dt = time.perf_counter() - t0
     ops.PROFILER = None
+    if args.dump_outputs and rank == 0:
+        # what the caller of the step receives: the loss dict (train) or the stitched audio (infer); after a train step the
+        # updated parameter arenas are its product as well
+        if args.mode == "train":
+            names = sorted(result)
+            arrays = {"losses": torch.stack([torch.as_tensor(result[k], dtype=torch.float64).reshape(()).cpu() for k in names])}
+            for tag in ("G", "D"):
+                o = getattr(model, "optimizer_" + tag)
+                arrays["params_" + tag] = o.flat_p if getattr(o, "flat_p", None) is not None else torch.cat(
+                    [p.detach().reshape(-1).float() for g in o.param_groups for p in g["params"]])
+        else:
+            arrays = {"audio": result}
+        dump_outputs(args.dump_outputs, arrays)
     if amp_scale0 is not None and model.scaler.get_scale() != amp_scale0:
         raise RuntimeError("the loss scale moved inside the timed region (%r -> %r): a skipped optimiser step would have been timed"
                            % (amp_scale0, model.scaler.get_scale()))

@@ -3,7 +3,7 @@
 # traffic tables, the GPU suite.   usage (GPU box, repo root): bash scripts/final_round.sh r04
 tag=${1:-r04}
 R=$(pwd); out=$R/gpurun_out; mkdir -p $out
-python bench.py --gpus 1 --steps 20 --warmup 5 > $out/${tag}_bench_train_line.json 2> $out/${tag}_bench_train_line.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/${tag}_bench_train_line.json 2> $out/${tag}_bench_train_line.err
 tail -c 600 $out/${tag}_bench_train_line.json; echo
 python - "$out/${tag}_bench_train_line.json" "$out" "$tag" <<'PY'
 import json, sys

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 prof() {   # name, bench args...
     name=$1; shift
     rm -rf /tmp/prof_$name
-    rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -o p -- python $R/bench.py "$@" --no-cpu-baseline --no-also \
+    rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -o p -- python $R/bench.py "$@" --full --no-cpu-baseline --no-also \
         > $out/${tag}_${name}_line_profiled.json 2> /tmp/prof_$name.err
     f=$(find /tmp/prof_$name -name "*kernel_stats.csv" | head -1)
     [ -n "$f" ] && cp $f $out/${tag}_${name}_kernel_stats.csv
@@ -22,10 +22,10 @@ prof bench_cfg2_fp16 --config 2 --fp16 --steps 10 --warmup 2
 prof bench_infer_cfg4 --config 4 --steps 10 --warmup 2
 prof bench_codec --mode codec --steps 10 --warmup 2
 cd $R
-python bench.py --mode codec --steps 20 --warmup 5 > $out/${tag}_bench_codec_line.json 2>/dev/null
-python bench.py --config 2 --steps 20 --warmup 5 --no-also > $out/${tag}_bench_cfg2_f32_line.json 2>/dev/null
-python bench.py --fp16 --steps 20 --warmup 5 --no-also > $out/${tag}_bench_train_fp16_line.json 2>/dev/null
-python bench.py --steps 20 --warmup 5 > $out/${tag}_bench_train_line.json 2>/dev/null
+python bench.py --mode codec --steps 20 --warmup 5 --full > $out/${tag}_bench_codec_line.json 2>/dev/null
+python bench.py --config 2 --steps 20 --warmup 5 --full --no-also > $out/${tag}_bench_cfg2_f32_line.json 2>/dev/null
+python bench.py --fp16 --steps 20 --warmup 5 --full --no-also > $out/${tag}_bench_train_fp16_line.json 2>/dev/null
+python bench.py --steps 20 --warmup 5 --full > $out/${tag}_bench_train_line.json 2>/dev/null
 for f in bench_codec bench_cfg2_f32 bench_train_fp16 bench_train; do tail -c 300 $out/${tag}_${f}_line.json; echo; done
 
 # K1 / K2 micro-benchmark (the factored-transform product kernels of mdct_ct.h beside the retired bf16 x 3 and f32-pipe dense-table
