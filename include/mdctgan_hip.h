@@ -112,6 +112,24 @@ int mg_imdct4_stitched(const float* spec, int B, int F, int n_fft, const float* 
  * launched -- a static string ("mdct4_ct_kernel (csrc/mdct_ct.h)", ...).  Diagnostic: bench.py names the measured kernel with it. */
 const char* mg_mdct_last_kernel(int which);
 
+/* Backward passes of K2 / K1 (gradients through Audio2MDCT.to_audio / to_spectro and the raw IMDCT4 / MDCT4), n_fft = 512.
+ *   mg_imdct4_backward  grad_audio [B, out_len] (the gradient of K2's output) -> grad_spec [B, F, 256]
+ *                       = dX/ds(spec) * 4/N * MDCT(grad_audio), frames taken as K1 takes them with F frames, grad_audio zero past
+ *                       out_len (out_len <= (F-1)*256).  Same codec arguments as mg_imdct4_forward (RAW: spec may be NULL;
+ *                       min_b / max_b [B]: per-clip range, used as constants).
+ *   mg_mdct4_backward   grad_spec [B, F, 256] (the gradient of K1's normalised output spec) -> grad_audio [B, T]
+ *                       = N/4 * IMDCT(ds/dX(spec) * grad_spec) cropped to T, F = mg_mdct4_num_frames(T, 512); fixed range only.
+ *   dX/ds = c1 cosh(c1 s + c0) / gain (arcsinh), c1 (range), 1 (raw), c1 = ln10^[arcsinh] (max - min) / (nr1 - nr0) and
+ *   c0 = ln10^[arcsinh] (min - nr0 (max - min) / (nr1 - nr0)).  Deterministic (no atomics).  MG_ERR_UNSUPPORTED where the
+ *   factored kernels' guards fail (no dct4_image, T or out_len % 4, unaligned or > 4 GiB operands, MG_MDCT_CT=0 / MG_MDCT_FT):
+ *   the caller then composes mg_frames_window / mg_conv_fwd / mg_codec_backward / mg_overlap_add.  mg_mdct_last_kernel is not
+ *   touched. */
+int mg_imdct4_backward(const float* grad_audio, int B, int out_len, int F, int n_fft, const float* window, const float* dct4_image,
+                       int codec, float gain, float nr0, float nr1, float src_min, float src_max, const float* min_b,
+                       const float* max_b, const float* spec, float* grad_spec, void* stream);
+int mg_mdct4_backward(const float* grad_spec, const float* spec, int B, int T, int n_fft, const float* window, const float* dct4_image,
+                      int codec, float gain, float nr0, float nr1, float src_min, float src_max, float* grad_audio, void* stream);
+
 /* F1  torchaudio.functional.resample(waveform, orig_freq, new_freq) with its defaults (sinc_interp_hann,
  * lowpass_filter_width 6, rolloff 0.99) as the reference's data path calls it (data/audio_dataset.py:66-71, 171-177):
  * x [B, L] -> out [B, mg_resample_length(L, orig, new)], orig / new the gcd-reduced rates.  kern [new, 2*width + orig]
@@ -160,6 +178,12 @@ int mg_codec_forward(const float* X, int B, int n, int mode, float gain, float a
 /* spec [B][C][n] -> X [B][n]; min_b / max_b [B*C] or both null (src_min / src_max) */
 int mg_codec_inverse(const float* spec, int B, int n, int mode, float gain, float alpha, float min_value, float nr0, float nr1,
                      float src_min, float src_max, const float* min_b, const float* max_b, float* X, void* stream);
+/* Backward of the RAW / ARCSINH / RANGE codec on [B][n] (dX/ds as for mg_imdct4_backward; min_b / max_b [B] or (src_min, src_max)):
+ * to_spectro == 0: out = scale * grad * dX/ds(spec)   (to_audio's backward; scale = 4/n_fft after the framed contraction)
+ * to_spectro != 0: out = scale * grad / dX/ds(spec)   (to_spectro's backward).  spec may be NULL for RAW. */
+int mg_codec_backward(const float* grad, const float* spec, int B, int n, int mode, int to_spectro, float scale, float gain,
+                      float nr0, float nr1, float src_min, float src_max, const float* min_b, const float* max_b, float* out,
+                      void* stream);
 /* out[b, t] = 4/n_fft * sum_f window[k] * Y[b, f, k], k = t + crop - f*hop   (mdct.py:469-486), float32 or float64 out */
 int mg_overlap_add(const float* Y, int B, int F, int win, int hop, int n_fft, const float* window, int crop, void* out,
                    int out_len, int is_f64, void* stream);

@@ -65,6 +65,8 @@ SIGNATURES = {
     "mg_imdct4_forward": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _f, _f, _p, _p, _p, _i, _i, _p, _p]),
     "mg_imdct4_stitched": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _f, _f, _p, _p, _p, _ll, _i, _i, _ll, _i, _i, _p]),
     "mg_mdct_last_kernel": (C.c_char_p, [_i]),
+    "mg_imdct4_backward": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p]),
+    "mg_mdct4_backward": (_i, [_p, _p, _i, _i, _i, _p, _p, _i, _f, _f, _f, _f, _f, _p, _p]),
     "mg_conv_fwd": (_i, [_G, _p, _p, _p, _p, _i, _p, _sz, _p]),
     "mg_conv_fwd_workspace": (_sz, [_G]),
     "mg_conv_wino_weights_bytes": (_sz, [_G]),
@@ -101,6 +103,7 @@ SIGNATURES = {
     "mg_frames_window": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "mg_codec_forward": (_i, [_p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p]),
     "mg_codec_inverse": (_i, [_p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _p, _p, _p, _p]),
+    "mg_codec_backward": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p, _p, _p]),
     "mg_overlap_add": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p]),
     "mg_stitch_length": (_ll, [_i, _i, _i]),
     "mg_stitch_segments": (_i, [_p, _i, _i, _i, _p, _i, _p]),

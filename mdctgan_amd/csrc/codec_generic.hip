@@ -150,6 +150,30 @@ __global__ void overlap_add_kernel(const float* __restrict__ Y, int F, int win, 
     }
 }
 
+// Backward of the ARCSINH / RANGE / RAW codec ([B][n], one channel).  x = c1 s + c0 per clip (the constants of mdct_ct.h / K2);
+// dX/ds = c1 cosh(x) / gain (ARCSINH), c1 (RANGE), 1 (RAW).  to_spectro == 0: out = scale g dX/ds(s) (the to_audio backward);
+// to_spectro != 0: out = scale g / (dX/ds(s)) (the to_spectro backward).  s may be NULL in RAW mode.
+__global__ void codec_backward_kernel(const float* __restrict__ g, const float* __restrict__ s, int n, CodecG c, int to_spectro,
+                                      float scale, const float* __restrict__ mn_b, const float* __restrict__ mx_b,
+                                      float* __restrict__ out) {
+    const int b = blockIdx.y;
+    float c1 = 1.0f, c0 = 0.0f;
+    if (c.mode != C_RAW) {
+        const float mn = mn_b ? mn_b[b] : c.mn, mx = mx_b ? mx_b[b] : c.mx;
+        const double k = ((double)mx - (double)mn) / ((double)c.nr1 - (double)c.nr0);
+        const double sc = c.mode == C_ARCSINH ? (double)LN10F : 1.0;
+        c1 = (float)(k * sc); c0 = (float)(((double)mn - (double)c.nr0 * k) * sc);
+    }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const size_t o = (size_t)b * n + i;
+        float d = 1.0f;
+        if (c.mode == C_ARCSINH) d = c1 * coshf(fmaf(s[o], c1, c0)) / c.gain;
+        else if (c.mode == C_RANGE) d = c1;
+        const float v = scale * g[o];
+        out[o] = to_spectro ? v / d : v * d;
+    }
+}
+
 inline unsigned cg_grid(size_t n) {
     size_t b = (n + 255) / 256;
     return (unsigned)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
@@ -196,6 +220,19 @@ int mg_codec_inverse(const float* spec, int B, int n, int mode, float gain, floa
     const CodecG c{mode, gain, alpha, min_value, nr0, nr1, src_min, src_max};
     hipLaunchKernelGGL(codec_inverse_kernel, dim3(cg_grid(n) > 256 ? 256 : cg_grid(n), B), dim3(256), 0, (hipStream_t)stream, spec, n,
                        c, mode == C_EXPLICIT ? 2 : 1, min_b, max_b, X);
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+}
+
+int mg_codec_backward(const float* grad, const float* spec, int B, int n, int mode, int to_spectro, float scale, float gain,
+                      float nr0, float nr1, float src_min, float src_max, const float* min_b, const float* max_b, float* out,
+                      void* stream) {
+    if (!grad || !out || B <= 0 || n <= 0 || mode < C_RAW || mode > C_RANGE || (mode != C_RAW && !spec) ||
+        ((min_b == nullptr) != (max_b == nullptr)))
+        return MG_ERR_ARG;
+    const CodecG c{mode, gain, 0.0f, 0.0f, nr0, nr1, src_min, src_max};
+    hipLaunchKernelGGL(codec_backward_kernel, dim3(cg_grid(n) > 256 ? 256 : cg_grid(n), B), dim3(256), 0, (hipStream_t)stream, grad,
+                       spec, n, c, to_spectro, scale, min_b, max_b, out);
     MG_CHECK_LAUNCH();
     return MG_OK;
 }

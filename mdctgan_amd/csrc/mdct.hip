@@ -530,6 +530,72 @@ int mg_imdct4_stitched(const float* spec, int B, int F, int n_fft, const float* 
 
 const char* mg_mdct_last_kernel(int which) { return g_last_kernel[which == 1 ? 1 : 0]; }
 
+// See include/mdctgan_hip.h.  The factored kernels' guards (stage-matrix image, T % 4, 16-byte alignment, 32-bit buffer offsets,
+// MG_MDCT_CT / MG_MDCT_FT) decide as in the forward; where they fail MG_ERR_UNSUPPORTED sends the caller to the generic
+// composition.  g_last_kernel is left alone: it names the forward kernels.
+static bool ct_backward_allowed() {
+    if (getenv("MG_MDCT_FT")) return false;
+    if (const char* e = getenv("MG_MDCT_CT")) return atoi(e) != 0;
+    return true;
+}
+
+int mg_imdct4_backward(const float* grad_audio, int B, int out_len, int F, int n_fft, const float* window, const float* dct4_image,
+                       int codec, float gain, float nr0, float nr1, float src_min, float src_max, const float* min_b,
+                       const float* max_b, const float* spec, float* grad_spec, void* stream) {
+    if (!grad_audio || !window || !grad_spec || B <= 0 || F <= 1 || out_len <= 0 || out_len > (F - 1) * M) return MG_ERR_ARG;
+    if (codec < CODEC_RAW || codec > CODEC_RANGE || (codec != CODEC_RAW && !spec) || ((min_b == nullptr) != (max_b == nullptr)))
+        return MG_ERR_ARG;
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const long long rows = (long long)B * F;
+    if (n_fft != 2 * M || !dct4_image || !ct_backward_allowed() || out_len % 4 || !al16(grad_audio) || !al16(window) ||
+        !al16(dct4_image) || !al16(grad_spec) || (spec && !al16(spec)) || rows * M * 8 >= (1ll << 32) - (1ll << 18) ||
+        (long long)B * out_len * 4 >= (1ll << 32))
+        return MG_ERR_UNSUPPORTED;
+    CodecParams cp{codec, gain, nr0, nr1, src_min, src_max, min_b, max_b, (min_b && max_b) ? 1 : 0};
+    const long long n_tiles = (rows + CT_ROWS - 1) / CT_ROWS;
+    const dim3 grid((unsigned)(n_tiles < 512 ? n_tiles : 512));
+    hipStream_t st = (hipStream_t)stream;
+#define MG_K1_BWD(MODE_, PS_)                                                                                             \
+    do {                                                                                                                   \
+        static bool attr = false;                                                                                          \
+        if (!attr) { allow_lds(imdct4_ct_bwd_kernel<MODE_, PS_>, CT_K1_LDS); attr = true; }                               \
+        hipLaunchKernelGGL((imdct4_ct_bwd_kernel<MODE_, PS_>), grid, dim3(CT_NT), CT_K1_LDS, st, grad_audio, B, out_len, F,   \
+                           window, dct4_image, cp, spec, grad_spec);                                                       \
+    } while (0)
+#define MG_K1_BWD_S(MODE_) do { if (cp.per_sample) MG_K1_BWD(MODE_, true); else MG_K1_BWD(MODE_, false); } while (0)
+    if (codec == CODEC_RAW) MG_K1_BWD(CODEC_RAW, false); else if (codec == CODEC_ARCSINH) MG_K1_BWD_S(CODEC_ARCSINH); else MG_K1_BWD_S(CODEC_RANGE);
+#undef MG_K1_BWD_S
+#undef MG_K1_BWD
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+}
+
+int mg_mdct4_backward(const float* grad_spec, const float* spec, int B, int T, int n_fft, const float* window, const float* dct4_image,
+                      int codec, float gain, float nr0, float nr1, float src_min, float src_max, float* grad_audio, void* stream) {
+    if (!grad_spec || !window || !grad_audio || B <= 0 || T <= 0) return MG_ERR_ARG;
+    if (codec < CODEC_RAW || codec > CODEC_RANGE || (codec != CODEC_RAW && !spec)) return MG_ERR_ARG;
+    const int F = mg_mdct4_num_frames(T, 2 * M);
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (n_fft != 2 * M || !dct4_image || !ct_backward_allowed() || T % 4 || !al16(grad_spec) || !al16(window) || !al16(dct4_image) ||
+        !al16(grad_audio) || (spec && !al16(spec)) || (long long)B * F * M * 4 >= (1ll << 32) ||
+        (long long)B * T * 4 >= (1ll << 32) - (1ll << 16))
+        return MG_ERR_UNSUPPORTED;
+    CodecParams cp{codec, gain, nr0, nr1, src_min, src_max, nullptr, nullptr, 0};
+    const dim3 grid((unsigned)(B < 512 ? B : 512));
+    hipStream_t st = (hipStream_t)stream;
+#define MG_K2_BWD(MODE_)                                                                                                  \
+    do {                                                                                                                   \
+        static bool attr = false;                                                                                          \
+        if (!attr) { allow_lds(mdct4_ct_bwd_kernel<MODE_>, CT_K2_LDS); attr = true; }                                     \
+        hipLaunchKernelGGL((mdct4_ct_bwd_kernel<MODE_>), grid, dim3(CT_NT), CT_K2_LDS, st, grad_spec, spec, B, F, window,  \
+                           dct4_image, cp, grad_audio, T);                                                                 \
+    } while (0)
+    if (codec == CODEC_RAW) MG_K2_BWD(CODEC_RAW); else if (codec == CODEC_ARCSINH) MG_K2_BWD(CODEC_ARCSINH); else MG_K2_BWD(CODEC_RANGE);
+#undef MG_K2_BWD
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+}
+
 long long mg_stitch_length(int n_seg, int seg_len, int overlap) {
     if (n_seg <= 0 || seg_len <= 0 || overlap < 0 || 2 * overlap >= seg_len) return -1;
     if (overlap == 0) return (long long)n_seg * seg_len;

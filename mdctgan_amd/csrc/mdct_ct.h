@@ -380,4 +380,219 @@ __global__ __launch_bounds__(CT_NT, 4) void imdct4_ct_kernel(const float* __rest
 
 constexpr size_t CT_K2_LDS = (size_t)(CT_U1 + CT_YB + 2 * CT_OS) * sizeof(float);
 
+// ------------------------------------------------------------------------------------------------------------------
+// Backward passes (gradients through to_audio / to_spectro and the raw IMDCT4 / MDCT4).  With win = 2 hop the raw transforms are
+// adjoint up to a scale: IMDCT4^T(gy) = 4/N MDCT4(gy) (frames taken with the forward's F, gy zero past out_len) and
+// MDCT4^T(gX) = N/4 IMDCT4(gX) cropped to T.  So the to_audio backward is K1 run on the waveform gradient with the codec
+// derivative in its store, and the to_spectro backward is K2 with the inverse derivative in its decode.  Per clip
+// x = c1 s + c0 (K2's constants);  dX/ds = c1 cosh(x) / gain (ARCSINH), c1 (RANGE), 1 (RAW);  ds/dX = 1 / (dX/ds) at the same x,
+// recomputed from the stored spectrogram s.  No atomics: every output element is written once (bit-identical reruns).
+// ------------------------------------------------------------------------------------------------------------------
+template <int MODE>
+__device__ __forceinline__ void ct_codec_consts(float mn, float mx, const CodecParams& cp, float& c1, float& c0) {
+    const double k = ((double)mx - (double)mn) / ((double)cp.nr1 - (double)cp.nr0);
+    const double sc = (MODE == CODEC_ARCSINH) ? (double)LN10F : 1.0;
+    c1 = (float)(k * sc); c0 = (float)(((double)mn - (double)cp.nr0 * k) * sc);
+}
+// dX/ds at the normalised value s
+template <int MODE>
+__device__ __forceinline__ float ct_dxds(float s, float c1, float c0, float rgain) {
+    if (MODE == CODEC_RAW) return 1.0f;
+    if (MODE == CODEC_RANGE) return c1;
+    const float x = fabsf(fmaf(s, c1, c0));
+    const float e = __builtin_amdgcn_exp2f(x * 1.4426950408889634f);
+    return c1 * (0.5f * (e + __builtin_amdgcn_rcpf(e))) * rgain;        // cosh on v_exp_f32 (relative 3e-7)
+}
+
+// to_audio backward, K1's tile walk: gs[row] = dX/ds(s[row]) * 4/N * MDCT(gy)[row], rows = B * F, gy [B][T] (T = the forward's
+// out_len, F its frame count).  The spectrogram s is loaded as a float4 at the very addresses gs is stored to, issued with the
+// next tile's gy.  PS: per-clip ranges cp.mn_b / cp.mx_b [B] (a separate instance: its double constants per row cost registers).
+template <int MODE, bool PS>
+__global__ __launch_bounds__(CT_NT, 4) void imdct4_ct_bwd_kernel(const float* __restrict__ gy, int B, int T, int F,
+                                                                 const float* __restrict__ window, const float* __restrict__ img,
+                                                                 CodecParams cp, const float* __restrict__ s, float* __restrict__ gs) {
+    constexpr int Q = M / 2;
+    extern __shared__ __attribute__((aligned(16))) float ct_smem[];
+    float* U1 = ct_smem;
+    float* Yb = ct_smem + CT_U1;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int rows = B * F, n_tiles = (rows + CT_ROWS - 1) / CT_ROWS, G = gridDim.x;
+    const __amdgpu_buffer_rsrc_t r_gy = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gy), 0, (unsigned)B * (unsigned)T * 4u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(s), 0, MODE != CODEC_RAW ? (unsigned)rows * M * 4u : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_gs = __builtin_amdgcn_make_buffer_rsrc(gs, 0, (unsigned)rows * M * 4u, 0x00020000);
+    const float scale = 4.0f / (2 * M), rgain = 1.0f / cp.gain;
+    float c1 = 1.0f, c0 = 0.0f;
+    if (MODE != CODEC_RAW) ct_codec_consts<MODE>(cp.mn, cp.mx, cp, c1, c0);
+
+    float ma[2][4], mb[16];
+    ct_load_matrices(img, ma, mb, wave, lane);
+
+    // fold (K1): u = s z[straight] - rev(z[reversed]), z = fl32(gy w)
+    const int n = 4 * lane;
+    const bool lo = n < Q;
+    const int o1 = 3 * Q - 4 - n, o2 = lo ? 3 * Q + n : n - Q;
+    const float4 fw1 = bs_ld4(window + o1);
+    float4 fw2 = bs_ld4(window + o2);
+    if (lo) fw2 = make_float4(-fw2.x, -fw2.y, -fw2.z, -fw2.w);
+    const int w0 = ct_u1_word(n), w1 = ct_u1_word(n + 1), w2 = ct_u1_word(n + 2), w3 = ct_u1_word(n + 3);
+    bs_v4u x1[4], x2[4], sv[4];
+    auto load_tile = [&](int tile) {
+#pragma unroll
+        for (int gi = 0; gi < 4; ++gi) {
+            const int m = tile * CT_ROWS + wave + 8 * gi;
+            const int b = m / F, f = m - b * F;
+            const int t1 = f * M - M + o1, t2 = f * M - M + o2;             // T % 4 == 0: a float4 is inside or outside as a whole
+            const unsigned base = (unsigned)b * (unsigned)T;
+            const unsigned a1 = (m < rows && t1 >= 0 && t1 + 3 < T) ? (base + (unsigned)t1) * 4u : BS_OOB;
+            const unsigned a2 = (m < rows && t2 >= 0 && t2 + 3 < T) ? (base + (unsigned)t2) * 4u : BS_OOB;
+            x1[gi] = __builtin_amdgcn_raw_buffer_load_b128(r_gy, a1, 0, 0);
+            x2[gi] = __builtin_amdgcn_raw_buffer_load_b128(r_gy, a2, 0, 0);
+        }
+    };
+    auto fold_tile = [&]() {
+#pragma unroll
+        for (int gi = 0; gi < 4; ++gi) {
+            const float4 a = __builtin_bit_cast(float4, x1[gi]), c = __builtin_bit_cast(float4, x2[gi]);
+            const float4 z1 = make_float4(__fmul_rn(a.x, fw1.x), __fmul_rn(a.y, fw1.y), __fmul_rn(a.z, fw1.z), __fmul_rn(a.w, fw1.w));
+            const float4 z2 = make_float4(__fmul_rn(c.x, fw2.x), __fmul_rn(c.y, fw2.y), __fmul_rn(c.z, fw2.z), __fmul_rn(c.w, fw2.w));
+            float* dst = U1 + (wave + 8 * gi) * CT_FS1;
+            dst[w0] = z2.x - z1.w; dst[w1] = z2.y - z1.z; dst[w2] = z2.z - z1.y; dst[w3] = z2.w - z1.x;
+        }
+    };
+    const int j = lane & 31;
+    const int obin = ct_out_word(ct_bin(wave, j));
+    const int q4 = tid & 63, fr0 = tid >> 6;
+
+    int tile = blockIdx.x;
+    load_tile(tile < n_tiles ? tile : n_tiles);
+    for (; tile < n_tiles; tile += G) {
+        fold_tile();                                              // P1
+        __syncthreads();
+        f32x16 acc = ct_stages(U1, Yb, ma, mb, wave, lane);       // P2, barrier, P3
+        if (MODE != CODEC_RAW) {                                  // this tile's s at P5's addresses (out of range reads 0)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const unsigned row = (unsigned)(tile * CT_ROWS + fr0 + 8 * g);
+                sv[g] = __builtin_amdgcn_raw_buffer_load_b128(r_s, (row * M + 4u * q4) * 4u, 0, 0);
+            }
+        }
+        load_tile(tile + G < n_tiles ? tile + G : n_tiles);       // the next tile's gy: in flight under P4 / P5
+#pragma unroll
+        for (int r = 0; r < 16; ++r) U1[mfma32_row(r, lane) * CT_OS + obin] = acc[r];       // P4
+        __syncthreads();
+        // P5: gs = dX/ds(s) * (4/N v), whole rows, 16 bytes per lane
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int fr = fr0 + 8 * g;
+            const float4 v = ct_out_fix(bs_ld4(U1 + fr * CT_OS + 4 * ct_out_slot(q4)), q4);
+            const int row = tile * CT_ROWS + fr;
+            float4 o = make_float4(scale * v.x, scale * v.y, scale * v.z, scale * v.w);
+            if (MODE != CODEC_RAW) {
+                float rc1 = c1, rc0 = c0;
+                if (PS && row < rows) {
+                    const int b = row / F;
+                    ct_codec_consts<MODE>(cp.mn_b[b], cp.mx_b[b], cp, rc1, rc0);
+                }
+                const float4 sg = __builtin_bit_cast(float4, sv[g]);
+                o = make_float4(o.x * ct_dxds<MODE>(sg.x, rc1, rc0, rgain), o.y * ct_dxds<MODE>(sg.y, rc1, rc0, rgain),
+                                o.z * ct_dxds<MODE>(sg.z, rc1, rc0, rgain), o.w * ct_dxds<MODE>(sg.w, rc1, rc0, rgain));
+            }
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(bs_v4u, o), r_gs, ((unsigned)row * M + 4u * q4) * 4u, 0, 0);
+        }
+        __syncthreads();                                          // the tile has been read: the next fold may overwrite it
+    }
+}
+
+// to_spectro backward, K2's clip walk: ga[b] = N/4 IMDCT(ds/dX(s) * gs)[b] cropped to out_len = the forward's T (fixed range:
+// the per-sample normalisation's gradient through min / max is not built).  P1 loads gs and s at the same addresses; the
+// overlap-add has scale 1 where K2 has 4/N.
+template <int MODE>
+__global__ __launch_bounds__(CT_NT, 4) void mdct4_ct_bwd_kernel(const float* __restrict__ gsp, const float* __restrict__ s, int B, int F,
+                                                                const float* __restrict__ window, const float* __restrict__ img,
+                                                                CodecParams cp, float* __restrict__ ga, int out_len) {
+    constexpr int Q = M / 2;
+    extern __shared__ __attribute__((aligned(16))) float ct_smem[];
+    float* U1 = ct_smem;
+    float* Yb = ct_smem + CT_U1;
+    float* halo = Yb + CT_YB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tpc = (F + CT_ROWS - 1) / CT_ROWS, G = gridDim.x;
+    const int my_clips = ((int)blockIdx.x < B) ? (B - 1 - (int)blockIdx.x) / G + 1 : 0;
+    const int n_seq = my_clips * tpc;
+    const unsigned spec_bytes = (unsigned)B * (unsigned)F * M * 4u;
+    const __amdgpu_buffer_rsrc_t r_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gsp), 0, spec_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(s), 0, MODE != CODEC_RAW ? spec_bytes : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r_out = __builtin_amdgcn_make_buffer_rsrc(ga, 0, (unsigned)B * (unsigned)out_len * 4u, 0x00020000);
+
+    float ma[2][4], mb[16];
+    ct_load_matrices(img, ma, mb, wave, lane);
+    const int n = 4 * lane;
+    const bool lo = n < Q;
+    const int w0 = ct_u1_word(n), w1 = ct_u1_word(n + 1), w2 = ct_u1_word(n + 2), w3 = ct_u1_word(n + 3);
+    const float4 uw0 = bs_ld4(window + n), uw1 = bs_ld4(window + n + M);
+    const float rgain = 1.0f / cp.gain;
+    float c1 = 1.0f, c0 = 0.0f;
+    if (MODE != CODEC_RAW) ct_codec_consts<MODE>(cp.mn, cp.mx, cp, c1, c0);
+    const int j = lane & 31, kh = lane >> 5;
+    const int obin = ct_out_word(ct_bin(wave, j));
+    const int uc_q4 = (lo ? Q + n : 3 * Q - 4 - n) >> 2, up_q4 = (lo ? Q - 4 - n : n - Q) >> 2;
+    const int uc_w = 4 * ct_out_slot(uc_q4), up_w = 4 * ct_out_slot(up_q4);
+
+    int nx_clip = blockIdx.x, nx_t = 0;
+    bs_v4u xr[4], sr[4];
+    auto load_tile = [&]() {
+#pragma unroll
+        for (int gi = 0; gi < 4; ++gi) {
+            const int f = nx_t * CT_ROWS + wave + 8 * gi;
+            const bool ok = nx_clip < B && f < F;
+            const unsigned a = ok ? (((unsigned)nx_clip * F + (unsigned)f) * M + 4u * lane) * 4u : BS_OOB;
+            xr[gi] = __builtin_amdgcn_raw_buffer_load_b128(r_g, a, 0, 0);
+            if (MODE != CODEC_RAW) sr[gi] = __builtin_amdgcn_raw_buffer_load_b128(r_s, a, 0, 0);
+        }
+    };
+    for (int t = tid; t < 2 * CT_OS; t += CT_NT) halo[t] = 0.0f;
+    load_tile();
+    for (int i = 0; i < n_seq; ++i) {
+        const int clip = nx_clip, f0 = nx_t * CT_ROWS;
+        // P1: gX = gs / (dX/ds(s)) into the operand records (frames outside the clip: 0)
+#pragma unroll
+        for (int gi = 0; gi < 4; ++gi) {
+            float4 x = __builtin_bit_cast(float4, xr[gi]);
+            if (MODE != CODEC_RAW) {
+                const float4 sg = __builtin_bit_cast(float4, sr[gi]);
+                x = make_float4(x.x / ct_dxds<MODE>(sg.x, c1, c0, rgain), x.y / ct_dxds<MODE>(sg.y, c1, c0, rgain),
+                                x.z / ct_dxds<MODE>(sg.z, c1, c0, rgain), x.w / ct_dxds<MODE>(sg.w, c1, c0, rgain));
+            }
+            const bool ok = f0 + wave + 8 * gi < F;
+            float* dst = U1 + (wave + 8 * gi) * CT_FS1;
+            dst[w0] = ok ? x.x : 0.0f; dst[w1] = ok ? x.y : 0.0f; dst[w2] = ok ? x.z : 0.0f; dst[w3] = ok ? x.w : 0.0f;
+        }
+        if (++nx_t == tpc) { nx_t = 0; nx_clip += G; }
+        __syncthreads();
+        f32x16 acc = ct_stages(U1, Yb, ma, mb, wave, lane);
+        load_tile();
+#pragma unroll
+        for (int r = 0; r < 16; ++r) U1[mfma32_row(r, lane) * CT_OS + obin] = acc[r];
+        if (kh == 1) halo[(i & 1) * CT_OS + obin] = acc[15];
+        __syncthreads();
+        // P5: hop block h = f0 + fr:  ga[(h - 1) M + n] = w[n] y_h[n] + w[n + M] y_{h-1}[n + M]
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int fr = wave + 8 * g;
+            const float* vc = U1 + fr * CT_OS;
+            const float* vp = fr == 0 ? halo + ((i + 1) & 1) * CT_OS : U1 + (fr - 1) * CT_OS;
+            const float4 c = ct_out_fix(bs_ld4(vc + uc_w), uc_q4), q = ct_out_fix(bs_ld4(vp + up_w), up_q4);
+            const float4 yc = lo ? c : make_float4(-c.w, -c.z, -c.y, -c.x);
+            const float4 yp = lo ? make_float4(-q.w, -q.z, -q.y, -q.x) : make_float4(-q.x, -q.y, -q.z, -q.w);
+            const float4 o = make_float4(uw0.x * yc.x + uw1.x * yp.x, uw0.y * yc.y + uw1.y * yp.y,
+                                         uw0.z * yc.z + uw1.z * yp.z, uw0.w * yc.w + uw1.w * yp.w);
+            const int hh = f0 + fr, t0 = (hh - 1) * M + n;                   // out_len % 4 == 0
+            const bool ok = hh >= 1 && hh <= F - 1 && t0 + 3 < out_len;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(bs_v4u, o), r_out,
+                                                   ok ? ((unsigned)clip * (unsigned)out_len + (unsigned)t0) * 4u : BS_OOB, 0, 0);
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace

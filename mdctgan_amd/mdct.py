@@ -274,6 +274,124 @@ def imdct4_codec(spec, window, dct4, n_fft, *, codec=_lib.MG_CODEC_RAW, gain=1.0
     return audio, frames
 
 
+_UNSUPPORTED = -2       # MG_ERR_UNSUPPORTED: the fused backward's guards failed, the generic composition runs
+
+
+def _fused_image(n_fft, device):
+    """The stage-matrix image of the fused geometry's DCT-IV table (None for other n_fft)."""
+    if n_fft != 512:
+        return None
+    return dct4_image(dct4_table(n_fft // 2, device), n_fft // 2)
+
+
+def codec_backward(grad, spec, *, codec, to_spectro, scale=1.0, gain=1.0, norm_range=(0.0, 1.0), src_range=(0.0, 1.0),
+                   min_b=None, max_b=None):
+    """mg_codec_backward on [B, F, M]: scale * grad * dX/ds(spec) (to_spectro=False) or scale * grad / dX/ds(spec)."""
+    lib = _lib.load()
+    grad = _lib.f32c(grad)
+    B = grad.shape[0]
+    spec = _lib.f32c(spec) if spec is not None else None
+    if min_b is not None:
+        min_b, max_b = _lib.f32c(min_b.reshape(-1)), _lib.f32c(max_b.reshape(-1))
+        assert min_b.numel() == B and max_b.numel() == B
+    out = torch.empty_like(grad)
+    _lib.check(lib.mg_codec_backward(_lib.ptr(grad), _lib.ptr(spec), B, grad.numel() // B, codec, int(to_spectro), scale, gain,
+                                     norm_range[0], norm_range[1], src_range[0], src_range[1], _lib.ptr(min_b), _lib.ptr(max_b),
+                                     _lib.ptr(out), _lib.stream()), "mg_codec_backward")
+    return out
+
+
+def imdct4_backward(grad_audio, spec, window, n_fft, hop_length, F, center=True, *, codec=_lib.MG_CODEC_RAW, gain=1.0,
+                    norm_range=(0.0, 1.0), src_range=(0.0, 1.0), min_b=None, max_b=None, fused=True):
+    """Gradient of imdct4_codec / imdct4_generic (decode + IMDCT4) with respect to their spectrogram input.
+    grad_audio [B, T_out] -> grad_spec [B, F, n_fft/2].  fused: try the K1-shaped kernel (mg_imdct4_backward) first; the
+    generic composition runs where its guards fail: frames of grad_audio with the IMDCT's crop as start padding, window,
+    [frames, win] x [win, n_fft/2] on the exact-f32 GEMM, then dX/ds and the 4/N scale (mg_codec_backward)."""
+    lib = _lib.load()
+    gy = _lib.f32c(grad_audio)
+    B, t_out = gy.shape
+    dev = gy.device
+    if min_b is not None:
+        min_b, max_b = _lib.f32c(min_b.reshape(-1)), _lib.f32c(max_b.reshape(-1))
+    spec = _lib.f32c(spec) if (spec is not None and codec != _lib.MG_CODEC_RAW) else None
+    M = n_fft // 2
+    image = _fused_image(n_fft, dev) if fused else None
+    if image is not None:
+        gs = torch.empty(B, F, M, dtype=torch.float32, device=dev)
+        rc = lib.mg_imdct4_backward(_lib.ptr(gy), B, t_out, F, n_fft, _lib.ptr(window), image, codec, gain, norm_range[0],
+                                    norm_range[1], src_range[0], src_range[1], _lib.ptr(min_b), _lib.ptr(max_b), _lib.ptr(spec),
+                                    _lib.ptr(gs), _lib.stream())
+        if rc != _UNSUPPORTED:
+            _lib.check(rc, "mg_imdct4_backward")
+            return gs
+    win = window.numel()
+    frames = torch.empty(B, F, win, dtype=torch.float32, device=dev)
+    _lib.check(lib.mg_frames_window(_lib.ptr(gy), B, t_out, win, hop_length, win // 2 if center else 0, F, _lib.ptr(window),
+                                    _lib.ptr(frames), _lib.stream()), "mg_frames_window")
+    g = _dense(frames.view(B * F, win), mdct_table(n_fft, win, dev, True)).view(B, F, M)
+    return codec_backward(g, spec, codec=codec, to_spectro=False, scale=4.0 / n_fft, gain=gain, norm_range=norm_range,
+                          src_range=src_range, min_b=min_b, max_b=max_b)
+
+
+def mdct4_backward(grad_spec, spec, window, n_fft, hop_length, T, center=True, *, codec=_lib.MG_CODEC_RAW, gain=1.0,
+                   norm_range=(0.0, 1.0), src_range=(0.0, 1.0), fused=True):
+    """Gradient of mdct4_codec / mdct4_generic (MDCT4 + fixed-range encode) with respect to the audio: grad_spec [B, F, n_fft/2]
+    (gradient of the normalised output spec) -> grad_audio [B, T].  fused: the K2-shaped kernel (mg_mdct4_backward) where its
+    guards hold; otherwise ds/dX (mg_codec_backward), [F, n_fft/2] x [n_fft/2, win] on the exact-f32 GEMM, window and
+    overlap-add with the MDCT's start padding as crop (mg_overlap_add with n_fft = 4: scale 1)."""
+    lib = _lib.load()
+    g = _lib.f32c(grad_spec)
+    B, F, M = g.shape
+    dev = g.device
+    spec = _lib.f32c(spec) if (spec is not None and codec != _lib.MG_CODEC_RAW) else None
+    image = _fused_image(n_fft, dev) if fused else None
+    if image is not None:
+        ga = torch.empty(B, T, dtype=torch.float32, device=dev)
+        rc = lib.mg_mdct4_backward(_lib.ptr(g), _lib.ptr(spec), B, T, n_fft, _lib.ptr(window), image, codec, gain, norm_range[0],
+                                   norm_range[1], src_range[0], src_range[1], _lib.ptr(ga), _lib.stream())
+        if rc != _UNSUPPORTED:
+            _lib.check(rc, "mg_mdct4_backward")
+            return ga
+    if codec != _lib.MG_CODEC_RAW:
+        g = codec_backward(g, spec, codec=codec, to_spectro=True, gain=gain, norm_range=norm_range, src_range=src_range)
+    win = window.numel()
+    z = _dense(g.view(B * F, M), mdct_table(n_fft, win, dev, False)).view(B, F, win)
+    crop = hop_length if center else 0
+    covered = min(T, (F - 1) * hop_length + win - crop)        # samples past the last frame get no gradient
+    ga = torch.empty(B, covered, dtype=torch.float32, device=dev)
+    # mg_overlap_add scales by 4 / n_fft: n_fft = 4 makes it 1
+    _lib.check(lib.mg_overlap_add(_lib.ptr(z), B, F, win, hop_length, 4, _lib.ptr(window), crop, _lib.ptr(ga), covered, 0,
+                                  _lib.stream()), "mg_overlap_add")
+    if covered < T:
+        ga = torch.cat((ga, ga.new_zeros(B, T - covered)), dim=1)
+    return ga
+
+
+class CodecGrad(torch.autograd.Function):
+    """y = fwd(x) with the gradient bwd(grad_y, x, y).  fwd is today's launcher chain, unchanged (same kernels, same bits); the
+    extra tensor inputs are constants of the forward (norm_param's min / max): a gradient asked of them is not built."""
+
+    @staticmethod
+    def forward(ctx, fwd, bwd, x, *consts):
+        y = fwd(x)
+        ctx.bwd = bwd
+        ctx.save_for_backward(x, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        if any(ctx.needs_input_grad[3:]):
+            raise NotImplementedError("the gradient with respect to norm_param tensors (min / max) is not built")
+        x, y = ctx.saved_tensors
+        gx = ctx.bwd(grad_y, x, y) if ctx.needs_input_grad[2] else None
+        return (None, None, gx) + (None,) * (len(ctx.needs_input_grad) - 3)
+
+
+def wants_grad(*tensors) -> bool:
+    """The autograd Functions are entered only here: grad mode on and some input requiring grad (else today's path, no grad_fn)."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
 class MDCT4(torch.nn.Module):
     """models/mdct.py:359-425.  forward(signal, return_frames=False) -> (spec [..., F, n_fft/2], frames)."""
 
@@ -292,11 +410,25 @@ class MDCT4(torch.nn.Module):
         x = signal.reshape(-1, signal.shape[-1])
         if self.window.device != x.device:
             self.window = self.window.to(x.device)
-        if self.fused:
-            r = mdct4_codec(x, self.window, dct4_table(self.n_fft // 2, x.device), self.n_fft, want_frames=return_frames)
-            sp, fr = r["spec"], r["frames"]
+        def run(a):
+            if self.fused:
+                r = mdct4_codec(a, self.window, dct4_table(self.n_fft // 2, a.device), self.n_fft, want_frames=return_frames)
+                return r["spec"], r["frames"]
+            return mdct4_generic(a, self.window, self.n_fft, self.hop_length, self.center, return_frames)
+        if wants_grad(x):
+            held = {}
+
+            def fwd(a):
+                sp_, held["frames"] = run(a)
+                return sp_
+
+            def bwd(g, a, _):
+                return mdct4_backward(g, None, self.window, self.n_fft, self.hop_length, a.shape[-1], self.center,
+                                      fused=self.fused)
+            sp = CodecGrad.apply(fwd, bwd, x)
+            fr = held["frames"]
         else:
-            sp, fr = mdct4_generic(x, self.window, self.n_fft, self.hop_length, self.center, return_frames)
+            sp, fr = run(x)
         spec = sp.reshape(*lead, *sp.shape[1:]).to(self.out_dtype)
         frames = fr.reshape(*lead, *fr.shape[1:]) if return_frames else torch.empty(1)
         return spec, frames
@@ -321,10 +453,25 @@ class IMDCT4(torch.nn.Module):
             "The last dim of input tensor should match the n_fft. Expected %d ,got %d" % (self.n_fft, signal.size()[-1])
         if self.window.device != signal.device:
             self.window = self.window.to(signal.device)
-        if self.fused:
-            audio, frames = imdct4_codec(signal, self.window, dct4_table(self.n_fft // 2, signal.device), self.n_fft,
-                                         out_length=self.out_length, out_dtype=self.out_dtype, want_frames=return_frames)
+        def run(spec):
+            if self.fused:
+                return imdct4_codec(spec, self.window, dct4_table(self.n_fft // 2, spec.device), self.n_fft,
+                                    out_length=self.out_length, out_dtype=self.out_dtype, want_frames=return_frames)
+            return imdct4_generic(spec, self.window, self.n_fft, self.hop_length, self.center, self.out_length,
+                                  self.out_dtype, return_frames)
+        if wants_grad(signal):
+            held = {}
+
+            def fwd(spec):
+                audio_, held["frames"] = run(spec)
+                return audio_
+
+            def bwd(g, spec, _):
+                # the float64 output comes from the generic kernel: its backward takes the generic composition too
+                return imdct4_backward(g, None, self.window, self.n_fft, self.hop_length, spec.shape[1], self.center,
+                                       fused=self.fused and self.out_dtype == torch.float32)
+            audio = CodecGrad.apply(fwd, bwd, signal)
+            frames = held["frames"]
         else:
-            audio, frames = imdct4_generic(signal, self.window, self.n_fft, self.hop_length, self.center, self.out_length,
-                                           self.out_dtype, return_frames)
+            audio, frames = run(signal)
         return audio[:, None, None, :], (frames if return_frames else torch.zeros(1))

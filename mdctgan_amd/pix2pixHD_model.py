@@ -18,8 +18,8 @@ import torch
 from . import _lib, networks
 from . import amp
 from . import functional as Fh
-from .mdct import (IMDCT4, MDCT4, _check_geometry, codec_forward, codec_inverse, dct4_table, imdct4_codec, imdct4_generic,
-                   kbdwin, mdct4_codec, mdct4_generic)
+from .mdct import (IMDCT4, MDCT4, CodecGrad, _check_geometry, codec_forward, codec_inverse, dct4_table, imdct4_backward,
+                   imdct4_codec, imdct4_generic, kbdwin, mdct4_backward, mdct4_codec, mdct4_generic, wants_grad)
 from .optim import FusedAdam
 
 
@@ -114,7 +114,16 @@ class Audio2MDCT(torch.nn.Module):
 
     # -- reference API --------------------------------------------------------------------------
     def to_spectro(self, audio: torch.Tensor, mask: bool = False, mask_size: int = -1):
-        r = self.encode(audio)
+        if wants_grad(audio):
+            held = {}
+
+            def fwd(a):
+                held.update(self.encode(a))
+                return held["spec4"]
+            spec4 = CodecGrad.apply(fwd, self._to_spectro_backward, audio)
+            r = dict(held, spec4=spec4)
+        else:
+            r = self.encode(audio)
         log_spectro = r["spec4"]                              # [B, C, F, W] float32 (C = 2 for --explicit_encoding)
         pha = None
         if self.codec in (_lib.MG_CODEC_DB, _lib.MG_CODEC_EXPLICIT):
@@ -174,9 +183,50 @@ class Audio2MDCT(torch.nn.Module):
             return torch.sinh(x * torch.log(torch.tensor(10.0))) / self.arcsinh_gain
         return x
 
+    def _grad_codec(self, what):
+        """(codec, gain) of the backward passes: the arcsinh and range codecs only."""
+        if self.codec not in (_lib.MG_CODEC_ARCSINH, _lib.MG_CODEC_RANGE):
+            raise NotImplementedError("%s backward: the dB and explicit-encoding codecs have no gradient here" % what)
+        return self.codec, float(self.arcsinh_gain)
+
+    def _to_spectro_backward(self, grad, audio, spec4):
+        """d loss / d audio from d loss / d spec4 (fixed --abs_norm range only)."""
+        codec, gain = self._grad_codec("to_spectro")
+        if not self.abs_norm:
+            raise NotImplementedError("to_spectro backward with per-sample normalisation (no --abs_norm): the gradient through "
+                                      "the clip's min / max is not built")
+        nr, sr = self._ranges()
+        window, _ = self._tables(audio.device)
+        g = mdct4_backward(grad[:, 0], spec4[:, 0], window, self.n_fft, self.hop_length, audio.shape[-1], codec=codec,
+                           gain=gain, norm_range=nr, src_range=sr, fused=self.geom512)
+        return g.view(audio.shape)
+
+    def _to_audio_backward(self, grad, log_spectro, norm_param):
+        """d loss / d log_spectro from d loss / d audio (norm_param's min / max are constants)."""
+        codec, gain = self._grad_codec("to_audio")
+        nr, sr = self._ranges()
+        mn, mx = norm_param["min"], norm_param["max"]
+        per_sample = mn.numel() > 1
+        if not per_sample and not self.abs_norm:
+            sr = (float(mn.reshape(-1)[0]), float(mx.reshape(-1)[0]))
+        spec = log_spectro.squeeze(1) if log_spectro.dim() == 4 else log_spectro
+        window, _ = self._tables(log_spectro.device)
+        g = imdct4_backward(grad.reshape(spec.shape[0], -1), spec, window, self.n_fft, self.hop_length, spec.shape[1],
+                            codec=codec, gain=gain, norm_range=nr, src_range=sr, min_b=mn if per_sample else None,
+                            max_b=mx if per_sample else None, fused=self.geom512)
+        return g.view(log_spectro.shape)
+
     def to_audio(self, log_spectro: torch.Tensor, norm_param: Dict[str, torch.Tensor], pha: torch.Tensor = None, stitch=None):
         """pix2pixHD_model.py:139-165.  stitch = (out, gen_overlap, first_seg) (fused geometry only): K2 writes the segments
-        straight into the stitched waveform `out` (generate_audio.py:40-53 inside the kernel) and `out` is returned."""
+        straight into the stitched waveform `out` (generate_audio.py:40-53 inside the kernel) and `out` is returned.
+        Differentiable in log_spectro (arcsinh / range codecs; stitched decode stays forward-only)."""
+        mn, mx = norm_param["min"], norm_param["max"]
+        if stitch is None and wants_grad(log_spectro, mn, mx):
+            return CodecGrad.apply(lambda s: self._to_audio(s, norm_param, pha, None),
+                                   lambda g, s, _: self._to_audio_backward(g, s, norm_param), log_spectro, mn, mx)
+        return self._to_audio(log_spectro, norm_param, pha, stitch)
+
+    def _to_audio(self, log_spectro, norm_param, pha, stitch):
         if stitch is not None and not self.fused:
             raise NotImplementedError("stitched decode needs the fused 512 / 256 geometry")
         nr, sr = self._ranges()
