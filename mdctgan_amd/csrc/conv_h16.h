@@ -152,8 +152,7 @@ inline double h16_max_ratio() {
     return r;
 }
 bool h16_ok(const mg_conv_geom* g) {
-    constexpr bool off = false;
-    if (off || g->precision != MG_PRECISION_F16 || g->stride != 1) return false;
+    if (g->precision != MG_PRECISION_F16 || g->stride != 1) return false;
     if (g->Ci % 64 != 0 || g->Co % 64 != 0) return false;
     const long long M = (long long)g->B * g->OH * g->OW, Min = (long long)g->B * g->H * g->W;
     const long long Mx = M > Min ? M : Min;
@@ -235,9 +234,9 @@ inline void h16_launch(const H16Plan& p, bool brc, const HgArgs& a, hipStream_t 
 // MG_NO_HGEMM_SA=1: the round-2..5 kernels (im2col matrix + hgemm_kernel) instead of the weight-streaming form (read per call: the
 // bit-identity test flips it)
 inline bool h16_sa_on() { return getenv("MG_NO_HGEMM_SA") == nullptr; }
-// x16_pre (nullable): float16(x) already written by x's producer (MG_TILES_V_FILLED)
+// x16_pre (nullable): float16(x) already written by x's producer (MG_TILES_V_FILLED); defer (nullable): FwdDefer
 int h16_fwd(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int act, char* ws,
-            hipStream_t st, const void* w16_pre, const void* x16_pre = nullptr) {
+            hipStream_t st, const void* w16_pre, const void* x16_pre, FwdDefer* defer) {
     const long long M = (long long)g->B * g->OH * g->OW;
     const int K = g->KH * g->KW * g->Ci;
     const H16Plan p = h16_plan(M, g->Co, K, false);
@@ -275,8 +274,8 @@ int h16_fwd(const mg_conv_geom* g, const float* x, const float* w, const float* 
     probe_end(st);
     if (!fused_epilogue) {
         const size_t n = (size_t)M * g->Co;
-        if (g_fwd_defer && act == MG_ACT_NONE && p.splits > 1) {
-            *g_fwd_defer = FwdDefer{part, p.splits, bias, 1, true};        // the caller's InstanceNorm kernel finishes the sum
+        if (defer && act == MG_ACT_NONE && p.splits > 1) {
+            *defer = FwdDefer{part, p.splits, bias, 1, true};        // the caller's InstanceNorm kernel finishes the sum
         } else {
             hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(h16_grid(n / 4)), dim3(256), 0, st, (const float*)part, p.splits, n, g->Co,
                                bias, act, y, 1);
@@ -320,11 +319,10 @@ int h16_dgrad(const mg_conv_geom* g, const float* dy, const float* w, float* dx,
 }
 
 // Short reductions (the padded pixel count is the K of this GEMM: 256 on the 2048-channel 4x8 trunk) run A-stationary
-// (hgemm_as_kernel); MG_HGEMM_AS=0 keeps them on hgemm_kernel.
+// (hgemm_as_kernel).
 inline bool h16_wgrad_as(const mg_conv_geom* g) {
-    constexpr bool on = true;
     const long long M = (long long)g->B * g->OH * g->OW;
-    return on && hgemm_as_ok(g->Co, g->KH * g->KW * g->Ci, h16_mp(M));
+    return hgemm_as_ok(g->Co, g->KH * g->KW * g->Ci, h16_mp(M));
 }
 // dw16 != NULL (only with h16_wgrad_as(g)): the gradient is stored as float16 there and dw is not touched
 int h16_wgrad(const mg_conv_geom* g, const float* x, const float* dy, float* dw, int accumulate, char* ws, hipStream_t st,

@@ -957,142 +957,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(Geom g, const float* __
         }
 }
 
-// ================================================================================================
-// Lean dense C[M][N] = A^T B for the Winograd-domain weight gradients (A = Md [K][M], B = V [K][N], K = tiles): the
-// same 64x64 tile, k-major LDS images and hand-pipelined chunk as conv_wgrad_kernel<64, 64, true, true, 1>, without
-// the convolution geometry (tap / pixel state, border cases, the generic loaders) that a K = 256 reduction -- 128 MFMAs
-// per wave -- cannot amortise, and with NSUB 16-deep sub-chunks per barrier.  M multiple of 64, N of 64 NB, K of 16 * NSUB.
-// grid: x = tiles (XCD-remapped), y = batch, z = K splits.
-// ================================================================================================
-template <int NSUB, int TAG, int NB = 1>      // TAG: 1 = F(2x2,3x3), 5 = the 25-position families; tile 64 x (64 NB)
-__global__ __launch_bounds__(256) void dense_tn64_kernel(const float* __restrict__ A, const float* __restrict__ B,
-                                                         float* __restrict__ C, int M, int N, int K, long long sa,
-                                                         long long sb, long long sc, int cps) {
-    constexpr int BKW = BK * NSUB, LDA = 64, BN = 64 * NB, LDB = BN;
-    __shared__ __attribute__((aligned(16))) float smem[2 * BKW * (LDA + LDB)];
-    auto As = [&](int buf) -> float* { return smem + buf * (BKW * LDA); };
-    auto Bs = [&](int buf) -> float* { return smem + 2 * BKW * LDA + buf * (BKW * LDB); };
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tiles_m = M / 64, tiles_n = N / BN;
-    const int t = xcd_remap(blockIdx.x, tiles_m * tiles_n);
-    const int m0 = (t % tiles_m) * 64, n0 = (t / tiles_m) * BN;
-    const int total_chunks = K / BKW;
-    const int c_begin = blockIdx.z * cps, c_end = min(total_chunks, c_begin + cps);
-    const int kl = tid >> 4, q = tid & 15;            // A: k row inside a 16-deep sub-chunk, float4 column
-    const int klb = tid / (BN / 4), qb = tid % (BN / 4);   // B: 256 / (BN/4) k rows per pass
-    constexpr int BROWS = 1024 / BN, NVB = BK / BROWS;
-    const float* pa = A + (size_t)blockIdx.y * sa + (size_t)(c_begin * BKW + kl) * M + m0 + 4 * q;
-    const float* pb = B + (size_t)blockIdx.y * sb + (size_t)(c_begin * BKW + klb) * N + n0 + 4 * qb;
-    const size_t stepa = (size_t)BK * M;
-    float4 va[NSUB], vb[NSUB][NVB];
-    auto load = [&]() {
-#pragma unroll
-        for (int i = 0; i < NSUB; ++i) {
-            va[i] = ld4(pa);
-            pa += stepa;
-#pragma unroll
-            for (int j = 0; j < NVB; ++j) vb[i][j] = ld4(pb + (size_t)(j * BROWS) * N);
-            pb += (size_t)BK * N;
-        }
-    };
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < NSUB; ++i) {
-            *reinterpret_cast<float4*>(As(buf) + (kl + BK * i) * LDA + 4 * q) = va[i];
-#pragma unroll
-            for (int j = 0; j < NVB; ++j)
-                *reinterpret_cast<float4*>(Bs(buf) + (klb + j * BROWS + BK * i) * LDB + 4 * qb) = vb[i][j];
-        }
-    };
-    f32x16 acc[1][NB];
-#pragma unroll
-    for (int ni = 0; ni < NB; ++ni) acc[0][ni] = f32x16{0};
-    const int wm0 = (wave >> 1) * 32, wn0 = (wave & 1) * (BN / 2);
-    if (c_begin < c_end) {
-        load();
-        stash(0);
-    }
-    __syncthreads();
-    if (c_begin + 1 < c_end) load();
-    for (int c = c_begin; c < c_end; ++c) {
-        const int cur = (c - c_begin) & 1;
-        auto f0 = [&]() { if (c + 1 < c_end) stash(cur ^ 1); };
-        auto f1 = [&]() { if (c + 2 < c_end) load(); };
-        auto nop = [&]() {};
-        mma_chunk<1, NB, LDA, LDB>(As(cur), Bs(cur), acc, wm0, wn0, lane, f0, f1);
-#pragma unroll
-        for (int sc_ = 1; sc_ < NSUB; ++sc_)
-            mma_chunk<1, NB, LDA, LDB>(As(cur) + sc_ * BK * LDA, Bs(cur) + sc_ * BK * LDB, acc, wm0, wn0, lane, nop, nop);
-        __syncthreads();
-    }
-    float* o = C + ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * ((size_t)M * N);
-    if (gridDim.z == 1) o = C + (size_t)blockIdx.y * sc;
-#pragma unroll
-    for (int ni = 0; ni < NB; ++ni) {
-        const int col = n0 + wn0 + 32 * ni + (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[(size_t)(m0 + wm0 + mfma32_row(r, lane)) * N + col] = acc[0][ni][r];
-    }
-}
-
-// Lean dense C[M][N] = A B for the Winograd-domain data gradients (A = Md [M][K] with K = Co contiguous, B = U [K][N]):
-// conv_dgrad_kernel<64, 64, true, true, 1>'s tile and chunk without the convolution geometry.  N, K multiples of 64 / 16;
-// rows past M re-read the last row and are not stored.  grid: x = tiles (XCD-remapped), y = K splits, z = batch.
-template <int TAG>
-__global__ __launch_bounds__(256) void dense_nn64_kernel(const float* __restrict__ A, const float* __restrict__ B,
-                                                         float* __restrict__ C, float* __restrict__ part, int M, int N,
-                                                         int K, long long sa, long long sb, long long sc, int cps) {
-    constexpr int LDA = 64 + 4, LDB = 64;           // A is scattered in with ds_write_b32 (2-way at pitch 68), B row-wise
-    __shared__ __attribute__((aligned(16))) float smem[2 * BK * (LDA + LDB)];
-    auto As = [&](int buf) -> float* { return smem + buf * (BK * LDA); };
-    auto Bs = [&](int buf) -> float* { return smem + 2 * BK * LDA + buf * (BK * LDB); };
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tiles_m = (M + 63) / 64, tiles_n = N / 64;
-    const int t = xcd_remap(blockIdx.x, tiles_m * tiles_n);
-    const int m0 = (t % tiles_m) * 64, n0 = (t / tiles_m) * 64;
-    const int total_chunks = K / BK;
-    const int c_begin = blockIdx.y * cps, c_end = min(total_chunks, c_begin + cps);
-    const int qa = tid & 3, ra = tid >> 2;            // A: 4 consecutive k of row ra
-    const int kb = tid >> 4, qb = tid & 15;           // B: row kb of the chunk, float4 column qb
-    const float* pa = A + (size_t)blockIdx.z * sa + (size_t)min(m0 + ra, M - 1) * K + c_begin * BK + 4 * qa;
-    const float* pb = B + (size_t)blockIdx.z * sb + (size_t)(c_begin * BK + kb) * N + n0 + 4 * qb;
-    const size_t stepb = (size_t)BK * N;
-    float4 va, vb;
-    auto load = [&]() {
-        va = ld4(pa);
-        vb = ld4(pb);
-        pa += BK;
-        pb += stepb;
-    };
-    auto stash = [&](int buf) {
-        st_kcontig<LDA>(As(buf), ra, qa, va);
-        *reinterpret_cast<float4*>(Bs(buf) + kb * LDB + 4 * qb) = vb;
-    };
-    f32x16 acc[1][1];
-    acc[0][0] = f32x16{0};
-    const int wm0 = (wave >> 1) * 32, wn0 = (wave & 1) * 32;
-    if (c_begin < c_end) {
-        load();
-        stash(0);
-    }
-    __syncthreads();
-    if (c_begin + 1 < c_end) load();
-    for (int c = c_begin; c < c_end; ++c) {
-        const int cur = (c - c_begin) & 1;
-        auto f0 = [&]() { if (c + 1 < c_end) stash(cur ^ 1); };
-        auto f1 = [&]() { if (c + 2 < c_end) load(); };
-        mma_chunk<1, 1, LDA, LDB>(As(cur), Bs(cur), acc, wm0, wn0, lane, f0, f1);
-        __syncthreads();
-    }
-    float* o = part ? part + ((size_t)blockIdx.y * gridDim.z + blockIdx.z) * ((size_t)M * N) : C + (size_t)blockIdx.z * sc;
-    const int col = n0 + wn0 + (lane & 31);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm0 + mfma32_row(r, lane);
-        if (row < M) o[(size_t)row * N + col] = acc[0][0][r];
-    }
-}
-
 __global__ void splitk_reduce_kernel(const float* __restrict__ part, int S, size_t n, float* __restrict__ out,
                                      int accumulate) {
     const size_t n4 = n / 4;
@@ -1227,17 +1091,16 @@ inline DenseDims dense_dims(int pass, long long T, int Co, int Kc) {
     return {(long long)Co, Kc, (int)T};
 }
 DensePlan dense_plan(int pass, int P, long long T, int Co, int Kc, bool hp) {
-    constexpr bool off = false, no_dma = false;      // (rounds 1-4 had ablation switches here; the register-staged path below stays for shapes the DMA path does not take)
     const DenseDims dd = dense_dims(pass, T, Co, Kc);
     DensePlan p{64, 64, 1, 1 << 28, false, false};
-    if (off || hp || dd.N % 64 != 0 || dd.K % 4 != 0 || dd.K < 4 || dd.M < 1 || T >= (1LL << 31)) return p;
+    if (hp || dd.N % 64 != 0 || dd.K % 4 != 0 || dd.K < 4 || dd.M < 1 || T >= (1LL << 31)) return p;
     if (pass == 2 && dd.M % 4 != 0) return p;
     // every operand of one position must stay below 2 GiB (32-bit byte offsets of the LDS-DMA path)
     if ((double)dd.M * dd.K * 4.0 >= 2e9 || (double)dd.N * dd.K * 4.0 >= 2e9) return p;
     p.ok = true;
     // LDS-DMA staging: whole 32-deep chunks, or the weight-gradient GEMM (both operands [K][rows]: the K tail is zero-filled
-    // by the buffer range check)
-    p.dma = (dd.K % DG_BK == 0 || pass == 2) && !no_dma;
+    // by the buffer range check); the register-staged path stays for the shapes the DMA path does not take
+    p.dma = dd.K % DG_BK == 0 || pass == 2;
     // Cost model calibrated on scripts/ubench/gemm_bench.hip (MI355X): the workgroups of one CU share its MFMA pipe, so a
     // launch takes ceil(workgroups / 256) tile-times; efficiencies are the measured large-grid figures per tile; a grid with
     // fewer than two workgroups per CU cannot cover its barrier drains (x 0.85); split-K pays one pass over the slabs.
@@ -1270,10 +1133,6 @@ DensePlan dense_plan(int pass, int P, long long T, int Co, int Kc, bool hp) {
     if (best == 1e300) { p.ok = false; return p; }
     if (p.splits == 1) p.cps = 1 << 28;
     return p;
-}
-inline int dense_splits(int pass, int P, long long T, int Co, int Kc, bool hp) {
-    const DensePlan p = dense_plan(pass, P, T, Co, Kc, hp);
-    return p.ok ? p.splits : 0;
 }
 // MG_F32_SPLIT=1 (opt-in, read per call so a test can flip it): the Winograd-domain GEMMs multiply float32 operands as three
 // exact bf16 pieces each on v_mfma_f32_32x32x16_bf16 (dense_gemm.h: dg_chunk_b8; 8 of the 9 piece products, float32
@@ -1340,11 +1199,9 @@ inline unsigned dense_grid(size_t n) {
     size_t b = (n + 255) / 256;
     return (unsigned)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
 }
-// Runs the GEMM (and its split-K combine) when the shape is eligible; false: the caller takes the convolution kernels.
-bool dense_wino_gemm(int pass, int P, long long T, int Co, int Kc, const float* A, const float* B, float* C, float* part,
-                     bool hp, hipStream_t st) {
-    const DensePlan p = dense_plan(pass, P, T, Co, Kc, hp);
-    if (!p.ok) return false;
+// Runs the GEMM (and its split-K combine) on plan p (p.ok)
+void dense_wino_gemm(const DensePlan& p, int pass, int P, long long T, int Co, int Kc, const float* A, const float* B, float* C,
+                     float* part, hipStream_t st) {
     const DenseDims dd = dense_dims(pass, T, Co, Kc);
     DgArgs a{};
     a.A = A; a.B = B; a.C = C; a.part = p.splits > 1 ? part : nullptr;
@@ -1368,7 +1225,6 @@ bool dense_wino_gemm(int pass, int P, long long T, int Co, int Kc, const float* 
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3(dense_grid(n / 4)), dim3(256), 0, st, (const float*)part, p.splits, n, C,
                            0);
     }
-    return true;
 }
 inline size_t slab_count(int old_splits, int dense) {      // split-K slabs a workspace must hold (either path may run)
     const int m = old_splits > dense ? old_splits : dense;
@@ -1377,9 +1233,8 @@ inline size_t slab_count(int old_splits, int dense) {      // split-K slabs a wo
 
 // A forward convolution whose caller normalises the result right away (mg_conv_fwd_instnorm_*) may leave its split-K slabs
 // unreduced: the InstanceNorm slab kernel sums them itself (norm_act.hip: mg_instnorm_fwd_slabs) -- one launch fewer per layer.
-// The caller arms g_fwd_defer; a path that can oblige fills it INSTEAD of launching splitk_epilogue_kernel.
+// The caller passes a FwdDefer; a path that can oblige fills it INSTEAD of launching splitk_epilogue_kernel.
 struct FwdDefer { const float* part; int splits; const float* bias; int round_f16; bool filled; };
-static thread_local FwdDefer* g_fwd_defer = nullptr;
 #include "dense_gemm_h.h"
 #include "conv_h16.h"
 #include "conv_dma.h"
@@ -1389,12 +1244,16 @@ inline void cd_cast16(const float* src, void* dst, size_t n, hipStream_t st) {
     hipLaunchKernelGGL(h16_cast_kernel, dim3(h16_grid(n / 8)), dim3(256), 0, st, src, (_Float16*)dst, n / 8);
 }
 // ReflectionPad2d(1) + 3x3 stride-1 data gradient on the DMA kernel: the zero-padded "full" data gradient over the padded
-// (H+2) x (W+2) domain (geometry gp: pad 0, same OH x OW), folded back onto H x W by wino_fold_reflect_kernel
-inline bool cd_reflect_dgrad_geom(const mg_conv_geom* g, mg_conv_geom* gp) {
+// (H+2) x (W+2) domain (cd_reflect_geom: pad 0, same OH x OW), folded back onto H x W by wino_fold_reflect_kernel
+inline mg_conv_geom cd_reflect_geom(const mg_conv_geom* g) {
+    mg_conv_geom gp = *g;
+    gp.H += 2; gp.W += 2; gp.pad = 0; gp.reflect = 0;
+    return gp;
+}
+inline bool cd_reflect_dgrad_ok(const mg_conv_geom* g) {
     if (!g->reflect || g->stride != 1 || g->pad != 1 || g->KH != 3 || g->KW != 3 || g->Ci % 4) return false;
-    *gp = *g;
-    gp->H += 2; gp->W += 2; gp->pad = 0; gp->reflect = 0;
-    return conv_dma_dgrad_ok(gp);
+    const mg_conv_geom gp = cd_reflect_geom(g);
+    return conv_dma_dgrad_ok(&gp);
 }
 // staging + split-K slabs of the DMA data gradient
 inline size_t cd_dgrad_ws(const mg_conv_geom* g) {
@@ -1406,22 +1265,7 @@ inline size_t cd_reflect_dxp_bytes(const mg_conv_geom* gp) { return cd_al((size_
 // the DMA data gradient proper.  wsp: cd_dgrad_ws(g) bytes (may be null when nothing is needed); round_f16: autocast output
 // rounding of the direct result (the reflect wrapper rounds after its fold instead)
 int cd_dgrad_run(const mg_conv_geom* g, const float* dy, const float* w, const float* bias, float* dx, int act, char* wsp,
-                 hipStream_t st, const float* u, float* md, int round_f16, int dy16_filled = 0);
-// a layer any of whose passes runs on the float16 implicit GEMMs keeps a cached float16 copy of its weights
-// (mutually exclusive with the Winograd path, which the pass entry points try FIRST: a layer that is wino_ok() keeps
-// float32 U / V / Md images under MG_PRECISION_F16, so it must never be handed the float16-sized buffers of this path)
-bool wino_ok(const mg_conv_geom* g);
-inline bool conv_dma_h_any(const mg_conv_geom* g) {
-    mg_conv_geom gp;
-    return conv_dma_half(g) && !h16_ok(g) && !mg_conv_rowdot_kq(g) && !wino_ok(g) &&
-           (conv_dma_fwd_ok(g) || conv_dma_dgrad_ok(g) || cd_reflect_dgrad_geom(g, &gp));
-}
-inline bool cd_dgrad_any(const mg_conv_geom* g) {
-    mg_conv_geom gp;
-    return conv_dma_dgrad_ok(g) || cd_reflect_dgrad_geom(g, &gp);
-}
-int cd_dgrad_run(const mg_conv_geom* g, const float* dy, const float* w, const float* bias, float* dx, int act, char* wsp,
-                 hipStream_t st, const float* u, float* md, int round_f16, int dy16_filled) {
+                 hipStream_t st, const float* u, float* md, int round_f16, int dy16_filled = 0) {
     CdPlan cp = conv_dma_dgrad_plan(g);
     const bool half = conv_dma_half(g);
     const void* dyin = dy;
@@ -1507,7 +1351,7 @@ TilePlan gemm_plan(long long M, int N, int chunks, int classes, bool can_split, 
     static const Tuned tuned[] = {
         {0, 256, 1024, 64, 16, 64, 64, 1, 1},      // Winograd forward GEMMs, 1024-channel 8x16 ResNet blocks
         {1, 256, 1024, 64, 16, 64, 64, 1, 0},      // Winograd data-gradient GEMMs (transposed pipeline: same 256 tiles)
-        {1, 360, 1024, 64, 16, 128, 128, 2, 0},    // ... and over the 10x18 padded domain (MG_WINO_DGRAD=padded)
+        {1, 360, 1024, 64, 16, 128, 128, 2, 0},    // ... 360 tiles (measured for a since-removed padded-domain form; float16 keeps it)
         {0, 1024, 1024, 288, 1, 128, 128, 8, 1},   // 512->1024 stride-2 forward (and the 1024->512 ConvTranspose backward)
         {0, 4096, 512, 144, 1, 128, 128, 4, 1},    // 256->512
         {0, 16384, 256, 72, 1, 64, 64, 1, 1},      // 128->256
@@ -1640,499 +1484,38 @@ WgradPlan wgrad_plan(const mg_conv_geom* g) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Winograd F(2x2,3x3) orchestration (transforms in wino.h, the 16 GEMMs as one batched implicit-GEMM launch)
+// Kernel families.  conv_route() (after the family predicates, below) names the one a pass of a layer takes; the launchers,
+// the workspace sizes, the shared images and mg_conv_plan_* all switch on it.  A pass whose buffers do not suit its family
+// (alignment, workspace size, a bias / activation that data gradient cannot fuse) takes the generic tail instead --
+// conv_route(pass, g, true): DMA (over the reflect-padded domain for a data gradient), else the implicit GEMM -- and a co1
+// pass tries rowdot first.
+// ---------------------------------------------------------------------------------------------------------
+enum ConvRoute { R_IGEMM, R_DMA, R_DMA_REFLECT, R_CO1, R_ROWDOT, R_H16, R_WINO, R_WINO4, R_WINO42, R_SMALLC };
+ConvRoute conv_route(int pass, const mg_conv_geom* g, bool generic = false);
+
+// ---------------------------------------------------------------------------------------------------------
+// Winograd orchestration: F(2x2,3x3) (wino.h), F(2x2,4x4) for the stride-1 4x4 PatchGAN layers (wino4.h) and F(4x4,2x2)
+// over the space-to-depth view for the stride-2 ones (wino42.h).  Every pass is one pipeline: transforms into the Winograd
+// domain, the P position GEMMs as one batched launch, the transform back.
 // ---------------------------------------------------------------------------------------------------------
 bool h16_ok(const mg_conv_geom* g);
 bool wino_ok(const mg_conv_geom* g) {
     static const bool off = getenv("MG_NO_WINOGRAD") != nullptr;
     if (h16_ok(g)) return false;             // weight-dominated autocast layers take the float16 GEMM path (conv_h16.h)
-    constexpr bool off_h = false;
     // f16 GEMMs are fast enough that Winograd only pays where the 16 transformed-weight matrices are amortised over
     // many tiles: wide layers (>= 256 channels) with >= 256 tiles (the 1024-channel 8x16 blocks of configs[1]; not the
     // 2048-channel 4x8 trunk of configs[2], where reading 16 * Co * Ci transformed weights would dominate)
     constexpr int min_tiles_h = 256;       // (64 measured slower on configs[2])
-    if (prec_h(g) && (off_h || g->Ci < 256 || g->Co < 256 || (long long)g->B * (g->H / 2) * (g->W / 2) < min_tiles_h)) return false;
+    if (prec_h(g) && (g->Ci < 256 || g->Co < 256 || (long long)g->B * (g->H / 2) * (g->W / 2) < min_tiles_h)) return false;
     return !off && g->KH == 3 && g->KW == 3 && g->stride == 1 && g->pad == 1 && g->Ci % 16 == 0 && g->Co % 16 == 0 &&
            g->Ci >= 32 && g->Co >= 32 && g->H % 2 == 0 && g->W % 2 == 0 && g->H >= 2 && g->W >= 2;
 }
-struct WinoDims { long long T, Tp; int TH, TW, THp, TWp; };
-WinoDims wino_dims(const mg_conv_geom* g) {
-    WinoDims d;
-    d.TH = g->H / 2; d.TW = g->W / 2; d.T = (long long)g->B * d.TH * d.TW;
-    d.THp = (g->H + 2) / 2; d.TWp = (g->W + 2) / 2; d.Tp = (long long)g->B * d.THp * d.TWp;
-    return d;
-}
-inline size_t al256(size_t n) { return (n + 63) / 64 * 64; }   // in floats
-
-size_t wino_fwd_ws(const mg_conv_geom* g) {
-    const WinoDims d = wino_dims(g);
-    const TilePlan tp = gemm_plan(d.T, g->Co, g->Ci / BK, 16, true, 0);
-    return (al256((size_t)16 * g->Co * g->Ci) + al256((size_t)16 * d.T * g->Ci) + al256((size_t)16 * d.T * g->Co) +
-            al256(slab_count(tp.splits, dense_splits(0, 16, d.T, g->Co, g->Ci, prec_h(g))) * 16 * d.T * g->Co)) * sizeof(float) + 256;
-}
-size_t wino_dgrad_ws(const mg_conv_geom* g) {      // U | A dy A^T | dV | dd | split-K slabs
-    const WinoDims d = wino_dims(g);
-    const TilePlan tp = gemm_plan(d.T, g->Ci, g->Co / BK, 16, true, 1);
-    return (al256((size_t)16 * g->Co * g->Ci) + al256((size_t)16 * d.T * g->Co) + 2 * al256((size_t)16 * d.T * g->Ci) +
-            al256(slab_count(tp.splits, dense_splits(1, 16, d.T, g->Co, g->Ci, prec_h(g))) * 16 * d.T * g->Ci)) * sizeof(float) + 256;
-}
-struct WinoWgradPlan { bool big; int tiles, splits, cps; };
-WinoWgradPlan wino_wgrad_plan(const mg_conv_geom* g) {
-    const WinoDims d = wino_dims(g);
-    const int chunks = (int)((d.T + BK - 1) / BK);
-    const int t128 = ((g->Co + 127) / 128) * ((g->Ci + 127) / 128);
-    // short reductions (<= 1024 tiles per position, the 8x16 blocks of configs[1]): 64x64 tiles measured 125 vs 148 us
-    bool big = g->Co >= 128 && g->Ci >= 128 && d.T > 1024;
-    const int want = -1;
-    const int tiles = big ? t128 : ((g->Co + 63) / 64) * ((g->Ci + 63) / 64);
-    int splits = want > 0 ? want : (tiles * 16 >= 512 ? 1 : (768 + tiles * 16 - 1) / (tiles * 16));
-    const int max_splits = chunks / 8 > 0 ? chunks / 8 : 1;
-    if (splits > max_splits) splits = max_splits;
-    int cps = (chunks + splits - 1) / splits;
-    splits = (chunks + cps - 1) / cps;
-    return {big, tiles, splits, cps};
-}
-inline size_t wino_wgrad_slabs(const mg_conv_geom* g) {
-    return slab_count(wino_wgrad_plan(g).splits, dense_splits(2, 16, wino_dims(g).T, g->Co, g->Ci, prec_h(g)));
-}
-size_t wino_wgrad_ws(const mg_conv_geom* g) {
-    const WinoDims d = wino_dims(g);
-    const WinoWgradPlan p = wino_wgrad_plan(g);
-    const size_t cs = (mg_colsum_workspace((long long)g->B * g->OH * g->OW, g->Co) + 255) / 4;
-    return (al256((size_t)16 * d.T * g->Ci) + al256((size_t)16 * d.T * g->Co) + al256((size_t)16 * g->Co * g->Ci) +
-            al256(wino_wgrad_slabs(g) * 16 * g->Co * g->Ci) + al256(cs)) * sizeof(float) + 256;
-}
-
-template <typename Launch>
-int wino_launch_tiles(const TilePlan& tp, Launch&& launch) {
-    if (tp.bm == 128 && tp.bn == 128) launch(std::integral_constant<int, 128>{}, std::integral_constant<int, 128>{});
-    else if (tp.bm == 64) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 64>{});
-    else launch(std::integral_constant<int, 128>{}, std::integral_constant<int, 64>{});
-    return 0;
-}
-
-// The Winograd-domain weight-gradient GEMM on dense_tn64_kernel (64x64 tiles, float32): Kc = Ci, or 4 Ci for wino42
-inline bool lean_wgrad_ok(const WinoWgradPlan& p, long long T, int Co, int Kc, bool hp) {
-    constexpr bool off = false;
-    return !off && !hp && !p.big && Co % 64 == 0 && Kc % 64 == 0 && T % BK == 0;
-}
-// 64 x 128 tiles (two MFMAs per A fragment) where they still give >= 4 workgroups per CU: 83 -> 79.5 us on the
-// 1024-channel layer
-inline bool lean_wgrad_wide(const WinoWgradPlan& p, int P, int Co, int Kc) {
-    constexpr bool on = true;
-    return on && P == 16 && Kc % 128 == 0 && (long long)(Co / 64) * (Kc / 128) * P * p.splits >= 1024;
-}
-inline void launch_lean_wgrad(const WinoWgradPlan& p, int P, long long T, int Co, int Kc, const float* Md, const float* V,
-                              float* target, hipStream_t st) {
-    dim3 grid((unsigned)((Co / 64) * (Kc / 64)), P, p.splits);
-    const int cps = p.splits == 1 ? (1 << 29) : p.cps;
-    if (lean_wgrad_wide(p, P, Co, Kc)) {
-        dim3 g2((unsigned)((Co / 64) * (Kc / 128)), P, p.splits);
-        hipLaunchKernelGGL((dense_tn64_kernel<1, 1, 2>), g2, dim3(256), 0, st, Md, V, target, Co, Kc, (int)T, T * Co, T * Kc,
-                           (long long)Co * Kc, cps);
-        return;
-    }
-    if (P == 16)
-        hipLaunchKernelGGL((dense_tn64_kernel<1, 1>), grid, dim3(256), 0, st, Md, V, target, Co, Kc, (int)T, T * Co, T * Kc,
-                           (long long)Co * Kc, cps);
-    else
-        hipLaunchKernelGGL((dense_tn64_kernel<1, 5>), grid, dim3(256), 0, st, Md, V, target, Co, Kc, (int)T, T * Co, T * Kc,
-                           (long long)Co * Kc, cps);
-}
-
-// ... and the data-gradient GEMM on dense_nn64_kernel (64x64 plans only)
-inline bool lean_dgrad_ok(const TilePlan& tp, long long T, int Nc, int Kc, bool hp) {
-    constexpr bool off = false;
-    return !off && !hp && tp.bm == 64 && tp.bn == 64 && Nc % 64 == 0 && Kc % BK == 0 && T >= 1;
-}
-inline void launch_lean_dgrad(const TilePlan& tp, int P, long long T, int Nc, int Kc, const float* Md, const float* U,
-                              float* dV, float* part, hipStream_t st) {
-    dim3 grid((unsigned)(((T + 63) / 64) * (Nc / 64)), tp.splits, P);
-    const int cps = tp.splits == 1 ? (1 << 29) : tp.cps;
-    if (P == 16)
-        hipLaunchKernelGGL(dense_nn64_kernel<1>, grid, dim3(256), 0, st, Md, U, dV, part, (int)T, Nc, Kc, T * Kc,
-                           (long long)Kc * Nc, T * Nc, cps);
-    else
-        hipLaunchKernelGGL(dense_nn64_kernel<5>, grid, dim3(256), 0, st, Md, U, dV, part, (int)T, Nc, Kc, T * Kc,
-                           (long long)Kc * Nc, T * Nc, cps);
-}
-
-int wino_fwd(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int act, float* ws,
-             hipStream_t st, const float* u_pre, float* v_keep, const WinoNorm* nrm = nullptr, bool v_filled = false) {
-    const WinoDims d = wino_dims(g);
-    float* U = ws;
-    float* V = U + al256((size_t)16 * g->Co * g->Ci);
-    float* Mx = V + al256((size_t)16 * d.T * g->Ci);
-    float* part = Mx + al256((size_t)16 * d.T * g->Co);
-    if (u_pre) U = const_cast<float*>(u_pre);
-    else hipLaunchKernelGGL(wino_weight_xform_kernel, dim3(wino_grid((size_t)g->Co * g->Ci / 4)), dim3(256), 0, st, w,
-                            g->Co, g->Ci, U);
-    if (v_keep) V = v_keep;          // the caller keeps B^T x B for the weight gradient
-    // (v_filled: x's producer wrote B^T x B already -- mg_conv_fwd_instnorm_next of the layer in front)
-    if (!(v_filled && v_keep))
-        hipLaunchKernelGGL(wino_input_xform_kernel, dim3(wino_grid((size_t)d.T * g->Ci / 4)), dim3(256), 0, st, x, g->B, g->H,
-                           g->W, g->Ci, d.TH, d.TW, 1, g->reflect, V);
-    if (!dense_wino_gemm(0, 16, d.T, g->Co, g->Ci, V, U, Mx, part, prec_h(g), st)) {
-    const Geom gg{1, 1, (int)d.T, g->Ci, 1, (int)d.T, g->Co, 1, 1, 1, 0, 0};
-    const TilePlan tp = gemm_plan(d.T, g->Co, g->Ci / BK, 16, true, 0);
-    float* pp = tp.splits > 1 ? part : nullptr;
-    const Batch bt{d.T * g->Ci, (long long)g->Co * g->Ci, d.T * g->Co, 0};
-    probe_begin(st);
-    const bool hp = prec_h(g);
-    const bool k32 = hp ? (fwd32_enabled() && g->Ci % BK2 == 0 && (tp.splits == 1 || tp.cps % 2 == 0)) : use_k32(tp, g->Ci);
-    wino_launch_tiles(tp, [&](auto bm, auto bn) {
-        constexpr int BM_ = decltype(bm)::value, BN_ = decltype(bn)::value;
-        dim3 grid((unsigned)(((d.T + BM_ - 1) / BM_) * ((g->Co + BN_ - 1) / BN_)), tp.splits, 16);
-        if (hp && k32)
-            launch_fwd32<BM_, BN_, 3>(grid, st, gg, V, U, nullptr, Mx, MG_ACT_NONE, tp.splits == 1 ? (1 << 29) : tp.cps / 2,
-                                      pp, bt);
-        else if (hp)
-            hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, true, 3>), grid, dim3(256), 0, st, gg, (const float*)V,
-                               (const float*)U, (const float*)nullptr, Mx, MG_ACT_NONE, tp.cps, pp, bt);
-        else if (k32)
-            launch_fwd32<BM_, BN_, 1>(grid, st, gg, V, U, nullptr, Mx, MG_ACT_NONE, tp.splits == 1 ? (1 << 29) : tp.cps / 2,
-                                      pp, bt);
-        else
-            hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, true, 1>), grid, dim3(256), 0, st, gg, (const float*)V,
-                               (const float*)U, (const float*)nullptr, Mx, MG_ACT_NONE, tp.cps, pp, bt);
-    });
-    probe_end(st);
-    if (pp) {
-        const size_t n = (size_t)16 * d.T * g->Co;
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(wino_grid(n / 4)), dim3(256), 0, st, (const float*)pp, tp.splits,
-                           n, g->Co, (const float*)nullptr, MG_ACT_NONE, Mx);
-    }
-    }
-    if (nrm) {           // output transform + InstanceNorm in one kernel (y = the raw convolution output, nrm->y the normalised one)
-        const dim3 grid(g->Co / 32, g->B);
-        const int nt = (d.TH * d.TW + 31) / 32;
-#define MG_OUT_NORM(NT_) hipLaunchKernelGGL(wino_out_norm_kernel<NT_>, grid, dim3(256), 0, st, (const float*)Mx, g->B, d.TH, d.TW, g->Co, bias, *nrm, y)
-#define MG_OUT_NORM_NEXT(NT_) hipLaunchKernelGGL((wino_out_norm_kernel<NT_, true>), grid, dim3(256), 0, st, (const float*)Mx, g->B, d.TH, d.TW, g->Co, bias, *nrm, y)
-        if (nrm->v_next && nt == 1) MG_OUT_NORM_NEXT(1);
-        else if (nrm->v_next && nt == 2) MG_OUT_NORM_NEXT(2);
-        else if (nrm->v_next) return MG_ERR_ARG;       // (callers ask mg_conv_wino_vnext_ok first)
-        else if (nt == 1) MG_OUT_NORM(1); else if (nt == 2) MG_OUT_NORM(2); else if (nt == 3) MG_OUT_NORM(3); else if (nt == 4) MG_OUT_NORM(4); else MG_OUT_NORM(5);
-#undef MG_OUT_NORM_NEXT
-#undef MG_OUT_NORM
-        MG_CHECK_LAUNCH();
-        return MG_OK;
-    }
-    hipLaunchKernelGGL(wino_output_xform_kernel, dim3(wino_grid((size_t)d.T * g->Co / 4)), dim3(256), 0, st,
-                       (const float*)Mx, g->B, d.TH, d.TW, g->Co, bias, act, y, (int)prec_h(g));
-    MG_CHECK_LAUNCH();
-    return MG_OK;
-}
-
-// mg_wino_tiles.add of the mg_conv_dgrad_w call in flight on this thread: a path that can fold "dx += add" into its last
-// kernel takes it and clears it; whatever is left is added by a separate pass at the end of the call.
-static thread_local const float* g_dgrad_add = nullptr;
-
-// Data gradient as the transpose of the forward pipeline (wino.h): T tiles, no padded domain.
-int wino_dgrad_t(const mg_conv_geom* g, const float* dy, const float* w, const float* bias, float* dx, int act, float* ws,
-                 hipStream_t st, const float* u_pre, float* md_keep) {
-    const WinoDims d = wino_dims(g);
-    const long long T = d.T;
-    float* U = ws;
-    float* Md = U + al256((size_t)16 * g->Co * g->Ci);
-    float* dV = Md + al256((size_t)16 * T * g->Co);
-    float* dd = dV + al256((size_t)16 * T * g->Ci);
-    float* part = dd + al256((size_t)16 * T * g->Ci);
-    if (u_pre) U = const_cast<float*>(u_pre);
-    else hipLaunchKernelGGL(wino_weight_xform_kernel, dim3(wino_grid((size_t)g->Co * g->Ci / 4)), dim3(256), 0, st, w,
-                            g->Co, g->Ci, U);
-    if (md_keep) Md = md_keep;       // the caller keeps A dy A^T for the weight gradient
-    if (dy)                          // dy == nullptr: md_keep already holds it (mg_instnorm_bwd_wino_md)
-        hipLaunchKernelGGL(wino_dy_xform_kernel, dim3(wino_grid((size_t)T * g->Co / 4)), dim3(256), 0, st, dy, g->B, d.TH,
-                           d.TW, g->Co, Md);
-    if (!dense_wino_gemm(1, 16, T, g->Co, g->Ci, Md, U, dV, part, prec_h(g), st)) {
-    const Geom gg{1, 1, (int)T, g->Ci, 1, (int)T, g->Co, 1, 1, 1, 0, 0};
-    const TilePlan tp = gemm_plan(T, g->Ci, g->Co / BK, 16, true, 1);
-    float* pp = tp.splits > 1 ? part : nullptr;
-    const Batch bt{T * g->Co, (long long)g->Co * g->Ci, T * g->Ci, 0};      // dV_z = dM_z U_z: same position, no flip
-    probe_begin(st);
-    if (lean_dgrad_ok(tp, T, g->Ci, g->Co, prec_h(g)))
-        launch_lean_dgrad(tp, 16, T, g->Ci, g->Co, Md, U, dV, pp, st);
-    else
-    wino_launch_tiles(tp, [&](auto bm, auto bn) {
-        constexpr int BM_ = decltype(bm)::value, BN_ = decltype(bn)::value;
-        dim3 grid((unsigned)(((T + BM_ - 1) / BM_) * ((g->Ci + BN_ - 1) / BN_)), tp.splits, 16);
-        if (prec_h(g))
-            hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, true, true, 3>), grid, dim3(256), 0, st, gg, (const float*)Md,
-                               (const float*)U, (const float*)nullptr, dV, MG_ACT_NONE, tp.cps, pp, bt);
-        else
-            hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, true, true, 1>), grid, dim3(256), 0, st, gg, (const float*)Md,
-                               (const float*)U, (const float*)nullptr, dV, MG_ACT_NONE, tp.cps, pp, bt);
-    });
-    probe_end(st);
-    if (pp) {
-        const size_t n = (size_t)16 * T * g->Ci;
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(wino_grid(n / 4)), dim3(256), 0, st, (const float*)pp, tp.splits,
-                           n, g->Ci, (const float*)nullptr, MG_ACT_NONE, dV);
-    }
-    }
-    if (!prec_h(g) && wino_dd_gather_ok(g->H, g->W, g->Ci)) {      // small maps: patches through LDS, one kernel
-        const int ts = (g->H / 2) * (g->W / 2);
-        const size_t lds = (size_t)ts * 16 * 8 * sizeof(float4);
-        const dim3 grid(g->Ci / 32, g->B);
-        auto go = [&](auto kern) {
-            hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const float*)dV, g->B, g->H, g->W, g->Ci, g->reflect, bias, act, dx,
-                               g_dgrad_add);
-            g_dgrad_add = nullptr;                 // consumed: mg_conv_dgrad_w has nothing left to add
-        };
-        if (ts <= 32) go(wino_dd_gather_kernel<1>); else go(wino_dd_gather_kernel<2>);
-        MG_CHECK_LAUNCH();
-        return MG_OK;
-    }
-    hipLaunchKernelGGL(wino_dd_xform_kernel, dim3(wino_grid((size_t)T * g->Ci / 4)), dim3(256), 0, st, (const float*)dV, T,
-                       g->Ci, dd);
-    hipLaunchKernelGGL(wino_dx_gather_kernel, dim3(wino_grid((size_t)g->B * g->H * g->W * g->Ci / 4)), dim3(256), 0, st,
-                       (const float*)dd, g->B, g->H, g->W, g->Ci, g->reflect, bias, act, dx, (int)prec_h(g));
-    MG_CHECK_LAUNCH();
-    return MG_OK;
-}
-
-int wino_dgrad(const mg_conv_geom* g, const float* dy, const float* w, const float* bias, float* dx, int act, float* ws,
-               hipStream_t st, const float* u_pre, float* md_keep) {
-    return wino_dgrad_t(g, dy, w, bias, dx, act, ws, st, u_pre, md_keep);
-}
-
-int wino_wgrad(const mg_conv_geom* g, const float* x, const float* dy, float* dw, int accumulate, float* ws,
-               hipStream_t st, const float* v_in, const float* md_in, const mg_wino_adam* ad = nullptr) {
-    const WinoDims d = wino_dims(g);
-    const WinoWgradPlan p = wino_wgrad_plan(g);
-    float* V = ws;
-    float* Md = V + al256((size_t)16 * d.T * g->Ci);
-    float* dU = Md + al256((size_t)16 * d.T * g->Co);
-    float* part = dU + al256((size_t)16 * g->Co * g->Ci);
-    if (v_in) V = const_cast<float*>(v_in);
-    else hipLaunchKernelGGL(wino_input_xform_kernel, dim3(wino_grid((size_t)d.T * g->Ci / 4)), dim3(256), 0, st, x, g->B,
-                            g->H, g->W, g->Ci, d.TH, d.TW, 1, g->reflect, V);
-    if (md_in) Md = const_cast<float*>(md_in);
-    else hipLaunchKernelGGL(wino_dy_xform_kernel, dim3(wino_grid((size_t)d.T * g->Co / 4)), dim3(256), 0, st, dy, g->B,
-                            d.TH, d.TW, g->Co, Md);
-    if (!dense_wino_gemm(2, 16, d.T, g->Co, g->Ci, Md, V, dU, part, prec_h(g), st)) {
-    const Geom gg{1, 1, (int)d.T, g->Ci, 1, (int)d.T, g->Co, 1, 1, 1, 0, 0};
-    float* target = p.splits > 1 ? part : dU;
-    const Batch bt{d.T * g->Ci, d.T * g->Co, (long long)g->Co * g->Ci, 0};
-    dim3 grid((unsigned)p.tiles, 16, p.splits);
-    probe_begin(st);
-    if (lean_wgrad_ok(p, d.T, g->Co, g->Ci, prec_h(g)))
-        launch_lean_wgrad(p, 16, d.T, g->Co, g->Ci, Md, V, target, st);
-    else
-    if (p.big && prec_h(g))
-        hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, true, true, 3>), grid, dim3(256), 0, st, gg, (const float*)V,
-                           (const float*)Md, target, p.cps, 0, bt);
-    else if (p.big)
-        hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, true, true, 1>), grid, dim3(256), 0, st, gg, (const float*)V,
-                           (const float*)Md, target, p.cps, 0, bt);
-    else if (prec_h(g))
-        hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, true, true, 3>), grid, dim3(256), 0, st, gg, (const float*)V,
-                           (const float*)Md, target, p.cps, 0, bt);
-    else
-        hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, true, true, 1>), grid, dim3(256), 0, st, gg, (const float*)V,
-                           (const float*)Md, target, p.cps, 0, bt);
-    probe_end(st);
-    if (p.splits > 1) {
-        const size_t n = (size_t)16 * g->Co * g->Ci;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(wino_grid(n / 4)), dim3(256), 0, st, (const float*)part, p.splits, n,
-                           dU, 0);
-    }
-    }
-    if (ad)     // dw IS the weight tensor here: inverse transform + Adam + next iteration's forward transform in one pass
-        hipLaunchKernelGGL(wino_adam_kernel, dim3(wino_grid((size_t)g->Co * g->Ci / 4)), dim3(256), 0, st, (const float*)dU, g->Co,
-                           g->Ci, dw, ad->m, ad->v, ad->u, ad->state, ad->beta1, ad->beta2, ad->eps, ad->grad_scale);
-    else
-    hipLaunchKernelGGL(wino_dweight_xform_kernel, dim3(wino_grid((size_t)g->Co * g->Ci / 4)), dim3(256), 0, st,
-                       (const float*)dU, g->Co, g->Ci, dw, accumulate);
-    MG_CHECK_LAUNCH();
-    return MG_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Winograd F(2x2,4x4) orchestration (transforms in wino4.h): the stride-1 4x4 PatchGAN layers.  25 GEMMs as one
-// batched launch of the same kernels the F(2x2,3x3) path uses.
-// ---------------------------------------------------------------------------------------------------------
 bool wino4_ok(const mg_conv_geom* g) {
     static const bool off = getenv("MG_NO_WINOGRAD4") != nullptr;
     constexpr int min_c = 32;
     return !off && !prec_h(g) && g->KH == 4 && g->KW == 4 && g->stride == 1 && g->pad == 2 && !g->reflect &&
            g->Ci % 16 == 0 && g->Co % 16 == 0 && g->Ci >= min_c && g->Co >= min_c && (g->H & 1) && (g->W & 1);
 }
-struct Wino4Dims { long long T; int TH, TW; };
-Wino4Dims wino4_dims(const mg_conv_geom* g) {
-    Wino4Dims d;
-    d.TH = (g->H + 1) / 2; d.TW = (g->W + 1) / 2; d.T = (long long)g->B * d.TH * d.TW;
-    return d;
-}
-WinoWgradPlan wino4_wgrad_plan(const mg_conv_geom* g) {
-    const Wino4Dims d = wino4_dims(g);
-    const int chunks = (int)((d.T + BK - 1) / BK);
-    bool big = g->Co >= 128 && g->Ci >= 128 && d.T > 4096;      // measured at 2448 tiles: 64x64 232 us, 128x128 252 us
-    int want = -1;
-    const int tiles = big ? ((g->Co + 127) / 128) * ((g->Ci + 127) / 128) : ((g->Co + 63) / 64) * ((g->Ci + 63) / 64);
-    int splits = want > 0 ? want : (tiles * 25 >= 512 ? (chunks >= 128 ? 3 : 1) : (768 + tiles * 25 - 1) / (tiles * 25));
-    const int max_splits = chunks / 8 > 0 ? chunks / 8 : 1;
-    if (splits > max_splits) splits = max_splits;
-    int cps = (chunks + splits - 1) / splits;
-    splits = (chunks + cps - 1) / cps;
-    return {big, tiles, splits, cps};
-}
-inline size_t wino4_wgrad_slabs(const mg_conv_geom* g) {
-    return slab_count(wino4_wgrad_plan(g).splits, dense_splits(2, 25, wino4_dims(g).T, g->Co, g->Ci, false));
-}
-size_t wino4_fwd_ws(const mg_conv_geom* g) {
-    const Wino4Dims d = wino4_dims(g);
-    const TilePlan tp = gemm_plan(d.T, g->Co, g->Ci / BK, 25, true, 0);
-    return (al256((size_t)25 * g->Co * g->Ci) + al256((size_t)25 * d.T * g->Ci) + al256((size_t)25 * d.T * g->Co) +
-            al256(slab_count(tp.splits, dense_splits(0, 25, d.T, g->Co, g->Ci, false)) * 25 * d.T * g->Co)) * sizeof(float) + 256;
-}
-size_t wino4_dgrad_ws(const mg_conv_geom* g) {      // U | A dy A^T | dV | dd | split-K slabs
-    const Wino4Dims d = wino4_dims(g);
-    const TilePlan tp = gemm_plan(d.T, g->Ci, g->Co / BK, 25, true, 1);
-    return (al256((size_t)25 * g->Co * g->Ci) + al256((size_t)25 * d.T * g->Co) + 2 * al256((size_t)25 * d.T * g->Ci) +
-            al256(slab_count(tp.splits, dense_splits(1, 25, d.T, g->Co, g->Ci, false)) * 25 * d.T * g->Ci)) * sizeof(float) + 256;
-}
-size_t wino4_wgrad_ws(const mg_conv_geom* g) {
-    const Wino4Dims d = wino4_dims(g);
-    const WinoWgradPlan p = wino4_wgrad_plan(g);
-    const size_t cs = (mg_colsum_workspace((long long)g->B * g->OH * g->OW, g->Co) + 255) / 4;
-    return (al256((size_t)25 * d.T * g->Ci) + al256((size_t)25 * d.T * g->Co) + al256((size_t)25 * g->Co * g->Ci) +
-            al256(wino4_wgrad_slabs(g) * 25 * g->Co * g->Ci) + al256(cs)) * sizeof(float) + 256;
-}
-
-int wino4_fwd(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int act, float* ws,
-              hipStream_t st, const float* u_pre, float* v_keep) {
-    const Wino4Dims d = wino4_dims(g);
-    float* U = ws;
-    float* V = U + al256((size_t)25 * g->Co * g->Ci);
-    float* Mx = V + al256((size_t)25 * d.T * g->Ci);
-    float* part = Mx + al256((size_t)25 * d.T * g->Co);
-    if (u_pre) U = const_cast<float*>(u_pre);
-    else hipLaunchKernelGGL(wino4_weight_xform_kernel, dim3(wino_grid((size_t)g->Co * g->Ci / 2)), dim3(256), 0, st, w,
-                            g->Co, g->Ci, U);
-    if (v_keep) V = v_keep;
-    hipLaunchKernelGGL(wino4_input_xform_kernel, dim3(wino_grid((size_t)d.T * g->Ci / 2)), dim3(256), 0, st, x, g->B, g->H,
-                       g->W, g->Ci, d.TH, d.TW, V);
-    if (!dense_wino_gemm(0, 25, d.T, g->Co, g->Ci, V, U, Mx, part, false, st)) {
-    const Geom gg{1, 1, (int)d.T, g->Ci, 1, (int)d.T, g->Co, 1, 1, 1, 0, 0};
-    const TilePlan tp = gemm_plan(d.T, g->Co, g->Ci / BK, 25, true, 0);
-    float* pp = tp.splits > 1 ? part : nullptr;
-    const Batch bt{d.T * g->Ci, (long long)g->Co * g->Ci, d.T * g->Co, 0};
-    probe_begin(st);
-    const bool k32 = use_k32(tp, g->Ci);
-    wino_launch_tiles(tp, [&](auto bm, auto bn) {
-        constexpr int BM_ = decltype(bm)::value, BN_ = decltype(bn)::value;
-        dim3 grid((unsigned)(((d.T + BM_ - 1) / BM_) * ((g->Co + BN_ - 1) / BN_)), tp.splits, 25);
-        if (k32)
-            launch_fwd32<BM_, BN_, 5>(grid, st, gg, V, U, nullptr, Mx, MG_ACT_NONE, tp.splits == 1 ? (1 << 29) : tp.cps / 2,
-                                      pp, bt);
-        else
-            hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, true, 5>), grid, dim3(256), 0, st, gg, (const float*)V,
-                               (const float*)U, (const float*)nullptr, Mx, MG_ACT_NONE, tp.cps, pp, bt);
-    });
-    probe_end(st);
-    if (pp) {
-        const size_t n = (size_t)25 * d.T * g->Co;
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(wino_grid(n / 4)), dim3(256), 0, st, (const float*)pp, tp.splits,
-                           n, g->Co, (const float*)nullptr, MG_ACT_NONE, Mx);
-    }
-    }
-    hipLaunchKernelGGL(wino4_output_xform_kernel, dim3(wino_grid((size_t)d.T * g->Co / 2)), dim3(256), 0, st,
-                       (const float*)Mx, g->B, d.TH, d.TW, g->Co, bias, act, y);
-    MG_CHECK_LAUNCH();
-    return MG_OK;
-}
-
-int wino4_dgrad(const mg_conv_geom* g, const float* dy, const float* w, float* dx, float* ws, hipStream_t st,
-                const float* u_pre, float* md_keep) {
-    const Wino4Dims d = wino4_dims(g);
-    const long long T = d.T;
-    float* U = ws;
-    float* Md = U + al256((size_t)25 * g->Co * g->Ci);
-    float* dV = Md + al256((size_t)25 * T * g->Co);
-    float* dd = dV + al256((size_t)25 * T * g->Ci);
-    float* part = dd + al256((size_t)25 * T * g->Ci);
-    if (u_pre) U = const_cast<float*>(u_pre);
-    else hipLaunchKernelGGL(wino4_weight_xform_kernel, dim3(wino_grid((size_t)g->Co * g->Ci / 2)), dim3(256), 0, st, w,
-                            g->Co, g->Ci, U);
-    if (md_keep) Md = md_keep;
-    hipLaunchKernelGGL(wino4_dy_xform_kernel, dim3(wino_grid((size_t)T * g->Co / 2)), dim3(256), 0, st, dy, g->B, d.TH,
-                       d.TW, g->Co, Md);
-    if (!dense_wino_gemm(1, 25, T, g->Co, g->Ci, Md, U, dV, part, false, st)) {
-    const Geom gg{1, 1, (int)T, g->Ci, 1, (int)T, g->Co, 1, 1, 1, 0, 0};
-    const TilePlan tp = gemm_plan(T, g->Ci, g->Co / BK, 25, true, 1);
-    float* pp = tp.splits > 1 ? part : nullptr;
-    const Batch bt{T * g->Co, (long long)g->Co * g->Ci, T * g->Ci, 0};
-    probe_begin(st);
-    if (lean_dgrad_ok(tp, T, g->Ci, g->Co, false))
-        launch_lean_dgrad(tp, 25, T, g->Ci, g->Co, Md, U, dV, pp, st);
-    else
-    wino_launch_tiles(tp, [&](auto bm, auto bn) {
-        constexpr int BM_ = decltype(bm)::value, BN_ = decltype(bn)::value;
-        dim3 grid((unsigned)(((T + BM_ - 1) / BM_) * ((g->Ci + BN_ - 1) / BN_)), tp.splits, 25);
-        hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, true, true, 5>), grid, dim3(256), 0, st, gg, (const float*)Md,
-                           (const float*)U, (const float*)nullptr, dV, MG_ACT_NONE, tp.cps, pp, bt);
-    });
-    probe_end(st);
-    if (pp) {
-        const size_t n = (size_t)25 * T * g->Ci;
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(wino_grid(n / 4)), dim3(256), 0, st, (const float*)pp, tp.splits,
-                           n, g->Ci, (const float*)nullptr, MG_ACT_NONE, dV);
-    }
-    }
-    hipLaunchKernelGGL(wino4_dd_xform_kernel, dim3(wino_grid((size_t)T * g->Ci / 2)), dim3(256), 0, st, (const float*)dV, T,
-                       g->Ci, dd);
-    hipLaunchKernelGGL(wino4_dx_gather_kernel, dim3(wino_grid((size_t)g->B * g->H * g->W * g->Ci / 4)), dim3(256), 0, st,
-                       (const float*)dd, g->B, g->H, g->W, g->Ci, d.TH, d.TW, dx);
-    MG_CHECK_LAUNCH();
-    return MG_OK;
-}
-
-int wino4_wgrad(const mg_conv_geom* g, const float* x, const float* dy, float* dw, int accumulate, float* ws,
-                hipStream_t st, const float* v_in, const float* md_in) {
-    const Wino4Dims d = wino4_dims(g);
-    const WinoWgradPlan p = wino4_wgrad_plan(g);
-    float* V = ws;
-    float* Md = V + al256((size_t)25 * d.T * g->Ci);
-    float* dU = Md + al256((size_t)25 * d.T * g->Co);
-    float* part = dU + al256((size_t)25 * g->Co * g->Ci);
-    if (v_in) V = const_cast<float*>(v_in);
-    else hipLaunchKernelGGL(wino4_input_xform_kernel, dim3(wino_grid((size_t)d.T * g->Ci / 2)), dim3(256), 0, st, x, g->B,
-                            g->H, g->W, g->Ci, d.TH, d.TW, V);
-    if (md_in) Md = const_cast<float*>(md_in);
-    else hipLaunchKernelGGL(wino4_dy_xform_kernel, dim3(wino_grid((size_t)d.T * g->Co / 2)), dim3(256), 0, st, dy, g->B,
-                            d.TH, d.TW, g->Co, Md);
-    if (!dense_wino_gemm(2, 25, d.T, g->Co, g->Ci, Md, V, dU, part, false, st)) {
-    const Geom gg{1, 1, (int)d.T, g->Ci, 1, (int)d.T, g->Co, 1, 1, 1, 0, 0};
-    float* target = p.splits > 1 ? part : dU;
-    const Batch bt{d.T * g->Ci, d.T * g->Co, (long long)g->Co * g->Ci, 0};
-    dim3 grid((unsigned)p.tiles, 25, p.splits);
-    probe_begin(st);
-    if (lean_wgrad_ok(p, d.T, g->Co, g->Ci, false))
-        launch_lean_wgrad(p, 25, d.T, g->Co, g->Ci, Md, V, target, st);
-    else if (p.big)
-        hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, true, true, 5>), grid, dim3(256), 0, st, gg, (const float*)V,
-                           (const float*)Md, target, p.cps, 0, bt);
-    else
-        hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, true, true, 5>), grid, dim3(256), 0, st, gg, (const float*)V,
-                           (const float*)Md, target, p.cps, 0, bt);
-    probe_end(st);
-    if (p.splits > 1) {
-        const size_t n = (size_t)25 * g->Co * g->Ci;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(wino_grid(n / 4)), dim3(256), 0, st, (const float*)part, p.splits, n,
-                           dU, 0);
-    }
-    }
-    hipLaunchKernelGGL(wino4_dweight_xform_kernel, dim3(wino_grid((size_t)g->Co * g->Ci / 2)), dim3(256), 0, st,
-                       (const float*)dU, g->Co, g->Ci, dw, accumulate);
-    MG_CHECK_LAUNCH();
-    return MG_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Winograd F(4x4,2x2) over the space-to-depth view (wino42.h): the stride-2 4x4 PatchGAN layers.  K = 4 Ci.
-// ---------------------------------------------------------------------------------------------------------
 bool wino42_ok(const mg_conv_geom* g) {
     static const bool off = getenv("MG_NO_WINOGRAD42") != nullptr;
     constexpr int min_c = 16;
@@ -2147,192 +1530,289 @@ bool wino42_ok(const mg_conv_geom* g) {
     const double T = (double)g->B * ((g->OH + 3) / 4) * ((g->OW + 3) / 4);
     return T * 4.0 * g->Ci * g->Co >= min_work;
 }
-struct Wino42Dims { long long T; int TH, TW, K4; };
-Wino42Dims wino42_dims(const mg_conv_geom* g) {
-    Wino42Dims d;
-    d.TH = (g->OH + 3) / 4; d.TW = (g->OW + 3) / 4; d.T = (long long)g->B * d.TH * d.TW; d.K4 = 4 * g->Ci;
-    return d;
+
+// Per family: positions P, channels per thread of the transform kernels (their grid divisor), and the weight-gradient plan's
+// tile count above which it takes 128x128 tiles, and whether a full grid still splits a deep reduction in three
+struct WinoFamily { int P, vec; long long big_T; bool split3; };
+constexpr WinoFamily kWinoFamily[3] = {
+    {16, 4, 1024, false},      // F(2x2,3x3); short reductions (the 8x16 blocks of configs[1]): 64x64 tiles measured 125 vs 148 us
+    {25, 2, 4096, true},       // F(2x2,4x4); measured at 2448 tiles: 64x64 232 us, 128x128 252 us
+    {25, 2, 4096, true},       // F(4x4,2x2)
+};
+// A layer in the Winograd domain: T = B * TH * TW tiles, Kc = the GEMMs' input depth (4 Ci for F(4x4,2x2))
+struct WinoGeo { ConvRoute r; WinoFamily f; long long T; int TH, TW, Kc; bool hp; };
+WinoGeo wino_geo(ConvRoute r, const mg_conv_geom* g) {
+    WinoGeo w{r, kWinoFamily[r - R_WINO], 0, 0, 0, r == R_WINO42 ? 4 * g->Ci : g->Ci, prec_h(g)};
+    if (r == R_WINO) { w.TH = g->H / 2; w.TW = g->W / 2; }
+    else if (r == R_WINO4) { w.TH = (g->H + 1) / 2; w.TW = (g->W + 1) / 2; }
+    else { w.TH = (g->OH + 3) / 4; w.TW = (g->OW + 3) / 4; }
+    w.T = (long long)g->B * w.TH * w.TW;
+    return w;
 }
-WinoWgradPlan wino42_wgrad_plan(const mg_conv_geom* g) {
-    const Wino42Dims d = wino42_dims(g);
-    const int chunks = (int)((d.T + BK - 1) / BK);
-    bool big = g->Co >= 128 && d.K4 >= 128 && d.T > 4096;
-    int want = -1;
-    const int tiles = big ? ((g->Co + 127) / 128) * ((d.K4 + 127) / 128) : ((g->Co + 63) / 64) * ((d.K4 + 63) / 64);
-    int splits = want > 0 ? want : (tiles * 25 >= 512 ? (chunks >= 128 ? 3 : 1) : (768 + tiles * 25 - 1) / (tiles * 25));
-    const int max_splits = chunks / 8 > 0 ? chunks / 8 : 1;
-    if (splits > max_splits) splits = max_splits;
-    int cps = (chunks + splits - 1) / splits;
-    splits = (chunks + cps - 1) / cps;
-    return {big, tiles, splits, cps};
-}
-inline size_t wino42_wgrad_slabs(const mg_conv_geom* g) {
-    return slab_count(wino42_wgrad_plan(g).splits, dense_splits(2, 25, wino42_dims(g).T, g->Co, wino42_dims(g).K4, false));
-}
-size_t wino42_fwd_ws(const mg_conv_geom* g) {
-    const Wino42Dims d = wino42_dims(g);
-    const TilePlan tp = gemm_plan(d.T, g->Co, d.K4 / BK, 25, true, 0);
-    return (al256((size_t)25 * g->Co * d.K4) + al256((size_t)25 * d.T * d.K4) + al256((size_t)25 * d.T * g->Co) +
-            al256(slab_count(tp.splits, dense_splits(0, 25, d.T, g->Co, d.K4, false)) * 25 * d.T * g->Co)) * sizeof(float) + 256;
-}
-size_t wino42_dgrad_ws(const mg_conv_geom* g) {      // U | A dy A^T | dV | dd | split-K slabs
-    const Wino42Dims d = wino42_dims(g);
-    const TilePlan tp = gemm_plan(d.T, d.K4, g->Co / BK, 25, true, 1);
-    return (al256((size_t)25 * g->Co * d.K4) + al256((size_t)25 * d.T * g->Co) + 2 * al256((size_t)25 * d.T * d.K4) +
-            al256(slab_count(tp.splits, dense_splits(1, 25, d.T, g->Co, d.K4, false)) * 25 * d.T * d.K4)) * sizeof(float) + 256;
-}
-size_t wino42_wgrad_ws(const mg_conv_geom* g) {
-    const Wino42Dims d = wino42_dims(g);
-    const WinoWgradPlan p = wino42_wgrad_plan(g);
-    const size_t cs = (mg_colsum_workspace((long long)g->B * g->OH * g->OW, g->Co) + 255) / 4;
-    return (al256((size_t)25 * d.T * d.K4) + al256((size_t)25 * d.T * g->Co) + al256((size_t)25 * g->Co * d.K4) +
-            al256(wino42_wgrad_slabs(g) * 25 * g->Co * d.K4) + al256(cs)) * sizeof(float) + 256;
+inline size_t al256(size_t n) { return (n + 63) / 64 * 64; }   // in floats
+
+// The GEMM stage of a pass (dense_dims): dense_gemm.h where dense_plan takes the shape, else the convolution kernels (TAG 1;
+// 3 = float16; 5 = the 25-position families) on tile plan tp (forward: k32 = the 32-deep kernel).  The one plan that the
+// launch, the workspace (split-K slabs of either path) and mg_conv_plan_name use.
+struct WinoGemm { DensePlan dp; TilePlan tp; int tag; };
+WinoGemm wino_gemm_plan(const WinoGeo& w, int pass, const mg_conv_geom* g) {
+    WinoGemm s{dense_plan(pass, w.f.P, w.T, g->Co, w.Kc, w.hp), {}, w.hp ? 3 : w.f.P == 16 ? 1 : 5};
+    if (pass == 0) {
+        s.tp = gemm_plan(w.T, g->Co, w.Kc / BK, w.f.P, true, 0);
+        // f16: the 32-deep kernel whenever the shape allows it
+        s.tp.k32 = w.hp ? fwd32_enabled() && w.Kc % BK2 == 0 && (s.tp.splits == 1 || s.tp.cps % 2 == 0) : use_k32(s.tp, w.Kc);
+    } else if (pass == 1) {
+        s.tp = gemm_plan(w.T, w.Kc, g->Co / BK, w.f.P, true, 1);
+    } else {        // dU [Co][Kc] on 64x64 or 128x128 tiles, the tiles' reduction split over blockIdx.z
+        const int chunks = (int)((w.T + BK - 1) / BK);
+        const int t = g->Co >= 128 && w.Kc >= 128 && w.T > w.f.big_T ? 128 : 64;
+        const int wgs = ((g->Co + t - 1) / t) * ((w.Kc + t - 1) / t) * w.f.P;
+        int splits = wgs >= 512 ? (w.f.split3 && chunks >= 128 ? 3 : 1) : (768 + wgs - 1) / wgs;
+        const int max_splits = chunks / 8 > 0 ? chunks / 8 : 1;
+        if (splits > max_splits) splits = max_splits;
+        const int cps = (chunks + splits - 1) / splits;
+        s.tp = {t, t, (chunks + cps - 1) / cps, cps, false};
+    }
+    return s;
 }
 
-int wino42_fwd(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int act, float* ws,
-               hipStream_t st, const float* u_pre, float* v_keep) {
-    const Wino42Dims d = wino42_dims(g);
-    float* U = ws;
-    float* V = U + al256((size_t)25 * g->Co * d.K4);
-    float* Mx = V + al256((size_t)25 * d.T * d.K4);
-    float* part = Mx + al256((size_t)25 * d.T * g->Co);
-    if (u_pre) U = const_cast<float*>(u_pre);
-    else hipLaunchKernelGGL(wino42_weight_xform_kernel, dim3(wino_grid((size_t)g->Co * d.K4 / 2)), dim3(256), 0, st, w,
-                            g->Co, g->Ci, U);
-    if (v_keep) V = v_keep;
-    hipLaunchKernelGGL(wino42_input_xform_kernel, dim3(wino_grid((size_t)d.T * d.K4 / 2)), dim3(256), 0, st, x, g->B, g->H,
-                       g->W, g->Ci, d.TH, d.TW, V);
-    if (!dense_wino_gemm(0, 25, d.T, g->Co, d.K4, V, U, Mx, part, false, st)) {
-    const Geom gg{1, 1, (int)d.T, d.K4, 1, (int)d.T, g->Co, 1, 1, 1, 0, 0};
-    const TilePlan tp = gemm_plan(d.T, g->Co, d.K4 / BK, 25, true, 0);
+// Workspace of a pass (float offsets, 256-byte aligned): forward U | V | Mx | slabs, data gradient U | Md | dV | dd | slabs,
+// weight gradient V | Md | dU | slabs | the bias gradient's column sums
+struct WinoWs { size_t u, v, md, mx, dv, dd, du, part, cs, bytes; };
+WinoWs wino_ws(const WinoGeo& w, const WinoGemm& s, int pass, const mg_conv_geom* g) {
+    const size_t P = w.f.P, nu = al256(P * g->Co * w.Kc), nv = al256(P * w.T * w.Kc), nm = al256(P * w.T * g->Co);
+    const size_t slabs = slab_count(s.tp.splits, s.dp.ok ? s.dp.splits : 0);
+    WinoWs o{};
+    size_t at = 0;
+    auto take = [&](size_t& off, size_t n) { off = at; at += n; };
+    if (pass == 0) {
+        take(o.u, nu); take(o.v, nv); take(o.mx, nm); take(o.part, al256(slabs * P * w.T * g->Co));
+    } else if (pass == 1) {
+        take(o.u, nu); take(o.md, nm); take(o.dv, nv); take(o.dd, nv); take(o.part, al256(slabs * P * w.T * w.Kc));
+    } else {
+        take(o.v, nv); take(o.md, nm); take(o.du, nu); take(o.part, al256(slabs * P * g->Co * w.Kc));
+        take(o.cs, al256((mg_colsum_workspace((long long)g->B * g->OH * g->OW, g->Co) + 255) / 4));
+    }
+    o.bytes = at * sizeof(float) + 256;
+    return o;
+}
+size_t wino_ws_bytes(ConvRoute r, int pass, const mg_conv_geom* g) {
+    const WinoGeo w = wino_geo(r, g);
+    return wino_ws(w, wino_gemm_plan(w, pass, g), pass, g).bytes;
+}
+
+template <typename Launch>
+int wino_launch_tiles(const TilePlan& tp, Launch&& launch) {
+    if (tp.bm == 128 && tp.bn == 128) launch(std::integral_constant<int, 128>{}, std::integral_constant<int, 128>{});
+    else if (tp.bm == 64) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 64>{});
+    else launch(std::integral_constant<int, 128>{}, std::integral_constant<int, 64>{});
+    return 0;
+}
+
+// pass 0: Mx = V U^T (a = V, b = U); 1: dV = Md U (a = Md, b = U); 2: dU = Md^T V (a = Md, b = V).  part: split-K slabs.
+void wino_gemm(const WinoGeo& w, const WinoGemm& s, int pass, const mg_conv_geom* g, const float* a, const float* b, float* c,
+               float* part, hipStream_t st) {
+    const int P = w.f.P, Co = g->Co, Kc = w.Kc;
+    const long long T = w.T;
+    if (s.dp.ok) {
+        dense_wino_gemm(s.dp, pass, P, T, Co, Kc, a, b, c, part, st);
+        return;
+    }
+    const TilePlan& tp = s.tp;
+    const Geom gg{1, 1, (int)T, Kc, 1, (int)T, Co, 1, 1, 1, 0, 0};
     float* pp = tp.splits > 1 ? part : nullptr;
-    const Batch bt{d.T * d.K4, (long long)g->Co * d.K4, d.T * g->Co, 0};
+    auto launch = [&](auto tag) {
+        constexpr int TAG = decltype(tag)::value;
+        if (pass == 2) {
+            const dim3 grid((unsigned)(((Co + tp.bm - 1) / tp.bm) * ((Kc + tp.bn - 1) / tp.bn)), P, tp.splits);
+            const Batch bt{T * Kc, T * Co, (long long)Co * Kc, 0};
+            float* target = pp ? pp : c;
+            if (tp.bm == 128)
+                hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, true, true, TAG>), grid, dim3(256), 0, st, gg, b, a, target, tp.cps, 0, bt);
+            else
+                hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, true, true, TAG>), grid, dim3(256), 0, st, gg, b, a, target, tp.cps, 0, bt);
+            return;
+        }
+        wino_launch_tiles(tp, [&](auto bm, auto bn) {
+            constexpr int BM_ = decltype(bm)::value, BN_ = decltype(bn)::value;
+            const dim3 grid((unsigned)(((T + BM_ - 1) / BM_) * (((pass == 0 ? Co : Kc) + BN_ - 1) / BN_)), tp.splits, P);
+            if (pass == 1)          // dV_z = dM_z U_z: same position, no flip
+                hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, true, true, TAG>), grid, dim3(256), 0, st, gg, a, b, (const float*)nullptr,
+                                   c, MG_ACT_NONE, tp.cps, pp, Batch{T * Co, (long long)Co * Kc, T * Kc, 0});
+            else if (tp.k32)
+                launch_fwd32<BM_, BN_, TAG>(grid, st, gg, a, b, nullptr, c, MG_ACT_NONE, tp.splits == 1 ? (1 << 29) : tp.cps / 2, pp,
+                                            Batch{T * Kc, (long long)Co * Kc, T * Co, 0});
+            else
+                hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, true, TAG>), grid, dim3(256), 0, st, gg, a, b, (const float*)nullptr, c,
+                                   MG_ACT_NONE, tp.cps, pp, Batch{T * Kc, (long long)Co * Kc, T * Co, 0});
+        });
+    };
     probe_begin(st);
-    const bool k32 = use_k32(tp, d.K4);
-    wino_launch_tiles(tp, [&](auto bm, auto bn) {
-        constexpr int BM_ = decltype(bm)::value, BN_ = decltype(bn)::value;
-        dim3 grid((unsigned)(((d.T + BM_ - 1) / BM_) * ((g->Co + BN_ - 1) / BN_)), tp.splits, 25);
-        if (k32)
-            launch_fwd32<BM_, BN_, 5>(grid, st, gg, V, U, nullptr, Mx, MG_ACT_NONE, tp.splits == 1 ? (1 << 29) : tp.cps / 2,
-                                      pp, bt);
+    if (s.tag == 1) launch(std::integral_constant<int, 1>{});
+    else if (s.tag == 3) launch(std::integral_constant<int, 3>{});
+    else launch(std::integral_constant<int, 5>{});
+    probe_end(st);
+    if (!pp) return;
+    if (pass == 2) {
+        const size_t n = (size_t)P * Co * Kc;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(wino_grid(n / 4)), dim3(256), 0, st, (const float*)pp, tp.splits, n, c, 0);
+    } else {
+        const int N = pass == 0 ? Co : Kc;
+        const size_t n = (size_t)P * T * N;
+        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(wino_grid(n / 4)), dim3(256), 0, st, (const float*)pp, tp.splits, n, N,
+                           (const float*)nullptr, MG_ACT_NONE, c);
+    }
+}
+
+// The family's transforms into the Winograd domain: U = G w G^T, V = B^T x B, Md = A dy A^T
+void wino_xform_u(const WinoGeo& w, const mg_conv_geom* g, const float* wt, float* U, hipStream_t st) {
+    const dim3 grid(wino_grid((size_t)g->Co * w.Kc / w.f.vec));
+    if (w.r == R_WINO) hipLaunchKernelGGL(wino_weight_xform_kernel, grid, dim3(256), 0, st, wt, g->Co, g->Ci, U);
+    else if (w.r == R_WINO4) hipLaunchKernelGGL(wino4_weight_xform_kernel, grid, dim3(256), 0, st, wt, g->Co, g->Ci, U);
+    else hipLaunchKernelGGL(wino42_weight_xform_kernel, grid, dim3(256), 0, st, wt, g->Co, g->Ci, U);
+}
+void wino_xform_v(const WinoGeo& w, const mg_conv_geom* g, const float* x, float* V, hipStream_t st) {
+    const dim3 grid(wino_grid((size_t)w.T * w.Kc / w.f.vec));
+    if (w.r == R_WINO)
+        hipLaunchKernelGGL(wino_input_xform_kernel, grid, dim3(256), 0, st, x, g->B, g->H, g->W, g->Ci, w.TH, w.TW, 1, g->reflect, V);
+    else if (w.r == R_WINO4)
+        hipLaunchKernelGGL(wino4_input_xform_kernel, grid, dim3(256), 0, st, x, g->B, g->H, g->W, g->Ci, w.TH, w.TW, V);
+    else
+        hipLaunchKernelGGL(wino42_input_xform_kernel, grid, dim3(256), 0, st, x, g->B, g->H, g->W, g->Ci, w.TH, w.TW, V);
+}
+void wino_xform_md(const WinoGeo& w, const mg_conv_geom* g, const float* dy, float* Md, hipStream_t st) {
+    const dim3 grid(wino_grid((size_t)w.T * g->Co / w.f.vec));
+    if (w.r == R_WINO) hipLaunchKernelGGL(wino_dy_xform_kernel, grid, dim3(256), 0, st, dy, g->B, w.TH, w.TW, g->Co, Md);
+    else if (w.r == R_WINO4) hipLaunchKernelGGL(wino4_dy_xform_kernel, grid, dim3(256), 0, st, dy, g->B, w.TH, w.TW, g->Co, Md);
+    else hipLaunchKernelGGL(wino42_dy_xform_kernel, grid, dim3(256), 0, st, dy, g->B, g->OH, g->OW, w.TH, w.TW, g->Co, Md);
+}
+
+// u_pre: the caller's U (mg_conv_wino_prepare); v_keep: the caller keeps V for the weight gradient; v_filled: x's producer
+// wrote V already (mg_conv_fwd_instnorm_next of the layer in front).  nrm (F(2x2,3x3), float32): output transform +
+// InstanceNorm in one kernel (y = the raw convolution output, nrm->y the normalised one).
+int wino_fwd(const WinoGeo& w, const mg_conv_geom* g, const float* x, const float* wt, const float* bias, float* y, int act,
+             float* ws, hipStream_t st, const float* u_pre, float* v_keep, bool v_filled, const WinoNorm* nrm = nullptr) {
+    const WinoGemm s = wino_gemm_plan(w, 0, g);
+    const WinoWs o = wino_ws(w, s, 0, g);
+    float* U = u_pre ? const_cast<float*>(u_pre) : ws + o.u;
+    float* V = v_keep ? v_keep : ws + o.v;
+    float* Mx = ws + o.mx;
+    if (!u_pre) wino_xform_u(w, g, wt, U, st);
+    if (!(v_filled && v_keep)) wino_xform_v(w, g, x, V, st);
+    wino_gemm(w, s, 0, g, V, U, Mx, ws + o.part, st);
+    if (nrm) {
+        const dim3 grid(g->Co / 32, g->B);
+        const int nt = (w.TH * w.TW + 31) / 32;
+#define MG_OUT_NORM(NT_) hipLaunchKernelGGL(wino_out_norm_kernel<NT_>, grid, dim3(256), 0, st, (const float*)Mx, g->B, w.TH, w.TW, g->Co, bias, *nrm, y)
+#define MG_OUT_NORM_NEXT(NT_) hipLaunchKernelGGL((wino_out_norm_kernel<NT_, true>), grid, dim3(256), 0, st, (const float*)Mx, g->B, w.TH, w.TW, g->Co, bias, *nrm, y)
+        if (nrm->v_next && nt == 1) MG_OUT_NORM_NEXT(1);
+        else if (nrm->v_next && nt == 2) MG_OUT_NORM_NEXT(2);
+        else if (nrm->v_next) return MG_ERR_ARG;       // (callers ask mg_conv_wino_vnext_ok first)
+        else if (nt == 1) MG_OUT_NORM(1); else if (nt == 2) MG_OUT_NORM(2); else if (nt == 3) MG_OUT_NORM(3); else if (nt == 4) MG_OUT_NORM(4); else MG_OUT_NORM(5);
+#undef MG_OUT_NORM_NEXT
+#undef MG_OUT_NORM
+        MG_CHECK_LAUNCH();
+        return MG_OK;
+    }
+    const dim3 grid(wino_grid((size_t)w.T * g->Co / w.f.vec));
+    if (w.r == R_WINO)
+        hipLaunchKernelGGL(wino_output_xform_kernel, grid, dim3(256), 0, st, (const float*)Mx, g->B, w.TH, w.TW, g->Co, bias, act, y,
+                           (int)w.hp);
+    else if (w.r == R_WINO4)
+        hipLaunchKernelGGL(wino4_output_xform_kernel, grid, dim3(256), 0, st, (const float*)Mx, g->B, w.TH, w.TW, g->Co, bias, act, y);
+    else
+        hipLaunchKernelGGL(wino42_output_xform_kernel, grid, dim3(256), 0, st, (const float*)Mx, g->B, g->OH, g->OW, w.TH, w.TW, g->Co,
+                           bias, act, y);
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+}
+
+// Data gradient as the transpose of the forward pipeline (T tiles, no padded domain).  md_keep: the caller keeps Md for the
+// weight gradient; dy == nullptr (F(2x2,3x3)): md_keep already holds it (mg_instnorm_bwd_wino_md).  bias / act: F(2x2,3x3)
+// only.  addend (in / out): a tensor to add to dx (mg_wino_tiles.add); the one-kernel gather of small maps takes it and
+// clears *addend.
+int wino_dgrad(const WinoGeo& w, const mg_conv_geom* g, const float* dy, const float* wt, const float* bias, float* dx, int act,
+               float* ws, hipStream_t st, const float* u_pre, float* md_keep, const float** addend) {
+    const WinoGemm s = wino_gemm_plan(w, 1, g);
+    const WinoWs o = wino_ws(w, s, 1, g);
+    float* U = u_pre ? const_cast<float*>(u_pre) : ws + o.u;
+    float* Md = md_keep ? md_keep : ws + o.md;
+    float* dV = ws + o.dv;
+    float* dd = ws + o.dd;
+    if (!u_pre) wino_xform_u(w, g, wt, U, st);
+    if (dy) wino_xform_md(w, g, dy, Md, st);
+    wino_gemm(w, s, 1, g, Md, U, dV, ws + o.part, st);
+    if (w.r == R_WINO && !w.hp && wino_dd_gather_ok(g->H, g->W, g->Ci)) {      // small maps: patches through LDS, one kernel
+        const int ts = w.TH * w.TW;
+        const size_t lds = (size_t)ts * 16 * 8 * sizeof(float4);
+        const dim3 grid(g->Ci / 32, g->B);
+        const float* add = *addend;
+        *addend = nullptr;                     // consumed: mg_conv_dgrad_w has nothing left to add
+        auto go = [&](auto kern) {
+            hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const float*)dV, g->B, g->H, g->W, g->Ci, g->reflect, bias, act, dx, add);
+        };
+        if (ts <= 32) go(wino_dd_gather_kernel<1>); else go(wino_dd_gather_kernel<2>);
+        MG_CHECK_LAUNCH();
+        return MG_OK;
+    }
+    const dim3 grid(wino_grid((size_t)w.T * w.Kc / w.f.vec)), gx(wino_grid((size_t)g->B * g->H * g->W * g->Ci / 4));
+    if (w.r == R_WINO) {
+        hipLaunchKernelGGL(wino_dd_xform_kernel, grid, dim3(256), 0, st, (const float*)dV, w.T, w.Kc, dd);
+        hipLaunchKernelGGL(wino_dx_gather_kernel, gx, dim3(256), 0, st, (const float*)dd, g->B, g->H, g->W, g->Ci, g->reflect, bias,
+                           act, dx, (int)w.hp);
+    } else {
+        hipLaunchKernelGGL(wino4_dd_xform_kernel, grid, dim3(256), 0, st, (const float*)dV, w.T, w.Kc, dd);
+        if (w.r == R_WINO4)
+            hipLaunchKernelGGL(wino4_dx_gather_kernel, gx, dim3(256), 0, st, (const float*)dd, g->B, g->H, g->W, g->Ci, w.TH, w.TW, dx);
         else
-            hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, true, 5>), grid, dim3(256), 0, st, gg, (const float*)V,
-                               (const float*)U, (const float*)nullptr, Mx, MG_ACT_NONE, tp.cps, pp, bt);
-    });
-    probe_end(st);
-    if (pp) {
-        const size_t n = (size_t)25 * d.T * g->Co;
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(wino_grid(n / 4)), dim3(256), 0, st, (const float*)pp, tp.splits,
-                           n, g->Co, (const float*)nullptr, MG_ACT_NONE, Mx);
+            hipLaunchKernelGGL(wino42_dx_gather_kernel, gx, dim3(256), 0, st, (const float*)dd, g->B, g->H, g->W, g->Ci, w.TH, w.TW, dx);
     }
-    }
-    hipLaunchKernelGGL(wino42_output_xform_kernel, dim3(wino_grid((size_t)d.T * g->Co / 2)), dim3(256), 0, st,
-                       (const float*)Mx, g->B, g->OH, g->OW, d.TH, d.TW, g->Co, bias, act, y);
     MG_CHECK_LAUNCH();
     return MG_OK;
 }
 
-int wino42_dgrad(const mg_conv_geom* g, const float* dy, const float* w, float* dx, float* ws, hipStream_t st,
-                 const float* u_pre, float* md_keep) {
-    const Wino42Dims d = wino42_dims(g);
-    const long long T = d.T;
-    float* U = ws;
-    float* Md = U + al256((size_t)25 * g->Co * d.K4);
-    float* dV = Md + al256((size_t)25 * T * g->Co);
-    float* dd = dV + al256((size_t)25 * T * d.K4);
-    float* part = dd + al256((size_t)25 * T * d.K4);
-    if (u_pre) U = const_cast<float*>(u_pre);
-    else hipLaunchKernelGGL(wino42_weight_xform_kernel, dim3(wino_grid((size_t)g->Co * d.K4 / 2)), dim3(256), 0, st, w,
-                            g->Co, g->Ci, U);
-    if (md_keep) Md = md_keep;
-    hipLaunchKernelGGL(wino42_dy_xform_kernel, dim3(wino_grid((size_t)T * g->Co / 2)), dim3(256), 0, st, dy, g->B, g->OH,
-                       g->OW, d.TH, d.TW, g->Co, Md);
-    if (!dense_wino_gemm(1, 25, T, g->Co, d.K4, Md, U, dV, part, false, st)) {
-    const Geom gg{1, 1, (int)T, d.K4, 1, (int)T, g->Co, 1, 1, 1, 0, 0};
-    const TilePlan tp = gemm_plan(T, d.K4, g->Co / BK, 25, true, 1);
-    float* pp = tp.splits > 1 ? part : nullptr;
-    const Batch bt{T * g->Co, (long long)g->Co * d.K4, T * d.K4, 0};
-    probe_begin(st);
-    if (lean_dgrad_ok(tp, T, d.K4, g->Co, false))
-        launch_lean_dgrad(tp, 25, T, d.K4, g->Co, Md, U, dV, pp, st);
+// v_in / md_in: the images the forward / data-gradient calls kept.  ad (F(2x2,3x3), float32): dw IS the weight tensor --
+// inverse transform + Adam + next iteration's forward transform in one pass.  dbias: the bias gradient (column sums of dy).
+int wino_wgrad(const WinoGeo& w, const mg_conv_geom* g, const float* x, const float* dy, float* dw, float* dbias, int accumulate,
+               float* ws, hipStream_t st, const float* v_in, const float* md_in, const mg_wino_adam* ad = nullptr) {
+    const WinoGemm s = wino_gemm_plan(w, 2, g);
+    const WinoWs o = wino_ws(w, s, 2, g);
+    float* V = v_in ? const_cast<float*>(v_in) : ws + o.v;
+    float* Md = md_in ? const_cast<float*>(md_in) : ws + o.md;
+    float* dU = ws + o.du;
+    if (!v_in) wino_xform_v(w, g, x, V, st);
+    if (!md_in) wino_xform_md(w, g, dy, Md, st);
+    wino_gemm(w, s, 2, g, Md, V, dU, ws + o.part, st);
+    const dim3 grid(wino_grid((size_t)g->Co * w.Kc / w.f.vec));
+    if (ad)
+        hipLaunchKernelGGL(wino_adam_kernel, grid, dim3(256), 0, st, (const float*)dU, g->Co, g->Ci, dw, ad->m, ad->v, ad->u,
+                           ad->state, ad->beta1, ad->beta2, ad->eps, ad->grad_scale);
+    else if (w.r == R_WINO)
+        hipLaunchKernelGGL(wino_dweight_xform_kernel, grid, dim3(256), 0, st, (const float*)dU, g->Co, g->Ci, dw, accumulate);
+    else if (w.r == R_WINO4)
+        hipLaunchKernelGGL(wino4_dweight_xform_kernel, grid, dim3(256), 0, st, (const float*)dU, g->Co, g->Ci, dw, accumulate);
     else
-    wino_launch_tiles(tp, [&](auto bm, auto bn) {
-        constexpr int BM_ = decltype(bm)::value, BN_ = decltype(bn)::value;
-        dim3 grid((unsigned)(((T + BM_ - 1) / BM_) * ((d.K4 + BN_ - 1) / BN_)), tp.splits, 25);
-        hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, true, true, 5>), grid, dim3(256), 0, st, gg, (const float*)Md,
-                           (const float*)U, (const float*)nullptr, dV, MG_ACT_NONE, tp.cps, pp, bt);
-    });
-    probe_end(st);
-    if (pp) {
-        const size_t n = (size_t)25 * T * d.K4;
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(wino_grid(n / 4)), dim3(256), 0, st, (const float*)pp, tp.splits,
-                           n, d.K4, (const float*)nullptr, MG_ACT_NONE, dV);
-    }
-    }
-    hipLaunchKernelGGL(wino4_dd_xform_kernel, dim3(wino_grid((size_t)T * d.K4 / 2)), dim3(256), 0, st, (const float*)dV, T,
-                       d.K4, dd);
-    hipLaunchKernelGGL(wino42_dx_gather_kernel, dim3(wino_grid((size_t)g->B * g->H * g->W * g->Ci / 4)), dim3(256), 0, st,
-                       (const float*)dd, g->B, g->H, g->W, g->Ci, d.TH, d.TW, dx);
+        hipLaunchKernelGGL(wino42_dweight_xform_kernel, grid, dim3(256), 0, st, (const float*)dU, g->Co, g->Ci, dw, accumulate);
     MG_CHECK_LAUNCH();
-    return MG_OK;
-}
-
-int wino42_wgrad(const mg_conv_geom* g, const float* x, const float* dy, float* dw, int accumulate, float* ws,
-                 hipStream_t st, const float* v_in, const float* md_in) {
-    const Wino42Dims d = wino42_dims(g);
-    const WinoWgradPlan p = wino42_wgrad_plan(g);
-    float* V = ws;
-    float* Md = V + al256((size_t)25 * d.T * d.K4);
-    float* dU = Md + al256((size_t)25 * d.T * g->Co);
-    float* part = dU + al256((size_t)25 * g->Co * d.K4);
-    if (v_in) V = const_cast<float*>(v_in);
-    else hipLaunchKernelGGL(wino42_input_xform_kernel, dim3(wino_grid((size_t)d.T * d.K4 / 2)), dim3(256), 0, st, x, g->B,
-                            g->H, g->W, g->Ci, d.TH, d.TW, V);
-    if (md_in) Md = const_cast<float*>(md_in);
-    else hipLaunchKernelGGL(wino42_dy_xform_kernel, dim3(wino_grid((size_t)d.T * g->Co / 2)), dim3(256), 0, st, dy, g->B,
-                            g->OH, g->OW, d.TH, d.TW, g->Co, Md);
-    if (!dense_wino_gemm(2, 25, d.T, g->Co, d.K4, Md, V, dU, part, false, st)) {
-    const Geom gg{1, 1, (int)d.T, d.K4, 1, (int)d.T, g->Co, 1, 1, 1, 0, 0};
-    float* target = p.splits > 1 ? part : dU;
-    const Batch bt{d.T * d.K4, d.T * g->Co, (long long)g->Co * d.K4, 0};
-    dim3 grid((unsigned)p.tiles, 25, p.splits);
-    probe_begin(st);
-    if (lean_wgrad_ok(p, d.T, g->Co, d.K4, false))
-        launch_lean_wgrad(p, 25, d.T, g->Co, d.K4, Md, V, target, st);
-    else if (p.big)
-        hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, true, true, 5>), grid, dim3(256), 0, st, gg, (const float*)V,
-                           (const float*)Md, target, p.cps, 0, bt);
-    else
-        hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, true, true, 5>), grid, dim3(256), 0, st, gg, (const float*)V,
-                           (const float*)Md, target, p.cps, 0, bt);
-    probe_end(st);
-    if (p.splits > 1) {
-        const size_t n = (size_t)25 * g->Co * d.K4;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(wino_grid(n / 4)), dim3(256), 0, st, (const float*)part, p.splits, n,
-                           dU, 0);
+    if (dbias) {
+        const long long M = (long long)g->B * g->OH * g->OW;
+        return mg_colsum(dy, M, g->Co, dbias, accumulate, ws + o.cs, mg_colsum_workspace(M, g->Co), st);
     }
-    }
-    hipLaunchKernelGGL(wino42_dweight_xform_kernel, dim3(wino_grid((size_t)g->Co * d.K4 / 2)), dim3(256), 0, st,
-                       (const float*)dU, g->Co, g->Ci, dw, accumulate);
-    MG_CHECK_LAUNCH();
     return MG_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // Ci <= 4 layers (conv_smallc.h): VALU kernels for the data gradient and the weight gradient
 // ---------------------------------------------------------------------------------------------------------
-bool smallc_enabled() {
-    constexpr bool off = false;
-    return !off;
-}
 bool smallc_dgrad_ok(const mg_conv_geom* g) {
     const int s = g->stride;       // the class's weights sit in LDS: taps x Co float4s
-    return smallc_enabled() && g->Ci >= 1 && g->Ci <= 4 && !g->reflect && g->Co % 4 == 0 && g->Co >= 16 &&
+    return g->Ci >= 1 && g->Ci <= 4 && !g->reflect && g->Co % 4 == 0 && g->Co >= 16 &&
            (size_t)((g->KH + s - 1) / s) * ((g->KW + s - 1) / s) * g->Co * 16 <= 60 * 1024;
 }
 // 0: not eligible; otherwise the template instance id
 int smallc_wgrad_kind(const mg_conv_geom* g) {
-    if (!smallc_enabled() || g->Co < 16 || ((g->stride * g->Ci) & 1)) return 0;
+    if (g->Co < 16 || ((g->stride * g->Ci) & 1)) return 0;
     if ((size_t)g->KH * (((g->OW - 1) * g->stride + g->KW) * g->Ci + 4) * sizeof(float) > 60000) return 0;
     if ((long long)g->B * g->OH > 65535LL * 32) return 0;
     if (g->KH == 4 && g->KW == 4 && g->Ci == 3) return 1;
@@ -2344,8 +1824,7 @@ int smallc_wgrad_kind(const mg_conv_geom* g) {
 struct SmallcWgradPlan { int wgs, rowlen; size_t lds; int mfma_g; };     // wgs: partial rows; mfma_g: 0 or the MFMA kernel's pixel groups
 // the MFMA form (conv_smallc_wgrad_mfma_kernel): pixel groups per output row (each writes a partial row), 0 = VALU kernel
 int smallc_wgrad_mfma_groups(const mg_conv_geom* g, int rowlen) {
-    constexpr bool off = false;
-    if (off || (size_t)g->KH * rowlen > 256 * 16 || g->Co % 64 != 0) return 0;
+    if ((size_t)g->KH * rowlen > 256 * 16 || g->Co % 64 != 0) return 0;
     if (g->KH == 7 && g->KW == 7 && g->Ci == 2 && g->stride == 1) return 1;     // K = 98: four k blocks, one per wave
     if (g->KH == 4 && g->KW == 4 && g->Ci == 3 && g->stride == 2) return 2;     // K = 48: two k blocks x two pixel groups
     return 0;
@@ -2392,14 +1871,11 @@ int smallc_wgrad(const mg_conv_geom* g, const float* x, const float* dy, float* 
 }
 // forward on the MFMA pipe (conv_smallc_fwd_kernel): 0 = not eligible, else the template instance
 int smallc_fwd_kind(const mg_conv_geom* g) {
-    constexpr bool off = false;
-    if (!smallc_enabled() || off || g->Co % 64 != 0 || (long long)g->B * g->OH > 0x7fffffffLL) return 0;
+    if (g->Co % 64 != 0 || (long long)g->B * g->OH > 0x7fffffffLL) return 0;
     if ((size_t)g->KH * (((g->OW - 1) * g->stride + g->KW) * g->Ci + 4) > 256 * 16) return 0;      // staged through 16 registers per thread
     if (g->KH == 7 && g->KW == 7 && g->Ci == 2 && g->stride == 1) return 1;      // the generator stem: 66 against 93 us
-    // the 3 -> 64 4x4 stride-2 first discriminator layer (K = 48, 129-pixel rows = 5 pixel blocks for 4 waves) measured
-    // SLOWER here than on the generic kernel (44 against 37 us at batch 16): instance kept for MG_SMALLC_FWD_D=1 only
-    constexpr bool with_d = false;
-    if (with_d && g->KH == 4 && g->KW == 4 && g->Ci == 3 && g->stride == 2) return 2;
+    // (the 3 -> 64 4x4 stride-2 first discriminator layer -- K = 48, 129-pixel rows = 5 pixel blocks for 4 waves -- measured
+    // SLOWER here than on the generic kernel: 44 against 37 us at batch 16)
     return 0;
 }
 int smallc_fwd(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int act, hipStream_t st) {
@@ -2410,11 +1886,8 @@ int smallc_fwd(const mg_conv_geom* g, const float* x, const float* w, const floa
     while ((long long)((rows + rpw - 1) / rpw) * cblocks > 1024 && rpw < 8) ++rpw;
     const dim3 grid((unsigned)((rows + rpw - 1) / rpw), (unsigned)cblocks);
     const size_t lds = p.lds + (size_t)64 * ((g->KH * g->KW * g->Ci) | 1) * sizeof(float);
-    switch (smallc_fwd_kind(g)) {
-    case 1: hipLaunchKernelGGL((conv_smallc_fwd_kernel<7, 7, 2, 1>), grid, dim3(256), lds, st, gg, x, w, bias, y, act, p.rowlen, rpw, (int)prec_h(g)); break;
-    case 2: hipLaunchKernelGGL((conv_smallc_fwd_kernel<4, 4, 3, 2>), grid, dim3(256), lds, st, gg, x, w, bias, y, act, p.rowlen, rpw, (int)prec_h(g)); break;
-    default: return MG_ERR_UNSUPPORTED;
-    }
+    if (smallc_fwd_kind(g) != 1) return MG_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((conv_smallc_fwd_kernel<7, 7, 2, 1>), grid, dim3(256), lds, st, gg, x, w, bias, y, act, p.rowlen, rpw, (int)prec_h(g));
     MG_CHECK_LAUNCH();
     return MG_OK;
 }
@@ -2439,6 +1912,30 @@ int smallc_dgrad(const mg_conv_geom* g, const float* dy, const float* w, float* 
     return MG_OK;
 }
 
+// The kernel family of a pass (0 fwd, 1 dgrad, 2 wgrad) of a layer; generic: only the tail every family falls back to.  The
+// special families' predicates are pairwise disjoint apart from co1 / rowdot (both Co == 1: co1 first), so their order here
+// is no priority.
+ConvRoute conv_route(int pass, const mg_conv_geom* g, bool generic) {
+    if (!generic) {
+        if (co1_gemm_ok(g)) return R_CO1;
+        if (pass != 1 && mg_conv_rowdot_kq(g)) return R_ROWDOT;
+        if (h16_ok(g)) return R_H16;
+        if (wino_ok(g)) return R_WINO;
+        if (wino4_ok(g)) return R_WINO4;
+        if (wino42_ok(g)) return R_WINO42;
+        if (pass == 0 ? smallc_fwd_kind(g) != 0 : pass == 1 ? smallc_dgrad_ok(g) : smallc_wgrad_kind(g) != 0) return R_SMALLC;
+    }
+    if (pass == 0) return conv_dma_fwd_ok(g) ? R_DMA : R_IGEMM;
+    if (pass == 2) return conv_dma_wgrad_ok(g) ? R_DMA : R_IGEMM;
+    return conv_dma_dgrad_ok(g) ? R_DMA : cd_reflect_dgrad_ok(g) ? R_DMA_REFLECT : R_IGEMM;
+}
+// a layer any of whose passes runs on the float16 implicit GEMMs keeps a cached float16 copy of its weights (a Winograd
+// layer keeps float32 U / V / Md images under MG_PRECISION_F16: it must never be handed the float16-sized buffers of this path)
+inline bool conv_dma_h_any(const mg_conv_geom* g) {
+    const ConvRoute d = conv_route(1, g);
+    return conv_dma_half(g) && (conv_route(0, g) == R_DMA || d == R_DMA || d == R_DMA_REFLECT);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2460,43 +1957,44 @@ void mg_probe_arm(void* e0, void* e1) {
 }
 
 // FLOPs the main GEMM kernel of a pass issues for this geometry (2*M*N*K of the GEMM it actually runs: the direct
-// convolution's 2*MACs, or 16 Winograd-domain GEMMs = 1/2.25 of that on the unpadded tile grid).
+// convolution's 2*MACs, or P Winograd-domain GEMMs -- 16 of them = 1/2.25 of that on the unpadded tile grid).
 double mg_conv_plan_flops(int pass, const mg_conv_geom* g) {
     if (!geom_ok(g)) return 0.0;
-    const double direct = 2.0 * g->B * g->OH * g->OW * (double)g->Co * g->KH * g->KW * g->Ci;
-    if (co1_gemm_ok(g)) return 2.0 * CO1_TAPS * (double)g->B * g->H * g->W * g->Ci;      // the 64-tap GEMM (conv_co1.h)
-    if (wino_ok(g) && !mg_conv_rowdot_kq(g)) {
-        const WinoDims d = wino_dims(g);
-        const double T = (double)d.T;
-        return 2.0 * 16.0 * T * (double)g->Co * g->Ci;
+    switch (const ConvRoute r = conv_route(pass, g)) {
+    case R_CO1: return 2.0 * CO1_TAPS * (double)g->B * g->H * g->W * g->Ci;      // the 64-tap GEMM (conv_co1.h)
+    case R_WINO: case R_WINO4: case R_WINO42: {
+        const WinoGeo w = wino_geo(r, g);
+        return 2.0 * w.f.P * (double)w.T * (double)g->Co * w.Kc;
     }
-    if (wino4_ok(g) && !mg_conv_rowdot_kq(g)) return 2.0 * 25.0 * (double)wino4_dims(g).T * (double)g->Co * g->Ci;
-    if (wino42_ok(g)) return 2.0 * 25.0 * (double)wino42_dims(g).T * (double)g->Co * 4.0 * g->Ci;
-    return direct;
+    default: return 2.0 * g->B * g->OH * g->OW * (double)g->Co * g->KH * g->KW * g->Ci;
+    }
 }
 
+// Split-K factor of the LDS-DMA kernels a pass runs (0: another family)
+int mg_conv_plan_splits(int pass, const mg_conv_geom* g) {
+    if (!geom_ok(g) || pass < 0 || pass > 2) return 0;
+    const ConvRoute r = conv_route(pass, g);
+    if (r == R_DMA_REFLECT) {
+        const mg_conv_geom gp = cd_reflect_geom(g);
+        return conv_dma_dgrad_plan(&gp).splits;
+    }
+    if (r != R_DMA) return 0;
+    return (pass == 0 ? conv_dma_fwd_plan(g) : pass == 1 ? conv_dma_dgrad_plan(g) : conv_dma_wgrad_plan(g)).splits;
+}
 // Name of the kernel instance a pass would launch for this geometry (matches the symbol rocprofv3 reports,
 // minus the anonymous-namespace prefix).  pass: 0 fwd, 1 dgrad, 2 wgrad.
-int mg_conv_plan_splits(int pass, const mg_conv_geom* g) {
-    char name[96];
-    if (!geom_ok(g) || mg_conv_plan_name(pass, g, name, (int)sizeof name) != MG_OK) return 0;
-    if (pass == 0 && strncmp(name, "conv_fwd_dma_kernel", 19) == 0) return conv_dma_fwd_plan(g).splits;
-    if (pass == 2 && strncmp(name, "conv_wgrad_dma_kernel", 21) == 0) return conv_dma_wgrad_plan(g).splits;
-    if (pass == 1 && strncmp(name, "conv_dgrad_dma_kernel", 21) == 0) {
-        mg_conv_geom gp;
-        return (conv_dma_dgrad_ok(g) ? conv_dma_dgrad_plan(g) : (cd_reflect_dgrad_geom(g, &gp), conv_dma_dgrad_plan(&gp))).splits;
-    }
-    return 0;
-}
 int mg_conv_plan_name(int pass, const mg_conv_geom* g, char* out, int out_len) {
-    if (!geom_ok(g) || !out || out_len < 64) return MG_ERR_ARG;
-    const int kq = mg_conv_rowdot_kq(g);
-    if (co1_gemm_ok(g)) {          // single-output-channel layers as tap GEMMs (conv_co1.h)
+    if (!geom_ok(g) || !out || out_len < 64 || pass < 0 || pass > 2) return MG_ERR_ARG;
+    const char* half = prec_h(g) ? "true" : "false";
+    switch (const ConvRoute r = conv_route(pass, g)) {
+    case R_CO1:          // single-output-channel layers as tap GEMMs (conv_co1.h)
         snprintf(out, out_len, pass == 0 ? "dgemm32g_kernel<64, 128, 2, 2, 0, 0, 2, 0, 0>"
                                : pass == 1 ? "dgemm32g_kernel<128, 64, 2, 2, 1, 1, 2, 0, 0>" : "dgemm32g_kernel<64, 64, 2, 2, 0, 1, 2, 0, 0>");
-        return MG_OK;
-    }
-    if (h16_ok(g) && !kq) {
+        break;
+    case R_ROWDOT:
+        snprintf(out, out_len, pass == 0 ? "conv_rowdot_fwd_kernel<%d>" : "conv_rowdot_wgrad_kernel<%d>", mg_conv_rowdot_kq(g));
+        break;
+    case R_H16: {
         const long long px = (long long)g->B * g->OH * g->OW;
         const int Kw = g->KH * g->KW * g->Ci;
         bool deep;
@@ -2509,148 +2007,96 @@ int mg_conv_plan_name(int pass, const mg_conv_geom* g, char* out, int out_len) {
         else if (pass != 2 && h16_sa_on() && hgemm_sa_ok(probe)) snprintf(out, out_len, pass == 1 ? "hgemm_sa_kernel<true, false>" : "hgemm_sa_kernel<false, true>");
         else
         snprintf(out, out_len, pass == 1 ? "hgemm_kernel<128, 128, 4, 2, true, %d>" : "hgemm_kernel<128, 128, 4, 2, false, %d>", deep ? 3 : 2);
-    } else if (wino_ok(g) && !kq && 
-        dense_plan(pass, 16, wino_dims(g).T, g->Co, g->Ci, prec_h(g)).ok) {
-        dense_name(pass, 16, dense_plan(pass, 16, wino_dims(g).T, g->Co, g->Ci, prec_h(g)), dense_dims(pass, wino_dims(g).T, g->Co, g->Ci).N, out, out_len);
-    } else if (wino4_ok(g) && !kq && dense_plan(pass, 25, wino4_dims(g).T, g->Co, g->Ci, false).ok) {
-        dense_name(pass, 25, dense_plan(pass, 25, wino4_dims(g).T, g->Co, g->Ci, false), dense_dims(pass, wino4_dims(g).T, g->Co, g->Ci).N, out, out_len);
-    } else if (wino42_ok(g) && !kq && dense_plan(pass, 25, wino42_dims(g).T, g->Co, wino42_dims(g).K4, false).ok) {
-        dense_name(pass, 25, dense_plan(pass, 25, wino42_dims(g).T, g->Co, wino42_dims(g).K4, false), dense_dims(pass, wino42_dims(g).T, g->Co, wino42_dims(g).K4).N, out, out_len);
-    } else if (wino_ok(g) && !kq) {
-        const WinoDims d = wino_dims(g);
-        if (pass == 0) {
-            const TilePlan tp = gemm_plan(d.T, g->Co, g->Ci / BK, 16, true, 0);
-            const bool k32h = fwd32_enabled() && g->Ci % BK2 == 0 && (tp.splits == 1 || tp.cps % 2 == 0);
-            if (prec_h(g) && k32h)
-                snprintf(out, out_len, "conv_fwd32_kernel<%d, %d, 3>", tp.bm, tp.bn);
-            else if (prec_h(g))
-                snprintf(out, out_len, "conv_fwd_kernel<%d, %d, true, 3>", tp.bm, tp.bn);
-            else if (use_k32(tp, g->Ci))
-                snprintf(out, out_len, "conv_fwd32_kernel<%d, %d, 1>", tp.bm, tp.bn);
-            else
-                snprintf(out, out_len, "conv_fwd_kernel<%d, %d, true, 1>", tp.bm, tp.bn);
-        } else if (pass == 1) {
-            const TilePlan tp = gemm_plan(d.T, g->Ci, g->Co / BK, 16, true, 1);
-            if (lean_dgrad_ok(tp, d.T, g->Ci, g->Co, prec_h(g))) snprintf(out, out_len, "dense_nn64_kernel<1>");
-            else
-            snprintf(out, out_len, "conv_dgrad_kernel<%d, %d, true, true, %d>", tp.bm, tp.bn, prec_h(g) ? 3 : 1);
-        } else {
-            const WinoWgradPlan p = wino_wgrad_plan(g);
-            if (lean_wgrad_ok(p, d.T, g->Co, g->Ci, prec_h(g)))
-                snprintf(out, out_len, lean_wgrad_wide(p, 16, g->Co, g->Ci) ? "dense_tn64_kernel<1, 1, 2>" : "dense_tn64_kernel<1, 1, 1>");
-            else
-            snprintf(out, out_len, "conv_wgrad_kernel<%d, %d, true, true, %d>", p.big ? 128 : 64, p.big ? 128 : 64,
-                     prec_h(g) ? 3 : 1);
-        }
-    } else if (wino4_ok(g) && !kq) {
-        const Wino4Dims d = wino4_dims(g);
-        if (pass == 0) {
-            const TilePlan tp = gemm_plan(d.T, g->Co, g->Ci / BK, 25, true, 0);
-            if (use_k32(tp, g->Ci)) snprintf(out, out_len, "conv_fwd32_kernel<%d, %d, 5>", tp.bm, tp.bn);
-            else snprintf(out, out_len, "conv_fwd_kernel<%d, %d, true, 5>", tp.bm, tp.bn);
-        } else if (pass == 1) {
-            const TilePlan tp = gemm_plan(d.T, g->Ci, g->Co / BK, 25, true, 1);
-            if (lean_dgrad_ok(tp, d.T, g->Ci, g->Co, false)) snprintf(out, out_len, "dense_nn64_kernel<5>");
-            else
-            snprintf(out, out_len, "conv_dgrad_kernel<%d, %d, true, true, 5>", tp.bm, tp.bn);
-        } else {
-            const WinoWgradPlan p = wino4_wgrad_plan(g);
-            if (lean_wgrad_ok(p, d.T, g->Co, g->Ci, false)) snprintf(out, out_len, "dense_tn64_kernel<1, 5, 1>");
-            else
-            snprintf(out, out_len, "conv_wgrad_kernel<%d, %d, true, true, 5>", p.big ? 128 : 64, p.big ? 128 : 64);
-        }
-    } else if (wino42_ok(g) && !kq) {
-        const Wino42Dims d = wino42_dims(g);
-        if (pass == 0) {
-            const TilePlan tp = gemm_plan(d.T, g->Co, d.K4 / BK, 25, true, 0);
-            if (use_k32(tp, d.K4)) snprintf(out, out_len, "conv_fwd32_kernel<%d, %d, 5>", tp.bm, tp.bn);
-            else snprintf(out, out_len, "conv_fwd_kernel<%d, %d, true, 5>", tp.bm, tp.bn);
-        } else if (pass == 1) {
-            const TilePlan tp = gemm_plan(d.T, d.K4, g->Co / BK, 25, true, 1);
-            if (lean_dgrad_ok(tp, d.T, d.K4, g->Co, false)) snprintf(out, out_len, "dense_nn64_kernel<5>");
-            else
-            snprintf(out, out_len, "conv_dgrad_kernel<%d, %d, true, true, 5>", tp.bm, tp.bn);
-        } else {
-            const WinoWgradPlan p = wino42_wgrad_plan(g);
-            if (lean_wgrad_ok(p, d.T, g->Co, d.K4, false)) snprintf(out, out_len, "dense_tn64_kernel<1, 5, 1>");
-            else
-            snprintf(out, out_len, "conv_wgrad_kernel<%d, %d, true, true, 5>", p.big ? 128 : 64, p.big ? 128 : 64);
-        }
-    } else if (pass == 0 && !kq && smallc_fwd_kind(g)) {
-        snprintf(out, out_len, "conv_smallc_fwd_kernel<%d, %d, %d, %d>", g->KH, g->KW, g->Ci, g->stride);
-    } else if (pass == 1 && smallc_dgrad_ok(g)) {
-        snprintf(out, out_len, "conv_smallc_dgrad_kernel<%d, %s>", g->Ci, prec_h(g) ? "true" : "false");
-    } else if (pass == 2 && !kq && smallc_wgrad_kind(g)) {
-        if (smallc_wgrad_plan(g).mfma_g) snprintf(out, out_len, "conv_smallc_wgrad_mfma_kernel<%d, %d, %d, %d>", g->KH, g->KW, g->Ci, g->stride);
+        break;
+    }
+    case R_WINO: case R_WINO4: case R_WINO42: {
+        const WinoGeo w = wino_geo(r, g);
+        const WinoGemm s = wino_gemm_plan(w, pass, g);
+        if (s.dp.ok) dense_name(pass, w.f.P, s.dp, dense_dims(pass, w.T, g->Co, w.Kc).N, out, out_len);
+        else if (pass == 0 && s.tp.k32) snprintf(out, out_len, "conv_fwd32_kernel<%d, %d, %d>", s.tp.bm, s.tp.bn, s.tag);
+        else snprintf(out, out_len, pass == 0 ? "conv_fwd_kernel<%d, %d, true, %d>" : pass == 1 ? "conv_dgrad_kernel<%d, %d, true, true, %d>"
+                                                                                         : "conv_wgrad_kernel<%d, %d, true, true, %d>",
+                      s.tp.bm, s.tp.bn, s.tag);
+        break;
+    }
+    case R_SMALLC:
+        if (pass == 0) snprintf(out, out_len, "conv_smallc_fwd_kernel<%d, %d, %d, %d>", g->KH, g->KW, g->Ci, g->stride);
+        else if (pass == 1) snprintf(out, out_len, "conv_smallc_dgrad_kernel<%d, %s>", g->Ci, half);
+        else if (smallc_wgrad_plan(g).mfma_g) snprintf(out, out_len, "conv_smallc_wgrad_mfma_kernel<%d, %d, %d, %d>", g->KH, g->KW, g->Ci, g->stride);
         else snprintf(out, out_len, "conv_smallc_wgrad_kernel<%d, %d, %d>", g->KH, g->KW, g->Ci);
-    } else if (kq && pass == 0) {
-        snprintf(out, out_len, "conv_rowdot_fwd_kernel<%d>", kq);
-    } else if (kq && pass == 2) {
-        snprintf(out, out_len, "conv_rowdot_wgrad_kernel<%d>", kq);
-    } else if (pass == 1 && cd_dgrad_any(g) && !smallc_dgrad_ok(g)) {
-        mg_conv_geom gp;
-        const CdPlan cp = conv_dma_dgrad_ok(g) ? conv_dma_dgrad_plan(g) : (cd_reflect_dgrad_geom(g, &gp), conv_dma_dgrad_plan(&gp));
-        snprintf(out, out_len, "conv_dgrad_dma_kernel<%d, %d, %s, %d>", cp.bm, cp.bn, prec_h(g) ? "true" : "false", prec_h(g) ? cd_half_nbuf() : 2);
-    } else if (pass == 0 && conv_dma_fwd_ok(g)) {
-        const CdPlan cp = conv_dma_fwd_plan(g);
-        snprintf(out, out_len, "conv_fwd_dma_kernel<%d, %d, %s, %d>", cp.bm, cp.bn, prec_h(g) ? "true" : "false", prec_h(g) ? cd_half_nbuf() : 2);
-    } else if (pass == 2 && conv_dma_wgrad_ok(g)) {
-        const CdPlan cp = conv_dma_wgrad_plan(g);
-        const bool rr = conv_dma_wgrad_rowreg(g) && !getenv("MG_NO_WGRAD_RR") && (!prec_h(g) || cd_half_nbuf() == 2);
-        snprintf(out, out_len, "conv_wgrad_dma_kernel<%d, %d, %s, %d, %s>", cp.bm, cp.bn, prec_h(g) ? "true" : "false", prec_h(g) ? cd_half_nbuf() : 2,
-                 rr ? "true" : "false");
-    } else if (pass == 0) {
-        const TilePlan tp = fwd_plan(g);
-        const bool vec16 = g->Ci % BK == 0;
-        const bool k32h = vec16 && fwd32_enabled() && g->Ci % BK2 == 0 && (tp.splits == 1 || tp.cps % 2 == 0);
-        if (prec_h(g) && k32h)
-            snprintf(out, out_len, "conv_fwd32_kernel<%d, %d, 2>", tp.bm, tp.bn);
-        else if (!prec_h(g) && use_k32(tp, g->Ci))
-            snprintf(out, out_len, "conv_fwd32_kernel<%d, %d, 0>", tp.bm, tp.bn);
-        else
-            snprintf(out, out_len, "conv_fwd_kernel<%d, %d, %s, %d>", tp.bm, tp.bn, (g->Ci % BK == 0) ? "true" : "false",
-                     prec_h(g) ? 2 : 0);
-    } else if (pass == 1) {
-        const TilePlan tp = dgrad_plan(g);
-        snprintf(out, out_len, "conv_dgrad_kernel<%d, %d, %s, %s, %d>", tp.bm, tp.bn, (g->Co % BK == 0) ? "true" : "false",
-                 (g->Ci % 4 == 0) ? "true" : "false", prec_h(g) ? 2 : 0);
-    } else if (pass == 2) {
-        const WgradPlan p = wgrad_plan(g);
-        snprintf(out, out_len, "conv_wgrad_kernel<%d, %d, %s, %s, %d>", p.big ? 128 : 64, p.big ? 128 : 64,
-                 (g->Co % 4 == 0) ? "true" : "false", (g->Ci % 4 == 0) ? "true" : "false", prec_h(g) ? 2 : 0);
-    } else {
-        return MG_ERR_ARG;
+        break;
+    case R_DMA: case R_DMA_REFLECT: {
+        const int nbuf = prec_h(g) ? cd_half_nbuf() : 2;
+        if (pass == 0) {
+            const CdPlan cp = conv_dma_fwd_plan(g);
+            snprintf(out, out_len, "conv_fwd_dma_kernel<%d, %d, %s, %d>", cp.bm, cp.bn, half, nbuf);
+        } else if (pass == 1) {
+            const mg_conv_geom gp = r == R_DMA ? *g : cd_reflect_geom(g);
+            const CdPlan cp = conv_dma_dgrad_plan(&gp);
+            snprintf(out, out_len, "conv_dgrad_dma_kernel<%d, %d, %s, %d>", cp.bm, cp.bn, half, nbuf);
+        } else {
+            const CdPlan cp = conv_dma_wgrad_plan(g);
+            const bool rr = conv_dma_wgrad_rowreg(g) && !getenv("MG_NO_WGRAD_RR") && (!prec_h(g) || cd_half_nbuf() == 2);
+            snprintf(out, out_len, "conv_wgrad_dma_kernel<%d, %d, %s, %d, %s>", cp.bm, cp.bn, half, nbuf, rr ? "true" : "false");
+        }
+        break;
+    }
+    default:
+        if (pass == 0) {
+            const TilePlan tp = fwd_plan(g);
+            const bool vec16 = g->Ci % BK == 0;
+            const bool k32h = vec16 && fwd32_enabled() && g->Ci % BK2 == 0 && (tp.splits == 1 || tp.cps % 2 == 0);
+            if (prec_h(g) && k32h)
+                snprintf(out, out_len, "conv_fwd32_kernel<%d, %d, 2>", tp.bm, tp.bn);
+            else if (!prec_h(g) && use_k32(tp, g->Ci))
+                snprintf(out, out_len, "conv_fwd32_kernel<%d, %d, 0>", tp.bm, tp.bn);
+            else
+                snprintf(out, out_len, "conv_fwd_kernel<%d, %d, %s, %d>", tp.bm, tp.bn, (g->Ci % BK == 0) ? "true" : "false",
+                         prec_h(g) ? 2 : 0);
+        } else if (pass == 1) {
+            const TilePlan tp = dgrad_plan(g);
+            snprintf(out, out_len, "conv_dgrad_kernel<%d, %d, %s, %s, %d>", tp.bm, tp.bn, (g->Co % BK == 0) ? "true" : "false",
+                     (g->Ci % 4 == 0) ? "true" : "false", prec_h(g) ? 2 : 0);
+        } else {
+            const WgradPlan p = wgrad_plan(g);
+            snprintf(out, out_len, "conv_wgrad_kernel<%d, %d, %s, %s, %d>", p.big ? 128 : 64, p.big ? 128 : 64,
+                     (g->Co % 4 == 0) ? "true" : "false", (g->Ci % 4 == 0) ? "true" : "false", prec_h(g) ? 2 : 0);
+        }
     }
     return MG_OK;
 }
 
 size_t mg_conv_fwd_workspace(const mg_conv_geom* g) {
     if (!geom_ok(g)) return 0;
-    if (co1_gemm_ok(g)) return co1_fwd_ws(g);
-    if (h16_ok(g)) return h16_fwd_ws(g);
-    if (wino_ok(g)) return wino_fwd_ws(g);
-    if (wino4_ok(g) && !mg_conv_rowdot_kq(g)) return wino4_fwd_ws(g);
-    if (wino42_ok(g)) return wino42_fwd_ws(g);
+    const ConvRoute r = conv_route(0, g);
+    switch (r) {
+    case R_CO1: return co1_fwd_ws(g);
+    case R_H16: return h16_fwd_ws(g);
+    case R_WINO: case R_WINO4: case R_WINO42: return wino_ws_bytes(r, 0, g);
+    default: break;
+    }
     const TilePlan tp = fwd_plan(g);
     int sp = tp.splits;
-    if (conv_dma_fwd_ok(g) && conv_dma_fwd_plan(g).splits > sp) sp = conv_dma_fwd_plan(g).splits;
-    const size_t stage = (conv_dma_fwd_ok(g) && conv_dma_half(g)) ? conv_dma_h_x_bytes(g) + conv_dma_h_w_bytes(g) : 0;
+    if (r == R_DMA && conv_dma_fwd_plan(g).splits > sp) sp = conv_dma_fwd_plan(g).splits;
+    const size_t stage = (r == R_DMA && conv_dma_half(g)) ? conv_dma_h_x_bytes(g) + conv_dma_h_w_bytes(g) : 0;
     return stage + (sp > 1 ? (size_t)sp * g->B * g->OH * g->OW * g->Co * sizeof(float) + 256 : 256);
 }
 size_t mg_conv_dgrad_workspace(const mg_conv_geom* g) {
     if (!geom_ok(g)) return 0;
-    if (co1_gemm_ok(g)) return co1_dgrad_ws(g);
-    if (h16_ok(g)) return h16_dgrad_ws(g);
-    if (wino_ok(g)) return wino_dgrad_ws(g);
-    if (wino4_ok(g)) return wino4_dgrad_ws(g);
-    if (wino42_ok(g)) return wino42_dgrad_ws(g);
+    const ConvRoute r = conv_route(1, g);
+    switch (r) {
+    case R_CO1: return co1_dgrad_ws(g);
+    case R_H16: return h16_dgrad_ws(g);
+    case R_WINO: case R_WINO4: case R_WINO42: return wino_ws_bytes(r, 1, g);
+    default: break;
+    }
     const TilePlan tp = dgrad_plan(g);
     int sp = tp.splits;
     size_t base = sp > 1 ? (size_t)sp * g->B * g->H * g->W * g->Ci * sizeof(float) + 256 : 256;
-    mg_conv_geom gp;
-    if (conv_dma_dgrad_ok(g)) {
+    if (r == R_DMA) {
         if (cd_dgrad_ws(g) > base) base = cd_dgrad_ws(g);
-    } else if (cd_reflect_dgrad_geom(g, &gp)) {
+    } else if (r == R_DMA_REFLECT) {
+        const mg_conv_geom gp = cd_reflect_geom(g);
         const size_t need = cd_reflect_dxp_bytes(&gp) + cd_dgrad_ws(&gp);
         if (need > base) base = need;
     }
@@ -2659,64 +2105,46 @@ size_t mg_conv_dgrad_workspace(const mg_conv_geom* g) {
 
 size_t mg_conv_wino_weights_bytes(const mg_conv_geom* g) {
     if (!geom_ok(g)) return 0;
-    if (co1_gemm_ok(g)) return (size_t)CO1_TAPS * g->Ci * sizeof(float);      // tap GEMM: the weights zero-padded to 64 tap rows
-    if (mg_conv_rowdot_kq(g)) return 0;
-    if (h16_ok(g)) return h16_weights_bytes(g);         // the float16 weight copy of the autocast GEMM path (conv_h16.h)
-    if (conv_dma_h_any(g)) return h16_weights_bytes(g); // ... and of the float16 implicit GEMMs (conv_dma.h)
-    if (wino4_ok(g)) return (size_t)25 * g->Co * g->Ci * sizeof(float);
-    if (wino42_ok(g)) return (size_t)25 * g->Co * 4 * g->Ci * sizeof(float);
-    if (!wino_ok(g)) return 0;
-    return (size_t)16 * g->Co * g->Ci * sizeof(float);
+    switch (const ConvRoute r = conv_route(0, g)) {
+    case R_CO1: return (size_t)CO1_TAPS * g->Ci * sizeof(float);      // tap GEMM: the weights zero-padded to 64 tap rows
+    case R_H16: return h16_weights_bytes(g);                          // the float16 weight copy of the autocast GEMM path (conv_h16.h)
+    case R_WINO: case R_WINO4: case R_WINO42: {
+        const WinoGeo w = wino_geo(r, g);
+        return (size_t)w.f.P * g->Co * w.Kc * sizeof(float);
+    }
+    default: return conv_dma_h_any(g) ? h16_weights_bytes(g) : 0;     // ... and of the float16 implicit GEMMs (conv_dma.h)
+    }
 }
 int mg_conv_wino_prepare(const mg_conv_geom* g, const float* w, float* u, void* stream) {
     if (!mg_conv_wino_weights_bytes(g) || !w || !u || !aligned16(w) || !aligned16(u)) return MG_ERR_ARG;
-    if (co1_gemm_ok(g)) {
-        co1_pad_w(g, w, u, (hipStream_t)stream);
-        MG_CHECK_LAUNCH();
-        return MG_OK;
+    switch (const ConvRoute r = conv_route(0, g)) {
+    case R_CO1: co1_pad_w(g, w, u, (hipStream_t)stream); break;
+    case R_WINO: case R_WINO4: case R_WINO42: wino_xform_u(wino_geo(r, g), g, w, u, (hipStream_t)stream); break;
+    default: return h16_prepare(g, w, u, (hipStream_t)stream);
     }
-    if (h16_ok(g) || conv_dma_h_any(g)) return h16_prepare(g, w, u, (hipStream_t)stream);
-    if (wino4_ok(g)) {
-        hipLaunchKernelGGL(wino4_weight_xform_kernel, dim3(wino_grid((size_t)g->Co * g->Ci / 2)), dim3(256), 0,
-                           (hipStream_t)stream, w, g->Co, g->Ci, u);
-        MG_CHECK_LAUNCH();
-        return MG_OK;
-    }
-    if (wino42_ok(g)) {
-        hipLaunchKernelGGL(wino42_weight_xform_kernel, dim3(wino_grid((size_t)g->Co * 4 * g->Ci / 2)), dim3(256), 0,
-                           (hipStream_t)stream, w, g->Co, g->Ci, u);
-        MG_CHECK_LAUNCH();
-        return MG_OK;
-    }
-    hipLaunchKernelGGL(wino_weight_xform_kernel, dim3(wino_grid((size_t)g->Co * g->Ci / 4)), dim3(256), 0,
-                       (hipStream_t)stream, w, g->Co, g->Ci, u);
     MG_CHECK_LAUNCH();
     return MG_OK;
 }
 
 size_t mg_conv_wino_tiles_bytes(const mg_conv_geom* g, int which) {
-    if (!mg_conv_wino_weights_bytes(g) || h16_ok(g)) return 0;
-    if (co1_gemm_ok(g)) return which == 1 ? co1_zt_bytes(g) : (which == 0 ? co1_xr_bytes(g) : 0);   // Gt (data gradient -> weight gradient); autocast: the rounded x
-    if (conv_dma_h_any(g)) {
+    if (!mg_conv_wino_weights_bytes(g)) return 0;
+    switch (const ConvRoute r = conv_route(0, g)) {
+    case R_H16: return 0;
+    case R_CO1: return which == 1 ? co1_zt_bytes(g) : (which == 0 ? co1_xr_bytes(g) : 0);   // Gt (data gradient -> weight gradient); autocast: the rounded x
+    case R_WINO: case R_WINO4: case R_WINO42: {
+        const WinoGeo w = wino_geo(r, g);
+        return which == 0 ? (size_t)w.f.P * w.T * w.Kc * sizeof(float) : which == 1 ? (size_t)w.f.P * w.T * g->Co * sizeof(float) : 0;
+    }
+    default: {
         // float16 implicit GEMMs: the "tiles" are the float16 copies of x (forward -> weight gradient) and of dy (data
         // gradient -> weight gradient), so that each tensor is cast once per step
-        if (!conv_dma_wgrad_ok(g)) return 0;
-        if (which == 0) return conv_dma_fwd_ok(g) ? conv_dma_h_x_bytes(g) : 0;
-        if (which == 1) return cd_dgrad_any(g) ? conv_dma_h_dy_bytes(g) : 0;
+        const ConvRoute d = conv_route(1, g);
+        if (conv_route(2, g) != R_DMA) return 0;
+        if (which == 0) return r == R_DMA ? conv_dma_h_x_bytes(g) : 0;
+        if (which == 1) return (d == R_DMA || d == R_DMA_REFLECT) ? conv_dma_h_dy_bytes(g) : 0;
         return 0;
     }
-    if (wino4_ok(g)) {
-        const Wino4Dims d4 = wino4_dims(g);
-        return which == 0 ? (size_t)25 * d4.T * g->Ci * sizeof(float) : which == 1 ? (size_t)25 * d4.T * g->Co * sizeof(float) : 0;
     }
-    if (wino42_ok(g)) {
-        const Wino42Dims d2 = wino42_dims(g);
-        return which == 0 ? (size_t)25 * d2.T * d2.K4 * sizeof(float) : which == 1 ? (size_t)25 * d2.T * g->Co * sizeof(float) : 0;
-    }
-    const WinoDims d = wino_dims(g);
-    if (which == 0) return (size_t)16 * d.T * g->Ci * sizeof(float);
-    if (which == 1) return (size_t)16 * d.T * g->Co * sizeof(float);
-    return 0;
 }
 static bool wino_tiles_ok(const mg_conv_geom* g, const mg_wino_tiles* t) {
     if (!t || (!t->u && !t->v && !t->md)) return true;
@@ -2737,17 +2165,19 @@ int mg_conv_wgrad(const mg_conv_geom* g, const float* x, const float* dy, float*
     return mg_conv_wgrad_w(g, x, dy, dw, dbias, accumulate, workspace, workspace_bytes, stream, nullptr);
 }
 
-int mg_conv_wino_md_from_norm_ok(const mg_conv_geom* g) {
-    return (geom_ok(g) && wino_ok(g) && !prec_h(g) && !mg_conv_rowdot_kq(g) &&
-            wino_out_norm_ok(g->OH / 2, g->OW / 2, g->Co)) ? 1 : 0;
+// The F(2x2,3x3) output transform + InstanceNorm kernel (wino.h: wino_out_norm_kernel) and its backward: float32, maps of
+// <= 160 tiles per sample
+static bool wino_norm_ok(const mg_conv_geom* g) {
+    return geom_ok(g) && conv_route(0, g) == R_WINO && !prec_h(g) && wino_out_norm_ok(g->OH / 2, g->OW / 2, g->Co);
 }
+int mg_conv_wino_md_from_norm_ok(const mg_conv_geom* g) { return wino_norm_ok(g) ? 1 : 0; }
 int mg_instnorm_bwd_wino_md(const mg_conv_geom* g, const float* gy, const float* y_raw, const float* mean, const float* rstd,
                             int act, float* md, void* stream) {
     if (!gy || !y_raw || !mean || !rstd || !md) return MG_ERR_ARG;
     if (!mg_conv_wino_md_from_norm_ok(g)) return MG_ERR_UNSUPPORTED;
     if (act != MG_ACT_NONE && act != MG_ACT_RELU && act != MG_ACT_LRELU02) return MG_ERR_UNSUPPORTED;   // the only derivatives wino_norm_bwd_dy_kernel has
     if (!aligned16(gy) || !aligned16(y_raw) || !aligned16(mean) || !aligned16(rstd) || !aligned16(md)) return MG_ERR_ARG;
-    const WinoDims d = wino_dims(g);
+    const WinoGeo d = wino_geo(R_WINO, g);
     const dim3 grid(g->Co / 32, g->B);
     const int nt = (d.TH * d.TW + 31) / 32;
     hipStream_t st = (hipStream_t)stream;
@@ -2768,10 +2198,9 @@ int mg_conv_fwd_instnorm_w(const mg_conv_geom* g, const float* x, const float* w
     return mg_conv_fwd_instnorm_h(g, x, w, bias, y_raw, eps, act, residual, y, mean, rstd, workspace, workspace_bytes, stream, wt, nullptr);
 }
 // The fused F(2x2,3x3) output transform + InstanceNorm kernel can also write the NEXT 3x3 stride-1 pad-1 layer's input image
-// (wino.h: wino_out_norm_kernel<NT, true>): float32, maps of <= 64 tiles per sample.
+// (wino.h: wino_out_norm_kernel<NT, true>): maps of <= 64 tiles per sample.
 static bool wino_vnext_ok(const mg_conv_geom* g) {
-    return geom_ok(g) && wino_ok(g) && !prec_h(g) && !mg_conv_rowdot_kq(g) && wino_out_norm_ok(g->OH / 2, g->OW / 2, g->Co) &&
-           wino_out_norm_next_ok(g->OH / 2, g->OW / 2, g->Co) && g->Co % 16 == 0;
+    return wino_norm_ok(g) && wino_out_norm_next_ok(g->OH / 2, g->OW / 2, g->Co) && g->Co % 16 == 0;
 }
 int mg_conv_wino_vnext_ok(const mg_conv_geom* g) { return g && wino_vnext_ok(g) ? 1 : 0; }
 
@@ -2779,6 +2208,8 @@ static int conv_fwd_instnorm_impl(const mg_conv_geom* g, const float* x, const f
                                   int act, const float* residual, float* y, float* mean, float* rstd, void* workspace,
                                   size_t workspace_bytes, void* stream, const mg_wino_tiles* wt, void* y16, float* v_next,
                                   int next_reflect);
+static int conv_fwd(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int act, void* workspace,
+                    size_t workspace_bytes, void* stream, const mg_wino_tiles* wt, FwdDefer* defer);
 
 int mg_conv_fwd_instnorm_next(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y_raw, float eps,
                               int act, const float* residual, float* y, float* mean, float* rstd, void* workspace,
@@ -2805,12 +2236,11 @@ static int conv_fwd_instnorm_impl(const mg_conv_geom* g, const float* x, const f
     if (!workspace || workspace_bytes < mg_conv_fwd_instnorm_workspace(g)) return MG_ERR_ARG;
     // y_raw == NULL (inference: no backward pass will read the raw convolution output): the fused kernel skips that store -- a
     // fifth of its HBM bytes at batch 64 -- and the two-call path normalises in place
-    if (wino_ok(g) && !prec_h(g) && !mg_conv_rowdot_kq(g) && wino_out_norm_ok(g->OH / 2, g->OW / 2, g->Co) && aligned16(x) &&
-        aligned16(w) && (!y_raw || aligned16(y_raw)) && aligned16(y) && aligned16(mean) && aligned16(rstd) && aligned16(workspace) &&
-        (!bias || aligned16(bias)) && (!residual || aligned16(residual))) {
+    if (wino_norm_ok(g) && aligned16(x) && aligned16(w) && (!y_raw || aligned16(y_raw)) && aligned16(y) && aligned16(mean) &&
+        aligned16(rstd) && aligned16(workspace) && (!bias || aligned16(bias)) && (!residual || aligned16(residual))) {
         const WinoNorm nrm{eps, act, residual, y, mean, rstd, v_next, next_reflect};
-        return wino_fwd(g, x, w, bias, y_raw, MG_ACT_NONE, (float*)workspace, (hipStream_t)stream, wt ? wt->u : nullptr,
-                        wt ? wt->v : nullptr, &nrm, wt && wt->v && (wt->flags & MG_TILES_V_FILLED));
+        return wino_fwd(wino_geo(R_WINO, g), g, x, w, bias, y_raw, MG_ACT_NONE, (float*)workspace, (hipStream_t)stream,
+                        wt ? wt->u : nullptr, wt ? wt->v : nullptr, wt && wt->v && (wt->flags & MG_TILES_V_FILLED), &nrm);
     }
     if (v_next) return MG_ERR_ARG;           // (unreachable after wino_vnext_ok: the fused path above is the only writer of v_next)
     float* const raw_out = y_raw;            // NULL under no_grad: the slab kernel then skips that store, the two-launch path normalises in place
@@ -2819,9 +2249,7 @@ static int conv_fwd_instnorm_impl(const mg_conv_geom* g, const float* x, const f
     FwdDefer defer{nullptr, 0, nullptr, 0, false};
     const bool no_defer = getenv("MG_NO_FWD_DEFER") != nullptr;      // (read per call: the bit-identity test flips it)
     const bool can_defer = !no_defer && mg_instnorm_slab_ok(g->OH * g->OW, g->Co) && g->Co % 4 == 0 && (!bias || aligned16(bias));
-    g_fwd_defer = can_defer ? &defer : nullptr;
-    const int rc = mg_conv_fwd_w(g, x, w, bias, y_raw, MG_ACT_NONE, workspace, workspace_bytes, stream, wt);
-    g_fwd_defer = nullptr;
+    const int rc = conv_fwd(g, x, w, bias, y_raw, MG_ACT_NONE, workspace, workspace_bytes, stream, wt, can_defer ? &defer : nullptr);
     if (rc != MG_OK) return rc;
     if (defer.filled)
         return mg_instnorm_fwd_slabs(defer.part, defer.splits, defer.bias, defer.round_f16, raw_out, g->B, g->OH * g->OW, g->Co, eps, act,
@@ -2831,43 +2259,51 @@ static int conv_fwd_instnorm_impl(const mg_conv_geom* g, const float* x, const f
 
 int mg_conv_fwd_w(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int act,
                   void* workspace, size_t workspace_bytes, void* stream, const mg_wino_tiles* wt) {
+    return conv_fwd(g, x, w, bias, y, act, workspace, workspace_bytes, stream, wt, nullptr);
+}
+// defer (nullable): the caller's InstanceNorm sums the split-K slabs of a DMA / h16 forward pass (FwdDefer)
+static int conv_fwd(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int act, void* workspace,
+                    size_t workspace_bytes, void* stream, const mg_wino_tiles* wt, FwdDefer* defer) {
     if (!geom_ok(g) || !x || !w || !y) return MG_ERR_ARG;
     if (!wino_tiles_ok(g, wt)) return MG_ERR_ARG;
     const float* u = wt ? wt->u : nullptr;
-    if (h16_ok(g) && workspace && workspace_bytes >= h16_fwd_ws(g) && aligned16(x) && aligned16(w) && aligned16(y) &&
-        aligned16(workspace) && (!bias || aligned16(bias)))
-        return h16_fwd(g, x, w, bias, y, act, (char*)workspace, (hipStream_t)stream, u,
-                       (wt && wt->v && (wt->flags & MG_TILES_V_FILLED)) ? (const void*)wt->v : nullptr);
-    if (co1_gemm_ok(g) && workspace && workspace_bytes >= co1_fwd_ws(g) && aligned16(x) && aligned16(w) && aligned16(workspace))
-        return co1_fwd(g, x, w, bias, y, act, (char*)workspace, (hipStream_t)stream, u, wt ? wt->v : nullptr);
-    if (mg_conv_rowdot_kq(g) && aligned16(x) && aligned16(w)) {
-        probe_begin((hipStream_t)stream);
-        const int rc = mg_conv_rowdot_fwd(g, x, w, bias, y, act, stream);
-        probe_end((hipStream_t)stream);
+    float* v = wt ? wt->v : nullptr;
+    const bool v_filled = v && (wt->flags & MG_TILES_V_FILLED);
+    hipStream_t st = (hipStream_t)stream;
+    const bool al = workspace && aligned16(x) && aligned16(w) && aligned16(y) && aligned16(workspace) && (!bias || aligned16(bias));
+    switch (const ConvRoute r = conv_route(0, g)) {
+    case R_H16:
+        if (al && workspace_bytes >= h16_fwd_ws(g)) return h16_fwd(g, x, w, bias, y, act, (char*)workspace, st, u, v_filled ? v : nullptr, defer);
+        break;
+    case R_CO1:
+        if (workspace && workspace_bytes >= co1_fwd_ws(g) && aligned16(x) && aligned16(w) && aligned16(workspace))
+            return co1_fwd(g, x, w, bias, y, act, (char*)workspace, st, u, v);
+        [[fallthrough]];
+    case R_ROWDOT:
+        if (mg_conv_rowdot_kq(g) && aligned16(x) && aligned16(w)) {
+            probe_begin(st);
+            const int rc = mg_conv_rowdot_fwd(g, x, w, bias, y, act, stream);
+            probe_end(st);
+            return rc;
+        }
+        break;
+    case R_WINO: case R_WINO4: case R_WINO42:
+        if (al && workspace_bytes >= wino_ws_bytes(r, 0, g))
+            return wino_fwd(wino_geo(r, g), g, x, w, bias, y, act, (float*)workspace, st, u, v, r == R_WINO && !prec_h(g) && v_filled);
+        break;
+    case R_SMALLC: {
+        probe_begin(st);
+        const int rc = smallc_fwd(g, x, w, bias, y, act, st);
+        probe_end(st);
         return rc;
     }
-    if (wino_ok(g) && workspace && workspace_bytes >= wino_fwd_ws(g) && aligned16(x) && aligned16(w) && aligned16(y) &&
-        aligned16(workspace) && (!bias || aligned16(bias)))
-        return wino_fwd(g, x, w, bias, y, act, (float*)workspace, (hipStream_t)stream, u, wt ? wt->v : nullptr, nullptr,
-                        wt && wt->v && !prec_h(g) && (wt->flags & MG_TILES_V_FILLED));
-    if (wino4_ok(g) && workspace && workspace_bytes >= wino4_fwd_ws(g) && aligned16(x) && aligned16(w) && aligned16(y) &&
-        aligned16(workspace) && (!bias || aligned16(bias)))
-        return wino4_fwd(g, x, w, bias, y, act, (float*)workspace, (hipStream_t)stream, u, wt ? wt->v : nullptr);
-    if (wino42_ok(g) && workspace && workspace_bytes >= wino42_fwd_ws(g) && aligned16(x) && aligned16(w) && aligned16(y) &&
-        aligned16(workspace) && (!bias || aligned16(bias)))
-        return wino42_fwd(g, x, w, bias, y, act, (float*)workspace, (hipStream_t)stream, u, wt ? wt->v : nullptr);
-    if (smallc_fwd_kind(g)) {
-        probe_begin((hipStream_t)stream);
-        const int rc = smallc_fwd(g, x, w, bias, y, act, (hipStream_t)stream);
-        probe_end((hipStream_t)stream);
-        return rc;
+    default: break;
     }
     const Geom gg = to_geom(g);
-    hipStream_t st = (hipStream_t)stream;
     const long long M = (long long)g->B * g->OH * g->OW;
     const int N = g->Co;
     const bool cd_half = conv_dma_half(g);
-    if (conv_dma_fwd_ok(g) && aligned16(x) && aligned16(w) && aligned16(y) && (!bias || aligned16(bias)) &&
+    if (conv_route(0, g, true) == R_DMA && aligned16(x) && aligned16(w) && aligned16(y) && (!bias || aligned16(bias)) &&
         (!cd_half || (workspace && aligned16(workspace) && workspace_bytes >= mg_conv_fwd_workspace(g)))) {
         CdPlan cp = conv_dma_fwd_plan(g);
         if (cp.splits > 1 && (!workspace || workspace_bytes < mg_conv_fwd_workspace(g) || !aligned16(workspace))) {
@@ -2898,8 +2334,8 @@ int mg_conv_fwd_w(const mg_conv_geom* g, const float* x, const float* w, const f
         MG_CHECK_LAUNCH();
         if (cp.splits > 1) {
             const size_t n = (size_t)M * N;
-            if (g_fwd_defer && act == MG_ACT_NONE) {
-                *g_fwd_defer = FwdDefer{(const float*)wsp, cp.splits, bias, cd_half ? 1 : 0, true};
+            if (defer && act == MG_ACT_NONE) {
+                *defer = FwdDefer{(const float*)wsp, cp.splits, bias, cd_half ? 1 : 0, true};
                 return MG_OK;
             }
             const unsigned blocks = (unsigned)((n / 4 + 255) / 256 > 4096 ? 4096 : (n / 4 + 255) / 256);
@@ -2948,69 +2384,71 @@ int mg_conv_fwd_w(const mg_conv_geom* g, const float* x, const float* w, const f
     return MG_OK;
 }
 
-static int dgrad_dispatch(const mg_conv_geom* g, const float* dy, const float* w, const float* bias, float* dx, int act,
-                          void* workspace, size_t workspace_bytes, void* stream, const mg_wino_tiles* wt);
+static int conv_dgrad(const mg_conv_geom* g, const float* dy, const float* w, const float* bias, float* dx, int act,
+                      void* workspace, size_t workspace_bytes, void* stream, const mg_wino_tiles* wt, const float** addend);
 int mg_conv_dgrad_w(const mg_conv_geom* g, const float* dy, const float* w, const float* bias, float* dx, int act,
                     void* workspace, size_t workspace_bytes, void* stream, const mg_wino_tiles* wt) {
     if (wt && wt->add && !aligned16(wt->add)) return MG_ERR_ARG;
-    g_dgrad_add = wt ? wt->add : nullptr;
-    int rc = dgrad_dispatch(g, dy, w, bias, dx, act, workspace, workspace_bytes, stream, wt);
-    const float* left = g_dgrad_add;
-    g_dgrad_add = nullptr;
+    const float* left = wt ? wt->add : nullptr;       // a path that can fold "dx += add" into its last kernel takes it
+    int rc = conv_dgrad(g, dy, w, bias, dx, act, workspace, workspace_bytes, stream, wt, &left);
     if (rc == MG_OK && left) rc = mg_add(dx, left, dx, (long long)g->B * g->H * g->W * g->Ci, stream);
     return rc;
 }
-static int dgrad_dispatch(const mg_conv_geom* g, const float* dy, const float* w, const float* bias, float* dx, int act,
-                          void* workspace, size_t workspace_bytes, void* stream, const mg_wino_tiles* wt) {
+// addend (in / out): mg_wino_tiles.add, cleared by the path that adds it
+static int conv_dgrad(const mg_conv_geom* g, const float* dy, const float* w, const float* bias, float* dx, int act,
+                      void* workspace, size_t workspace_bytes, void* stream, const mg_wino_tiles* wt, const float** addend) {
     if (!geom_ok(g) || !w || !dx) return MG_ERR_ARG;
     if (!wino_tiles_ok(g, wt)) return MG_ERR_ARG;
     // dy == NULL: wt->md already holds A dy A^T (mg_instnorm_bwd_wino_md) -- F(2x2,3x3) layers in the transposed formulation
     if (!dy && !(wt && wt->md && mg_conv_wino_md_from_norm_ok(g) && !bias && act == MG_ACT_NONE && workspace &&
-                 workspace_bytes >= wino_dgrad_ws(g) && aligned16(w) && aligned16(dx) && aligned16(workspace)))
+                 workspace_bytes >= mg_conv_dgrad_workspace(g) && aligned16(w) && aligned16(dx) && aligned16(workspace)))
         return MG_ERR_ARG;
     const float* u = wt ? wt->u : nullptr;
-    if (g->reflect && g->stride != 1) return MG_ERR_UNSUPPORTED;
-    if (h16_ok(g) && !bias && act == MG_ACT_NONE && workspace && workspace_bytes >= h16_dgrad_ws(g) && aligned16(dy) &&
-        aligned16(w) && aligned16(dx) && aligned16(workspace))
-        return h16_dgrad(g, dy, w, dx, (char*)workspace, (hipStream_t)stream, u, &g_dgrad_add);
-    if (co1_gemm_ok(g) && !bias && act == MG_ACT_NONE && workspace && workspace_bytes >= co1_dgrad_ws(g) && aligned16(w) &&
-        aligned16(dx) && aligned16(workspace))
-        return co1_dgrad(g, dy, w, dx, (char*)workspace, (hipStream_t)stream, u, wt ? wt->md : nullptr);
-    if (smallc_dgrad_ok(g) && !bias && act == MG_ACT_NONE && aligned16(dy)) {
-        probe_begin((hipStream_t)stream);
-        const int rc = smallc_dgrad(g, dy, w, dx, (hipStream_t)stream);
-        probe_end((hipStream_t)stream);
-        return rc;
-    }
-    if (wino_ok(g) && workspace &&
-        workspace_bytes >= wino_dgrad_ws(g) &&
-        aligned16(dy) && aligned16(w) && aligned16(dx) && aligned16(workspace) && (!bias || aligned16(bias)))
-        return wino_dgrad(g, dy, w, bias, dx, act, (float*)workspace, (hipStream_t)stream, u, wt ? wt->md : nullptr);
-    if (wino4_ok(g) && !bias && act == MG_ACT_NONE && workspace && workspace_bytes >= wino4_dgrad_ws(g) && aligned16(dy) &&
-        aligned16(w) && aligned16(dx) && aligned16(workspace))
-        return wino4_dgrad(g, dy, w, dx, (float*)workspace, (hipStream_t)stream, u, wt ? wt->md : nullptr);
-    if (wino42_ok(g) && !bias && act == MG_ACT_NONE && workspace && workspace_bytes >= wino42_dgrad_ws(g) && aligned16(dy) &&
-        aligned16(w) && aligned16(dx) && aligned16(workspace))
-        return wino42_dgrad(g, dy, w, dx, (float*)workspace, (hipStream_t)stream, u, wt ? wt->md : nullptr);
-    const Geom gg = to_geom(g);
+    float* md = wt ? wt->md : nullptr;
     hipStream_t st = (hipStream_t)stream;
+    if (g->reflect && g->stride != 1) return MG_ERR_UNSUPPORTED;
+    const bool plain = !bias && act == MG_ACT_NONE;       // all but the F(2x2,3x3) and generic data gradients need it
+    const bool al = workspace && aligned16(dy) && aligned16(w) && aligned16(dx) && aligned16(workspace);
+    switch (const ConvRoute r = conv_route(1, g)) {
+    case R_H16:
+        if (plain && al && workspace_bytes >= h16_dgrad_ws(g)) return h16_dgrad(g, dy, w, dx, (char*)workspace, st, u, addend);
+        break;
+    case R_CO1:
+        if (plain && workspace && workspace_bytes >= co1_dgrad_ws(g) && aligned16(w) && aligned16(dx) && aligned16(workspace))
+            return co1_dgrad(g, dy, w, dx, (char*)workspace, st, u, md);
+        break;
+    case R_SMALLC:
+        if (plain && aligned16(dy)) {
+            probe_begin(st);
+            const int rc = smallc_dgrad(g, dy, w, dx, st);
+            probe_end(st);
+            return rc;
+        }
+        break;
+    case R_WINO: case R_WINO4: case R_WINO42:
+        if ((r == R_WINO ? !bias || aligned16(bias) : plain) && al && workspace_bytes >= wino_ws_bytes(r, 1, g))
+            return wino_dgrad(wino_geo(r, g), g, dy, w, bias, dx, act, (float*)workspace, st, u, md, addend);
+        break;
+    default: break;
+    }
+    const Geom gg = to_geom(g);
     const int s = g->stride;
     if (aligned16(dy) && aligned16(w) && aligned16(dx) && (!bias || aligned16(bias)) && workspace && aligned16(workspace) &&
         workspace_bytes >= mg_conv_dgrad_workspace(g)) {
-        float* md = wt ? wt->md : nullptr;
-        if (conv_dma_dgrad_ok(g))
+        const ConvRoute r = conv_route(1, g, true);
+        if (r == R_DMA)
             return cd_dgrad_run(g, dy, w, bias, dx, act, (char*)workspace, st, u, md, conv_dma_half(g) ? 1 : 0,
                                 (wt && (wt->flags & MG_TILES_MD_FILLED)) ? 1 : 0);
-        mg_conv_geom gp;
-        if (!bias && act == MG_ACT_NONE && cd_reflect_dgrad_geom(g, &gp)) {
+        if (r == R_DMA_REFLECT && plain) {
+            const mg_conv_geom gp = cd_reflect_geom(g);
             float* dxp = (float*)workspace;
             const int rc = cd_dgrad_run(&gp, dy, w, nullptr, dxp, MG_ACT_NONE, (char*)workspace + cd_reflect_dxp_bytes(&gp), st, u,
                                         md, 0, (wt && (wt->flags & MG_TILES_MD_FILLED)) ? 1 : 0);
             if (rc != MG_OK) return rc;
-            const float* addend = g_dgrad_add;      // the skip connection's gradient rides in the fold (mg_wino_tiles.add)
-            g_dgrad_add = nullptr;
+            const float* add = *addend;      // the skip connection's gradient rides in the fold (mg_wino_tiles.add)
+            *addend = nullptr;
             hipLaunchKernelGGL(wino_fold_reflect_kernel, dim3(wino_grid((size_t)g->B * g->H * g->W * g->Ci / 4)), dim3(256), 0,
-                               st, (const float*)dxp, g->B, g->H, g->W, g->Ci, dx, (int)prec_h(g), addend);
+                               st, (const float*)dxp, g->B, g->H, g->W, g->Ci, dx, (int)prec_h(g), add);
             MG_CHECK_LAUNCH();
             return MG_OK;
         }
@@ -3085,24 +2523,26 @@ int mg_colsum(const float* a, long long M, int C, float* out, int accumulate, vo
 
 size_t mg_conv_wgrad_workspace(const mg_conv_geom* g) {
     if (!geom_ok(g)) return 0;
-    if (co1_gemm_ok(g)) return co1_wgrad_ws(g);
-    if (mg_conv_rowdot_kq(g)) return mg_conv_rowdot_wgrad_workspace(g);
-    if (h16_ok(g)) return h16_wgrad_ws(g);
-    if (wino_ok(g)) return wino_wgrad_ws(g);
-    if (wino4_ok(g)) return wino4_wgrad_ws(g);
-    if (wino42_ok(g)) return wino42_wgrad_ws(g);
-    if (smallc_wgrad_kind(g)) return smallc_wgrad_ws(g);
+    const ConvRoute r = conv_route(2, g);
+    switch (r) {
+    case R_CO1: return co1_wgrad_ws(g);
+    case R_ROWDOT: return mg_conv_rowdot_wgrad_workspace(g);
+    case R_H16: return h16_wgrad_ws(g);
+    case R_WINO: case R_WINO4: case R_WINO42: return wino_ws_bytes(r, 2, g);
+    case R_SMALLC: return smallc_wgrad_ws(g);
+    default: break;
+    }
     const WgradPlan p = wgrad_plan(g);
     int sp = p.splits;
-    if (conv_dma_wgrad_ok(g) && conv_dma_wgrad_plan(g).splits > sp) sp = conv_dma_wgrad_plan(g).splits;
+    if (r == R_DMA && conv_dma_wgrad_plan(g).splits > sp) sp = conv_dma_wgrad_plan(g).splits;
     size_t wg = sp > 1 ? (size_t)sp * g->Co * g->KH * g->KW * g->Ci * sizeof(float) : 0;
-    if (conv_dma_wgrad_ok(g) && conv_dma_half(g)) wg += conv_dma_h_x_bytes(g) + conv_dma_h_dy_bytes(g);
+    if (r == R_DMA && conv_dma_half(g)) wg += conv_dma_h_x_bytes(g) + conv_dma_h_dy_bytes(g);
     const size_t cs = mg_colsum_workspace((long long)g->B * g->OH * g->OW, g->Co);
     return (wg > cs ? wg : cs) + 256;
 }
 
 int mg_conv_wgrad_adam_ok(const mg_conv_geom* g) {
-    return (geom_ok(g) && !co1_gemm_ok(g) && !mg_conv_rowdot_kq(g) && !h16_ok(g) && wino_ok(g) && !prec_h(g) && g->Ci % 4 == 0) ? 1 : 0;
+    return (geom_ok(g) && conv_route(2, g) == R_WINO && !prec_h(g) && g->Ci % 4 == 0) ? 1 : 0;
 }
 int mg_conv_wgrad_adam_w(const mg_conv_geom* g, const float* x, const float* dy, float* w, const mg_wino_adam* ad,
                          void* workspace, size_t workspace_bytes, void* stream, const mg_wino_tiles* wt) {
@@ -3113,7 +2553,8 @@ int mg_conv_wgrad_adam_w(const mg_conv_geom* g, const float* x, const float* dy,
     if (!aligned16(w) || !aligned16(ad->m) || !aligned16(ad->v) || !aligned16(ad->u) || !aligned16(workspace) ||
         (x && !aligned16(x)) || (dy && !aligned16(dy)))
         return MG_ERR_ARG;
-    return wino_wgrad(g, x, dy, w, 0, (float*)workspace, (hipStream_t)stream, wt ? wt->v : nullptr, wt ? wt->md : nullptr, ad);
+    return wino_wgrad(wino_geo(R_WINO, g), g, x, dy, w, nullptr, 0, (float*)workspace, (hipStream_t)stream, wt ? wt->v : nullptr,
+                      wt ? wt->md : nullptr, ad);
 }
 
 int mg_conv_wgrad_w(const mg_conv_geom* g, const float* x, const float* dy, float* dw, float* dbias, int accumulate,
@@ -3121,7 +2562,7 @@ int mg_conv_wgrad_w(const mg_conv_geom* g, const float* x, const float* dy, floa
     return mg_conv_wgrad_chk(g, x, dy, dw, dbias, accumulate, workspace, workspace_bytes, stream, wt, nullptr);
 }
 int mg_conv_wgrad_checks_finite(const mg_conv_geom* g) {
-    return (geom_ok(g) && !co1_gemm_ok(g) && !mg_conv_rowdot_kq(g) && h16_ok(g) && h16_wgrad_as(g)) ? 1 : 0;
+    return (geom_ok(g) && conv_route(2, g) == R_H16 && h16_wgrad_as(g)) ? 1 : 0;
 }
 int mg_conv_wgrad_h16_ok(const mg_conv_geom* g) { return mg_conv_wgrad_checks_finite(g); }
 int mg_conv_wgrad_h16(const mg_conv_geom* g, const float* x, const float* dy, void* dw16, int accumulate, void* workspace,
@@ -3142,79 +2583,49 @@ int mg_conv_wgrad_chk(const mg_conv_geom* g, const float* x, const float* dy, fl
     if ((!x || !dy) && !(wt && wt->v && wt->md && mg_conv_wino_md_from_norm_ok(g) && !dbias && aligned16(dw) && aligned16(workspace)))
         return MG_ERR_ARG;
     if (workspace_bytes < mg_conv_wgrad_workspace(g) || !workspace) return MG_ERR_ARG;
-    if (co1_gemm_ok(g) && aligned16(x) && aligned16(workspace))
-        return co1_wgrad(g, x, dy, dw, dbias, accumulate, (char*)workspace, (hipStream_t)stream, wt ? wt->v : nullptr, wt ? wt->md : nullptr);
-    if (mg_conv_rowdot_kq(g) && aligned16(x) && aligned16(workspace)) {
-        probe_begin((hipStream_t)stream);
-        const int rc = mg_conv_rowdot_wgrad(g, x, dy, dw, dbias, accumulate, workspace, workspace_bytes, stream);
-        probe_end((hipStream_t)stream);
-        return rc;
-    }
-    if (h16_ok(g) && aligned16(x) && aligned16(dy) && aligned16(dw) && aligned16(workspace)) {
-        const int rc = h16_wgrad(g, x, dy, dw, accumulate, (char*)workspace, (hipStream_t)stream, found_inf);
-        if (rc != MG_OK) return rc;
-        if (dbias)
-            return mg_colsum(dy, (long long)g->B * g->OH * g->OW, g->Co, dbias, accumulate, (char*)workspace + h16_wgrad_cs_offset(g),
-                             mg_colsum_workspace((long long)g->B * g->OH * g->OW, g->Co), stream);
-        return MG_OK;
-    }
-    if (wino_ok(g) && aligned16(x) && aligned16(dy) && aligned16(dw) && aligned16(workspace)) {
-        const int rc = wino_wgrad(g, x, dy, dw, accumulate, (float*)workspace, (hipStream_t)stream, wt ? wt->v : nullptr,
-                                  wt ? wt->md : nullptr);
-        if (rc != MG_OK) return rc;
-        if (dbias) {
-            const WinoDims d = wino_dims(g);
-            float* cs = (float*)workspace + al256((size_t)16 * d.T * g->Ci) + al256((size_t)16 * d.T * g->Co) +
-                        al256((size_t)16 * g->Co * g->Ci) +
-                        al256(wino_wgrad_slabs(g) * 16 * g->Co * g->Ci);
-            return mg_colsum(dy, (long long)g->B * g->OH * g->OW, g->Co, dbias, accumulate, cs,
-                             mg_colsum_workspace((long long)g->B * g->OH * g->OW, g->Co), stream);
+    hipStream_t st = (hipStream_t)stream;
+    const long long M = (long long)g->B * g->OH * g->OW;
+    const bool al = aligned16(x) && aligned16(dy) && aligned16(dw) && aligned16(workspace);
+    switch (const ConvRoute r = conv_route(2, g)) {
+    case R_CO1:
+        if (aligned16(x) && aligned16(workspace))
+            return co1_wgrad(g, x, dy, dw, dbias, accumulate, (char*)workspace, st, wt ? wt->v : nullptr, wt ? wt->md : nullptr);
+        [[fallthrough]];
+    case R_ROWDOT:
+        if (mg_conv_rowdot_kq(g) && aligned16(x) && aligned16(workspace)) {
+            probe_begin(st);
+            const int rc = mg_conv_rowdot_wgrad(g, x, dy, dw, dbias, accumulate, workspace, workspace_bytes, stream);
+            probe_end(st);
+            return rc;
         }
-        return MG_OK;
-    }
-    if (smallc_wgrad_kind(g) && aligned16(dw) && aligned16(workspace)) {
-        probe_begin((hipStream_t)stream);
-        const int rc = smallc_wgrad(g, x, dy, dw, accumulate, (float*)workspace, (hipStream_t)stream);
-        probe_end((hipStream_t)stream);
-        if (rc != MG_OK) return rc;
-        if (dbias) {
-            float* cs = (float*)workspace + smallc_wgrad_layout(g).cs;
-            return mg_colsum(dy, (long long)g->B * g->OH * g->OW, g->Co, dbias, accumulate, cs,
-                             mg_colsum_workspace((long long)g->B * g->OH * g->OW, g->Co), stream);
+        break;
+    case R_H16:
+        if (al) {
+            const int rc = h16_wgrad(g, x, dy, dw, accumulate, (char*)workspace, st, found_inf);
+            if (rc != MG_OK || !dbias) return rc;
+            return mg_colsum(dy, M, g->Co, dbias, accumulate, (char*)workspace + h16_wgrad_cs_offset(g), mg_colsum_workspace(M, g->Co),
+                             stream);
         }
-        return MG_OK;
-    }
-    if (wino4_ok(g) && aligned16(x) && aligned16(dy) && aligned16(dw) && aligned16(workspace)) {
-        const int rc = wino4_wgrad(g, x, dy, dw, accumulate, (float*)workspace, (hipStream_t)stream, wt ? wt->v : nullptr,
-                                   wt ? wt->md : nullptr);
-        if (rc != MG_OK) return rc;
-        if (dbias) {
-            const Wino4Dims d = wino4_dims(g);
-            const WinoWgradPlan p4 = wino4_wgrad_plan(g);
-            float* cs = (float*)workspace + al256((size_t)25 * d.T * g->Ci) + al256((size_t)25 * d.T * g->Co) +
-                        al256((size_t)25 * g->Co * g->Ci) + al256(wino4_wgrad_slabs(g) * 25 * g->Co * g->Ci);
-            return mg_colsum(dy, (long long)g->B * g->OH * g->OW, g->Co, dbias, accumulate, cs,
-                             mg_colsum_workspace((long long)g->B * g->OH * g->OW, g->Co), stream);
+        break;
+    case R_WINO: case R_WINO4: case R_WINO42:
+        if (al)
+            return wino_wgrad(wino_geo(r, g), g, x, dy, dw, dbias, accumulate, (float*)workspace, st, wt ? wt->v : nullptr,
+                              wt ? wt->md : nullptr);
+        break;
+    case R_SMALLC:
+        if (aligned16(dw) && aligned16(workspace)) {
+            probe_begin(st);
+            const int rc = smallc_wgrad(g, x, dy, dw, accumulate, (float*)workspace, st);
+            probe_end(st);
+            if (rc != MG_OK || !dbias) return rc;
+            return mg_colsum(dy, M, g->Co, dbias, accumulate, (float*)workspace + smallc_wgrad_layout(g).cs,
+                             mg_colsum_workspace(M, g->Co), stream);
         }
-        return MG_OK;
-    }
-    if (wino42_ok(g) && aligned16(x) && aligned16(dy) && aligned16(dw) && aligned16(workspace)) {
-        const int rc = wino42_wgrad(g, x, dy, dw, accumulate, (float*)workspace, (hipStream_t)stream, wt ? wt->v : nullptr,
-                                    wt ? wt->md : nullptr);
-        if (rc != MG_OK) return rc;
-        if (dbias) {
-            const Wino42Dims d = wino42_dims(g);
-            const WinoWgradPlan p4 = wino42_wgrad_plan(g);
-            float* cs = (float*)workspace + al256((size_t)25 * d.T * d.K4) + al256((size_t)25 * d.T * g->Co) +
-                        al256((size_t)25 * g->Co * d.K4) + al256(wino42_wgrad_slabs(g) * 25 * g->Co * d.K4);
-            return mg_colsum(dy, (long long)g->B * g->OH * g->OW, g->Co, dbias, accumulate, cs,
-                             mg_colsum_workspace((long long)g->B * g->OH * g->OW, g->Co), stream);
-        }
-        return MG_OK;
+        break;
+    default: break;
     }
     const Geom gg = to_geom(g);
-    hipStream_t st = (hipStream_t)stream;
-    if (conv_dma_wgrad_ok(g) && aligned16(x) && aligned16(dy) && aligned16(dw) && aligned16(workspace)) {
+    if (conv_route(2, g, true) == R_DMA && al) {
         const CdPlan cp = conv_dma_wgrad_plan(g);
         const size_t n_out = (size_t)g->Co * g->KH * g->KW * g->Ci;
         const void* xin = x;

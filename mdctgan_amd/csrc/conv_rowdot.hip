@@ -266,8 +266,7 @@ __global__ __launch_bounds__(256) void co1_tile_wgrad_kernel(Geom g, const float
 }
 
 inline int co1_tile_kind(const mg_conv_geom* g) {      // 0: not eligible, 1: 7x7, 2: 4x4
-    constexpr bool off = false;
-    if (off || g->Co != 1 || g->stride != 1 || g->Ci % CT_CC != 0) return 0;
+    if (g->Co != 1 || g->stride != 1 || g->Ci % CT_CC != 0) return 0;
     if (g->reflect && (g->pad >= g->H || g->pad >= g->W)) return 0;
     if (g->KH == 7 && g->KW == 7) return 1;
     // 4x4 PatchGAN outputs (512 channels on 19x35 maps: few tiles, 32 channel chunks each) measured 4x slower than

@@ -5,8 +5,7 @@
 //
 //   forward   Y  = A^T [ sum_ci (G g G^T) .* (B^T d B) ] A            d: 4x4 input patch (reflect / zero pad 1)
 //   dgrad     the exact transpose of forward: dd_t = B [ (A dy A^T) x U ] B^T per tile, gathered back into dx (the
-//             reflection / zero padding is the transpose of the forward gather); MG_WINO_DGRAD=padded selects the older
-//             formulation dXp = A^T [ sum_co (G g' G^T) .* (B^T dy B) ] A over the (H+2)x(W+2) padded domain
+//             reflection / zero padding is the transpose of the forward gather)
 //   wgrad     dg = G^T [ sum_tiles (B^T d B) .* (A dy A^T) ] G
 // The element-wise products summed over channels / tiles are 16 independent GEMMs, run as ONE batched launch of
 // the implicit-GEMM kernels with a 1x1 geometry (conv_igemm.hip); everything here is the HBM-bound transforms.
@@ -415,8 +414,7 @@ __global__ __launch_bounds__(256) void wino_norm_bwd_dy_kernel(const float* __re
     }
 }
 inline bool wino_out_norm_ok(int TH, int TW, int C) {
-    constexpr bool off = false;
-    return !off && C % 32 == 0 && TH * TW <= 160;
+    return C % 32 == 0 && TH * TW <= 160;
 }
 
 // ReflectionPad2d(1) backward: dX[i][j] = sum of the padded positions aliasing (i, j).  dXp: [B][H+2][W+2][C]
@@ -588,8 +586,7 @@ __global__ __launch_bounds__(256) void wino_dd_gather_kernel(const float* __rest
     }
 }
 inline bool wino_dd_gather_ok(int H, int W, int C) {
-    constexpr bool off = false;
-    return !off && C % 32 == 0 && (H / 2) * (W / 2) <= 64;
+    return C % 32 == 0 && (H / 2) * (W / 2) <= 64;
 }
 
 // Mdy[16][T][C] = A dy A^T for the 2x2 tiles of dy [B][2TH][2TW][C]
