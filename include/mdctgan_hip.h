@@ -130,6 +130,42 @@ int mg_imdct4_backward(const float* grad_audio, int B, int out_len, int F, int n
 int mg_mdct4_backward(const float* grad_spec, const float* spec, int B, int T, int n_fft, const float* window, const float* dct4_image,
                       int codec, float gain, float nr0, float nr1, float src_min, float src_max, float* grad_audio, void* stream);
 
+/* K1' / K2' (csrc/mdct_pow2.hip): the fused transform + codec kernels of the power-of-two geometries other than 512:
+ *   win_length == n_fft == 2 * hop_length, centre padding, n_fft in {256, 1024, 2048}.  TDAC fold + DCT-IV as an n_fft/4-point
+ *   complex FFT between two twiddles (plain float32, radix-4 Stockham stages in LDS); the frames never travel through HBM.
+ *   mg_mdct_pow2_supported   1 when (n_fft, hop_length, win_length, center) is such a geometry, else 0 (n_fft == 512 belongs to
+ *                            K1 / K2: 0).  Pure host query.
+ *   mg_mdct_pow2_twiddle_floats / mg_mdct_pow2_twiddles   the twiddle buffer the three calls below read: 3 * n_fft/2 floats =
+ *                            [pre | post | root], n_fft/4 interleaved complex each: pre[n] = exp(-i pi (4n+1) / (2 n_fft)),
+ *                            post[k] = exp(-i pi 4k / (2 n_fft)), root[t] = exp(-i pi 16t / (2 n_fft)).  Filled on the HOST into
+ *                            `out` (float32, or float64 when as_f64: the values before their one rounding); the caller copies
+ *                            the float32 form to the device once per geometry (not inside a graph capture).  16-byte aligned.
+ *   mg_mdct4_pow2_forward    audio [B, T] -> spec [B, F, n_fft/2] with mg_mdct4_forward's codec arguments (RAW / ARCSINH / RANGE
+ *                            with the fixed range; stats as there).  F is the caller's: mg_mdct4_num_frames(T, n_fft) for
+ *                            MDCT4.forward; frame f covers samples (f-1) hop .. (f+1) hop - 1, zeros outside [0, T).  Any T.
+ *                            per_sample != 0, frames_out != NULL, an unaligned spec: MG_ERR_UNSUPPORTED.
+ *   mg_imdct4_pow2_forward   spec [B, F, n_fft/2] -> audio [B, out_len] float32, out_len <= (F-1) hop, with mg_imdct4_forward's
+ *                            codec arguments; out_scale replaces the transform's 4 / n_fft (the adjoint of K1' is K2' with scale 1).
+ *                            No atomics: identical bits run to run.  out_f64 != 0, an unaligned spec: MG_ERR_UNSUPPORTED.
+ *   mg_imdct4_pow2_stitched  mg_imdct4_stitched's arguments and semantics on these geometries (float32 only); equal to
+ *                            mg_imdct4_pow2_forward followed by mg_stitch_segments bit for bit.
+ *   MG_ERR_UNSUPPORTED sends the caller to the composition (mg_frames_window / mg_conv_fwd / mg_codec_* / mg_overlap_add).
+ *   mg_mdct_last_kernel(0 | 1) names these kernels after the calls ("mdct4_pow2_kernel ...", "imdct4_pow2_kernel ...",
+ *   "imdct4_pow2_kernel<stitched> ..."). */
+int mg_mdct_pow2_supported(int n_fft, int hop_length, int win_length, int center);
+long long mg_mdct_pow2_twiddle_floats(int n_fft);
+int mg_mdct_pow2_twiddles(int n_fft, void* out, int as_f64);
+int mg_mdct4_pow2_forward(const float* audio, int B, int T, int F, int n_fft, const float* window, const float* twiddles, int codec,
+                          float gain, float nr0, float nr1, float src_min, float src_max, int per_sample, float* spec,
+                          float* frames_out, double* stats, void* stream);
+int mg_imdct4_pow2_forward(const float* spec, int B, int F, int n_fft, const float* window, const float* twiddles, int codec,
+                           float gain, float nr0, float nr1, float src_min, float src_max, const float* min_b, const float* max_b,
+                           void* audio, int out_len, int out_f64, float out_scale, void* stream);
+int mg_imdct4_pow2_stitched(const float* spec, int B, int F, int n_fft, const float* window, const float* twiddles, int codec,
+                            float gain, float nr0, float nr1, float src_min, float src_max, const float* min_b, const float* max_b,
+                            void* out, long long out_total, int seg_len, int overlap, long long first_seg, int zero_out,
+                            int out_f64, void* stream);
+
 /* F1  torchaudio.functional.resample(waveform, orig_freq, new_freq) with its defaults (sinc_interp_hann,
  * lowpass_filter_width 6, rolloff 0.99) as the reference's data path calls it (data/audio_dataset.py:66-71, 171-177):
  * x [B, L] -> out [B, mg_resample_length(L, orig, new)], orig / new the gcd-reduced rates.  kern [new, 2*width + orig]

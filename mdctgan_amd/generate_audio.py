@@ -3,8 +3,8 @@
 The reference script walks the dataset loader, calls ``model.inference`` per batch, copies every ``sr_audio`` to the
 host and concatenates (or cross-fades with ``F.fold`` when ``--gen_overlap > 0``).  Here the waveform is built in HBM by
 the decoder itself: batches of low-rate segments go through ``model.inference`` and K2's overlap-add store writes each
-segment at its place in the stitched waveform, cross-fade included (``mg_imdct4_stitched``); codec geometries K2 does not
-cover decode per batch and one gather kernel (``mg_stitch_segments``) stitches.  Dataset loading, resampling and the
+segment at its place in the stitched waveform, cross-fade included (``mg_imdct4_stitched``, ``mg_imdct4_pow2_stitched`` at
+n_fft 256 / 1024 / 2048); codec geometries neither covers decode per batch and one gather kernel (``mg_stitch_segments``) stitches.  Dataset loading, resampling and the
 metrics of ``util.compute_matrics`` are outside the hot path.
 """
 from __future__ import annotations
@@ -38,11 +38,12 @@ def generate(model, lr_segments: torch.Tensor, batch_size: int = 64, gen_overlap
     if lr_segments.dim() != 2:
         raise ValueError("lr_segments must be [n_seg, T]")
     outs = []
-    # The fused codec geometry: K2's overlap-add store writes every batch's segments straight into the stitched waveform
+    # A codec geometry with a stitched decoder (K2 at n_fft 512, K2' at 256 / 1024 / 2048): the overlap-add store writes every
+    # batch's segments straight into the stitched waveform
     # (mg_imdct4_stitched: the halving, F.fold and the crop of generate_audio.py:43-50 -- or the torch.cat of :52 -- happen in
     # the store; no list of segments, no concatenation, no stitching launch).  Other geometries decode per batch and stitch after.
     pre = model.preprocess
-    fused = bool(getattr(pre, "fused", False)) and os.environ.get("MG_NO_STITCHED_K2") != "1"
+    fused = bool(getattr(pre, "has_stitched_decoder", False)) and os.environ.get("MG_NO_STITCHED_K2") != "1"
     out = None
     if fused:
         n_seg, T = lr_segments.shape

@@ -14,10 +14,15 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
   win_length, e.g. the class default n_fft = 2048) runs the generic path of csrc/codec_generic.hip: framing + window, the
   [frames, win] x [win, n_fft/2] cosine contraction as a dense exact-float32 MFMA GEMM (the 1x1 case of mg_conv_fwd),
   window + overlap-add.  There is no eager / CPU fallback.
+* the other Princen-Bradley power-of-two geometries (win_length == n_fft == 2 * hop_length, centre padding, n_fft in 256 /
+  1024 / 2048, e.g. the class default) run the fused kernels K1' / K2' of csrc/mdct_pow2.hip (TDAC fold + DCT-IV as an
+  n_fft/4-point FFT in LDS) -- the ``.fast`` attribute; ``.fused`` keeps naming the 512 kernels only.  MG_MDCT_POW2=0 (read at call
+  time) sends them back to the generic path.
 """
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 
@@ -277,6 +282,112 @@ def imdct4_codec(spec, window, dct4, n_fft, *, codec=_lib.MG_CODEC_RAW, gain=1.0
 _UNSUPPORTED = -2       # MG_ERR_UNSUPPORTED: the fused backward's guards failed, the generic composition runs
 
 
+def pow2_enabled() -> bool:
+    """The MG_MDCT_POW2 switch, read at call time (0: every route of K1' / K2' goes back to the generic composition)."""
+    return os.environ.get("MG_MDCT_POW2", "1") != "0"
+
+
+def pow2_geometry(n_fft, hop_length, win_length, center=True) -> bool:
+    """mg_mdct_pow2_supported: a geometry of the fused K1' / K2' kernels (csrc/mdct_pow2.hip); a pure host query."""
+    return bool(_lib.load().mg_mdct_pow2_supported(int(n_fft), int(hop_length), int(win_length), int(bool(center))))
+
+
+def pow2_radices(n_fft: int):
+    """Stage radices of the n_fft/4-point Stockham FFT inside K1' / K2' (csrc/mdct_pow2.hip pw_dct4): radix 8, after one radix-2 /
+    radix-4 stage when log2 is not a multiple of 3."""
+    bits = (n_fft // 4).bit_length() - 1
+    return ([1 << (bits % 3)] if bits % 3 else []) + [8] * (bits // 3)
+
+
+def pow2_twiddles_host(n_fft: int, dtype=torch.float32) -> torch.Tensor:
+    """mg_mdct_pow2_twiddles on the host: [3, n_fft/4, 2] = (pre, post, root) as (re, im); float64: before the rounding."""
+    lib = _lib.load()
+    n = int(lib.mg_mdct_pow2_twiddle_floats(n_fft))
+    if n <= 0:
+        raise NotImplementedError("no K1' / K2' kernels for n_fft = %d" % n_fft)
+    t = torch.empty(n, dtype=dtype)
+    _lib.check(lib.mg_mdct_pow2_twiddles(n_fft, t.data_ptr(), int(dtype == torch.float64)), "mg_mdct_pow2_twiddles")
+    return t.view(3, n_fft // 4, 2)
+
+
+_pow2_tw_cache = {}
+
+
+def pow2_twiddles(n_fft: int, device) -> torch.Tensor:
+    """The device copy of the twiddle buffer, built on the first (eager) call per geometry and device."""
+    key = (n_fft, str(device))
+    t = _pow2_tw_cache.get(key)
+    if t is None:
+        t = pow2_twiddles_host(n_fft).reshape(-1).to(device)
+        _pow2_tw_cache[key] = t
+    return t
+
+
+def mdct4_pow2(audio, window, n_fft, F=None, *, codec=_lib.MG_CODEC_RAW, gain=1.0, norm_range=(0.0, 1.0), src_range=(0.0, 1.0),
+               want_stats=False):
+    """K1' launcher.  audio [B, T] -> dict like mdct4_codec (spec [B, F, n_fft/2], stats), F frames (default: num_frames(T));
+    None where the kernel's guards refuse (MG_ERR_UNSUPPORTED): the caller runs the composition."""
+    lib = _lib.load()
+    audio = _lib.f32c(audio)
+    B, T = audio.shape
+    M = n_fft // 2
+    if F is None:
+        F = num_frames(T, n_fft, M, True)
+    if F <= 0:
+        raise ValueError("signal of %d samples is too short for win_length=%d" % (T, n_fft))
+    dev = audio.device
+    tw = pow2_twiddles(n_fft, dev)
+    spec = torch.empty(B, F, M, dtype=torch.float32, device=dev)
+    stats = torch.empty(2, dtype=torch.float64, device=dev) if want_stats else None
+    rc = lib.mg_mdct4_pow2_forward(_lib.ptr(audio), B, T, F, n_fft, _lib.ptr(window), _lib.ptr(tw), codec, gain, norm_range[0],
+                                   norm_range[1], src_range[0], src_range[1], 0, _lib.ptr(spec), None, _lib.ptr(stats),
+                                   _lib.stream())
+    if rc == _UNSUPPORTED:
+        return None
+    _lib.check(rc, "mg_mdct4_pow2_forward")
+    return {"spec": spec, "pair": None, "frames": None, "min": None, "max": None, "stats": stats}
+
+
+def imdct4_pow2(spec, window, n_fft, *, codec=_lib.MG_CODEC_RAW, gain=1.0, norm_range=(0.0, 1.0), src_range=(0.0, 1.0),
+                min_b=None, max_b=None, out_length=None, scale=None, stitch=None):
+    """K2' launcher.  spec [B, F, n_fft/2] -> audio [B, T_out] (scale: in place of the transform's 4 / n_fft), or the stitched
+    waveform (stitch as in imdct4_codec, plus an optional fifth element zero_out -- default: first_seg == 0 -- for callers that
+    clear `out` themselves and hand the batches over in another order); None where the kernel's guards refuse and nothing has
+    been written."""
+    lib = _lib.load()
+    spec = _lib.f32c(spec)
+    B, F, M = spec.shape
+    t_out = (F - 1) * M
+    if out_length is not None:
+        t_out = min(t_out, int(out_length))
+    tw = pow2_twiddles(n_fft, spec.device)
+    if min_b is not None:
+        min_b, max_b = _lib.f32c(min_b.reshape(-1)), _lib.f32c(max_b.reshape(-1))
+        assert min_b.numel() == B and max_b.numel() == B
+    if stitch is not None:
+        out, overlap, first = stitch[:3]
+        if len(stitch) > 3 and int(stitch[3]) != t_out:
+            raise ValueError("stitched K2': the output was sized for %d-sample segments, the spectrogram decodes to %d"
+                             % (int(stitch[3]), t_out))
+        if out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("stitched K2': contiguous float32 output")
+        rc = lib.mg_imdct4_pow2_stitched(_lib.ptr(spec), B, F, n_fft, _lib.ptr(window), _lib.ptr(tw), codec, gain, norm_range[0],
+                                         norm_range[1], src_range[0], src_range[1], _lib.ptr(min_b), _lib.ptr(max_b),
+                                         _lib.ptr(out), out.numel(), t_out, int(overlap), int(first),
+                                         int(stitch[4] if len(stitch) > 4 else first == 0), 0,
+                                         _lib.stream())
+        _lib.check(rc, "mg_imdct4_pow2_stitched")
+        return out
+    audio = torch.empty(B, t_out, dtype=torch.float32, device=spec.device)
+    rc = lib.mg_imdct4_pow2_forward(_lib.ptr(spec), B, F, n_fft, _lib.ptr(window), _lib.ptr(tw), codec, gain, norm_range[0],
+                                    norm_range[1], src_range[0], src_range[1], _lib.ptr(min_b), _lib.ptr(max_b), _lib.ptr(audio),
+                                    t_out, 0, 4.0 / n_fft if scale is None else float(scale), _lib.stream())
+    if rc == _UNSUPPORTED:
+        return None
+    _lib.check(rc, "mg_imdct4_pow2_forward")
+    return audio
+
+
 def _fused_image(n_fft, device):
     """The stage-matrix image of the fused geometry's DCT-IV table (None for other n_fft)."""
     if n_fft != 512:
@@ -302,11 +413,12 @@ def codec_backward(grad, spec, *, codec, to_spectro, scale=1.0, gain=1.0, norm_r
 
 
 def imdct4_backward(grad_audio, spec, window, n_fft, hop_length, F, center=True, *, codec=_lib.MG_CODEC_RAW, gain=1.0,
-                    norm_range=(0.0, 1.0), src_range=(0.0, 1.0), min_b=None, max_b=None, fused=True):
+                    norm_range=(0.0, 1.0), src_range=(0.0, 1.0), min_b=None, max_b=None, fused=True, fast=False):
     """Gradient of imdct4_codec / imdct4_generic (decode + IMDCT4) with respect to their spectrogram input.
     grad_audio [B, T_out] -> grad_spec [B, F, n_fft/2].  fused: try the K1-shaped kernel (mg_imdct4_backward) first; the
     generic composition runs where its guards fail: frames of grad_audio with the IMDCT's crop as start padding, window,
-    [frames, win] x [win, n_fft/2] on the exact-f32 GEMM, then dX/ds and the 4/N scale (mg_codec_backward)."""
+    [frames, win] x [win, n_fft/2] on the exact-f32 GEMM, then dX/ds and the 4/N scale (mg_codec_backward).  fast: K1' in RAW
+    mode with the forward's F is the framing + contraction leg (the adjoint of K2' is 4/N K1')."""
     lib = _lib.load()
     gy = _lib.f32c(grad_audio)
     B, t_out = gy.shape
@@ -325,20 +437,25 @@ def imdct4_backward(grad_audio, spec, window, n_fft, hop_length, F, center=True,
             _lib.check(rc, "mg_imdct4_backward")
             return gs
     win = window.numel()
-    frames = torch.empty(B, F, win, dtype=torch.float32, device=dev)
-    _lib.check(lib.mg_frames_window(_lib.ptr(gy), B, t_out, win, hop_length, win // 2 if center else 0, F, _lib.ptr(window),
-                                    _lib.ptr(frames), _lib.stream()), "mg_frames_window")
-    g = _dense(frames.view(B * F, win), mdct_table(n_fft, win, dev, True)).view(B, F, M)
+    r = mdct4_pow2(gy, window, n_fft, F) if (fast and center and pow2_enabled()) else None
+    if r is not None:
+        g = r["spec"]
+    else:
+        frames = torch.empty(B, F, win, dtype=torch.float32, device=dev)
+        _lib.check(lib.mg_frames_window(_lib.ptr(gy), B, t_out, win, hop_length, win // 2 if center else 0, F, _lib.ptr(window),
+                                        _lib.ptr(frames), _lib.stream()), "mg_frames_window")
+        g = _dense(frames.view(B * F, win), mdct_table(n_fft, win, dev, True)).view(B, F, M)
     return codec_backward(g, spec, codec=codec, to_spectro=False, scale=4.0 / n_fft, gain=gain, norm_range=norm_range,
                           src_range=src_range, min_b=min_b, max_b=max_b)
 
 
 def mdct4_backward(grad_spec, spec, window, n_fft, hop_length, T, center=True, *, codec=_lib.MG_CODEC_RAW, gain=1.0,
-                   norm_range=(0.0, 1.0), src_range=(0.0, 1.0), fused=True):
+                   norm_range=(0.0, 1.0), src_range=(0.0, 1.0), fused=True, fast=False):
     """Gradient of mdct4_codec / mdct4_generic (MDCT4 + fixed-range encode) with respect to the audio: grad_spec [B, F, n_fft/2]
     (gradient of the normalised output spec) -> grad_audio [B, T].  fused: the K2-shaped kernel (mg_mdct4_backward) where its
     guards hold; otherwise ds/dX (mg_codec_backward), [F, n_fft/2] x [n_fft/2, win] on the exact-f32 GEMM, window and
-    overlap-add with the MDCT's start padding as crop (mg_overlap_add with n_fft = 4: scale 1)."""
+    overlap-add with the MDCT's start padding as crop (mg_overlap_add with n_fft = 4: scale 1).  fast: K2' in RAW mode with
+    output scale 1 is the contraction + overlap-add leg (the adjoint of K1')."""
     lib = _lib.load()
     g = _lib.f32c(grad_spec)
     B, F, M = g.shape
@@ -355,13 +472,17 @@ def mdct4_backward(grad_spec, spec, window, n_fft, hop_length, T, center=True, *
     if codec != _lib.MG_CODEC_RAW:
         g = codec_backward(g, spec, codec=codec, to_spectro=True, gain=gain, norm_range=norm_range, src_range=src_range)
     win = window.numel()
-    z = _dense(g.view(B * F, M), mdct_table(n_fft, win, dev, False)).view(B, F, win)
     crop = hop_length if center else 0
     covered = min(T, (F - 1) * hop_length + win - crop)        # samples past the last frame get no gradient
-    ga = torch.empty(B, covered, dtype=torch.float32, device=dev)
-    # mg_overlap_add scales by 4 / n_fft: n_fft = 4 makes it 1
-    _lib.check(lib.mg_overlap_add(_lib.ptr(z), B, F, win, hop_length, 4, _lib.ptr(window), crop, _lib.ptr(ga), covered, 0,
-                                  _lib.stream()), "mg_overlap_add")
+    ga = None
+    if fast and center and pow2_enabled() and F > 1 and covered <= (F - 1) * hop_length:
+        ga = imdct4_pow2(g, window, n_fft, out_length=covered, scale=1.0)
+    if ga is None:
+        z = _dense(g.view(B * F, M), mdct_table(n_fft, win, dev, False)).view(B, F, win)
+        ga = torch.empty(B, covered, dtype=torch.float32, device=dev)
+        # mg_overlap_add scales by 4 / n_fft: n_fft = 4 makes it 1
+        _lib.check(lib.mg_overlap_add(_lib.ptr(z), B, F, win, hop_length, 4, _lib.ptr(window), crop, _lib.ptr(ga), covered, 0,
+                                      _lib.stream()), "mg_overlap_add")
     if covered < T:
         ga = torch.cat((ga, ga.new_zeros(B, T - covered)), dim=1)
     return ga
@@ -401,9 +522,15 @@ class MDCT4(torch.nn.Module):
         self.n_fft, self.pad_mode, self.device, self.hop_length, self.center = n_fft, pad_mode, device, hop_length, center
         self.window, self.win_length = _make_window(window, win_length, device)
         self.fused = _check_geometry(self.n_fft, self.hop_length, self.win_length) and center
+        self._pow2 = pow2_geometry(self.n_fft, self.hop_length, self.win_length, center)
         if pad_mode != "constant":
             raise NotImplementedError("HIP MDCT4 implements zero ('constant') padding")
         self.out_dtype = dtype
+
+    @property
+    def fast(self) -> bool:
+        """The fused K1' kernel (csrc/mdct_pow2.hip) runs this geometry (MG_MDCT_POW2=0, read here, says no)."""
+        return self._pow2 and pow2_enabled()
 
     def forward(self, signal, return_frames: bool = False):
         lead = signal.shape[:-1]
@@ -414,6 +541,10 @@ class MDCT4(torch.nn.Module):
             if self.fused:
                 r = mdct4_codec(a, self.window, dct4_table(self.n_fft // 2, a.device), self.n_fft, want_frames=return_frames)
                 return r["spec"], r["frames"]
+            if self.fast and not return_frames:
+                r = mdct4_pow2(a, self.window, self.n_fft)
+                if r is not None:
+                    return r["spec"], None
             return mdct4_generic(a, self.window, self.n_fft, self.hop_length, self.center, return_frames)
         if wants_grad(x):
             held = {}
@@ -424,7 +555,7 @@ class MDCT4(torch.nn.Module):
 
             def bwd(g, a, _):
                 return mdct4_backward(g, None, self.window, self.n_fft, self.hop_length, a.shape[-1], self.center,
-                                      fused=self.fused)
+                                      fused=self.fused, fast=self.fast)
             sp = CodecGrad.apply(fwd, bwd, x)
             fr = held["frames"]
         else:
@@ -444,7 +575,13 @@ class IMDCT4(torch.nn.Module):
         self.center, self.out_length = center, out_length
         self.window, self.win_length = _make_window(window, win_length, device)
         self.fused = _check_geometry(self.n_fft, self.hop_length, self.win_length) and center
+        self._pow2 = pow2_geometry(self.n_fft, self.hop_length, self.win_length, center)
         self.out_dtype = dtype
+
+    @property
+    def fast(self) -> bool:
+        """The fused K2' kernel (csrc/mdct_pow2.hip) runs this geometry (MG_MDCT_POW2=0, read here, says no)."""
+        return self._pow2 and pow2_enabled()
 
     def forward(self, signal, return_frames: bool = False):
         assert signal.dim() == 3, "Only tensors shaped in BHW are supported, got tensor of shape %s" % (
@@ -457,6 +594,10 @@ class IMDCT4(torch.nn.Module):
             if self.fused:
                 return imdct4_codec(spec, self.window, dct4_table(self.n_fft // 2, spec.device), self.n_fft,
                                     out_length=self.out_length, out_dtype=self.out_dtype, want_frames=return_frames)
+            if self.fast and not return_frames and self.out_dtype == torch.float32 and spec.shape[1] > 1:
+                audio_ = imdct4_pow2(spec, self.window, self.n_fft, out_length=self.out_length)
+                if audio_ is not None:
+                    return audio_, None
             return imdct4_generic(spec, self.window, self.n_fft, self.hop_length, self.center, self.out_length,
                                   self.out_dtype, return_frames)
         if wants_grad(signal):
@@ -469,7 +610,8 @@ class IMDCT4(torch.nn.Module):
             def bwd(g, spec, _):
                 # the float64 output comes from the generic kernel: its backward takes the generic composition too
                 return imdct4_backward(g, None, self.window, self.n_fft, self.hop_length, spec.shape[1], self.center,
-                                       fused=self.fused and self.out_dtype == torch.float32)
+                                       fused=self.fused and self.out_dtype == torch.float32,
+                                       fast=self.fast and self.out_dtype == torch.float32)
             audio = CodecGrad.apply(fwd, bwd, signal)
             frames = held["frames"]
         else:

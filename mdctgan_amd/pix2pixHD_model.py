@@ -19,7 +19,8 @@ from . import _lib, networks
 from . import amp
 from . import functional as Fh
 from .mdct import (IMDCT4, MDCT4, CodecGrad, _check_geometry, codec_forward, codec_inverse, dct4_table, imdct4_backward,
-                   imdct4_codec, imdct4_generic, kbdwin, mdct4_backward, mdct4_codec, mdct4_generic, wants_grad)
+                   imdct4_codec, imdct4_generic, imdct4_pow2, kbdwin, mdct4_backward, mdct4_codec, mdct4_generic, mdct4_pow2,
+                   pow2_enabled, pow2_geometry, wants_grad)
 from .optim import FusedAdam
 
 
@@ -52,15 +53,37 @@ class Audio2MDCT(torch.nn.Module):
         # generic kernels of csrc/codec_generic.hip (transform as a dense GEMM + elementwise codec)
         self.geom512 = _check_geometry(self.n_fft, self.hop_length, self.win_length)
         self.fused = self.geom512 and self.codec in (_lib.MG_CODEC_ARCSINH, _lib.MG_CODEC_RANGE)
+        # the other power-of-two geometries (n_fft 256 / 1024 / 2048, hop = n_fft / 2): K1' / K2' of csrc/mdct_pow2.hip -- `fast`
+        self._pow2 = pow2_geometry(self.n_fft, self.hop_length, self.win_length, True)
         self.return_stats = True      # mean / std of norm_param (returned only; costs two atomics per wave)
         self.return_frames = False    # norm_param['frames'] (dead on the hot path; [B, F, 512] of extra traffic)
         self.return_pha = False       # pha = sign(X) * noise is dead on the arcsinh / raw paths
+
+    @property
+    def fast(self) -> bool:
+        """K1' / K2' run this geometry (MG_MDCT_POW2=0, read at call time, restores the generic composition)."""
+        return self._pow2 and pow2_enabled()
+
+    @property
+    def fast_codec(self) -> bool:
+        """... with the codec inside the kernels (arcsinh / range); other codecs run them in RAW mode around mg_codec_*."""
+        return self.fast and self.codec in (_lib.MG_CODEC_ARCSINH, _lib.MG_CODEC_RANGE)
+
+    @property
+    def has_stitched_decoder(self) -> bool:
+        """to_audio(..., stitch=...) is served: K2 at n_fft 512, K2' at the other power-of-two geometries."""
+        return self.fused or self.fast_codec
 
     # -- helpers --------------------------------------------------------------------------------
     def _tables(self, dev):
         if self.window.device != dev:
             self.window = self.window.to(dev)
         return self.window, dct4_table(self.n_fft // 2, dev)
+
+    def _window(self, dev):
+        if self.window.device != dev:
+            self.window = self.window.to(dev)
+        return self.window
 
     def _ranges(self):
         return (float(self.norm_range[0]), float(self.norm_range[1])), (float(self.src_range[0]), float(self.src_range[1]))
@@ -73,6 +96,10 @@ class Audio2MDCT(torch.nn.Module):
             return r["spec"], r["frames"]
         if self.window.device != audio.device:
             self.window = self.window.to(audio.device)
+        if self.fast and not want_frames:
+            r = mdct4_pow2(audio, self.window, self.n_fft)
+            if r is not None:
+                return r["spec"], None
         return mdct4_generic(audio, self.window, self.n_fft, self.hop_length, True, want_frames)
 
     def encode(self, audio, want_pair=False, want_stats=None, want_frames=None):
@@ -88,6 +115,14 @@ class Audio2MDCT(torch.nn.Module):
                             want_stats=want_stats, want_frames=want_frames)
             r["spec4"], r["raw"] = r["spec"][:, None], None
             return r
+        if self.fast_codec and self.abs_norm and not want_pair and not want_frames:
+            # K1' with the fixed-range codec and the statistics inside (per-sample ranges and the NHWC pair: RAW mode below)
+            window = self._window(audio.device)
+            r = mdct4_pow2(audio.reshape(-1, audio.shape[-1]), window, self.n_fft, codec=self.codec, gain=float(self.arcsinh_gain),
+                           norm_range=nr, src_range=sr, want_stats=want_stats)
+            if r is not None:
+                r["spec4"], r["raw"] = r["spec"][:, None], None
+                return r
         raw, frames = self._raw(_lib.f32c(audio.reshape(-1, audio.shape[-1])), want_frames)
         r = codec_forward(raw, codec=self.codec, gain=float(self.arcsinh_gain), alpha=float(self.alpha),
                           min_value=float(self.min_value), norm_range=nr, src_range=sr, per_sample=not self.abs_norm,
@@ -198,7 +233,7 @@ class Audio2MDCT(torch.nn.Module):
         nr, sr = self._ranges()
         window, _ = self._tables(audio.device)
         g = mdct4_backward(grad[:, 0], spec4[:, 0], window, self.n_fft, self.hop_length, audio.shape[-1], codec=codec,
-                           gain=gain, norm_range=nr, src_range=sr, fused=self.geom512)
+                           gain=gain, norm_range=nr, src_range=sr, fused=self.geom512, fast=self.fast)
         return g.view(audio.shape)
 
     def _to_audio_backward(self, grad, log_spectro, norm_param):
@@ -213,11 +248,11 @@ class Audio2MDCT(torch.nn.Module):
         window, _ = self._tables(log_spectro.device)
         g = imdct4_backward(grad.reshape(spec.shape[0], -1), spec, window, self.n_fft, self.hop_length, spec.shape[1],
                             codec=codec, gain=gain, norm_range=nr, src_range=sr, min_b=mn if per_sample else None,
-                            max_b=mx if per_sample else None, fused=self.geom512)
+                            max_b=mx if per_sample else None, fused=self.geom512, fast=self.fast)
         return g.view(log_spectro.shape)
 
     def to_audio(self, log_spectro: torch.Tensor, norm_param: Dict[str, torch.Tensor], pha: torch.Tensor = None, stitch=None):
-        """pix2pixHD_model.py:139-165.  stitch = (out, gen_overlap, first_seg) (fused geometry only): K2 writes the segments
+        """pix2pixHD_model.py:139-165.  stitch = (out, gen_overlap, first_seg) (has_stitched_decoder only): K2 / K2' writes the segments
         straight into the stitched waveform `out` (generate_audio.py:40-53 inside the kernel) and `out` is returned.
         Differentiable in log_spectro (arcsinh / range codecs; stitched decode stays forward-only)."""
         mn, mx = norm_param["min"], norm_param["max"]
@@ -227,7 +262,7 @@ class Audio2MDCT(torch.nn.Module):
         return self._to_audio(log_spectro, norm_param, pha, stitch)
 
     def _to_audio(self, log_spectro, norm_param, pha, stitch):
-        if stitch is not None and not self.fused:
+        if stitch is not None and not self.has_stitched_decoder:
             raise NotImplementedError("stitched decode needs the fused 512 / 256 geometry")
         nr, sr = self._ranges()
         mn, mx = norm_param["min"], norm_param["max"]
@@ -241,6 +276,13 @@ class Audio2MDCT(torch.nn.Module):
                                     norm_range=nr, src_range=sr, min_b=mn if per_sample else None,
                                     max_b=mx if per_sample else None, stitch=stitch)
             return audio if stitch is not None else audio[:, None, None, :]
+        if self.fast_codec:
+            window = self._window(log_spectro.device)
+            spec = log_spectro.squeeze(1) if log_spectro.dim() == 4 else log_spectro
+            audio = imdct4_pow2(spec, window, self.n_fft, codec=self.codec, gain=float(self.arcsinh_gain), norm_range=nr,
+                                src_range=sr, min_b=mn if per_sample else None, max_b=mx if per_sample else None, stitch=stitch)
+            if audio is not None:
+                return audio if stitch is not None else audio[:, None, None, :]
         spec4 = log_spectro if log_spectro.dim() == 4 else log_spectro[:, None]
         raw = codec_inverse(spec4, codec=self.codec, gain=float(self.arcsinh_gain), alpha=float(self.alpha),
                             min_value=float(self.min_value), norm_range=nr, src_range=sr,
@@ -260,7 +302,9 @@ class Audio2MDCT(torch.nn.Module):
         else:
             if self.window.device != raw.device:
                 self.window = self.window.to(raw.device)
-            audio, _ = imdct4_generic(raw, self.window, self.n_fft, self.hop_length, True)
+            audio = imdct4_pow2(raw, self.window, self.n_fft) if (self.fast and raw.shape[1] > 1) else None
+            if audio is None:
+                audio, _ = imdct4_generic(raw, self.window, self.n_fft, self.hop_length, True)
         return audio[:, None, None, :]
 
     def forward(self, lr_audio: torch.Tensor):
