@@ -108,6 +108,35 @@ int mg_imdct4_stitched(const float* spec, int B, int F, int n_fft, const float* 
                        const float* min_b, const float* max_b, void* out, long long out_total, int seg_len, int overlap,
                        long long first_seg, int zero_out, int out_f64, void* stream);
 
+/* Row tables: batched inference over utterances of different lengths (segments of any number of utterances share a batch).
+ *   mg_seg_row (a DEVICE array, one entry per batch row): sample t of row r is index p = pos + t of a packed buffer that holds all
+ *   utterances; the sample exists only if lo <= p < hi ([lo, hi) is the row's utterance); lo == hi marks a dead row.  pos may be
+ *   negative or anything else: only positions inside the window are touched (a window that sticks out of the buffer is cut to it).
+ *   mg_segments_gather       data/audio_dataset.py:153-167 (seg_pad_audio: pad + unfold) from the packed waveform `wave`
+ *                            [wave_total]: out[r][t] = (lo <= pos + t < hi) ? wave[pos + t] : 0 for out [n_rows, seg_len]; dead rows
+ *                            come out as zeros.  16-byte loads where pos and the pointers allow, scalar loads otherwise.  No atomics.
+ *   mg_imdct4_stitched_rows  mg_imdct4_stitched with `rows` [B] in place of first_seg; out / out_total are the whole packed buffer.
+ *                            Per row the semantics of mg_imdct4_stitched with the row's window in place of [0, out_total): sample t
+ *                            lands at pos + t and is dropped outside [lo, hi) (the reference's final crop), the first / last
+ *                            `overlap` samples of every segment are halved and added (so the windows must be zero beforehand when
+ *                            overlap > 0), the rest is stored; a dead row writes nothing; nothing outside the windows is written.
+ *                            zero_out != 0 clears the whole packed buffer first (a memset node).  The same kernels as
+ *                            mg_imdct4_stitched by the same guards (overlap % 4 == 0 for the factored one), so a row table that
+ *                            describes one utterance gives that call's bits; 16-byte stores where pos % 4 == 0.
+ *   mg_imdct4_pow2_stitched_rows  the same for mg_imdct4_pow2_stitched (n_fft 256 / 1024 / 2048, float32).
+ *   mg_mdct_last_kernel(1) names the variants "...<stitched rows> ...". */
+typedef struct { long long pos, lo, hi; } mg_seg_row;
+int mg_segments_gather(const float* wave, long long wave_total, const mg_seg_row* rows, int n_rows, int seg_len, float* out,
+                       void* stream);
+int mg_imdct4_stitched_rows(const float* spec, int B, int F, int n_fft, const float* window, const float* dct4,
+                            const float* dct4_image, int codec, float gain, float nr0, float nr1, float src_min, float src_max,
+                            const float* min_b, const float* max_b, void* out, long long out_total, int seg_len, int overlap,
+                            const mg_seg_row* rows, int zero_out, int out_f64, void* stream);
+int mg_imdct4_pow2_stitched_rows(const float* spec, int B, int F, int n_fft, const float* window, const float* twiddles, int codec,
+                                 float gain, float nr0, float nr1, float src_min, float src_max, const float* min_b,
+                                 const float* max_b, void* out, long long out_total, int seg_len, int overlap,
+                                 const mg_seg_row* rows, int zero_out, int out_f64, void* stream);
+
 /* Which kernel the last mg_mdct4_forward (which == 0) / mg_imdct4_forward / mg_imdct4_stitched (which == 1) call of this process
  * launched -- a static string ("mdct4_ct_kernel (csrc/mdct_ct.h)", ...).  Diagnostic: bench.py names the measured kernel with it. */
 const char* mg_mdct_last_kernel(int which);

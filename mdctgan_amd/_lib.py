@@ -64,6 +64,9 @@ SIGNATURES = {
     "mg_dct4_image_floats": (_ll, [_i]),
     "mg_imdct4_forward": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _f, _f, _p, _p, _p, _i, _i, _p, _p]),
     "mg_imdct4_stitched": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _f, _f, _p, _p, _p, _ll, _i, _i, _ll, _i, _i, _p]),
+    "mg_segments_gather": (_i, [_p, _ll, _p, _i, _i, _p, _p]),
+    "mg_imdct4_stitched_rows": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _f, _f, _p, _p, _p, _ll, _i, _i, _p, _i, _i, _p]),
+    "mg_imdct4_pow2_stitched_rows": (_i, [_p, _i, _i, _i, _p, _p, _i, _f, _f, _f, _f, _f, _p, _p, _p, _ll, _i, _i, _p, _i, _i, _p]),
     "mg_mdct_last_kernel": (C.c_char_p, [_i]),
     "mg_imdct4_backward": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _f, _f, _f, _f, _f, _p, _p, _p, _p, _p]),
     "mg_mdct4_backward": (_i, [_p, _p, _i, _i, _i, _p, _p, _i, _f, _f, _f, _f, _f, _p, _p]),

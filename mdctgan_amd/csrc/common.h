@@ -8,6 +8,17 @@
 #define MG_ERR_ARG (-1)      // bad argument (shape / alignment / null)
 #define MG_ERR_UNSUPPORTED (-2)
 
+// One batch row of a packed waveform buffer (mg_seg_row in include/mdctgan_hip.h): sample t of the row is index p = pos + t of the
+// buffer and exists only for lo <= p < hi; lo == hi is a dead row.
+struct SegRow { long long pos, lo, hi; };
+// (a window that sticks out of the buffer is cut to it: a bad table drops samples, it cannot touch memory outside the buffer)
+__device__ __forceinline__ SegRow seg_row_clamped(const SegRow* rows, int r, long long total) {
+    SegRow rw = rows[r];
+    rw.lo = rw.lo < 0 ? 0 : rw.lo;
+    rw.hi = rw.hi > total ? total : rw.hi;
+    return rw;
+}
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

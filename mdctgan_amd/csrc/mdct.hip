@@ -19,6 +19,7 @@
 // size and they were retired from the library in round 5 -- scripts/ubench/mdct_bs.h, mdct_b3.h keep the latter two for the harnesses.)
 #include <cstdlib>
 #include "common.h"
+#include "mdctgan_hip.h"
 
 namespace {
 
@@ -39,7 +40,10 @@ struct CodecParams {
 
 // K2 writing into ONE stitched waveform (generate_audio.py:40-53): segment index of clip 0 times pitch minus overlap, samples of
 // the waveform, pitch = segment length - overlap, overlap.  pitch == 0: the plain [B, out_len] output.
-struct StitchArgs { long long base, total; int pitch, overlap; };
+// Row-table form (mg_imdct4_stitched_rows): `rows` takes the place of `base`, clip b is rows[b] of a packed buffer of `total` samples
+// and its window [lo, hi) the place of [0, total); pitch is non-zero and otherwise unused.
+struct StitchArgs { union { long long base; const SegRow* rows; }; long long total; int pitch, overlap; };
+enum Stitch { ST_NONE = 0, ST_SEG = 1, ST_ROWS = 2 };
 
 constexpr float LN10F = 2.3025851249694824f;   // float32(log(10)), as torch.log(torch.tensor(10.0))
 
@@ -193,7 +197,7 @@ __global__ void fill_u32_pairs(unsigned* p, int n_pairs) {
 //   half overlaps hop-block f0) as a VALU dot product riding in the MFMA shadow, then emits hop-blocks
 //   h = f0 .. f0+31:  out[(h-1)*M + n] = 4/N * ( w[n] * y_h[n] + w[n+M] * y_{h-1}[n+M] ).
 // ---------------------------------------------------------------------------------------------
-template <typename OutT, int FT>
+template <typename OutT, int FT, bool ROWS = false>
 __global__ __launch_bounds__(256) void imdct4_kernel(
     const float* __restrict__ spec, int F, const float* __restrict__ window, const float* __restrict__ dct4,
     CodecParams cp, OutT* __restrict__ audio, int out_len, float* __restrict__ frames_out, StitchArgs sa) {
@@ -264,6 +268,8 @@ __global__ __launch_bounds__(256) void imdct4_kernel(
     // unfold y = [v2, -v2_r, -v1_r, -v1], window, overlap-add, scale, centre crop
     constexpr int Q = M / 2;
     const float scale = 4.0f / (2 * M);
+    SegRow rw{0, 0, 0};                     // ROWS: the workgroup's clip is one row of the table
+    if (ROWS) rw = seg_row_clamped(sa.rows, b, sa.total);
     for (int i = tid; i < FT * M; i += 256) {
         const int j = i / M, n = i % M;
         const int h = f0 + j;
@@ -275,6 +281,13 @@ __global__ __launch_bounds__(256) void imdct4_kernel(
         const int t = (h - 1) * M + n;
         if (t >= out_len) continue;
         const OutT o = (OutT)(scale * (ws[n] * yc + ws[n + M] * yp));
+        if (ROWS) {     // the row's window of the packed buffer in place of [0, total)
+            const long long gi = rw.pos + t;
+            if (gi < rw.lo || gi >= rw.hi) continue;
+            if (t < sa.overlap || t >= out_len - sa.overlap) unsafeAtomicAdd(audio + gi, (OutT)0.5 * o);
+            else audio[gi] = o;
+            continue;
+        }
         if (sa.pitch == 0) { audio[(size_t)b * out_len + t] = o; continue; }
         // the stitched waveform (see imdct4_ct_kernel): halved and added inside the cross-fade zones, stored elsewhere
         const long long gi = sa.base + (long long)b * sa.pitch + t;
@@ -323,6 +336,33 @@ __global__ void stitch_kernel(const T* __restrict__ seg, int n_seg, int L, int o
             acc += (k < overlap || k >= L - overlap) ? v * (T)0.5 : v;
         }
         out[o] = acc;
+    }
+}
+
+// data/audio_dataset.py:153-167 (seg_pad_audio) for any number of utterances in one launch: row r of out [n_rows, L] is the window
+// rows[r] of the packed waveform, zeros outside [lo, hi) (the front / tail padding; a dead row comes out as zeros).  One thread =
+// 4 samples: one 16-byte load where the position is a multiple of 4 inside the window (VEC: 16-byte aligned pointers, L % 4 == 0),
+// scalar loads otherwise; always one 16-byte (VEC) store.
+template <bool VEC>
+__global__ __launch_bounds__(256) void segments_gather_kernel(const float* __restrict__ wave, long long wave_total,
+                                                              const SegRow* __restrict__ rows, int L, float* __restrict__ out) {
+    const SegRow rw = seg_row_clamped(rows, blockIdx.y, wave_total);
+    float* dst = out + (size_t)blockIdx.y * L;
+    for (int t0 = 4 * (blockIdx.x * blockDim.x + threadIdx.x); t0 < L; t0 += 4 * gridDim.x * blockDim.x) {
+        const long long p0 = rw.pos + t0;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (VEC && (p0 & 3) == 0 && p0 >= rw.lo && p0 + 3 < rw.hi) {
+            v = *reinterpret_cast<const float4*>(wave + p0);
+        } else {
+            float e[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { const long long p = p0 + k; e[k] = (p >= rw.lo && p < rw.hi) ? wave[p] : 0.0f; }
+            v = make_float4(e[0], e[1], e[2], e[3]);
+        }
+        if (VEC) { *reinterpret_cast<float4*>(dst + t0) = v; continue; }
+        const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) if (t0 + k < L) dst[t0 + k] = e[k];
     }
 }
 
@@ -446,7 +486,7 @@ int mg_mdct4_num_frames(int T, int n_fft) {
 static int imdct4_dispatch(const float* spec, int B, int F, int n_fft, const float* window, const float* dct4,
                            const float* dct4_image, int codec, float gain, float nr0, float nr1, float src_min, float src_max,
                            const float* min_b, const float* max_b, void* audio, int out_len, int out_f64,
-                           float* frames_out, StitchArgs sa, void* stream) {
+                           float* frames_out, StitchArgs sa, void* stream, bool rows = false) {
     if (!spec || !window || !dct4 || !audio || B <= 0 || F <= 0) return MG_ERR_ARG;
     if (n_fft != 2 * M) return MG_ERR_UNSUPPORTED;
     if (out_len <= 0 || out_len > (F - 1) * M) return MG_ERR_ARG;
@@ -458,6 +498,10 @@ static int imdct4_dispatch(const float* spec, int B, int F, int n_fft, const flo
         allow_lds(imdct4_kernel<double, 128>, (129 * LDA + 2 * M) * sizeof(float));
         allow_lds(imdct4_kernel<float, 64>, (65 * LDA + 2 * M) * sizeof(float));
         allow_lds(imdct4_kernel<double, 64>, (65 * LDA + 2 * M) * sizeof(float));
+        allow_lds(imdct4_kernel<float, 128, true>, (129 * LDA + 2 * M) * sizeof(float));
+        allow_lds(imdct4_kernel<double, 128, true>, (129 * LDA + 2 * M) * sizeof(float));
+        allow_lds(imdct4_kernel<float, 64, true>, (65 * LDA + 2 * M) * sizeof(float));
+        allow_lds(imdct4_kernel<double, 64, true>, (65 * LDA + 2 * M) * sizeof(float));
         attr_done = true;
     }
     {
@@ -481,19 +525,21 @@ static int imdct4_dispatch(const float* spec, int B, int F, int n_fft, const flo
         if (!attr) { allow_lds(imdct4_ct_kernel<MODE_, ST_>, CT_K2_LDS); attr = true; }                                    \
         hipLaunchKernelGGL((imdct4_ct_kernel<MODE_, ST_>), grid, dim3(CT_NT), CT_K2_LDS, st, spec, B, F, window, img, cp, (float*)audio, out_len, sa); \
     } while (0)
-#define MG_K2_CT_S(MODE_) do { if (st4) MG_K2_CT(MODE_, true); else MG_K2_CT(MODE_, false); } while (0)
+#define MG_K2_CT_S(MODE_) do { if (st4 && rows) MG_K2_CT(MODE_, ST_ROWS); else if (st4) MG_K2_CT(MODE_, ST_SEG); else MG_K2_CT(MODE_, ST_NONE); } while (0)
             if (codec == CODEC_RAW) MG_K2_CT_S(CODEC_RAW); else if (codec == CODEC_ARCSINH) MG_K2_CT_S(CODEC_ARCSINH); else MG_K2_CT_S(CODEC_RANGE);
 #undef MG_K2_CT_S
 #undef MG_K2_CT
             MG_CHECK_LAUNCH();
-            g_last_kernel[1] = st4 ? "imdct4_ct_kernel<stitched> (csrc/mdct_ct.h)" : "imdct4_ct_kernel (csrc/mdct_ct.h)";
+            g_last_kernel[1] = st4 ? (rows ? "imdct4_ct_kernel<stitched rows> (csrc/mdct_ct.h)" : "imdct4_ct_kernel<stitched> (csrc/mdct_ct.h)")
+                                   : "imdct4_ct_kernel (csrc/mdct_ct.h)";
             return MG_OK;
         }
     }
-#define MG_IMDCT(T_, FT_)                                                                                            \
-    hipLaunchKernelGGL((imdct4_kernel<T_, FT_>), dim3((F + FT_ - 1) / FT_, B), dim3(256),                            \
+#define MG_IMDCT_R(T_, FT_, ROWS_)                                                                                   \
+    hipLaunchKernelGGL((imdct4_kernel<T_, FT_, ROWS_>), dim3((F + FT_ - 1) / FT_, B), dim3(256),                     \
                        ((FT_ + 1) * LDA + 2 * M) * sizeof(float), st, spec, F, window, dct4, cp, (T_*)audio, out_len, \
                        frames_out, sa)
+#define MG_IMDCT(T_, FT_) do { if (rows) MG_IMDCT_R(T_, FT_, true); else MG_IMDCT_R(T_, FT_, false); } while (0)
     const int ft = frames_per_wg(B, F);
     if (ft == 128) {
         if (out_f64) MG_IMDCT(double, 128); else MG_IMDCT(float, 128);
@@ -503,8 +549,9 @@ static int imdct4_dispatch(const float* spec, int B, int F, int n_fft, const flo
         if (out_f64) MG_IMDCT(double, 32); else MG_IMDCT(float, 32);
     }
 #undef MG_IMDCT
+#undef MG_IMDCT_R
     MG_CHECK_LAUNCH();
-    g_last_kernel[1] = "imdct4_kernel (csrc/mdct.hip)";
+    g_last_kernel[1] = rows ? "imdct4_kernel<stitched rows> (csrc/mdct.hip)" : "imdct4_kernel (csrc/mdct.hip)";
     return MG_OK;
 }
 
@@ -526,6 +573,19 @@ int mg_imdct4_stitched(const float* spec, int B, int F, int n_fft, const float* 
     const int pitch = seg_len - overlap;
     return imdct4_dispatch(spec, B, F, n_fft, window, dct4, dct4_image, codec, gain, nr0, nr1, src_min, src_max, min_b, max_b, out,
                            seg_len, out_f64, nullptr, StitchArgs{first_seg * pitch - overlap, out_total, pitch, overlap}, stream);
+}
+
+// See include/mdctgan_hip.h: mg_imdct4_stitched with a device row table in place of first_seg.
+int mg_imdct4_stitched_rows(const float* spec, int B, int F, int n_fft, const float* window, const float* dct4,
+                            const float* dct4_image, int codec, float gain, float nr0, float nr1, float src_min, float src_max,
+                            const float* min_b, const float* max_b, void* out, long long out_total, int seg_len, int overlap,
+                            const mg_seg_row* rows, int zero_out, int out_f64, void* stream) {
+    if (!out || !rows || seg_len <= 0 || overlap < 0 || 2 * overlap >= seg_len || out_total <= 0) return MG_ERR_ARG;
+    if (zero_out) hipMemsetAsync(out, 0, (size_t)out_total * (out_f64 ? 8 : 4), (hipStream_t)stream);
+    StitchArgs sa{0, out_total, seg_len - overlap, overlap};
+    sa.rows = reinterpret_cast<const SegRow*>(rows);
+    return imdct4_dispatch(spec, B, F, n_fft, window, dct4, dct4_image, codec, gain, nr0, nr1, src_min, src_max, min_b, max_b, out,
+                           seg_len, out_f64, nullptr, sa, stream, true);
 }
 
 const char* mg_mdct_last_kernel(int which) { return g_last_kernel[which == 1 ? 1 : 0]; }
@@ -614,6 +674,23 @@ int mg_stitch_segments(const void* seg, int n_seg, int seg_len, int overlap, voi
     else
         hipLaunchKernelGGL(stitch_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)seg,
                            n_seg, seg_len, overlap, (float*)out, n);
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+}
+
+// See include/mdctgan_hip.h.
+int mg_segments_gather(const float* wave, long long wave_total, const mg_seg_row* rows, int n_rows, int seg_len, float* out,
+                       void* stream) {
+    if (!wave || !rows || !out || wave_total <= 0 || n_rows <= 0 || seg_len <= 0) return MG_ERR_ARG;
+    if (n_rows > 65535) return MG_ERR_UNSUPPORTED;
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const int per_row = (seg_len + 1023) / 1024;
+    const dim3 grid((unsigned)(per_row < 64 ? per_row : 64), (unsigned)n_rows);
+    const SegRow* rt = reinterpret_cast<const SegRow*>(rows);
+    if (seg_len % 4 == 0 && al16(wave) && al16(out))
+        hipLaunchKernelGGL(segments_gather_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, wave, wave_total, rt, seg_len, out);
+    else
+        hipLaunchKernelGGL(segments_gather_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, wave, wave_total, rt, seg_len, out);
     MG_CHECK_LAUNCH();
     return MG_OK;
 }

@@ -270,7 +270,10 @@ constexpr size_t CT_K1_LDS = (size_t)(CT_U1 + CT_YB) * sizeof(float);
 // outside [0, total) are the reference's final crop).  The first and last `overlap` samples of every segment are halved and ADDED
 // (global_atomic_add_f32 into a waveform the caller zeroed: at most two segments meet in a sample and a two-term float sum does
 // not depend on the order, so the result equals F.fold's bit for bit); everything else is a plain 16-byte store.  (StitchArgs: mdct.hip)
-template <int MODE, bool ST = false>
+// ST_ROWS (mg_imdct4_stitched_rows): clip c is row sa.rows[c] of a packed buffer of sa.total samples -- its sample t lands at
+// pos + t and is dropped outside the row's window [lo, hi); a dead row (lo == hi) writes nothing.  A float4 whose position is a
+// multiple of 4 inside the window and outside the cross-fade zones is one 16-byte store, everything else goes sample by sample.
+template <int MODE, int ST = ST_NONE>
 __global__ __launch_bounds__(CT_NT, 4) void imdct4_ct_kernel(const float* __restrict__ spec, int B, int F,
                                                              const float* __restrict__ window, const float* __restrict__ img,
                                                              CodecParams cp, float* __restrict__ audio, int out_len, StitchArgs sa) {
@@ -313,6 +316,8 @@ __global__ __launch_bounds__(CT_NT, 4) void imdct4_ct_kernel(const float* __rest
     load_tile();
     for (int i = 0; i < n_seq; ++i) {
         const int clip = nx_clip, f0 = nx_t * CT_ROWS;
+        SegRow rw{0, 0, 0};                                              // ST_ROWS: the clip's row, once per tile
+        if (ST == ST_ROWS) rw = seg_row_clamped(sa.rows, clip, sa.total);
         // P1: decode into the operand records.  x = v c1 + c0 (= ln10 ((v - nr0) / (nr1 - nr0) (max - min) + min)), X = sinh(x) / gain
         {
             float mn = cp.mn, mx = cp.mx;
@@ -358,6 +363,22 @@ __global__ __launch_bounds__(CT_NT, 4) void imdct4_ct_kernel(const float* __rest
             if (!ST) {
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(bs_v4u, o), r_out,
                                                        ok ? ((unsigned)clip * (unsigned)out_len + (unsigned)t0) * 4u : BS_OOB, 0, 0);
+            } else if (ST == ST_ROWS) {
+                // overlap, out_len % 4 == 0: a float4 is inside or outside a cross-fade zone as a whole; pos, lo, hi are any
+                const long long gi = rw.pos + t0;
+                const bool zone = t0 < sa.overlap || t0 >= out_len - sa.overlap;
+                const bool whole = ok && !zone && (gi & 3) == 0 && gi >= rw.lo && gi + 3 < rw.hi;
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(bs_v4u, o), r_out, whole ? (unsigned)gi * 4u : BS_OOB, 0, 0);
+                if (ok && !whole) {
+                    const float oe[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const long long p = gi + e;
+                        if (p < rw.lo || p >= rw.hi) continue;
+                        if (zone) unsafeAtomicAdd(audio + p, 0.5f * oe[e]);
+                        else audio[p] = oe[e];
+                    }
+                }
             } else {
                 // pitch, overlap, out_len % 4 == 0: a float4 is inside or outside a cross-fade zone / the final crop as a whole
                 const long long gi = sa.base + (long long)clip * sa.pitch + t0;

@@ -30,6 +30,7 @@
 #include <cmath>
 #include <cstdlib>
 #include "common.h"
+#include "mdctgan_hip.h"
 
 namespace {
 
@@ -43,7 +44,8 @@ struct CodecParams {
     const float* mx_b;
     int per_sample;
 };
-struct StitchArgs { long long base, total; int pitch, overlap; };
+struct StitchArgs { union { long long base; const SegRow* rows; }; long long total; int pitch, overlap; };   // as in mdct.hip
+enum Stitch { ST_NONE = 0, ST_SEG = 1, ST_ROWS = 2 };
 constexpr float LN10F = 2.3025851249694824f;   // float32(log(10)), as torch.log(torch.tensor(10.0))
 
 }  // namespace
@@ -270,7 +272,7 @@ __global__ __launch_bounds__(PW_NT) void mdct4_pow2_kernel(const float* __restri
 // K2'.  grid = min(tiles, cap), block = 256.  spec [B, F, M] -> audio [B, out_len] (or the stitched waveform, ST):
 //   out[(h - 1) M + n] = scale (w[n] y_h[n] + w[n + M] y_{h-1}[n + M]),   h = 1 .. F - 1,   y = unfold(DCT-IV(decode(spec)))
 // ------------------------------------------------------------------------------------------------------------------
-template <int M_, int MODE, bool ST, bool VEC>
+template <int M_, int MODE, int ST, bool VEC>
 __global__ __launch_bounds__(PW_NT) void imdct4_pow2_kernel(const float* __restrict__ spec, int B, int F,
                                                             const float* __restrict__ window, const float* __restrict__ twg,
                                                             CodecParams cp, float* __restrict__ audio, int out_len, float scale,
@@ -351,6 +353,23 @@ __global__ __launch_bounds__(PW_NT) void imdct4_pow2_kernel(const float* __restr
                 if (VEC && t0 + 3 < out_len) { *reinterpret_cast<float4*>(dst) = o; continue; }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) if (t0 + e < out_len) dst[e] = oe[e];
+            } else if (ST == ST_ROWS) {
+                // clip b is row sa.rows[b] of a packed buffer: sample t lands at pos + t, dropped outside the row's window [lo, hi)
+                // (a dead row, lo == hi, writes nothing).  VEC: overlap, out_len % 4 == 0 and a 16-byte aligned buffer; the 16-byte
+                // store also needs a position that is a multiple of 4
+                const SegRow rw = seg_row_clamped(sa.rows, b, sa.total);
+                const long long g0 = rw.pos + t0;
+                if (VEC && (g0 & 3) == 0 && t0 >= sa.overlap && t0 + 3 < out_len - sa.overlap && g0 >= rw.lo && g0 + 3 < rw.hi) {
+                    *reinterpret_cast<float4*>(audio + g0) = o;
+                    continue;
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const long long t = t0 + e, gi = g0 + e;
+                    if (t >= out_len || gi < rw.lo || gi >= rw.hi) continue;
+                    if (t < sa.overlap || t >= out_len - sa.overlap) unsafeAtomicAdd(audio + gi, 0.5f * oe[e]);
+                    else audio[gi] = oe[e];
+                }
             } else {
                 // clip b is segment first + b of one waveform: halved and added inside the cross-fade zones, stored elsewhere;
                 // positions outside [0, total) are the reference's final crop.  VEC: pitch, overlap, out_len % 4 == 0 and a
@@ -396,7 +415,7 @@ unsigned pw_grid(long long n_tiles) { return (unsigned)(n_tiles < 2048 ? n_tiles
 
 int imdct4_pow2_dispatch(const float* spec, int B, int F, int n_fft, const float* window, const float* tw, int codec, float gain,
                          float nr0, float nr1, float src_min, float src_max, const float* min_b, const float* max_b, void* audio,
-                         int out_len, int out_f64, float scale, StitchArgs sa, void* stream);
+                         int out_len, int out_f64, float scale, StitchArgs sa, void* stream, bool row_table = false);
 
 }  // namespace
 
@@ -483,13 +502,26 @@ int mg_imdct4_pow2_stitched(const float* spec, int B, int F, int n_fft, const fl
                                 stream);
 }
 
+int mg_imdct4_pow2_stitched_rows(const float* spec, int B, int F, int n_fft, const float* window, const float* twiddles, int codec,
+                                 float gain, float nr0, float nr1, float src_min, float src_max, const float* min_b,
+                                 const float* max_b, void* out, long long out_total, int seg_len, int overlap,
+                                 const mg_seg_row* rows, int zero_out, int out_f64, void* stream) {
+    if (!out || !rows || seg_len <= 0 || overlap < 0 || 2 * overlap >= seg_len || out_total <= 0) return MG_ERR_ARG;
+    if (out_f64 || !pw_size_ok(n_fft)) return MG_ERR_UNSUPPORTED;           // (before the clear: a refused call leaves `out` alone)
+    if (zero_out) hipMemsetAsync(out, 0, (size_t)out_total * 4, (hipStream_t)stream);
+    StitchArgs sa{0, out_total, seg_len - overlap, overlap};
+    sa.rows = reinterpret_cast<const SegRow*>(rows);
+    return imdct4_pow2_dispatch(spec, B, F, n_fft, window, twiddles, codec, gain, nr0, nr1, src_min, src_max, min_b, max_b, out,
+                                seg_len, out_f64, 4.0f / (float)n_fft, sa, stream, true);
+}
+
 }  // extern "C"
 
 namespace {
 
 int imdct4_pow2_dispatch(const float* spec, int B, int F, int n_fft, const float* window, const float* tw, int codec, float gain,
                          float nr0, float nr1, float src_min, float src_max, const float* min_b, const float* max_b, void* audio,
-                         int out_len, int out_f64, float scale, StitchArgs sa, void* stream) {
+                         int out_len, int out_f64, float scale, StitchArgs sa, void* stream, bool row_table) {
     if (!spec || !window || !tw || !audio || B <= 0 || F <= 1 || ((min_b == nullptr) != (max_b == nullptr))) return MG_ERR_ARG;
     if (!pw_size_ok(n_fft)) return MG_ERR_UNSUPPORTED;
     if (out_len <= 0 || (long long)out_len > (long long)(F - 1) * (n_fft / 2)) return MG_ERR_ARG;
@@ -508,7 +540,10 @@ int imdct4_pow2_dispatch(const float* spec, int B, int F, int n_fft, const float
                            tw, cp, (float*)audio, out_len, scale, sa);                                                     \
     } while (0)
 #define MG_PW_K2_V(M_, MODE_, ST_) do { if (vec) MG_PW_K2(M_, MODE_, ST_, true); else MG_PW_K2(M_, MODE_, ST_, false); } while (0)
-#define MG_PW_K2_S(M_, MODE_) do { if (stitched) MG_PW_K2_V(M_, MODE_, true); else MG_PW_K2_V(M_, MODE_, false); } while (0)
+#define MG_PW_K2_S(M_, MODE_)                                                                                              \
+    do {                                                                                                                   \
+        if (row_table) MG_PW_K2_V(M_, MODE_, ST_ROWS); else if (stitched) MG_PW_K2_V(M_, MODE_, ST_SEG); else MG_PW_K2_V(M_, MODE_, ST_NONE); \
+    } while (0)
 #define MG_PW_K2_C(M_)                                                                                                     \
     do {                                                                                                                   \
         if (codec == CODEC_RAW) MG_PW_K2_S(M_, CODEC_RAW);                                                                 \
@@ -521,7 +556,8 @@ int imdct4_pow2_dispatch(const float* spec, int B, int F, int n_fft, const float
 #undef MG_PW_K2_V
 #undef MG_PW_K2
     MG_CHECK_LAUNCH();
-    mg_mdct_note_kernel(1, stitched ? "imdct4_pow2_kernel<stitched> (csrc/mdct_pow2.hip)" : "imdct4_pow2_kernel (csrc/mdct_pow2.hip)");
+    mg_mdct_note_kernel(1, row_table ? "imdct4_pow2_kernel<stitched rows> (csrc/mdct_pow2.hip)"
+                           : stitched ? "imdct4_pow2_kernel<stitched> (csrc/mdct_pow2.hip)" : "imdct4_pow2_kernel (csrc/mdct_pow2.hip)");
     return MG_OK;
 }
 

@@ -6,11 +6,21 @@ the decoder itself: batches of low-rate segments go through ``model.inference`` 
 segment at its place in the stitched waveform, cross-fade included (``mg_imdct4_stitched``, ``mg_imdct4_pow2_stitched`` at
 n_fft 256 / 1024 / 2048); codec geometries neither covers decode per batch and one gather kernel (``mg_stitch_segments``) stitches.  Dataset loading, resampling and the
 metrics of ``util.compute_matrics`` are outside the hot path.
+
+Many short utterances (``generate_many``, ``make_graphed_generate_many``): the segments of any number of waveforms share the
+generator's batches.  Every waveform sits at an aligned start of one packed input buffer and one packed output buffer, and two
+device row tables (``mg_seg_row``: position, window) say where each batch row reads and writes: one gather launch per batch cuts
+the segments (``mg_segments_gather``), and the row-table decode (``mg_imdct4_stitched_rows``, ``mg_imdct4_pow2_stitched_rows``)
+stitches every utterance in its own window.  The launch topology does not depend on the mix of lengths, so one captured graph
+serves them all.
 """
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
+from typing import List
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -106,4 +116,260 @@ def make_graphed_generate(model, lr_segments: torch.Tensor, batch_size: int = 64
         graph.replay()
         return out
     run.graph, run.pinned = graph, pinned
+    return run
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Many utterances of different lengths in shared batches
+# ---------------------------------------------------------------------------------------------------------------------
+@dataclass
+class UtterancePlan:
+    """plan_utterances' result.  Per utterance: `segments` (segment_audio's count), `in_start` / `out_start` (first sample in the
+    packed input / output buffer) and `out_length` (mg_stitch_length of its segments).  `in_rows` / `out_rows`: the mg_seg_row
+    tables (int64 [n_rows, 3] = pos, lo, hi) in batch order -- utterance after utterance, segment after segment, then the dead
+    rows (lo == hi) that fill the last batch.  `in_total` / `out_total`: samples of the packed buffers."""
+    segment_length: int
+    out_segment_length: int
+    gen_overlap: int
+    batch_size: int
+    lengths: List[int]
+    segments: List[int]
+    in_start: List[int]
+    out_start: List[int]
+    out_length: List[int]
+    in_rows: np.ndarray
+    out_rows: np.ndarray
+    in_total: int
+    out_total: int
+    n_live: int
+
+    @property
+    def n_batches(self) -> int:
+        return self.in_rows.shape[0] // self.batch_size
+
+    @property
+    def live_fraction(self) -> float:
+        return self.n_live / float(self.in_rows.shape[0])
+
+
+def stitch_length(n_seg: int, seg_len: int, overlap: int) -> int:
+    """mg_stitch_length on the host (generate_audio.py:40-53: concatenation, or fold at stride seg_len - overlap and the crop)."""
+    if n_seg <= 0 or seg_len <= 0 or overlap < 0 or 2 * overlap >= seg_len:
+        return -1
+    return n_seg * seg_len if overlap == 0 else (n_seg - 1) * (seg_len - overlap) + seg_len - 2 * overlap
+
+
+def plan_utterances(lengths, segment_length: int, out_segment_length: int, gen_overlap: int, batch_size: int,
+                    align: int = 64) -> UtterancePlan:
+    """Where every segment of every utterance reads and writes (host only: no device call).
+
+    An utterance of `length` samples has segment_audio's segments: ceil(length / L) * L samples plus gen_overlap zeros on both
+    sides, cut at stride L - gen_overlap (segment k starts at k (L - gen_overlap) - gen_overlap of the waveform), or the single
+    segment [0, L) when it is shorter than L.  Its stitched output has mg_stitch_length(segments, out_segment_length, gen_overlap)
+    samples; segment k starts at k (L_out - gen_overlap) - gen_overlap of it.  Starts in both packed buffers are rounded up to
+    `align` samples, so a row's position keeps the alignment it has for a single utterance (the 16-byte paths of the kernels)."""
+    L, Lo, ov, bs = int(segment_length), int(out_segment_length), int(gen_overlap), int(batch_size)
+    lengths = [int(n) for n in lengths]
+    if L <= 0 or Lo <= 0 or bs <= 0 or align <= 0:
+        raise ValueError("segment_length, out_segment_length, batch_size and align must be positive")
+    if ov < 0 or ov >= L or 2 * ov >= Lo:
+        raise ValueError("gen_overlap must be in [0, segment_length) and below half a decoded segment")
+    if not lengths or min(lengths) <= 0:
+        raise ValueError("plan_utterances needs at least one utterance, each of at least one sample")
+    up = lambda n: -(-n // align) * align
+    segments, in_start, out_start, out_length, in_rows, out_rows = [], [], [], [], [], []
+    in_pos = out_pos = 0
+    for n in lengths:
+        if n >= L:
+            n_seg = (-(-n // L) * L + 2 * ov - L) // (L - ov) + 1
+            front = ov
+        else:
+            n_seg, front = 1, 0                 # (the short waveform is padded behind only)
+        total = stitch_length(n_seg, Lo, ov)
+        segments.append(n_seg)
+        in_start.append(in_pos)
+        out_start.append(out_pos)
+        out_length.append(total)
+        for k in range(n_seg):
+            in_rows.append((in_pos + k * (L - ov) - front, in_pos, in_pos + n))
+            out_rows.append((out_pos + k * (Lo - ov) - ov, out_pos, out_pos + total))
+        in_pos, out_pos = up(in_pos + n), up(out_pos + total)
+    n_live = len(in_rows)
+    dead = -n_live % bs
+    in_rows += [(0, 0, 0)] * dead
+    out_rows += [(0, 0, 0)] * dead
+    return UtterancePlan(L, Lo, ov, bs, lengths, segments, in_start, out_start, out_length,
+                         np.asarray(in_rows, dtype=np.int64).reshape(-1, 3), np.asarray(out_rows, dtype=np.int64).reshape(-1, 3),
+                         in_pos, out_pos, n_live)
+
+
+def check_capacity(plan: UtterancePlan, max_segments: int, max_samples: int) -> None:
+    """What make_graphed_generate_many's run() asks before it copies anything: the mix fits the captured batches
+    (ceil(max_segments / batch_size) of them) and its waveforms the packed input buffer (max_samples in all)."""
+    cap = -(-int(max_segments) // plan.batch_size)
+    if plan.n_batches > cap:
+        raise ValueError("%d segments (%d batches of %d) do not fit the %d captured batches (max_segments=%d)"
+                         % (plan.n_live, plan.n_batches, plan.batch_size, cap, max_segments))
+    if sum(plan.lengths) > int(max_samples):
+        raise ValueError("%d samples do not fit the packed input buffer (max_samples=%d)" % (sum(plan.lengths), max_samples))
+
+
+def _decoded_segment_length(pre, segment_length: int) -> int:
+    hop = pre.n_fft // 2
+    return -(-segment_length // hop) * hop          # (mg_mdct4_num_frames(T, n_fft) - 1) * hop
+
+
+def _fused_many(model) -> bool:
+    return bool(getattr(model.preprocess, "has_stitched_decoder", False)) and os.environ.get("MG_NO_STITCHED_K2") != "1"
+
+
+def _pack_waves(waves, plan: UtterancePlan, device, out=None) -> torch.Tensor:
+    """The packed input buffer: every waveform at its aligned start, written once -- one concatenation straight into `out`
+    (a device buffer of at least plan.in_total samples; default: a new one).  A list of host waveforms is concatenated on the
+    host and travels in one copy; a list that mixes devices is moved to `device` waveform by waveform."""
+    device = torch.device(device)
+    buf = torch.empty(plan.in_total, dtype=torch.float32, device=device) if out is None else out[:plan.in_total]
+    flat = [w.reshape(-1) for w in waves]
+    on_host = all(w.device.type == "cpu" for w in flat)
+    where = torch.device("cpu") if on_host else device
+    gap = torch.zeros(max(int(s1 - s0 - n) for s0, s1, n in
+                          zip(plan.in_start, plan.in_start[1:] + [plan.in_total], plan.lengths)) or 1,
+                      dtype=torch.float32, device=where)
+    parts = []
+    for w, s0, s1 in zip(flat, plan.in_start, plan.in_start[1:] + [plan.in_total]):
+        parts.append(w.to(device=where, dtype=torch.float32))
+        if s1 - s0 > w.numel():
+            parts.append(gap[:s1 - s0 - w.numel()])
+    if on_host and device.type != "cpu":
+        buf.copy_(torch.cat(parts), non_blocking=True)
+    else:
+        torch.cat(parts, out=buf)
+    return buf
+
+
+def _plan_for(model, waves, batch_size, gen_overlap, segment_length):
+    if len(waves) == 0:
+        raise ValueError("no waveforms")
+    L = int(segment_length if segment_length is not None else model.opt.segment_length)
+    if any(w.numel() == 0 for w in waves):
+        raise ValueError("an empty waveform has no segments")
+    return plan_utterances([w.numel() for w in waves], L, _decoded_segment_length(model.preprocess, L), gen_overlap, batch_size)
+
+
+def _views(out, plan: UtterancePlan):
+    return [out[s:s + n].view(1, -1) for s, n in zip(plan.out_start, plan.out_length)]
+
+
+def generate_many(model, waves, batch_size: int = 64, gen_overlap: int = 0, pad_batches: bool = False, segment_length=None):
+    """Whole-utterance inference over a list of low-rate waveforms ([T_u] or [1, T_u]) of any lengths, their segments sharing the
+    generator's batches -> list of stitched super-resolved waveforms [1, total_u] (views of one packed buffer), each what
+    generate(model, segment_audio(wave_u, ...), ...) stitches from the same generator outputs.  Per batch: one gather launch
+    (mg_segments_gather), model.inference, and its row-table decode that writes every utterance's window of the packed output.
+    pad_batches: every batch runs at the full batch_size (dead rows are zero segments and write nothing); otherwise the last batch
+    runs at its live size.  Codec geometries without a stitched decoder (or MG_NO_STITCHED_K2=1) decode per batch and stitch every
+    utterance with ops.stitch_segments.  segment_length: the model's --segment_length by default.
+    The factored n_fft-512 decode addresses its output with 32 bits: a packed output of 2^30 - 2^14 samples or more (about six
+    hours at 48 kHz; plan.out_total) still decodes correctly, but on the slower generic kernel (mg_mdct_last_kernel(1) names it)
+    -- split a larger corpus into several calls."""
+    from .mdct import seg_row_table, segments_gather
+    plan = _plan_for(model, waves, batch_size, gen_overlap, segment_length)
+    dev = next(model.netG.parameters()).device
+    packed = _pack_waves(waves, plan, dev)
+    tables = seg_row_table(np.stack([plan.in_rows, plan.out_rows]), dev).view(2, -1, 3)
+    fused = _fused_many(model)
+    # (zeros: the cross-fade zones are added into the buffer, and the alignment gaps between utterances are never written)
+    out = torch.zeros(plan.out_total, dtype=torch.float32, device=dev) if fused else None
+    outs = []
+    bs = plan.batch_size
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for r0 in range(0, plan.n_live, bs):
+                nb = bs if pad_batches else min(bs, plan.n_live - r0)
+                segs = segments_gather(packed, tables[0, r0:r0 + nb], plan.segment_length)
+                if fused:
+                    model.inference(segs, rows=(out, gen_overlap, tables[1, r0:r0 + nb], plan.out_segment_length, False))
+                else:
+                    outs.append(model.inference(segs)[1][:min(bs, plan.n_live - r0)])
+    finally:
+        model.train(was_training)
+    if fused:
+        return _views(out, plan)
+    audio = torch.cat(outs, dim=0)                      # [n_live, 1, 1, T]
+    first = np.concatenate([[0], np.cumsum(plan.segments)])
+    return [ops.stitch_segments(audio[first[u]:first[u + 1]], audio.shape[-1], gen_overlap) for u in range(len(waves))]
+
+
+def make_graphed_generate_many(model, max_segments: int, max_samples: int, batch_size: int = 64, gen_overlap: int = 0,
+                               warmup: int = 2, segment_length=None):
+    """Capture generate_many(pad_batches=True) for ANY mix of utterances of at most max_segments segments and max_samples samples
+    in all into one hipGraph -- ceil(max_segments / batch_size) iterations of gather, generator and row-table decode in one linear
+    chain, over static packed buffers and static row tables -- and return run(waves) -> list of [1, total_u] views of the static
+    output (the next replay overwrites them; run.last keeps the latest list).  run copies the packed samples and the new tables and replays; batches past the mix
+    run on dead rows.  A mix that does not fit raises ValueError before anything is copied.  The weights must not change between
+    capture and replay (see make_graphed_generate: the guard and the pinned Winograd images are the same)."""
+    from .mdct import seg_row_table, segments_gather
+    pre = model.preprocess
+    if not _fused_many(model):
+        raise NotImplementedError("make_graphed_generate_many needs a codec geometry with a stitched decoder")
+    L = int(segment_length if segment_length is not None else model.opt.segment_length)
+    Lo, bs, align = _decoded_segment_length(pre, L), int(batch_size), 64
+    plan_utterances([L], L, Lo, gen_overlap, bs, align)                 # (validates the geometry)
+    n_batches = -(-int(max_segments) // bs)
+    if n_batches <= 0 or max_samples <= 0:
+        raise ValueError("max_segments and max_samples must be positive")
+    n_rows = n_batches * bs
+    dev = next(model.netG.parameters()).device
+    # every utterance has at least one segment and wastes less than `align` samples in front of the next start
+    static_in = torch.zeros(int(max_samples) + n_rows * align, dtype=torch.float32, device=dev)
+    static_out = torch.zeros(n_rows * (Lo + align), dtype=torch.float32, device=dev)
+    static_rows = torch.zeros(2, n_rows, 3, dtype=torch.int64, device=dev)          # all dead
+    static_segs = torch.empty(bs, L, dtype=torch.float32, device=dev)
+
+    def body():
+        for b in range(n_batches):
+            segments_gather(static_in, static_rows[0, b * bs:(b + 1) * bs], L, out=static_segs)
+            # (the first batch clears the whole output when the cross-fade zones are added into it)
+            model.inference(static_segs, rows=(static_out, gen_overlap, static_rows[1, b * bs:(b + 1) * bs], Lo,
+                                               b == 0 and gen_overlap > 0))
+
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(max(warmup, 1)):
+                    body()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                body()
+    finally:
+        model.train(was_training)
+
+    # as in make_graphed_generate: pin the transformed-weight images the captured launches point at, refuse to replay once the
+    # weights have moved
+    params = list(model.netG.parameters())
+    pinned = [getattr(p, "_mg_u_cache", None) for p in params]
+    stamp = (Fh.WEIGHT_EPOCH[0], tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
+
+    def run(waves):
+        now = (Fh.WEIGHT_EPOCH[0], tuple(p._version for p in params), tuple(p.data_ptr() for p in params))
+        if now != stamp:
+            raise RuntimeError("the generator's weights changed after make_graphed_generate_many() captured them "
+                               "(optimizer step / load_state_dict): capture again")
+        plan = _plan_for(model, waves, bs, gen_overlap, L)
+        check_capacity(plan, max_segments, max_samples)
+        rows = np.zeros((2, n_rows, 3), dtype=np.int64)
+        rows[0, :plan.in_rows.shape[0]], rows[1, :plan.out_rows.shape[0]] = plan.in_rows, plan.out_rows
+        _pack_waves(waves, plan, dev, out=static_in)
+        static_rows.copy_(seg_row_table(rows).view(2, n_rows, 3), non_blocking=True)
+        graph.replay()
+        run.last = _views(static_out, plan)
+        return run.last
+    run.graph, run.pinned, run.last = graph, pinned, None
     return run

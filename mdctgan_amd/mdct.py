@@ -236,18 +236,38 @@ def mdct4_codec(audio, window, dct4, n_fft, *, codec=_lib.MG_CODEC_RAW, gain=1.0
 
 def imdct4_codec(spec, window, dct4, n_fft, *, codec=_lib.MG_CODEC_RAW, gain=1.0, norm_range=(0.0, 1.0),
                  src_range=(0.0, 1.0), min_b=None, max_b=None, out_length=None, out_dtype=torch.float32,
-                 want_frames=False, stitch=None):
+                 want_frames=False, stitch=None, rows=None):
     """K2 launcher.  spec [B, F, M] (device) -> (audio [B, T_out], frames|None).
 
     stitch = (out, gen_overlap, first_seg[, segment_length]): the clips are segments first_seg.. of ONE waveform and K2's overlap-add store writes them
     straight into `out` [mg_stitch_length(n_seg, T_out, gen_overlap)] with generate_audio.py:40-53's cross-fade (mg_imdct4_stitched);
-    returns (out, None).  The batch with first_seg == 0 clears `out` when gen_overlap > 0."""
+    returns (out, None).  The batch with first_seg == 0 clears `out` when gen_overlap > 0.
+
+    rows = (out, gen_overlap, table[, segment_length[, zero_out]]): the clips are the rows of a device row table (seg_row_table: one
+    (pos, lo, hi) per clip) of the packed buffer `out` that holds any number of stitched waveforms (mg_imdct4_stitched_rows);
+    returns (out, None).  zero_out (default False) clears the whole of `out` first."""
     lib = _lib.load()
     spec = _lib.f32c(spec)
     B, F, M = spec.shape
     t_out = (F - 1) * M
     if out_length is not None:
         t_out = min(t_out, int(out_length))
+    if rows is not None:
+        if stitch is not None:
+            raise ValueError("stitched K2: either stitch or rows")
+        out, overlap, table = rows[:3]
+        _check_rows(rows, table, B, t_out, "K2")
+        if want_frames or out.dtype != out_dtype or not out.is_contiguous():
+            raise ValueError("stitched K2: contiguous output of the requested dtype, no synthesis frames")
+        if min_b is not None:
+            min_b, max_b = _lib.f32c(min_b.reshape(-1)), _lib.f32c(max_b.reshape(-1))
+            assert min_b.numel() == B and max_b.numel() == B
+        rc = lib.mg_imdct4_stitched_rows(_lib.ptr(spec), B, F, n_fft, _lib.ptr(window), _lib.ptr(dct4), dct4_image(dct4, M), codec,
+                                         gain, norm_range[0], norm_range[1], src_range[0], src_range[1], _lib.ptr(min_b),
+                                         _lib.ptr(max_b), _lib.ptr(out), out.numel(), t_out, int(overlap), _lib.ptr(table),
+                                         int(bool(rows[4])) if len(rows) > 4 else 0, int(out_dtype == torch.float64), _lib.stream())
+        _lib.check(rc, "mg_imdct4_stitched_rows")
+        return out, None
     if stitch is not None:
         out, overlap, first = stitch[:3]
         if len(stitch) > 3 and int(stitch[3]) != t_out:
@@ -277,6 +297,37 @@ def imdct4_codec(spec, window, dct4, n_fft, *, codec=_lib.MG_CODEC_RAW, gain=1.0
                                _lib.ptr(frames), _lib.stream())
     _lib.check(rc, "mg_imdct4_forward")
     return audio, frames
+
+
+def _check_rows(rows, table, B, t_out, what):
+    """The row-table form of a stitched decode: an int64 [B, 3] device table, segments of the length the caller planned for."""
+    if table.dtype != torch.int64 or tuple(table.shape) != (B, 3) or not table.is_contiguous():
+        raise ValueError("stitched %s: the row table is a contiguous int64 [%d, 3] tensor (pos, lo, hi), got %s %s"
+                         % (what, B, table.dtype, tuple(table.shape)))
+    if len(rows) > 3 and rows[3] is not None and int(rows[3]) != t_out:
+        raise ValueError("stitched %s: the output was sized for %d-sample segments, the spectrogram decodes to %d"
+                         % (what, int(rows[3]), t_out))
+
+
+def seg_row_table(rows, device=None) -> torch.Tensor:
+    """mg_seg_row array from a sequence of (pos, lo, hi): an int64 [n, 3] tensor (on `device` when given)."""
+    t = torch.as_tensor(rows, dtype=torch.int64).reshape(-1, 3).contiguous()
+    return t if device is None else t.to(device)
+
+
+def segments_gather(wave, table, segment_length: int, out=None):
+    """mg_segments_gather: packed waveform [total] + row table [n, 3] -> [n, segment_length] (zeros outside each row's window)."""
+    lib = _lib.load()
+    wave = _lib.f32c(wave).reshape(-1)
+    n = table.shape[0]
+    _check_rows((), table, n, segment_length, "gather")
+    if out is None:
+        out = torch.empty(n, segment_length, dtype=torch.float32, device=wave.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (n, segment_length) or not out.is_contiguous():
+        raise ValueError("segments_gather: out is a contiguous float32 [%d, %d] tensor" % (n, segment_length))
+    _lib.check(lib.mg_segments_gather(_lib.ptr(wave), wave.numel(), _lib.ptr(table), n, int(segment_length), _lib.ptr(out),
+                                      _lib.stream()), "mg_segments_gather")
+    return out
 
 
 _UNSUPPORTED = -2       # MG_ERR_UNSUPPORTED: the fused backward's guards failed, the generic composition runs
@@ -349,11 +400,11 @@ def mdct4_pow2(audio, window, n_fft, F=None, *, codec=_lib.MG_CODEC_RAW, gain=1.
 
 
 def imdct4_pow2(spec, window, n_fft, *, codec=_lib.MG_CODEC_RAW, gain=1.0, norm_range=(0.0, 1.0), src_range=(0.0, 1.0),
-                min_b=None, max_b=None, out_length=None, scale=None, stitch=None):
+                min_b=None, max_b=None, out_length=None, scale=None, stitch=None, rows=None):
     """K2' launcher.  spec [B, F, n_fft/2] -> audio [B, T_out] (scale: in place of the transform's 4 / n_fft), or the stitched
     waveform (stitch as in imdct4_codec, plus an optional fifth element zero_out -- default: first_seg == 0 -- for callers that
-    clear `out` themselves and hand the batches over in another order); None where the kernel's guards refuse and nothing has
-    been written."""
+    clear `out` themselves and hand the batches over in another order; or rows as in imdct4_codec: mg_imdct4_pow2_stitched_rows);
+    None where the kernel's guards refuse and nothing has been written."""
     lib = _lib.load()
     spec = _lib.f32c(spec)
     B, F, M = spec.shape
@@ -364,6 +415,19 @@ def imdct4_pow2(spec, window, n_fft, *, codec=_lib.MG_CODEC_RAW, gain=1.0, norm_
     if min_b is not None:
         min_b, max_b = _lib.f32c(min_b.reshape(-1)), _lib.f32c(max_b.reshape(-1))
         assert min_b.numel() == B and max_b.numel() == B
+    if rows is not None:
+        if stitch is not None:
+            raise ValueError("stitched K2': either stitch or rows")
+        out, overlap, table = rows[:3]
+        _check_rows(rows, table, B, t_out, "K2'")
+        if out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("stitched K2': contiguous float32 output")
+        rc = lib.mg_imdct4_pow2_stitched_rows(_lib.ptr(spec), B, F, n_fft, _lib.ptr(window), _lib.ptr(tw), codec, gain, norm_range[0],
+                                              norm_range[1], src_range[0], src_range[1], _lib.ptr(min_b), _lib.ptr(max_b),
+                                              _lib.ptr(out), out.numel(), t_out, int(overlap), _lib.ptr(table),
+                                              int(bool(rows[4])) if len(rows) > 4 else 0, 0, _lib.stream())
+        _lib.check(rc, "mg_imdct4_pow2_stitched_rows")
+        return out
     if stitch is not None:
         out, overlap, first = stitch[:3]
         if len(stitch) > 3 and int(stitch[3]) != t_out:

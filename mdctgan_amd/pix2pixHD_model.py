@@ -251,18 +251,21 @@ class Audio2MDCT(torch.nn.Module):
                             max_b=mx if per_sample else None, fused=self.geom512, fast=self.fast)
         return g.view(log_spectro.shape)
 
-    def to_audio(self, log_spectro: torch.Tensor, norm_param: Dict[str, torch.Tensor], pha: torch.Tensor = None, stitch=None):
+    def to_audio(self, log_spectro: torch.Tensor, norm_param: Dict[str, torch.Tensor], pha: torch.Tensor = None, stitch=None,
+                 rows=None):
         """pix2pixHD_model.py:139-165.  stitch = (out, gen_overlap, first_seg) (has_stitched_decoder only): K2 / K2' writes the segments
         straight into the stitched waveform `out` (generate_audio.py:40-53 inside the kernel) and `out` is returned.
+        rows = (out, gen_overlap, table[, segment_length[, zero_out]]) (has_stitched_decoder only): the segments are the rows of a
+        device row table of the packed buffer `out`, which holds the stitched waveforms of any number of utterances (mdct.imdct4_codec).
         Differentiable in log_spectro (arcsinh / range codecs; stitched decode stays forward-only)."""
         mn, mx = norm_param["min"], norm_param["max"]
-        if stitch is None and wants_grad(log_spectro, mn, mx):
+        if stitch is None and rows is None and wants_grad(log_spectro, mn, mx):
             return CodecGrad.apply(lambda s: self._to_audio(s, norm_param, pha, None),
                                    lambda g, s, _: self._to_audio_backward(g, s, norm_param), log_spectro, mn, mx)
-        return self._to_audio(log_spectro, norm_param, pha, stitch)
+        return self._to_audio(log_spectro, norm_param, pha, stitch, rows)
 
-    def _to_audio(self, log_spectro, norm_param, pha, stitch):
-        if stitch is not None and not self.has_stitched_decoder:
+    def _to_audio(self, log_spectro, norm_param, pha, stitch, rows=None):
+        if (stitch is not None or rows is not None) and not self.has_stitched_decoder:
             raise NotImplementedError("stitched decode needs the fused 512 / 256 geometry")
         nr, sr = self._ranges()
         mn, mx = norm_param["min"], norm_param["max"]
@@ -274,15 +277,16 @@ class Audio2MDCT(torch.nn.Module):
             spec = log_spectro.squeeze(1) if log_spectro.dim() == 4 else log_spectro
             audio, _ = imdct4_codec(spec, window, d4, self.n_fft, codec=self.codec, gain=float(self.arcsinh_gain),
                                     norm_range=nr, src_range=sr, min_b=mn if per_sample else None,
-                                    max_b=mx if per_sample else None, stitch=stitch)
-            return audio if stitch is not None else audio[:, None, None, :]
+                                    max_b=mx if per_sample else None, stitch=stitch, rows=rows)
+            return audio if (stitch is not None or rows is not None) else audio[:, None, None, :]
         if self.fast_codec:
             window = self._window(log_spectro.device)
             spec = log_spectro.squeeze(1) if log_spectro.dim() == 4 else log_spectro
             audio = imdct4_pow2(spec, window, self.n_fft, codec=self.codec, gain=float(self.arcsinh_gain), norm_range=nr,
-                                src_range=sr, min_b=mn if per_sample else None, max_b=mx if per_sample else None, stitch=stitch)
+                                src_range=sr, min_b=mn if per_sample else None, max_b=mx if per_sample else None, stitch=stitch,
+                                rows=rows)
             if audio is not None:
-                return audio if stitch is not None else audio[:, None, None, :]
+                return audio if (stitch is not None or rows is not None) else audio[:, None, None, :]
         spec4 = log_spectro if log_spectro.dim() == 4 else log_spectro[:, None]
         raw = codec_inverse(spec4, codec=self.codec, gain=float(self.arcsinh_gain), alpha=float(self.alpha),
                             min_value=float(self.min_value), norm_range=nr, src_range=sr,
@@ -687,8 +691,9 @@ class Pix2PixHDModel(BaseModel):
             return eager
         return run
 
-    def inference(self, lr_audio, stitch=None):
-        """pix2pixHD_model.py:618-638.  stitch: see Audio2MDCT.to_audio (sr_audio is then the stitched waveform)."""
+    def inference(self, lr_audio, stitch=None, rows=None):
+        """pix2pixHD_model.py:618-638.  stitch / rows: see Audio2MDCT.to_audio (sr_audio is then the stitched waveform / the packed
+        buffer of stitched waveforms)."""
         self._finish_pending()
         with torch.no_grad():
             lr_spectro, lr_pha, lr_norm_param = self.preprocess.forward(lr_audio)
@@ -697,7 +702,7 @@ class Pix2PixHDModel(BaseModel):
                 lr_part = int(sr_spectro.size(-1) / self.preprocess.up_ratio)
                 sr_spectro[..., :lr_part] *= 1e-3
                 sr_spectro = Fh.add(sr_spectro, lr_spectro)
-            sr_audio = self.preprocess.to_audio(sr_spectro, lr_norm_param, lr_pha, stitch=stitch)
+            sr_audio = self.preprocess.to_audio(sr_spectro, lr_norm_param, lr_pha, stitch=stitch, rows=rows)
         return sr_spectro, sr_audio, lr_pha, lr_norm_param, lr_spectro
 
     # -- bookkeeping ----------------------------------------------------------------------------
