@@ -18,15 +18,96 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
   1024 / 2048, e.g. the class default) run the fused kernels K1' / K2' of csrc/mdct_pow2.hip (TDAC fold + DCT-IV as an
   n_fft/4-point FFT in LDS) -- the ``.fast`` attribute; ``.fused`` keeps naming the 512 kernels only.  MG_MDCT_POW2=0 (read at call
   time) sends them back to the generic path.
+
+Layout: the leaf launchers (one per kernel: mdct4_codec / imdct4_codec = K1 / K2, mdct4_pow2 / imdct4_pow2 = K1' / K2', mdct4_generic /
+imdct4_generic, codec_forward / codec_inverse / codec_backward) make the ABI calls; which of them serves a request is decided in one place,
+``Transform.route_analysis`` / ``Transform.route_synthesis`` (pure host functions), and ``Transform.analysis`` / ``synthesis`` / ``*_backward``
+run the route.  MDCT4, IMDCT4 and Audio2MDCT are shells around one Transform.  The codec's constants travel as one ``Codec`` record, a
+stitched decode's destination as one ``Stitch`` / ``Rows`` record.
 """
 from __future__ import annotations
 
 import math
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
 from . import _lib
+
+_FUSABLE = (_lib.MG_CODEC_RAW, _lib.MG_CODEC_ARCSINH, _lib.MG_CODEC_RANGE)        # the codecs K1 / K2 / K1' / K2' carry inside
+
+
+class Codec(NamedTuple):
+    """The codec block of the C ABI: the mode (MG_CODEC_*) and its constants.  ``codec._replace(src_range=...)`` for a per-call range."""
+    mode: int = _lib.MG_CODEC_RAW
+    gain: float = 1.0
+    alpha: float = 0.6
+    min_value: float = 1e-7
+    norm_range: tuple = (0.0, 1.0)
+    src_range: tuple = (0.0, 1.0)
+
+    def kw(self, full=False):
+        """The record as the leaf launchers' keywords (full: with the dB codec's alpha / min_value, for codec_forward / codec_inverse)."""
+        kw = dict(codec=self.mode, gain=self.gain, norm_range=self.norm_range, src_range=self.src_range)
+        return dict(kw, alpha=self.alpha, min_value=self.min_value) if full else kw
+
+
+RAW = Codec()
+
+
+def _per_clip(min_b, max_b, n):
+    """Per-clip (min, max) of a decode as flat contiguous float32 [n] tensors (None, None: the codec's fixed src_range)."""
+    if min_b is None:
+        return None, None
+    min_b, max_b = _lib.f32c(min_b.reshape(-1)), _lib.f32c(max_b.reshape(-1))
+    assert min_b.numel() == n and max_b.numel() == n
+    return min_b, max_b
+
+
+class Stitch(NamedTuple):
+    """Destination of a stitched decode: the clips are segments first_seg.. of ONE waveform `out` [mg_stitch_length(n_seg, T_out,
+    overlap)].  segment_length: what `out` was sized for (checked).  zero_out: clear `out` first when overlap > 0 (None: first_seg == 0)."""
+    out: torch.Tensor
+    overlap: int
+    first_seg: int
+    segment_length: Optional[int] = None
+    zero_out: Optional[bool] = None
+
+
+class Rows(NamedTuple):
+    """Destination of a row-table decode: the clips are the rows of a device row table (seg_row_table: one (pos, lo, hi) per clip) of the
+    packed buffer `out`, which holds any number of stitched waveforms.  zero_out clears the whole of `out` first."""
+    out: torch.Tensor
+    overlap: int
+    table: torch.Tensor
+    segment_length: Optional[int] = None
+    zero_out: bool = False
+
+
+def _destination(stitch, rows, B, t_out, out_dtype, want_frames, what):
+    """The validated destination of a stitched decode (a Stitch, a Rows, or None for a plain decode); `what` names the kernel."""
+    if stitch is None and rows is None:
+        return None
+    if stitch is not None and rows is not None:
+        raise ValueError("stitched %s: either stitch or rows" % what)
+    dest = Stitch(*stitch) if rows is None else Rows(*rows)
+    if rows is not None:
+        _check_table(dest.table, B, what)
+    if dest.segment_length is not None and int(dest.segment_length) != t_out:
+        # the caller sized `out` for segments of another length than the spectrogram decodes to: the store's bounds check would
+        # drop samples or leave part of `out` unwritten without a word
+        raise ValueError("stitched %s: the output was sized for %d-sample segments, the spectrogram decodes to %d"
+                         % (what, int(dest.segment_length), t_out))
+    if want_frames or dest.out.dtype != out_dtype or not dest.out.is_contiguous():
+        raise ValueError("stitched %s: contiguous output of the requested dtype, no synthesis frames" % what)
+    return dest
+
+
+def _check_table(table, B, what):
+    if table.dtype != torch.int64 or tuple(table.shape) != (B, 3) or not table.is_contiguous():
+        raise ValueError("stitched %s: the row table is a contiguous int64 [%d, 3] tensor (pos, lo, hi), got %s %s"
+                         % (what, B, table.dtype, tuple(table.shape)))
 
 
 def kbdwin(N: int, beta: float = 12.0, device="cpu") -> torch.Tensor:
@@ -189,9 +270,7 @@ def codec_inverse(spec4, *, codec, gain=1.0, alpha=0.6, min_value=1e-7, norm_ran
     B, C, F, M = spec4.shape
     assert C == (2 if codec == _lib.MG_CODEC_EXPLICIT else 1)
     raw = torch.empty(B, F, M, dtype=torch.float32, device=spec4.device)
-    if min_b is not None:
-        min_b, max_b = _lib.f32c(min_b.reshape(-1)), _lib.f32c(max_b.reshape(-1))
-        assert min_b.numel() == B * C and max_b.numel() == B * C
+    min_b, max_b = _per_clip(min_b, max_b, B * C)
     _lib.check(lib.mg_codec_inverse(_lib.ptr(spec4), B, F * M, codec, gain, alpha, min_value, norm_range[0], norm_range[1],
                                     src_range[0], src_range[1], _lib.ptr(min_b), _lib.ptr(max_b), _lib.ptr(raw),
                                     _lib.stream()), "mg_codec_inverse")
@@ -211,7 +290,6 @@ def mdct4_codec(audio, window, dct4, n_fft, *, codec=_lib.MG_CODEC_RAW, gain=1.0
     pair = torch.empty(B, F, M, 2, dtype=torch.float32, device=dev) if want_pair else None
     image = dct4_image(dct4, M)
     # with the pair the spectrogram is its channel 0 (a strided view): K1 then writes 393 216 B per clip instead of 526 848
-    import os
     legacy = os.environ.get("MG_MDCT_CT") == "0" or "MG_MDCT_FT" in os.environ      # (the generic kernels, forced)
     pair_only = (want_pair and image is not None and not per_sample and not want_frames and codec == _lib.MG_CODEC_ARCSINH
                  and T % 4 == 0 and audio.data_ptr() % 16 == 0 and window.data_ptr() % 16 == 0 and not legacy
@@ -238,75 +316,37 @@ def imdct4_codec(spec, window, dct4, n_fft, *, codec=_lib.MG_CODEC_RAW, gain=1.0
                  src_range=(0.0, 1.0), min_b=None, max_b=None, out_length=None, out_dtype=torch.float32,
                  want_frames=False, stitch=None, rows=None):
     """K2 launcher.  spec [B, F, M] (device) -> (audio [B, T_out], frames|None).
-
-    stitch = (out, gen_overlap, first_seg[, segment_length]): the clips are segments first_seg.. of ONE waveform and K2's overlap-add store writes them
-    straight into `out` [mg_stitch_length(n_seg, T_out, gen_overlap)] with generate_audio.py:40-53's cross-fade (mg_imdct4_stitched);
-    returns (out, None).  The batch with first_seg == 0 clears `out` when gen_overlap > 0.
-
-    rows = (out, gen_overlap, table[, segment_length[, zero_out]]): the clips are the rows of a device row table (seg_row_table: one
-    (pos, lo, hi) per clip) of the packed buffer `out` that holds any number of stitched waveforms (mg_imdct4_stitched_rows);
-    returns (out, None).  zero_out (default False) clears the whole of `out` first."""
+    stitch (a Stitch or its tuple): K2's overlap-add store writes the clips straight into the stitched waveform, with
+    generate_audio.py:40-53's cross-fade (mg_imdct4_stitched); rows (a Rows or its tuple): into the packed buffer of any number of
+    stitched waveforms (mg_imdct4_stitched_rows).  Both return (out, None)."""
     lib = _lib.load()
     spec = _lib.f32c(spec)
     B, F, M = spec.shape
     t_out = (F - 1) * M
     if out_length is not None:
         t_out = min(t_out, int(out_length))
-    if rows is not None:
-        if stitch is not None:
-            raise ValueError("stitched K2: either stitch or rows")
-        out, overlap, table = rows[:3]
-        _check_rows(rows, table, B, t_out, "K2")
-        if want_frames or out.dtype != out_dtype or not out.is_contiguous():
-            raise ValueError("stitched K2: contiguous output of the requested dtype, no synthesis frames")
-        if min_b is not None:
-            min_b, max_b = _lib.f32c(min_b.reshape(-1)), _lib.f32c(max_b.reshape(-1))
-            assert min_b.numel() == B and max_b.numel() == B
-        rc = lib.mg_imdct4_stitched_rows(_lib.ptr(spec), B, F, n_fft, _lib.ptr(window), _lib.ptr(dct4), dct4_image(dct4, M), codec,
-                                         gain, norm_range[0], norm_range[1], src_range[0], src_range[1], _lib.ptr(min_b),
-                                         _lib.ptr(max_b), _lib.ptr(out), out.numel(), t_out, int(overlap), _lib.ptr(table),
-                                         int(bool(rows[4])) if len(rows) > 4 else 0, int(out_dtype == torch.float64), _lib.stream())
-        _lib.check(rc, "mg_imdct4_stitched_rows")
-        return out, None
-    if stitch is not None:
-        out, overlap, first = stitch[:3]
-        if len(stitch) > 3 and int(stitch[3]) != t_out:
-            # the caller sized `out` for segments of stitch[3] samples; the spectrogram handed in decodes to t_out: the store's
-            # bounds check would drop samples or leave part of `out` unwritten without a word (ADVICE r4)
-            raise ValueError("stitched K2: the output was sized for %d-sample segments, the spectrogram decodes to %d"
-                             % (int(stitch[3]), t_out))
-        if want_frames or out.dtype != out_dtype or not out.is_contiguous():
-            raise ValueError("stitched K2: contiguous output of the requested dtype, no synthesis frames")
-        if min_b is not None:
-            min_b, max_b = _lib.f32c(min_b.reshape(-1)), _lib.f32c(max_b.reshape(-1))
-            assert min_b.numel() == B and max_b.numel() == B
-        rc = lib.mg_imdct4_stitched(_lib.ptr(spec), B, F, n_fft, _lib.ptr(window), _lib.ptr(dct4), dct4_image(dct4, M), codec, gain,
-                                    norm_range[0], norm_range[1], src_range[0], src_range[1], _lib.ptr(min_b), _lib.ptr(max_b),
-                                    _lib.ptr(out), out.numel(), t_out, int(overlap), int(first), int(first == 0),
-                                    int(out_dtype == torch.float64), _lib.stream())
-        _lib.check(rc, "mg_imdct4_stitched")
-        return out, None
+    dest = _destination(stitch, rows, B, t_out, out_dtype, want_frames, "K2")
+    min_b, max_b = _per_clip(min_b, max_b, B)
+    head = (_lib.ptr(spec), B, F, n_fft, _lib.ptr(window), _lib.ptr(dct4), dct4_image(dct4, M), codec, gain, norm_range[0], norm_range[1],
+            src_range[0], src_range[1], _lib.ptr(min_b), _lib.ptr(max_b))
+    f64 = int(out_dtype == torch.float64)
+    if dest is not None:
+        name = "mg_imdct4_stitched_rows" if rows is not None else "mg_imdct4_stitched"
+        _lib.check(getattr(lib, name)(*head, *_destination_args(dest, t_out, f64)), name)
+        return dest.out, None
     audio = torch.empty(B, t_out, dtype=out_dtype, device=spec.device)
     frames = torch.empty(B, F, n_fft, dtype=torch.float32, device=spec.device) if want_frames else None
-    if min_b is not None:
-        min_b, max_b = _lib.f32c(min_b.reshape(-1)), _lib.f32c(max_b.reshape(-1))
-        assert min_b.numel() == B and max_b.numel() == B
-    rc = lib.mg_imdct4_forward(_lib.ptr(spec), B, F, n_fft, _lib.ptr(window), _lib.ptr(dct4), dct4_image(dct4, M), codec, gain,
-                               norm_range[0], norm_range[1], src_range[0], src_range[1], _lib.ptr(min_b),
-                               _lib.ptr(max_b), _lib.ptr(audio), t_out, int(out_dtype == torch.float64),
-                               _lib.ptr(frames), _lib.stream())
-    _lib.check(rc, "mg_imdct4_forward")
+    _lib.check(lib.mg_imdct4_forward(*head, _lib.ptr(audio), t_out, f64, _lib.ptr(frames), _lib.stream()), "mg_imdct4_forward")
     return audio, frames
 
 
-def _check_rows(rows, table, B, t_out, what):
-    """The row-table form of a stitched decode: an int64 [B, 3] device table, segments of the length the caller planned for."""
-    if table.dtype != torch.int64 or tuple(table.shape) != (B, 3) or not table.is_contiguous():
-        raise ValueError("stitched %s: the row table is a contiguous int64 [%d, 3] tensor (pos, lo, hi), got %s %s"
-                         % (what, B, table.dtype, tuple(table.shape)))
-    if len(rows) > 3 and rows[3] is not None and int(rows[3]) != t_out:
-        raise ValueError("stitched %s: the output was sized for %d-sample segments, the spectrogram decodes to %d"
-                         % (what, int(rows[3]), t_out))
+def _destination_args(dest, t_out, f64):
+    """The arguments of mg_imdct4[_pow2]_stitched[_rows] that follow the codec block."""
+    if isinstance(dest, Rows):
+        where, zero = _lib.ptr(dest.table), dest.zero_out
+    else:
+        where, zero = int(dest.first_seg), (dest.first_seg == 0 if dest.zero_out is None else dest.zero_out)
+    return _lib.ptr(dest.out), dest.out.numel(), t_out, int(dest.overlap), where, int(bool(zero)), f64, _lib.stream()
 
 
 def seg_row_table(rows, device=None) -> torch.Tensor:
@@ -320,7 +360,7 @@ def segments_gather(wave, table, segment_length: int, out=None):
     lib = _lib.load()
     wave = _lib.f32c(wave).reshape(-1)
     n = table.shape[0]
-    _check_rows((), table, n, segment_length, "gather")
+    _check_table(table, n, "gather")
     if out is None:
         out = torch.empty(n, segment_length, dtype=torch.float32, device=wave.device)
     elif out.dtype != torch.float32 or tuple(out.shape) != (n, segment_length) or not out.is_contiguous():
@@ -401,10 +441,9 @@ def mdct4_pow2(audio, window, n_fft, F=None, *, codec=_lib.MG_CODEC_RAW, gain=1.
 
 def imdct4_pow2(spec, window, n_fft, *, codec=_lib.MG_CODEC_RAW, gain=1.0, norm_range=(0.0, 1.0), src_range=(0.0, 1.0),
                 min_b=None, max_b=None, out_length=None, scale=None, stitch=None, rows=None):
-    """K2' launcher.  spec [B, F, n_fft/2] -> audio [B, T_out] (scale: in place of the transform's 4 / n_fft), or the stitched
-    waveform (stitch as in imdct4_codec, plus an optional fifth element zero_out -- default: first_seg == 0 -- for callers that
-    clear `out` themselves and hand the batches over in another order; or rows as in imdct4_codec: mg_imdct4_pow2_stitched_rows);
-    None where the kernel's guards refuse and nothing has been written."""
+    """K2' launcher.  spec [B, F, n_fft/2] -> audio [B, T_out] (scale: in place of the transform's 4 / n_fft), or the destination of
+    stitch / rows as in imdct4_codec (mg_imdct4_pow2_stitched, mg_imdct4_pow2_stitched_rows); None where the kernel's guards
+    refuse a plain decode and nothing has been written."""
     lib = _lib.load()
     spec = _lib.f32c(spec)
     B, F, M = spec.shape
@@ -412,51 +451,20 @@ def imdct4_pow2(spec, window, n_fft, *, codec=_lib.MG_CODEC_RAW, gain=1.0, norm_
     if out_length is not None:
         t_out = min(t_out, int(out_length))
     tw = pow2_twiddles(n_fft, spec.device)
-    if min_b is not None:
-        min_b, max_b = _lib.f32c(min_b.reshape(-1)), _lib.f32c(max_b.reshape(-1))
-        assert min_b.numel() == B and max_b.numel() == B
-    if rows is not None:
-        if stitch is not None:
-            raise ValueError("stitched K2': either stitch or rows")
-        out, overlap, table = rows[:3]
-        _check_rows(rows, table, B, t_out, "K2'")
-        if out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("stitched K2': contiguous float32 output")
-        rc = lib.mg_imdct4_pow2_stitched_rows(_lib.ptr(spec), B, F, n_fft, _lib.ptr(window), _lib.ptr(tw), codec, gain, norm_range[0],
-                                              norm_range[1], src_range[0], src_range[1], _lib.ptr(min_b), _lib.ptr(max_b),
-                                              _lib.ptr(out), out.numel(), t_out, int(overlap), _lib.ptr(table),
-                                              int(bool(rows[4])) if len(rows) > 4 else 0, 0, _lib.stream())
-        _lib.check(rc, "mg_imdct4_pow2_stitched_rows")
-        return out
-    if stitch is not None:
-        out, overlap, first = stitch[:3]
-        if len(stitch) > 3 and int(stitch[3]) != t_out:
-            raise ValueError("stitched K2': the output was sized for %d-sample segments, the spectrogram decodes to %d"
-                             % (int(stitch[3]), t_out))
-        if out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("stitched K2': contiguous float32 output")
-        rc = lib.mg_imdct4_pow2_stitched(_lib.ptr(spec), B, F, n_fft, _lib.ptr(window), _lib.ptr(tw), codec, gain, norm_range[0],
-                                         norm_range[1], src_range[0], src_range[1], _lib.ptr(min_b), _lib.ptr(max_b),
-                                         _lib.ptr(out), out.numel(), t_out, int(overlap), int(first),
-                                         int(stitch[4] if len(stitch) > 4 else first == 0), 0,
-                                         _lib.stream())
-        _lib.check(rc, "mg_imdct4_pow2_stitched")
-        return out
+    dest = _destination(stitch, rows, B, t_out, torch.float32, False, "K2'")
+    min_b, max_b = _per_clip(min_b, max_b, B)
+    head = (_lib.ptr(spec), B, F, n_fft, _lib.ptr(window), _lib.ptr(tw), codec, gain, norm_range[0], norm_range[1], src_range[0],
+            src_range[1], _lib.ptr(min_b), _lib.ptr(max_b))
+    if dest is not None:
+        name = "mg_imdct4_pow2_stitched_rows" if rows is not None else "mg_imdct4_pow2_stitched"
+        _lib.check(getattr(lib, name)(*head, *_destination_args(dest, t_out, 0)), name)
+        return dest.out
     audio = torch.empty(B, t_out, dtype=torch.float32, device=spec.device)
-    rc = lib.mg_imdct4_pow2_forward(_lib.ptr(spec), B, F, n_fft, _lib.ptr(window), _lib.ptr(tw), codec, gain, norm_range[0],
-                                    norm_range[1], src_range[0], src_range[1], _lib.ptr(min_b), _lib.ptr(max_b), _lib.ptr(audio),
-                                    t_out, 0, 4.0 / n_fft if scale is None else float(scale), _lib.stream())
+    rc = lib.mg_imdct4_pow2_forward(*head, _lib.ptr(audio), t_out, 0, 4.0 / n_fft if scale is None else float(scale), _lib.stream())
     if rc == _UNSUPPORTED:
         return None
     _lib.check(rc, "mg_imdct4_pow2_forward")
     return audio
-
-
-def _fused_image(n_fft, device):
-    """The stage-matrix image of the fused geometry's DCT-IV table (None for other n_fft)."""
-    if n_fft != 512:
-        return None
-    return dct4_image(dct4_table(n_fft // 2, device), n_fft // 2)
 
 
 def codec_backward(grad, spec, *, codec, to_spectro, scale=1.0, gain=1.0, norm_range=(0.0, 1.0), src_range=(0.0, 1.0),
@@ -466,9 +474,7 @@ def codec_backward(grad, spec, *, codec, to_spectro, scale=1.0, gain=1.0, norm_r
     grad = _lib.f32c(grad)
     B = grad.shape[0]
     spec = _lib.f32c(spec) if spec is not None else None
-    if min_b is not None:
-        min_b, max_b = _lib.f32c(min_b.reshape(-1)), _lib.f32c(max_b.reshape(-1))
-        assert min_b.numel() == B and max_b.numel() == B
+    min_b, max_b = _per_clip(min_b, max_b, B)
     out = torch.empty_like(grad)
     _lib.check(lib.mg_codec_backward(_lib.ptr(grad), _lib.ptr(spec), B, grad.numel() // B, codec, int(to_spectro), scale, gain,
                                      norm_range[0], norm_range[1], src_range[0], src_range[1], _lib.ptr(min_b), _lib.ptr(max_b),
@@ -476,80 +482,213 @@ def codec_backward(grad, spec, *, codec, to_spectro, scale=1.0, gain=1.0, norm_r
     return out
 
 
+class Route(NamedTuple):
+    """What serves one request.  kernel: "k512" (K1 / K2 and their backward kernels), "pow2" (K1' / K2') or "generic" (framing / GEMM /
+    overlap-add).  codec_inside: no mg_codec_* launch accompanies the transform (else the transform runs in RAW mode beside one).
+    fallback: where the kernel answers MG_ERR_UNSUPPORTED the generic composition serves this call (else that raises)."""
+    kernel: str
+    codec_inside: bool
+    fallback: bool
+
+
+class Transform:
+    """One transform geometry: its float32 window, its tables and the ONE decision which kernel family serves a request on it --
+    "k512": n_fft == win == 2 hop == 512 with centre padding; "pow2": mg_mdct_pow2_supported; "generic": the rest."""
+
+    def __init__(self, n_fft, hop_length, win_length, window, center=True, device="cpu", allow=("k512", "pow2")) -> None:
+        self.window, self.win_length = _make_window(window, win_length, device)
+        self.n_fft, self.hop_length, self.center = n_fft, hop_length, center
+        self.fused = _check_geometry(n_fft, hop_length, self.win_length) and bool(center)
+        self._family = "k512" if self.fused else "pow2" if pow2_geometry(n_fft, hop_length, self.win_length, center) else "generic"
+        if self._family not in allow:           # (the fused= / fast= switches of mdct4_backward / imdct4_backward)
+            self._family = "generic"
+
+    @property
+    def family(self) -> str:
+        """The family at this call: MG_MDCT_POW2=0 (pow2_enabled, read here and nowhere else) turns "pow2" into "generic"."""
+        return "generic" if (self._family == "pow2" and not pow2_enabled()) else self._family
+
+    @property
+    def fast(self) -> bool:
+        return self.family == "pow2"
+
+    def window_on(self, device) -> torch.Tensor:
+        if self.window.device != device:
+            self.window = self.window.to(device)
+        return self.window
+
+    def dct4(self, device) -> torch.Tensor:
+        return dct4_table(self.n_fft // 2, device)
+
+    def covered(self, F, T) -> int:
+        """Samples of a T-sample signal that its F analysis frames reach (the rest gets no gradient)."""
+        return min(T, (F - 1) * self.hop_length + self.win_length - (self.hop_length if self.center else 0))
+
+    # -- routes: pure host functions, no launch, no allocation ------------------------------------
+    def route_analysis(self, codec=RAW, *, per_sample=False, want_pair=False, want_frames=False, backward=False, F=0, T=0) -> Route:
+        """The MDCT (+ encode) of a request; backward: its gradient with respect to the audio, from F frames back to T samples."""
+        fam = self.family
+        if backward:        # K2-shaped: mg_mdct4_backward, or K2' in RAW mode (scale 1) after mg_codec_backward
+            if fam == "pow2" and not (F > 1 and self.covered(F, T) <= (F - 1) * self.hop_length):
+                fam = "generic"
+            return Route(fam, fam == "k512", fam != "generic")
+        raw = codec.mode == _lib.MG_CODEC_RAW
+        if fam == "k512":
+            return Route(fam, codec.mode in _FUSABLE, False)
+        if fam == "pow2" and not want_frames:       # (K1' returns no frames)
+            return Route(fam, raw or (codec.mode in _FUSABLE and not per_sample and not want_pair), True)
+        return Route("generic", raw, False)
+
+    def route_synthesis(self, codec=RAW, *, F=2, out_dtype=torch.float32, want_frames=False, dest=False, backward=False) -> Route:
+        """The (decode +) IMDCT of an F-frame request (dest: into a Stitch / Rows destination); backward: its gradient with respect
+        to the spectrogram."""
+        fam = self.family
+        if backward:        # K1-shaped: mg_imdct4_backward, or K1' in RAW mode before mg_codec_backward; float64 came from the generic kernels
+            fam = fam if out_dtype == torch.float32 else "generic"
+            return Route(fam, fam == "k512", fam != "generic")
+        if fam == "pow2" and (want_frames or out_dtype != torch.float32 or F <= 1):       # (what K2' does not serve)
+            fam = "generic"
+        if dest and (fam == "generic" or codec.mode not in (_lib.MG_CODEC_ARCSINH, _lib.MG_CODEC_RANGE)):
+            raise NotImplementedError("stitched decode needs the fused 512 / 256 geometry")
+        if fam == "generic":
+            return Route(fam, codec.mode == _lib.MG_CODEC_RAW, False)
+        return Route(fam, codec.mode in _FUSABLE, fam == "pow2" and not dest)
+
+    # -- the operations ---------------------------------------------------------------------------
+    def analysis(self, audio, codec=RAW, *, per_sample=False, want_pair=False, want_stats=False, want_frames=False):
+        """audio [..., T] -> the launcher dict: spec [B, F, M], spec4 [B, C, F, M], pair, frames, min / max, stats, and raw (the
+        coefficients, where mg_codec_forward ran beside the transform)."""
+        r = self.route_analysis(codec, per_sample=per_sample, want_pair=want_pair, want_frames=want_frames)
+        a = audio if audio.dim() == 2 else audio.reshape(-1, audio.shape[-1])
+        window = self.window_on(a.device)
+        opts = dict(per_sample=per_sample, want_pair=want_pair, want_stats=want_stats)
+        inside = r.codec_inside
+        out = None
+        if r.kernel == "k512":
+            out = mdct4_codec(a, window, self.dct4(a.device), self.n_fft, want_frames=want_frames,
+                              **(dict(codec.kw(), **opts) if inside else {}))
+        elif r.kernel == "pow2":
+            out = mdct4_pow2(a, window, self.n_fft, **(dict(codec.kw(), want_stats=want_stats) if inside else {}))
+        if out is None:             # the generic family, a guard, or K1' refused
+            raw, frames = mdct4_generic(a, window, self.n_fft, self.hop_length, self.center, want_frames)
+            out = {"spec": raw, "pair": None, "frames": frames, "min": None, "max": None, "stats": None}
+            inside = codec.mode == _lib.MG_CODEC_RAW
+        if inside:
+            out["spec4"], out["raw"] = out["spec"][:, None], None
+            return out
+        raw, frames = out["spec"], out["frames"]
+        out = codec_forward(raw, **codec.kw(full=True), **opts)
+        out["frames"], out["raw"] = frames, raw
+        return out
+
+    def synthesis(self, spec, codec=RAW, *, min_b=None, max_b=None, out_length=None, out_dtype=torch.float32, want_frames=False,
+                  stitch=None, rows=None):
+        """spec [B, F, M] or [B, C, F, M] -> (audio [B, T_out], frames | None), or (the destination's `out`, None)."""
+        r = self.route_synthesis(codec, F=spec.shape[-2], out_dtype=out_dtype, want_frames=want_frames,
+                                 dest=stitch is not None or rows is not None)
+        window = self.window_on(spec.device)
+
+        def raw_of(s):
+            return codec_inverse(s if s.dim() == 4 else s[:, None], min_b=min_b, max_b=max_b, **codec.kw(full=True))
+        clip = dict(min_b=min_b, max_b=max_b)
+        if not r.codec_inside:
+            spec, codec, clip = raw_of(spec), RAW, {}
+        elif spec.dim() == 4:
+            spec = spec.squeeze(1)
+        if r.kernel == "k512":
+            return imdct4_codec(spec, window, self.dct4(spec.device), self.n_fft, out_length=out_length, out_dtype=out_dtype,
+                                want_frames=want_frames, stitch=stitch, rows=rows, **codec.kw(), **clip)
+        if r.kernel == "pow2":
+            audio = imdct4_pow2(spec, window, self.n_fft, out_length=out_length, stitch=stitch, rows=rows, **codec.kw(), **clip)
+            if audio is not None:
+                return audio, None
+            if codec.mode != _lib.MG_CODEC_RAW:             # refused with the codec inside
+                spec = raw_of(spec)
+        return imdct4_generic(spec, window, self.n_fft, self.hop_length, self.center, out_length, out_dtype, want_frames)
+
+    def synthesis_backward(self, grad_audio, spec, codec=RAW, *, F, min_b=None, max_b=None, out_dtype=torch.float32):
+        """Gradient of synthesis() with respect to its spectrogram: grad_audio [B, T_out] -> grad_spec [B, F, n_fft/2].  The K1-shaped
+        kernel (mg_imdct4_backward) where its guards hold; else frames of grad_audio with the IMDCT's crop as start padding, window,
+        [frames, win] x [win, n_fft/2] on the exact-f32 GEMM -- or K1' in RAW mode with the forward's F (the adjoint of K2' is 4/N K1')
+        -- then dX/ds and the 4/N scale (mg_codec_backward)."""
+        lib = _lib.load()
+        r = self.route_synthesis(codec, out_dtype=out_dtype, backward=True)
+        gy = _lib.f32c(grad_audio)
+        B, t_out = gy.shape
+        dev = gy.device
+        window, n_fft, win = self.window_on(dev), self.n_fft, self.win_length
+        min_b, max_b = _per_clip(min_b, max_b, B)
+        spec = _lib.f32c(spec) if (spec is not None and codec.mode != _lib.MG_CODEC_RAW) else None
+        M = n_fft // 2
+        if r.kernel == "k512":
+            gs = torch.empty(B, F, M, dtype=torch.float32, device=dev)
+            rc = lib.mg_imdct4_backward(_lib.ptr(gy), B, t_out, F, n_fft, _lib.ptr(window), dct4_image(self.dct4(dev), M), codec.mode,
+                                        codec.gain, *codec.norm_range, *codec.src_range, _lib.ptr(min_b), _lib.ptr(max_b),
+                                        _lib.ptr(spec), _lib.ptr(gs), _lib.stream())
+            if rc != _UNSUPPORTED:
+                _lib.check(rc, "mg_imdct4_backward")
+                return gs
+        out = mdct4_pow2(gy, window, n_fft, F) if r.kernel == "pow2" else None
+        if out is not None:
+            g = out["spec"]
+        else:
+            frames = torch.empty(B, F, win, dtype=torch.float32, device=dev)
+            _lib.check(lib.mg_frames_window(_lib.ptr(gy), B, t_out, win, self.hop_length, win // 2 if self.center else 0, F,
+                                            _lib.ptr(window), _lib.ptr(frames), _lib.stream()), "mg_frames_window")
+            g = _dense(frames.view(B * F, win), mdct_table(n_fft, win, dev, True)).view(B, F, M)
+        return codec_backward(g, spec, to_spectro=False, scale=4.0 / n_fft, min_b=min_b, max_b=max_b, **codec.kw())
+
+    def analysis_backward(self, grad_spec, spec, codec=RAW, *, T):
+        """Gradient of analysis() (fixed-range encode) with respect to the audio: grad_spec [B, F, n_fft/2] (gradient of the normalised
+        spec) -> grad_audio [B, T].  The K2-shaped kernel (mg_mdct4_backward) where its guards hold; else ds/dX (mg_codec_backward),
+        then [F, n_fft/2] x [n_fft/2, win] on the exact-f32 GEMM, window and overlap-add with the MDCT's start padding as crop
+        (mg_overlap_add with n_fft = 4: scale 1) -- or K2' in RAW mode with output scale 1 (the adjoint of K1')."""
+        lib = _lib.load()
+        g = _lib.f32c(grad_spec)
+        B, F, M = g.shape
+        r = self.route_analysis(codec, backward=True, F=F, T=T)
+        dev = g.device
+        window, n_fft, win = self.window_on(dev), self.n_fft, self.win_length
+        spec = _lib.f32c(spec) if (spec is not None and codec.mode != _lib.MG_CODEC_RAW) else None
+        if r.kernel == "k512":
+            ga = torch.empty(B, T, dtype=torch.float32, device=dev)
+            rc = lib.mg_mdct4_backward(_lib.ptr(g), _lib.ptr(spec), B, T, n_fft, _lib.ptr(window), dct4_image(self.dct4(dev), M),
+                                       codec.mode, codec.gain, *codec.norm_range, *codec.src_range, _lib.ptr(ga), _lib.stream())
+            if rc != _UNSUPPORTED:
+                _lib.check(rc, "mg_mdct4_backward")
+                return ga
+        if codec.mode != _lib.MG_CODEC_RAW:
+            g = codec_backward(g, spec, to_spectro=True, **codec.kw())
+        covered = self.covered(F, T)
+        ga = imdct4_pow2(g, window, n_fft, out_length=covered, scale=1.0) if r.kernel == "pow2" else None
+        if ga is None:
+            z = _dense(g.view(B * F, M), mdct_table(n_fft, win, dev, False)).view(B, F, win)
+            ga = torch.empty(B, covered, dtype=torch.float32, device=dev)
+            # mg_overlap_add scales by 4 / n_fft: n_fft = 4 makes it 1
+            _lib.check(lib.mg_overlap_add(_lib.ptr(z), B, F, win, self.hop_length, 4, _lib.ptr(window), self.hop_length if self.center else 0,
+                                          _lib.ptr(ga), covered, 0, _lib.stream()), "mg_overlap_add")
+        if covered < T:
+            ga = torch.cat((ga, ga.new_zeros(B, T - covered)), dim=1)
+        return ga
+
+
+def _legacy_transform(window, n_fft, hop_length, center, fused, fast):
+    return Transform(n_fft, hop_length, None, window, center, window.device,
+                     allow=tuple(name for name, on in (("k512", fused), ("pow2", fast)) if on))
+
+
 def imdct4_backward(grad_audio, spec, window, n_fft, hop_length, F, center=True, *, codec=_lib.MG_CODEC_RAW, gain=1.0,
                     norm_range=(0.0, 1.0), src_range=(0.0, 1.0), min_b=None, max_b=None, fused=True, fast=False):
-    """Gradient of imdct4_codec / imdct4_generic (decode + IMDCT4) with respect to their spectrogram input.
-    grad_audio [B, T_out] -> grad_spec [B, F, n_fft/2].  fused: try the K1-shaped kernel (mg_imdct4_backward) first; the
-    generic composition runs where its guards fail: frames of grad_audio with the IMDCT's crop as start padding, window,
-    [frames, win] x [win, n_fft/2] on the exact-f32 GEMM, then dX/ds and the 4/N scale (mg_codec_backward).  fast: K1' in RAW
-    mode with the forward's F is the framing + contraction leg (the adjoint of K2' is 4/N K1')."""
-    lib = _lib.load()
-    gy = _lib.f32c(grad_audio)
-    B, t_out = gy.shape
-    dev = gy.device
-    if min_b is not None:
-        min_b, max_b = _lib.f32c(min_b.reshape(-1)), _lib.f32c(max_b.reshape(-1))
-    spec = _lib.f32c(spec) if (spec is not None and codec != _lib.MG_CODEC_RAW) else None
-    M = n_fft // 2
-    image = _fused_image(n_fft, dev) if fused else None
-    if image is not None:
-        gs = torch.empty(B, F, M, dtype=torch.float32, device=dev)
-        rc = lib.mg_imdct4_backward(_lib.ptr(gy), B, t_out, F, n_fft, _lib.ptr(window), image, codec, gain, norm_range[0],
-                                    norm_range[1], src_range[0], src_range[1], _lib.ptr(min_b), _lib.ptr(max_b), _lib.ptr(spec),
-                                    _lib.ptr(gs), _lib.stream())
-        if rc != _UNSUPPORTED:
-            _lib.check(rc, "mg_imdct4_backward")
-            return gs
-    win = window.numel()
-    r = mdct4_pow2(gy, window, n_fft, F) if (fast and center and pow2_enabled()) else None
-    if r is not None:
-        g = r["spec"]
-    else:
-        frames = torch.empty(B, F, win, dtype=torch.float32, device=dev)
-        _lib.check(lib.mg_frames_window(_lib.ptr(gy), B, t_out, win, hop_length, win // 2 if center else 0, F, _lib.ptr(window),
-                                        _lib.ptr(frames), _lib.stream()), "mg_frames_window")
-        g = _dense(frames.view(B * F, win), mdct_table(n_fft, win, dev, True)).view(B, F, M)
-    return codec_backward(g, spec, codec=codec, to_spectro=False, scale=4.0 / n_fft, gain=gain, norm_range=norm_range,
-                          src_range=src_range, min_b=min_b, max_b=max_b)
+    """Transform.synthesis_backward for callers that hold a window (fused / fast: the 512 / the K1' kernels may run)."""
+    return _legacy_transform(window, n_fft, hop_length, center, fused, fast).synthesis_backward(
+        grad_audio, spec, Codec(codec, gain, norm_range=norm_range, src_range=src_range), F=F, min_b=min_b, max_b=max_b)
 
 
 def mdct4_backward(grad_spec, spec, window, n_fft, hop_length, T, center=True, *, codec=_lib.MG_CODEC_RAW, gain=1.0,
                    norm_range=(0.0, 1.0), src_range=(0.0, 1.0), fused=True, fast=False):
-    """Gradient of mdct4_codec / mdct4_generic (MDCT4 + fixed-range encode) with respect to the audio: grad_spec [B, F, n_fft/2]
-    (gradient of the normalised output spec) -> grad_audio [B, T].  fused: the K2-shaped kernel (mg_mdct4_backward) where its
-    guards hold; otherwise ds/dX (mg_codec_backward), [F, n_fft/2] x [n_fft/2, win] on the exact-f32 GEMM, window and
-    overlap-add with the MDCT's start padding as crop (mg_overlap_add with n_fft = 4: scale 1).  fast: K2' in RAW mode with
-    output scale 1 is the contraction + overlap-add leg (the adjoint of K1')."""
-    lib = _lib.load()
-    g = _lib.f32c(grad_spec)
-    B, F, M = g.shape
-    dev = g.device
-    spec = _lib.f32c(spec) if (spec is not None and codec != _lib.MG_CODEC_RAW) else None
-    image = _fused_image(n_fft, dev) if fused else None
-    if image is not None:
-        ga = torch.empty(B, T, dtype=torch.float32, device=dev)
-        rc = lib.mg_mdct4_backward(_lib.ptr(g), _lib.ptr(spec), B, T, n_fft, _lib.ptr(window), image, codec, gain, norm_range[0],
-                                   norm_range[1], src_range[0], src_range[1], _lib.ptr(ga), _lib.stream())
-        if rc != _UNSUPPORTED:
-            _lib.check(rc, "mg_mdct4_backward")
-            return ga
-    if codec != _lib.MG_CODEC_RAW:
-        g = codec_backward(g, spec, codec=codec, to_spectro=True, gain=gain, norm_range=norm_range, src_range=src_range)
-    win = window.numel()
-    crop = hop_length if center else 0
-    covered = min(T, (F - 1) * hop_length + win - crop)        # samples past the last frame get no gradient
-    ga = None
-    if fast and center and pow2_enabled() and F > 1 and covered <= (F - 1) * hop_length:
-        ga = imdct4_pow2(g, window, n_fft, out_length=covered, scale=1.0)
-    if ga is None:
-        z = _dense(g.view(B * F, M), mdct_table(n_fft, win, dev, False)).view(B, F, win)
-        ga = torch.empty(B, covered, dtype=torch.float32, device=dev)
-        # mg_overlap_add scales by 4 / n_fft: n_fft = 4 makes it 1
-        _lib.check(lib.mg_overlap_add(_lib.ptr(z), B, F, win, hop_length, 4, _lib.ptr(window), crop, _lib.ptr(ga), covered, 0,
-                                      _lib.stream()), "mg_overlap_add")
-    if covered < T:
-        ga = torch.cat((ga, ga.new_zeros(B, T - covered)), dim=1)
-    return ga
+    """Transform.analysis_backward for callers that hold a window (fused / fast: the 512 / the K2' kernels may run)."""
+    return _legacy_transform(window, n_fft, hop_length, center, fused, fast).analysis_backward(
+        grad_spec, spec, Codec(codec, gain, norm_range=norm_range, src_range=src_range), T=T)
 
 
 class CodecGrad(torch.autograd.Function):
@@ -577,107 +716,66 @@ def wants_grad(*tensors) -> bool:
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
-class MDCT4(torch.nn.Module):
+class _Shell(torch.nn.Module):
+    """What MDCT4 and IMDCT4 share: the reference's attributes over one Transform."""
+
+    def __init__(self, n_fft, hop_length, win_length, window, center, pad_mode, device, dtype) -> None:
+        super().__init__()
+        self.n_fft, self.pad_mode, self.device, self.hop_length, self.center = n_fft, pad_mode, device, hop_length, center
+        self.transform = Transform(n_fft, hop_length, win_length, window, center, device)
+        self.win_length, self.fused, self.out_dtype = self.transform.win_length, self.transform.fused, dtype
+
+    window = property(lambda self: self.transform.window)
+    fast = property(lambda self: self.transform.fast, doc="K1' / K2' (csrc/mdct_pow2.hip) run this geometry (MG_MDCT_POW2=0 says no)")
+
+    def _differentiable(self, run, bwd, x):
+        """run(x) -> (y, frames), through CodecGrad where a gradient is wanted."""
+        if not wants_grad(x):
+            return run(x)
+        held = {}
+
+        def fwd(a):
+            y, held["frames"] = run(a)
+            return y
+        return CodecGrad.apply(fwd, bwd, x), held["frames"]
+
+
+class MDCT4(_Shell):
     """models/mdct.py:359-425.  forward(signal, return_frames=False) -> (spec [..., F, n_fft/2], frames)."""
 
     def __init__(self, n_fft=2048, hop_length=None, win_length=None, window=None, center=True,
                  pad_mode="constant", device="cuda", dtype=torch.float32) -> None:
-        super().__init__()
-        self.n_fft, self.pad_mode, self.device, self.hop_length, self.center = n_fft, pad_mode, device, hop_length, center
-        self.window, self.win_length = _make_window(window, win_length, device)
-        self.fused = _check_geometry(self.n_fft, self.hop_length, self.win_length) and center
-        self._pow2 = pow2_geometry(self.n_fft, self.hop_length, self.win_length, center)
+        super().__init__(n_fft, hop_length, win_length, window, center, pad_mode, device, dtype)
         if pad_mode != "constant":
             raise NotImplementedError("HIP MDCT4 implements zero ('constant') padding")
-        self.out_dtype = dtype
-
-    @property
-    def fast(self) -> bool:
-        """The fused K1' kernel (csrc/mdct_pow2.hip) runs this geometry (MG_MDCT_POW2=0, read here, says no)."""
-        return self._pow2 and pow2_enabled()
 
     def forward(self, signal, return_frames: bool = False):
         lead = signal.shape[:-1]
         x = signal.reshape(-1, signal.shape[-1])
-        if self.window.device != x.device:
-            self.window = self.window.to(x.device)
+
         def run(a):
-            if self.fused:
-                r = mdct4_codec(a, self.window, dct4_table(self.n_fft // 2, a.device), self.n_fft, want_frames=return_frames)
-                return r["spec"], r["frames"]
-            if self.fast and not return_frames:
-                r = mdct4_pow2(a, self.window, self.n_fft)
-                if r is not None:
-                    return r["spec"], None
-            return mdct4_generic(a, self.window, self.n_fft, self.hop_length, self.center, return_frames)
-        if wants_grad(x):
-            held = {}
-
-            def fwd(a):
-                sp_, held["frames"] = run(a)
-                return sp_
-
-            def bwd(g, a, _):
-                return mdct4_backward(g, None, self.window, self.n_fft, self.hop_length, a.shape[-1], self.center,
-                                      fused=self.fused, fast=self.fast)
-            sp = CodecGrad.apply(fwd, bwd, x)
-            fr = held["frames"]
-        else:
-            sp, fr = run(x)
+            r = self.transform.analysis(a, want_frames=return_frames)
+            return r["spec"], r["frames"]
+        sp, fr = self._differentiable(run, lambda g, a, _: self.transform.analysis_backward(g, None, T=a.shape[-1]), x)
         spec = sp.reshape(*lead, *sp.shape[1:]).to(self.out_dtype)
         frames = fr.reshape(*lead, *fr.shape[1:]) if return_frames else torch.empty(1)
         return spec, frames
 
 
-class IMDCT4(torch.nn.Module):
+class IMDCT4(_Shell):
     """models/mdct.py:428-489.  forward(spec [B, F, n_fft/2], return_frames=False) -> (audio [B,1,1,T], frames)."""
 
     def __init__(self, n_fft=2048, hop_length=None, win_length=None, window=None, center=True,
                  pad_mode="constant", out_length=None, device="cuda", dtype=torch.float32) -> None:
-        super().__init__()
-        self.n_fft, self.pad_mode, self.device, self.hop_length = n_fft, pad_mode, device, hop_length
-        self.center, self.out_length = center, out_length
-        self.window, self.win_length = _make_window(window, win_length, device)
-        self.fused = _check_geometry(self.n_fft, self.hop_length, self.win_length) and center
-        self._pow2 = pow2_geometry(self.n_fft, self.hop_length, self.win_length, center)
-        self.out_dtype = dtype
-
-    @property
-    def fast(self) -> bool:
-        """The fused K2' kernel (csrc/mdct_pow2.hip) runs this geometry (MG_MDCT_POW2=0, read here, says no)."""
-        return self._pow2 and pow2_enabled()
+        super().__init__(n_fft, hop_length, win_length, window, center, pad_mode, device, dtype)
+        self.out_length = out_length
 
     def forward(self, signal, return_frames: bool = False):
         assert signal.dim() == 3, "Only tensors shaped in BHW are supported, got tensor of shape %s" % (
             str(signal.size()))
         assert signal.size()[-1] == self.n_fft // 2, \
             "The last dim of input tensor should match the n_fft. Expected %d ,got %d" % (self.n_fft, signal.size()[-1])
-        if self.window.device != signal.device:
-            self.window = self.window.to(signal.device)
-        def run(spec):
-            if self.fused:
-                return imdct4_codec(spec, self.window, dct4_table(self.n_fft // 2, spec.device), self.n_fft,
-                                    out_length=self.out_length, out_dtype=self.out_dtype, want_frames=return_frames)
-            if self.fast and not return_frames and self.out_dtype == torch.float32 and spec.shape[1] > 1:
-                audio_ = imdct4_pow2(spec, self.window, self.n_fft, out_length=self.out_length)
-                if audio_ is not None:
-                    return audio_, None
-            return imdct4_generic(spec, self.window, self.n_fft, self.hop_length, self.center, self.out_length,
-                                  self.out_dtype, return_frames)
-        if wants_grad(signal):
-            held = {}
-
-            def fwd(spec):
-                audio_, held["frames"] = run(spec)
-                return audio_
-
-            def bwd(g, spec, _):
-                # the float64 output comes from the generic kernel: its backward takes the generic composition too
-                return imdct4_backward(g, None, self.window, self.n_fft, self.hop_length, spec.shape[1], self.center,
-                                       fused=self.fused and self.out_dtype == torch.float32,
-                                       fast=self.fast and self.out_dtype == torch.float32)
-            audio = CodecGrad.apply(fwd, bwd, signal)
-            frames = held["frames"]
-        else:
-            audio, frames = run(signal)
+        audio, frames = self._differentiable(
+            lambda spec: self.transform.synthesis(spec, out_length=self.out_length, out_dtype=self.out_dtype, want_frames=return_frames),
+            lambda g, spec, _: self.transform.synthesis_backward(g, None, F=spec.shape[1], out_dtype=self.out_dtype), signal)
         return audio[:, None, None, :], (frames if return_frames else torch.zeros(1))

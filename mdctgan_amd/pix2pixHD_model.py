@@ -18,9 +18,7 @@ import torch
 from . import _lib, networks
 from . import amp
 from . import functional as Fh
-from .mdct import (IMDCT4, MDCT4, CodecGrad, _check_geometry, codec_forward, codec_inverse, dct4_table, imdct4_backward,
-                   imdct4_codec, imdct4_generic, imdct4_pow2, kbdwin, mdct4_backward, mdct4_codec, mdct4_generic, mdct4_pow2,
-                   pow2_enabled, pow2_geometry, wants_grad)
+from .mdct import RAW, Codec, CodecGrad, Transform, codec_inverse, kbdwin, wants_grad
 from .optim import FusedAdam
 
 
@@ -34,12 +32,7 @@ class Audio2MDCT(torch.nn.Module):
             setattr(self, k, v)
         self.device = "cuda" if len(self.gpu_ids) > 0 else "cpu"
         self.up_ratio = self.hr_sampling_rate / self.lr_sampling_rate
-        self.window = kbdwin(self.win_length).to(self.device)
         self.min_value = opt.min_value
-        self._mdct = MDCT4(n_fft=self.n_fft, hop_length=self.hop_length, win_length=self.win_length,
-                           window=self.window, device=self.device)
-        self._imdct = IMDCT4(n_fft=self.n_fft, hop_length=self.hop_length, win_length=self.win_length,
-                             window=self.window, device=self.device)
         # models/pix2pixHD_model.py:84-106: explicit encoding > arcsinh > raw > dB
         if getattr(self, "explicit_encoding", False):
             self.codec = _lib.MG_CODEC_EXPLICIT
@@ -49,86 +42,32 @@ class Audio2MDCT(torch.nn.Module):
             self.codec = _lib.MG_CODEC_RANGE
         else:
             self.codec = _lib.MG_CODEC_DB
-        # the hot path (n_fft 512, arcsinh / raw) runs the fused kernels K1 / K2; any other geometry or codec runs the
-        # generic kernels of csrc/codec_generic.hip (transform as a dense GEMM + elementwise codec)
-        self.geom512 = _check_geometry(self.n_fft, self.hop_length, self.win_length)
-        self.fused = self.geom512 and self.codec in (_lib.MG_CODEC_ARCSINH, _lib.MG_CODEC_RANGE)
-        # the other power-of-two geometries (n_fft 256 / 1024 / 2048, hop = n_fft / 2): K1' / K2' of csrc/mdct_pow2.hip -- `fast`
-        self._pow2 = pow2_geometry(self.n_fft, self.hop_length, self.win_length, True)
+        self._codec = Codec(self.codec, float(self.arcsinh_gain), float(self.alpha), float(self.min_value), *self._ranges())
+        # which kernels run a request (K1 / K2 at n_fft 512, K1' / K2' at 256 / 1024 / 2048, the generic kernels of
+        # csrc/codec_generic.hip otherwise) is the Transform's decision: mdct.Transform.route_analysis / route_synthesis
+        self.transform = Transform(self.n_fft, self.hop_length, self.win_length, kbdwin(self.win_length), True, self.device)
         self.return_stats = True      # mean / std of norm_param (returned only; costs two atomics per wave)
         self.return_frames = False    # norm_param['frames'] (dead on the hot path; [B, F, 512] of extra traffic)
         self.return_pha = False       # pha = sign(X) * noise is dead on the arcsinh / raw paths
 
-    @property
-    def fast(self) -> bool:
-        """K1' / K2' run this geometry (MG_MDCT_POW2=0, read at call time, restores the generic composition)."""
-        return self._pow2 and pow2_enabled()
-
-    @property
-    def fast_codec(self) -> bool:
-        """... with the codec inside the kernels (arcsinh / range); other codecs run them in RAW mode around mg_codec_*."""
-        return self.fast and self.codec in (_lib.MG_CODEC_ARCSINH, _lib.MG_CODEC_RANGE)
-
-    @property
-    def has_stitched_decoder(self) -> bool:
-        """to_audio(..., stitch=...) is served: K2 at n_fft 512, K2' at the other power-of-two geometries."""
-        return self.fused or self.fast_codec
-
-    # -- helpers --------------------------------------------------------------------------------
-    def _tables(self, dev):
-        if self.window.device != dev:
-            self.window = self.window.to(dev)
-        return self.window, dct4_table(self.n_fft // 2, dev)
-
-    def _window(self, dev):
-        if self.window.device != dev:
-            self.window = self.window.to(dev)
-        return self.window
+    window = property(lambda self: self.transform.window)
+    geom512 = property(lambda self: self.transform.fused, doc="K1 / K2's geometry")
+    _in_kernel = property(lambda self: self.codec in (_lib.MG_CODEC_ARCSINH, _lib.MG_CODEC_RANGE))
+    fused = property(lambda self: self.geom512 and self._in_kernel, doc="K1 / K2 with the codec inside")
+    fast = property(lambda self: self.transform.fast, doc="K1' / K2' run this geometry (MG_MDCT_POW2=0, read at call time, says no)")
+    fast_codec = property(lambda self: self.fast and self._in_kernel, doc="... with the codec inside (else RAW mode around mg_codec_*)")
+    has_stitched_decoder = property(lambda self: self.fused or self.fast_codec,
+                                    doc="to_audio(..., stitch=... / rows=...) is served: K2 at n_fft 512, K2' at 256 / 1024 / 2048")
 
     def _ranges(self):
         return (float(self.norm_range[0]), float(self.norm_range[1])), (float(self.src_range[0]), float(self.src_range[1]))
 
-    def _raw(self, audio, want_frames=False):
-        """Raw MDCT coefficients [B, F, M] (+ windowed frames) by the kernel that fits the geometry."""
-        if self.geom512:
-            window, d4 = self._tables(audio.device)
-            r = mdct4_codec(audio, window, d4, self.n_fft, codec=_lib.MG_CODEC_RAW, want_frames=want_frames)
-            return r["spec"], r["frames"]
-        if self.window.device != audio.device:
-            self.window = self.window.to(audio.device)
-        if self.fast and not want_frames:
-            r = mdct4_pow2(audio, self.window, self.n_fft)
-            if r is not None:
-                return r["spec"], None
-        return mdct4_generic(audio, self.window, self.n_fft, self.hop_length, True, want_frames)
-
     def encode(self, audio, want_pair=False, want_stats=None, want_frames=None):
-        """K1 (fused) or the generic transform + codec.  Returns the launcher dict (spec [B,F,W] / spec4 [B,C,F,W], pair
-        [B,F,W,2] NHWC, min/max, stats)."""
-        nr, sr = self._ranges()
-        want_stats = self.return_stats if want_stats is None else want_stats
-        want_frames = self.return_frames if want_frames is None else want_frames
-        if self.fused:
-            window, d4 = self._tables(audio.device)
-            r = mdct4_codec(audio, window, d4, self.n_fft, codec=self.codec, gain=float(self.arcsinh_gain),
-                            norm_range=nr, src_range=sr, per_sample=not self.abs_norm, want_pair=want_pair,
-                            want_stats=want_stats, want_frames=want_frames)
-            r["spec4"], r["raw"] = r["spec"][:, None], None
-            return r
-        if self.fast_codec and self.abs_norm and not want_pair and not want_frames:
-            # K1' with the fixed-range codec and the statistics inside (per-sample ranges and the NHWC pair: RAW mode below)
-            window = self._window(audio.device)
-            r = mdct4_pow2(audio.reshape(-1, audio.shape[-1]), window, self.n_fft, codec=self.codec, gain=float(self.arcsinh_gain),
-                           norm_range=nr, src_range=sr, want_stats=want_stats)
-            if r is not None:
-                r["spec4"], r["raw"] = r["spec"][:, None], None
-                return r
-        raw, frames = self._raw(_lib.f32c(audio.reshape(-1, audio.shape[-1])), want_frames)
-        r = codec_forward(raw, codec=self.codec, gain=float(self.arcsinh_gain), alpha=float(self.alpha),
-                          min_value=float(self.min_value), norm_range=nr, src_range=sr, per_sample=not self.abs_norm,
-                          want_pair=want_pair, want_stats=want_stats)
-        r["frames"], r["raw"] = frames, raw
-        return r
+        """The transform + codec by the route that fits (Transform.analysis).  Returns the launcher dict (spec [B,F,W] / spec4
+        [B,C,F,W], pair [B,F,W,2] NHWC, min/max, stats)."""
+        return self.transform.analysis(audio, self._codec, per_sample=not self.abs_norm, want_pair=want_pair,
+                                       want_stats=self.return_stats if want_stats is None else want_stats,
+                                       want_frames=self.return_frames if want_frames is None else want_frames)
 
     def _norm_param(self, r, dev):
         if self.abs_norm:
@@ -219,45 +158,43 @@ class Audio2MDCT(torch.nn.Module):
         return x
 
     def _grad_codec(self, what):
-        """(codec, gain) of the backward passes: the arcsinh and range codecs only."""
-        if self.codec not in (_lib.MG_CODEC_ARCSINH, _lib.MG_CODEC_RANGE):
+        """The codec of the backward passes: arcsinh and range only."""
+        if not self._in_kernel:
             raise NotImplementedError("%s backward: the dB and explicit-encoding codecs have no gradient here" % what)
-        return self.codec, float(self.arcsinh_gain)
+        return self._codec
+
+    def _decode_args(self, norm_param):
+        """(codec, per-clip min / max keywords) of a decode: norm_param's min / max per clip, or -- one value for all, without
+        --abs_norm -- as the codec's src_range."""
+        mn, mx = norm_param["min"], norm_param["max"]
+        if mn.numel() > 1:
+            return self._codec, dict(min_b=mn, max_b=mx)
+        if self.abs_norm:
+            return self._codec, {}
+        return self._codec._replace(src_range=(float(mn.reshape(-1)[0]), float(mx.reshape(-1)[0]))), {}
 
     def _to_spectro_backward(self, grad, audio, spec4):
         """d loss / d audio from d loss / d spec4 (fixed --abs_norm range only)."""
-        codec, gain = self._grad_codec("to_spectro")
+        codec = self._grad_codec("to_spectro")
         if not self.abs_norm:
             raise NotImplementedError("to_spectro backward with per-sample normalisation (no --abs_norm): the gradient through "
                                       "the clip's min / max is not built")
-        nr, sr = self._ranges()
-        window, _ = self._tables(audio.device)
-        g = mdct4_backward(grad[:, 0], spec4[:, 0], window, self.n_fft, self.hop_length, audio.shape[-1], codec=codec,
-                           gain=gain, norm_range=nr, src_range=sr, fused=self.geom512, fast=self.fast)
-        return g.view(audio.shape)
+        return self.transform.analysis_backward(grad[:, 0], spec4[:, 0], codec, T=audio.shape[-1]).view(audio.shape)
 
     def _to_audio_backward(self, grad, log_spectro, norm_param):
         """d loss / d log_spectro from d loss / d audio (norm_param's min / max are constants)."""
-        codec, gain = self._grad_codec("to_audio")
-        nr, sr = self._ranges()
-        mn, mx = norm_param["min"], norm_param["max"]
-        per_sample = mn.numel() > 1
-        if not per_sample and not self.abs_norm:
-            sr = (float(mn.reshape(-1)[0]), float(mx.reshape(-1)[0]))
+        self._grad_codec("to_audio")
+        codec, clip = self._decode_args(norm_param)
         spec = log_spectro.squeeze(1) if log_spectro.dim() == 4 else log_spectro
-        window, _ = self._tables(log_spectro.device)
-        g = imdct4_backward(grad.reshape(spec.shape[0], -1), spec, window, self.n_fft, self.hop_length, spec.shape[1],
-                            codec=codec, gain=gain, norm_range=nr, src_range=sr, min_b=mn if per_sample else None,
-                            max_b=mx if per_sample else None, fused=self.geom512, fast=self.fast)
+        g = self.transform.synthesis_backward(grad.reshape(spec.shape[0], -1), spec, codec, F=spec.shape[1], **clip)
         return g.view(log_spectro.shape)
 
     def to_audio(self, log_spectro: torch.Tensor, norm_param: Dict[str, torch.Tensor], pha: torch.Tensor = None, stitch=None,
                  rows=None):
-        """pix2pixHD_model.py:139-165.  stitch = (out, gen_overlap, first_seg) (has_stitched_decoder only): K2 / K2' writes the segments
-        straight into the stitched waveform `out` (generate_audio.py:40-53 inside the kernel) and `out` is returned.
-        rows = (out, gen_overlap, table[, segment_length[, zero_out]]) (has_stitched_decoder only): the segments are the rows of a
-        device row table of the packed buffer `out`, which holds the stitched waveforms of any number of utterances (mdct.imdct4_codec).
-        Differentiable in log_spectro (arcsinh / range codecs; stitched decode stays forward-only)."""
+        """pix2pixHD_model.py:139-165.  stitch (mdct.Stitch or its tuple (out, gen_overlap, first_seg[, segment_length])) / rows
+        (mdct.Rows or its tuple (out, gen_overlap, table[, segment_length[, zero_out]])), has_stitched_decoder only: K2 / K2' writes the
+        segments straight into the stitched waveform / the packed buffer of stitched waveforms `out` (generate_audio.py:40-53 inside
+        the kernel) and `out` is returned.  Differentiable in log_spectro (arcsinh / range codecs; stitched decode stays forward-only)."""
         mn, mx = norm_param["min"], norm_param["max"]
         if stitch is None and rows is None and wants_grad(log_spectro, mn, mx):
             return CodecGrad.apply(lambda s: self._to_audio(s, norm_param, pha, None),
@@ -265,51 +202,27 @@ class Audio2MDCT(torch.nn.Module):
         return self._to_audio(log_spectro, norm_param, pha, stitch, rows)
 
     def _to_audio(self, log_spectro, norm_param, pha, stitch, rows=None):
-        if (stitch is not None or rows is not None) and not self.has_stitched_decoder:
-            raise NotImplementedError("stitched decode needs the fused 512 / 256 geometry")
-        nr, sr = self._ranges()
-        mn, mx = norm_param["min"], norm_param["max"]
-        per_sample = mn.numel() > 1
-        if not per_sample:
-            sr = (float(mn.reshape(-1)[0]), float(mx.reshape(-1)[0])) if not self.abs_norm else sr
-        if self.fused:
-            window, d4 = self._tables(log_spectro.device)
-            spec = log_spectro.squeeze(1) if log_spectro.dim() == 4 else log_spectro
-            audio, _ = imdct4_codec(spec, window, d4, self.n_fft, codec=self.codec, gain=float(self.arcsinh_gain),
-                                    norm_range=nr, src_range=sr, min_b=mn if per_sample else None,
-                                    max_b=mx if per_sample else None, stitch=stitch, rows=rows)
-            return audio if (stitch is not None or rows is not None) else audio[:, None, None, :]
-        if self.fast_codec:
-            window = self._window(log_spectro.device)
-            spec = log_spectro.squeeze(1) if log_spectro.dim() == 4 else log_spectro
-            audio = imdct4_pow2(spec, window, self.n_fft, codec=self.codec, gain=float(self.arcsinh_gain), norm_range=nr,
-                                src_range=sr, min_b=mn if per_sample else None, max_b=mx if per_sample else None, stitch=stitch,
-                                rows=rows)
-            if audio is not None:
-                return audio if (stitch is not None or rows is not None) else audio[:, None, None, :]
-        spec4 = log_spectro if log_spectro.dim() == 4 else log_spectro[:, None]
-        raw = codec_inverse(spec4, codec=self.codec, gain=float(self.arcsinh_gain), alpha=float(self.alpha),
-                            min_value=float(self.min_value), norm_range=nr, src_range=sr,
-                            min_b=mn if per_sample else None, max_b=mx if per_sample else None)
-        if self.codec == _lib.MG_CODEC_DB and pha is not None and self.up_ratio > 1:
-            # pix2pixHD_model.py:147-157: the sign restore sits INSIDE `if self.up_ratio > 1` in the reference (at
-            # up_ratio == 1 its dB decode stays unsigned) -- mirrored as written
-            ph = pha.reshape(raw.shape).to(raw.device)
-            size = ph.size(-2)
-            keep = int(size * (1 / self.up_ratio))
-            pseudo = (2 * torch.randint(low=0, high=2, size=ph.size(), device=raw.device) - 1).to(ph.dtype)
-            ph = torch.cat((ph[..., :keep, :], pseudo[..., keep:, :]), dim=-2)
-            raw = raw * ph
-        if self.geom512:
-            window, d4 = self._tables(raw.device)
-            audio, _ = imdct4_codec(raw, window, d4, self.n_fft, codec=_lib.MG_CODEC_RAW)
+        dest = stitch is not None or rows is not None
+        if dest:
+            self.transform.route_synthesis(self._codec, dest=True)      # (raises where there is no stitched decoder)
+        codec, clip = self._decode_args(norm_param)
+        if self._in_kernel:
+            audio, _ = self.transform.synthesis(log_spectro, codec, stitch=stitch, rows=rows, **clip)
         else:
-            if self.window.device != raw.device:
-                self.window = self.window.to(raw.device)
-            audio = imdct4_pow2(raw, self.window, self.n_fft) if (self.fast and raw.shape[1] > 1) else None
-            if audio is None:
-                audio, _ = imdct4_generic(raw, self.window, self.n_fft, self.hop_length, True)
-        return audio[:, None, None, :]
+            # dB / explicit encoding: the phase goes in between mg_codec_inverse and the raw inverse transform
+            spec4 = log_spectro if log_spectro.dim() == 4 else log_spectro[:, None]
+            raw = codec_inverse(spec4, **codec.kw(full=True), **clip)
+            if self.codec == _lib.MG_CODEC_DB and pha is not None and self.up_ratio > 1:
+                # pix2pixHD_model.py:147-157: the sign restore sits INSIDE `if self.up_ratio > 1` in the reference (at
+                # up_ratio == 1 its dB decode stays unsigned) -- mirrored as written
+                ph = pha.reshape(raw.shape).to(raw.device)
+                size = ph.size(-2)
+                keep = int(size * (1 / self.up_ratio))
+                pseudo = (2 * torch.randint(low=0, high=2, size=ph.size(), device=raw.device) - 1).to(ph.dtype)
+                ph = torch.cat((ph[..., :keep, :], pseudo[..., keep:, :]), dim=-2)
+                raw = raw * ph
+            audio, _ = self.transform.synthesis(raw, RAW)
+        return audio if dest else audio[:, None, None, :]
 
     def forward(self, lr_audio: torch.Tensor):
         with torch.no_grad():

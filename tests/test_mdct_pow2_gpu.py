@@ -107,6 +107,39 @@ def test_raw_transforms_against_oracle(n_fft, hop, monkeypatch):
         assert (_kernel(0), _kernel(1)) == before                       # the composition names what it named before: nothing new
 
 
+def test_guarded_requests_do_not_reach_the_fused_kernels(monkeypatch):
+    """Analysis frames and a float64 waveform are requests K1' / K2' do not serve (mdct.Transform.route_analysis / route_synthesis):
+    they take the generic composition, which leaves mg_mdct_last_kernel alone -- after a 512 call it still names the 512 kernels --
+    and give the bits of the same calls under MG_MDCT_POW2=0.  n_fft 256, B = 2, T = 1024: more than one tile row per clip."""
+    from mdctgan_amd.mdct import IMDCT4, MDCT4, kbdwin
+    rng = np.random.default_rng(256)
+    w5 = kbdwin(512)
+    X5, _ = MDCT4(512, 256, 512, w5, device="cuda")(torch.from_numpy(rng.standard_normal((2, 2048)).astype(np.float32)).cuda())
+    IMDCT4(512, 256, 512, w5, device="cuda")(X5)
+    names = (_kernel(0), _kernel(1))
+    assert names[0].startswith("mdct4_") and names[1].startswith("imdct4_") and "pow2" not in names[0] + names[1], names
+    w = kbdwin(256)
+    m, im = MDCT4(256, 128, 256, w, device="cuda"), IMDCT4(256, 128, 256, w, device="cuda", dtype=torch.float64)
+    assert m.fast and im.fast
+    x = torch.from_numpy(rng.standard_normal((2, 1024)).astype(np.float32)).cuda()
+    spec = torch.from_numpy(rng.standard_normal((2, 9, 128)).astype(np.float32)).cuda()
+
+    def run():
+        (X, frames), (y, _) = m(x, return_frames=True), im(spec)
+        return X, frames, y
+    got = run()
+    assert (_kernel(0), _kernel(1)) == names
+    assert got[0].shape == (2, 9, 128) and got[1].shape == (2, 9, 256) and got[2].shape == (2, 1, 1, 1024) and got[2].dtype == torch.float64
+    monkeypatch.setenv("MG_MDCT_POW2", "0")
+    assert not m.fast and not im.fast
+    want = run()
+    monkeypatch.delenv("MG_MDCT_POW2")
+    for g, w_ in zip(got, want):
+        assert torch.equal(g, w_)
+    m(x)                                                                # (and the plain request does reach K1')
+    assert "pow2" in _kernel(0), _kernel(0)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. codec paths
 # ---------------------------------------------------------------------------------------------------------------------
