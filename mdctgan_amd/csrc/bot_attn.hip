@@ -75,7 +75,11 @@ __global__ __launch_bounds__(256) void bn_apply_fwd_kernel(const float* __restri
                                                            int act, float* __restrict__ y, float* __restrict__ save_mean,
                                                            float* __restrict__ save_rstd, const double* __restrict__ part,
                                                            double count) {
-    __shared__ float stat[2][64];
+    // stat[2]: what float32 dropped from the batch mean.  x - mean is exact for x near the mean, so with the remainder taken
+    // off as well xhat keeps float32 accuracy however far the data sit from zero (at mean = 1e4 sigma the rounding of the mean
+    // alone moved xhat by 4e-4 and with it ReLU decisions at |z| ~ 1e-5 max|z|; found by the offset case of
+    // tests/test_bot_attn_gpu.py).  save_mean, the running buffers and the backward pass keep the float32 mean.
+    __shared__ float stat[3][64];
     const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6, c = blockIdx.x * 64 + cl, sl = blockIdx.y;
     if (rg == 0 && c < C) {
         if (training) {
@@ -85,6 +89,7 @@ __global__ __launch_bounds__(256) void bn_apply_fwd_kernel(const float* __restri
             double var = b / count - mu * mu;
             if (var < 0.0) var = 0.0;
             stat[0][cl] = (float)mu;
+            stat[2][cl] = (float)(mu - (double)stat[0][cl]);
             stat[1][cl] = (float)(1.0 / sqrt(var + (double)eps));
             if (sl == 0) {
                 save_mean[c] = stat[0][cl];
@@ -98,16 +103,17 @@ __global__ __launch_bounds__(256) void bn_apply_fwd_kernel(const float* __restri
         } else {
             stat[0][cl] = run_mean[c];
             stat[1][cl] = 1.0f / sqrtf(run_var[c] + eps);
+            stat[2][cl] = 0.0f;
             if (sl == 0 && save_mean) { save_mean[c] = stat[0][cl]; save_rstd[c] = stat[1][cl]; }
         }
     }
     __syncthreads();
     if (c >= C) return;
     const int r0 = (int)((long long)R * sl / BN_RS), r1 = (int)((long long)R * (sl + 1) / BN_RS);
-    const float mu = stat[0][cl], rs = stat[1][cl], ga = gamma ? gamma[c] : 1.0f, be = beta ? beta[c] : 0.0f;
+    const float mu = stat[0][cl], rs = stat[1][cl], lo = stat[2][cl], ga = gamma ? gamma[c] : 1.0f, be = beta ? beta[c] : 0.0f;
     for (int r = r0 + rg; r < r1; r += 4) {
         const size_t i = (size_t)r * C + c;
-        float z = ga * ((x[i] - mu) * rs) + be;
+        float z = ga * (((x[i] - mu) - lo) * rs) + be;
         if (residual) z += residual[i];
         y[i] = act_fwd(z, act);
     }
@@ -399,7 +405,8 @@ static size_t attn_lds(int n, int d, bool fwd) {
 int mg_attention_fwd(const float* qkv, const float* emb_h, const float* emb_w, int B, int fh, int fw, int heads, int d,
                      float* out, float* P, void* stream) {
     const int n = fh * fw;
-    if (!qkv || !emb_h || !emb_w || !out || !P || B <= 0 || n <= 0 || n > 128 || d <= 0 || d > 128) return MG_ERR_ARG;
+    if (!qkv || !emb_h || !emb_w || !out || !P || B <= 0 || heads <= 0 || fh <= 0 || fw <= 0 || n > 128 || d <= 0 || d > 128)
+        return MG_ERR_ARG;     // attn_groups divides by B * heads
     const size_t lds = attn_lds(n, d, true);
     if (lds > 160 * 1024) return MG_ERR_UNSUPPORTED;
     static size_t granted = 0;     // raised once, outside any graph capture (warm-up steps run first)
@@ -422,7 +429,9 @@ int mg_attention_bwd(const float* qkv, const float* emb_h, const float* emb_w, c
                      int fh, int fw, int heads, int d, float* dqkv, float* demb_h, float* demb_w, int accumulate,
                      void* workspace, size_t workspace_bytes, void* stream) {
     const int n = fh * fw;
-    if (!qkv || !emb_h || !emb_w || !dout || !P || !dqkv || !workspace || n > 128 || d > 128) return MG_ERR_ARG;
+    if (!qkv || !emb_h || !emb_w || !dout || !P || !dqkv || !workspace || B <= 0 || heads <= 0 || fh <= 0 || fw <= 0 || n > 128 ||
+        d <= 0 || d > 128)
+        return MG_ERR_ARG;     // as mg_attention_fwd: nothing below divides by, or launches over, an empty dimension
     if (workspace_bytes < mg_attention_bwd_workspace(B, fh, fw, heads, d)) return MG_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     float* dS = (float*)workspace;

@@ -53,7 +53,8 @@ def judged(got, f32, f64, what, k=4.0):
     nrm = max(np.linalg.norm(f64), 1e-30)
     e_hip, e_32 = np.linalg.norm(got - f64) / nrm, np.linalg.norm(f32 - f64) / nrm
     # floor 5e-4: one mask flip in either float32 run already costs ~1e-4 (the op-level tests in test_conv_gpu /
-    # test_elementwise_gpu hold the tight 3e-5 bars; this test guards the wiring, where a bug costs O(1))
+    # test_elementwise_gpu and, for the K10 BatchNorm / attention kernels, test_bot_attn_gpu hold the tight 3e-5 bars;
+    # this test guards the wiring, where a bug costs O(1))
     assert e_hip <= max(k * e_32, 5e-4) + 2e-6, "%s: HIP rel-L2 err %.3e vs fp32-CPU %.3e" % (what, e_hip, e_32)
     # localised-garbage guard: 2 % of the tensor's scale, or 1.5 k x float32-CPU's own worst element where that is larger (a
     # ReLU-mask flip behind a 2048-channel reduction moves single elements by more than 2 % in ANY float32 run)
