@@ -466,7 +466,8 @@ int mg_batchnorm_bwd(const float* dy, const float* x, const float* y, int R, int
 /*  Multi-head self attention with absolute position embeddings (rel_pos_emb=False):
  *      qkv [B, fh*fw, 3*heads*d] (channel = which*heads*d + head*d + dd), emb_h [fh, d], emb_w [fw, d];
  *      sim = (q * d^-0.5) (k + emb_h[y] + emb_w[x])^T, out [B, fh*fw, heads*d] = softmax(sim) v.
- *      P [B, heads, n, n] receives the probabilities (saved for backward).  fh*fw <= 128, d <= 128.
+ *      P [B, heads, n, n] receives the probabilities (saved for backward).  fh*fw <= 256, d <= 128 (more than 128 tokens
+ *      run on the MFMA-tiled family of bot_attn.hip; larger maps are MG_ERR_ARG).
  *      Forward and backward both need B, fh, fw, heads and d >= 1 and return MG_ERR_ARG otherwise, before any launch.
  *      Backward: demb_h / demb_w may both be NULL (no table gradient); accumulate = 1 adds into them. */
 int mg_attention_fwd(const float* qkv, const float* emb_h, const float* emb_w, int B, int fh, int fw, int heads, int d,

@@ -7,8 +7,11 @@
 // reference; restated from its published algorithm -- parity UNPINNED):
 //     q, k, v = to_qkv(x).chunk(3);  q *= dim_head^-0.5
 //     sim = q k^T + q (h_emb (+) w_emb)^T  ==  q (k + e)^T ;  out = softmax(sim) v
-// Token counts are tiny (32 at 4x8, 128 at 8x16), so this is a latency-bound VALU kernel: one workgroup per
-// (sample, head) keeps K+E and V in LDS; the FLOPs are < 0.01 % of the step.
+// Token counts are tiny (32 at 4x8, 128 at 8x16), so up to 128 tokens this is a latency-bound VALU kernel: one workgroup
+// per (sample, head) keeps K+E and V in LDS; the FLOPs are < 0.01 % of the step.
+// 129 to 256 tokens (256 at 8x32: the n_fft-1024 map, and at 16x16: 256 frames of n_fft 512) no longer fit two [n][d+1]
+// operands into a CU's LDS; they run on the "wide" family below (attn_wide_*): one workgroup per (sample, head, block of 32
+// queries), every contraction on the exact-float32 MFMA, 38 KB of LDS.  More than 256 tokens are rejected.
 #include "common.h"
 #include "mdctgan_hip.h"
 
@@ -311,6 +314,275 @@ __global__ __launch_bounds__(256) void attn_bwd_b_kernel(const float* __restrict
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// attention, 128 < n <= 256: the "wide" family.  Same algorithm, same buffers; one workgroup (4 waves) per (b, head, block of
+// AW_Q = 32 rows), every contraction as 32x32 tiles of v_mfma_f32_32x32x2_f32 (a float32 fmaf chain in k order: exact float32,
+// fixed order).  P and dS live in HBM anyway, so a pass is a sequence of phases around one LDS tile st [32][257]:
+//   scores   st = X[32 rows][d] Y[n][d]^T      X, Y staged in feature chunks of 32 (xt [32][33], yt [256][33]; st reuses yt);
+//                                              wave w owns key tiles w and w + 4
+//   rows     softmax (forward) / dS = P .* (dP - rowsum(P .* dP)) (backward A): wave w owns rows 8w .. 8w + 7, a lane keys
+//            lane + 64 t as in the narrow kernels; the result goes to HBM and, forward, back into st
+//   apply    O[32 rows][d] = st Y[n][d]        wave w owns features 32w .. 32w + 31; Y straight from HBM (a row of Y is read
+//                                              by one wave, once: nothing to share through LDS), loads one batch ahead
+//   tn       O[32 keys][d] = M[n][n]^T Y[n][d] (dV = P^T dO, dKE = dS^T Q'): both operands straight from HBM, lanes along a
+//                                              row of M / of Y
+// Rows, keys and features past n / d are staged as zeros or read at a clamped index into a tile row / column that is never
+// written out.  LDS: (256 + 32) * 33 floats = 38 KB, static: no raised limit, four workgroups fit a CU.
+// A block's bits depend on (b, head, block) alone, never on the grid: a sample alone has the bits it has in a batch.
+// ------------------------------------------------------------------------------------------------------------
+constexpr int AW_Q = 32;                 // rows per workgroup
+constexpr int AW_N = 256;                // most tokens
+constexpr int AW_LS = AW_N + 1;          // row stride of st
+constexpr int AW_LC = 32 + 1;            // row stride of a staged feature chunk
+constexpr int AW_U = 8;                  // k steps per batch of HBM operand loads
+
+// st[32][AW_LS] = X[i0 .. i0 + 31][d] * xscale  x  (Y[n][d] (+ E))^T.  xt [32][AW_LC], yt [AW_N][AW_LC]; st may be yt.
+template <bool EMB>
+__device__ __forceinline__ void aw_scores(const float* __restrict__ xg, size_t xs, float xscale, int i0,
+                                          const float* __restrict__ yg, size_t ys, const float* __restrict__ eh,
+                                          const float* __restrict__ ew, int fw, int n, int d, float* xt, float* yt, float* st) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nk = (n + 31) >> 5;
+    const int lr = lane & 31, lh = lane >> 5;
+    f32x16 acc[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+    for (int d0 = 0; d0 < d; d0 += 32) {
+        for (int idx = threadIdx.x; idx < AW_Q * 32; idx += 256) {
+            const int r = idx >> 5, c = idx & 31, i = i0 + r, dd = d0 + c;
+            xt[r * AW_LC + c] = (i < n && dd < d) ? xg[(size_t)i * xs + dd] * xscale : 0.0f;
+        }
+        for (int idx = threadIdx.x; idx < nk * 32 * 32; idx += 256) {
+            const int j = idx >> 5, c = idx & 31, dd = d0 + c;
+            float v = 0.0f;
+            if (j < n && dd < d) {
+                v = yg[(size_t)j * ys + dd];
+                if (EMB) v += eh[(j / fw) * d + dd] + ew[(j % fw) * d + dd];
+            }
+            yt[j * AW_LC + c] = v;
+        }
+        __syncthreads();
+        const int kmax = min(32, (d - d0 + 1) & ~1);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const int kt = wave + 4 * t;
+            if (kt < nk)
+                for (int k = 0; k < kmax; k += 2)
+                    acc[t] = mfma32x32x2(xt[lr * AW_LC + k + lh], yt[(kt * 32 + lr) * AW_LC + k + lh], acc[t]);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int kt = wave + 4 * t;
+        if (kt < nk)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) st[mfma32_row(r, lane) * AW_LS + kt * 32 + lr] = acc[t][r];
+    }
+    __syncthreads();
+}
+
+// acc (this wave's features 32 * wave + (lane & 31), rows mfma32_row) = st[32][n] (Y[n][d] (+ E)).  st is zero in columns
+// n .. 255; et (EMB): [j] = (j / fw) * d, [AW_N + j] = (j % fw) * d.  Returns false for a wave without features.
+template <bool EMB>
+__device__ __forceinline__ bool aw_apply(const float* st, const float* __restrict__ yg, size_t ys,
+                                         const float* __restrict__ eh, const float* __restrict__ ew, const int* et, int n, int d,
+                                         f32x16& acc) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 31, lh = lane >> 5;
+    if (32 * wave >= d) return false;
+    const int ddc = min(32 * wave + lr, d - 1);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    float yn[AW_U], hn[AW_U], wn[AW_U];
+    auto load = [&](int k) {
+#pragma unroll
+        for (int u = 0; u < AW_U; ++u) {
+            const int j = min(k + 2 * u + lh, n - 1);
+            yn[u] = yg[(size_t)j * ys + ddc];
+            if (EMB) { hn[u] = eh[et[j] + ddc]; wn[u] = ew[et[AW_N + j] + ddc]; }
+        }
+    };
+    load(0);
+    for (int k = 0; k < n; k += 2 * AW_U) {
+        float yc[AW_U];
+#pragma unroll
+        for (int u = 0; u < AW_U; ++u) yc[u] = EMB ? yn[u] + (hn[u] + wn[u]) : yn[u];
+        load(k + 2 * AW_U);
+#pragma unroll
+        for (int u = 0; u < AW_U; ++u) acc = mfma32x32x2(st[lr * AW_LS + k + 2 * u + lh], yc[u], acc);
+    }
+    return true;
+}
+
+// acc (features 32 * wave + (lane & 31), keys j0 + mfma32_row) = M[n][n]^T[j0 .. j0 + 31] (Y[n][d] * yscale)
+__device__ __forceinline__ bool aw_tn(const float* __restrict__ M, const float* __restrict__ yg, size_t ys, float yscale,
+                                      int j0, int n, int d, f32x16& acc) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 31, lh = lane >> 5;
+    if (32 * wave >= d) return false;
+    const int ddc = min(32 * wave + lr, d - 1), jc = min(j0 + lr, n - 1);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    float mn[AW_U], yn[AW_U];
+    auto load = [&](int k) {
+#pragma unroll
+        for (int u = 0; u < AW_U; ++u) {
+            const int i = k + 2 * u + lh, ic = min(i, n - 1);
+            mn[u] = i < n ? M[(size_t)ic * n + jc] : 0.0f;
+            yn[u] = yg[(size_t)ic * ys + ddc];
+        }
+    };
+    load(0);
+    for (int k = 0; k < n; k += 2 * AW_U) {
+        float mc[AW_U], yc[AW_U];
+#pragma unroll
+        for (int u = 0; u < AW_U; ++u) { mc[u] = mn[u]; yc[u] = yn[u] * yscale; }
+        load(k + 2 * AW_U);
+#pragma unroll
+        for (int u = 0; u < AW_U; ++u) acc = mfma32x32x2(mc[u], yc[u], acc);
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(256) void attn_wide_fwd_kernel(const float* __restrict__ qkv, const float* __restrict__ eh,
+                                                            const float* __restrict__ ew, int n, int fw, int heads, int d,
+                                                            float scale, float* __restrict__ out, float* __restrict__ P) {
+    __shared__ float yt[AW_N * AW_LC];
+    __shared__ float xt[AW_Q * AW_LC];
+    float* st = yt;                 // [32][AW_LS] <= [256][33]
+    const int HD = heads * d, b = blockIdx.x / heads, h = blockIdx.x % heads, i0 = AW_Q * blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* base = qkv + (size_t)b * n * 3 * HD + h * d;
+    aw_scores<true>(base, (size_t)3 * HD, scale, i0, base + HD, (size_t)3 * HD, eh, ew, fw, n, d, xt, yt, st);
+    float* Pb = P + ((size_t)b * heads + h) * n * n;
+    for (int r = 8 * wave; r < 8 * wave + 8; ++r) {
+        const int i = i0 + r;
+        if (i >= n) break;
+        float s[4], mx = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int j = lane + 64 * t;
+            s[t] = j < n ? st[r * AW_LS + j] : -INFINITY;
+            mx = fmaxf(mx, s[t]);
+        }
+        mx = wave_max(mx);
+        float sum = 0.0f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            s[t] = (lane + 64 * t < n) ? expf(s[t] - mx) : 0.0f;
+            sum += s[t];
+        }
+        sum = wave_sum(sum);
+        const float inv = 1.0f / sum;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int j = lane + 64 * t;
+            const float p = s[t] * inv;                 // 0 past n: apply's clamped loads meet it there
+            st[r * AW_LS + j] = p;
+            if (j < n) Pb[(size_t)i * n + j] = p;
+        }
+    }
+    __syncthreads();
+    f32x16 acc;
+    if (aw_apply<false>(st, base + 2 * HD, (size_t)3 * HD, nullptr, nullptr, nullptr, n, d, acc)) {
+        const int dd = 32 * wave + (lane & 31);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int i = i0 + mfma32_row(r, lane);
+            if (i < n && dd < d) out[((size_t)b * n + i) * HD + h * d + dd] = acc[r];
+        }
+    }
+}
+
+// backward, part A: dS rows i0 .. i0 + 31 and dV of keys i0 .. i0 + 31
+__global__ __launch_bounds__(256) void attn_wide_bwd_a_kernel(const float* __restrict__ qkv, const float* __restrict__ dout,
+                                                              const float* __restrict__ P, int n, int heads, int d,
+                                                              float* __restrict__ dqkv, float* __restrict__ dS) {
+    __shared__ float yt[AW_N * AW_LC];
+    __shared__ float xt[AW_Q * AW_LC];
+    float* st = yt;
+    const int HD = heads * d, b = blockIdx.x / heads, h = blockIdx.x % heads, i0 = AW_Q * blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* vb = qkv + (size_t)b * n * 3 * HD + 2 * HD + h * d;
+    const float* dob = dout + (size_t)b * n * HD + h * d;
+    const float* Pb = P + ((size_t)b * heads + h) * n * n;
+    float* dSb = dS + ((size_t)b * heads + h) * n * n;
+    aw_scores<false>(dob, (size_t)HD, 1.0f, i0, vb, (size_t)3 * HD, nullptr, nullptr, 1, n, d, xt, yt, st);      // dP
+    for (int r = 8 * wave; r < 8 * wave + 8; ++r) {
+        const int i = i0 + r;
+        if (i >= n) break;
+        float dp[4], pv[4], dot = 0.0f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int j = lane + 64 * t;
+            dp[t] = 0.0f;
+            pv[t] = 0.0f;
+            if (j < n) {
+                dp[t] = st[r * AW_LS + j];
+                pv[t] = Pb[(size_t)i * n + j];
+                dot += pv[t] * dp[t];
+            }
+        }
+        dot = wave_sum(dot);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int j = lane + 64 * t;
+            if (j < n) dSb[(size_t)i * n + j] = pv[t] * (dp[t] - dot);
+        }
+    }
+    f32x16 acc;
+    if (aw_tn(Pb, dob, (size_t)HD, 1.0f, i0, n, d, acc)) {
+        const int dd = 32 * wave + (lane & 31);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int j = i0 + mfma32_row(r, lane);
+            if (j < n && dd < d) dqkv[((size_t)b * n + j) * 3 * HD + 2 * HD + h * d + dd] = acc[r];
+        }
+    }
+}
+
+// backward, part B: dq of rows i0 .. i0 + 31 (scale * dS KE), dk and the dE partials of keys i0 .. i0 + 31 (dS^T Q')
+__global__ __launch_bounds__(256) void attn_wide_bwd_b_kernel(const float* __restrict__ qkv, const float* __restrict__ eh,
+                                                              const float* __restrict__ ew, const float* __restrict__ dS,
+                                                              int n, int fw, int heads, int d, float scale,
+                                                              float* __restrict__ dqkv, float* __restrict__ dE) {
+    __shared__ float st[AW_Q * AW_LS];
+    __shared__ int et[2 * AW_N];
+    const int HD = heads * d, b = blockIdx.x / heads, h = blockIdx.x % heads, i0 = AW_Q * blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* base = qkv + (size_t)b * n * 3 * HD + h * d;
+    const float* dSb = dS + ((size_t)b * heads + h) * n * n;
+    for (int idx = threadIdx.x; idx < AW_Q * AW_N; idx += 256) {
+        const int r = idx >> 8, j = idx & 255, i = i0 + r;
+        st[r * AW_LS + j] = (i < n && j < n) ? dSb[(size_t)i * n + j] : 0.0f;
+    }
+    {
+        const int j = min((int)threadIdx.x, n - 1);
+        et[threadIdx.x] = (j / fw) * d;
+        et[AW_N + threadIdx.x] = (j % fw) * d;
+    }
+    __syncthreads();
+    f32x16 acc;
+    const int dd = 32 * wave + (lane & 31);
+    if (aw_apply<true>(st, base + HD, (size_t)3 * HD, eh, ew, et, n, d, acc)) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int i = i0 + mfma32_row(r, lane);
+            if (i < n && dd < d) dqkv[((size_t)b * n + i) * 3 * HD + h * d + dd] = acc[r] * scale;
+        }
+    }
+    if (aw_tn(dSb, base, (size_t)3 * HD, scale, i0, n, d, acc)) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int j = i0 + mfma32_row(r, lane);
+            if (j < n && dd < d) {
+                dqkv[((size_t)b * n + j) * 3 * HD + HD + h * d + dd] = acc[r];
+                dE[(((size_t)b * heads + h) * n + j) * d + dd] = acc[r];
+            }
+        }
+    }
+}
+
 // d height[y][dd] = sum_{b,h,x} dE[b,h][(y,x)][dd];  d width[x][dd] = sum_{b,h,y} dE[...]
 // one workgroup per row of the two tables (fh + fw of them), 1024 threads = (1024 / d) groups x d lanes: a group walks every
 // (1024 / d)-th (b, head) pair in ascending order, the groups meet in LDS in fixed order (deterministic).  (Rounds 1-2: one
@@ -405,8 +677,14 @@ static size_t attn_lds(int n, int d, bool fwd) {
 int mg_attention_fwd(const float* qkv, const float* emb_h, const float* emb_w, int B, int fh, int fw, int heads, int d,
                      float* out, float* P, void* stream) {
     const int n = fh * fw;
-    if (!qkv || !emb_h || !emb_w || !out || !P || B <= 0 || heads <= 0 || fh <= 0 || fw <= 0 || n > 128 || d <= 0 || d > 128)
+    if (!qkv || !emb_h || !emb_w || !out || !P || B <= 0 || heads <= 0 || fh <= 0 || fw <= 0 || n > 256 || d <= 0 || d > 128)
         return MG_ERR_ARG;     // attn_groups divides by B * heads
+    if (n > 128) {             // the wide family: a workgroup per block of 32 queries, static LDS
+        hipLaunchKernelGGL(attn_wide_fwd_kernel, dim3(B * heads, (n + AW_Q - 1) / AW_Q), dim3(256), 0, (hipStream_t)stream, qkv, emb_h,
+                           emb_w, n, fw, heads, d, 1.0f / sqrtf((float)d), out, P);
+        MG_CHECK_LAUNCH();
+        return MG_OK;
+    }
     const size_t lds = attn_lds(n, d, true);
     if (lds > 160 * 1024) return MG_ERR_UNSUPPORTED;
     static size_t granted = 0;     // raised once, outside any graph capture (warm-up steps run first)
@@ -429,13 +707,24 @@ int mg_attention_bwd(const float* qkv, const float* emb_h, const float* emb_w, c
                      int fh, int fw, int heads, int d, float* dqkv, float* demb_h, float* demb_w, int accumulate,
                      void* workspace, size_t workspace_bytes, void* stream) {
     const int n = fh * fw;
-    if (!qkv || !emb_h || !emb_w || !dout || !P || !dqkv || !workspace || B <= 0 || heads <= 0 || fh <= 0 || fw <= 0 || n > 128 ||
+    if (!qkv || !emb_h || !emb_w || !dout || !P || !dqkv || !workspace || B <= 0 || heads <= 0 || fh <= 0 || fw <= 0 || n > 256 ||
         d <= 0 || d > 128)
         return MG_ERR_ARG;     // as mg_attention_fwd: nothing below divides by, or launches over, an empty dimension
     if (workspace_bytes < mg_attention_bwd_workspace(B, fh, fw, heads, d)) return MG_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     float* dS = (float*)workspace;
     float* dE = dS + (size_t)B * heads * n * n;
+    if (n > 128) {             // the wide family
+        const dim3 grid(B * heads, (n + AW_Q - 1) / AW_Q);
+        hipLaunchKernelGGL(attn_wide_bwd_a_kernel, grid, dim3(256), 0, st, qkv, dout, P, n, heads, d, dqkv, dS);
+        hipLaunchKernelGGL(attn_wide_bwd_b_kernel, grid, dim3(256), 0, st, qkv, emb_h, emb_w, (const float*)dS, n, fw, heads, d,
+                           1.0f / sqrtf((float)d), dqkv, dE);
+        if (demb_h && demb_w)
+            hipLaunchKernelGGL(posemb_grad_kernel, dim3(fh + fw), dim3(1024), 0, st, (const float*)dE, B * heads, fh, fw, d, demb_h,
+                               demb_w, accumulate);
+        MG_CHECK_LAUNCH();
+        return MG_OK;
+    }
     const size_t lds = attn_lds(n, d, false);
     if (lds > 160 * 1024) return MG_ERR_UNSUPPORTED;
     static size_t granted = 0;

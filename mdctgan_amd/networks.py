@@ -272,8 +272,8 @@ class BottleStack(FusedModule):
         super().__init__()
         fmap_size = tuple(fmap_size) if isinstance(fmap_size, (tuple, list)) else (fmap_size, fmap_size)
         self.dim, self.fmap_size = dim, fmap_size
-        if fmap_size[0] * fmap_size[1] > 128 or dim_head > 128:
-            raise NotImplementedError("HIP attention kernel covers <= 128 tokens and dim_head <= 128")
+        if fmap_size[0] * fmap_size[1] > 256 or dim_head > 128:
+            raise NotImplementedError("HIP attention kernels cover <= 256 tokens and dim_head <= 128")
         layers = []
         for i in range(num_layers):
             layers.append(BottleBlock(dim=(dim if i == 0 else dim_out), fmap_size=fmap_size, dim_out=dim_out,
