@@ -204,6 +204,38 @@ long long mg_resample_length(long long L, int orig, int new_);
 int mg_resample(const float* x, int B, int L, const float* kern, int orig, int new_, int width, float* out, int out_len,
                 void* stream);
 
+/* The same data path for MANY utterances in shared launches (data/audio_dataset.py:66-78 and 141-186, --add_noise included):
+ * every utterance sits at its own place of one packed buffer, device row tables (arrays of long long, as mg_seg_row) say where
+ * each row reads and writes.  Windows are cut to their buffers inside the kernels (a bad table drops samples, it never touches
+ * memory outside them), a row of length 0 is a dead row, there are no atomics and every sum has one fixed order: an utterance has
+ * the same bits alone as inside any pack.  No host synchronisation; the launch count does not depend on n_rows.
+ *   mg_resample_rows   mg_resample over a packed buffer: row u reads x[in_pos, in_pos + in_len) and writes out[out_pos, out_pos +
+ *                      out_len), out_len = mg_resample_length(in_len, orig, new_) (the host builds the table so), one call per
+ *                      rate pair.  max_out_len (the longest out_len, known to the host) only sizes the grid.  shift [n_rows] or NULL:
+ *                      row u's samples enter as x + shift[u] (a float32 add; the zero padding around the row stays zero) -- the
+ *                      `raw += 1e-4 - mean(raw)` of :146.  Per output sample the fmaf chain of mg_resample in ascending tap order:
+ *                      bit-identical to mg_resample on the row alone (on x + shift with a shift).  Rows longer than INT_MAX are
+ *                      dropped.  Filter banks above 48 KB stay in global memory, as in mg_resample.
+ *   mg_rows_moments    out[r] = {sum x, sum x^2} (double) over the window [lo, hi) of rows[r] (pos is not used): chunks of
+ *                      MG_MOMENTS_CHUNK samples counted from lo, each summed by one workgroup in a fixed tree, then the chunks in
+ *                      ascending order.  max_len: the longest window (sizes the workspace and the grid; longer rows lose their
+ *                      tail).  workspace: mg_rows_moments_workspace(n_rows, max_len) bytes.  A dead row gives {0, 0}.
+ *   mg_add_noise_rows  :73-78 / :179-184 per row, in place on the packed low-rate buffer: lr = lr + a (noise - m) in float32, with
+ *                      m = sum n / N and a = sqrt((sum lr^2 / segment_length) / 10^(snr / 10)) / std(n) computed on the device
+ *                      from the two mg_rows_moments results; std is the unbiased one (N - 1), and the divisor of the signal
+ *                      power is segment_length, not N, as in the reference.  noise has lr's layout.  Rows of fewer than 2 samples
+ *                      are left alone (the caller refuses them). */
+#define MG_MOMENTS_CHUNK 4096
+typedef struct { long long in_pos, in_len, out_pos, out_len; } mg_resample_row;
+int mg_resample_rows(const float* x, long long x_total, const mg_resample_row* rows, int n_rows, long long max_out_len,
+                     const float* shift, const float* kern, int orig, int new_, int width, float* out, long long out_total,
+                     void* stream);
+size_t mg_rows_moments_workspace(int n_rows, long long max_len);
+int mg_rows_moments(const float* x, long long total, const mg_seg_row* rows, int n_rows, long long max_len, double* out,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int mg_add_noise_rows(float* lr, const float* noise, long long total, const mg_seg_row* rows, int n_rows, long long max_len,
+                      const double* lr_moments, const double* noise_moments, double snr, long long segment_length, void* stream);
+
 /* F2  util/util.py:132-177 compute_matrics on the device (train.py:104-134 eval_model, generate_audio.py:60).
  *   mg_metrics_rows   out[b] = {sum hr^2, sum (sr - hr)^2, sum (lr - hr)^2} (double) for clips [B, T]  -> MSE / SNR
  *   mg_stft_frames    reflect-padded (center != 0), windowed frames [B * F, n_fft], F = mg_stft_num_frames(): the A

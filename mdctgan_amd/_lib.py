@@ -105,7 +105,11 @@ SIGNATURES = {
     "mg_probe_arm": (None, [_p, _p]),
     "mg_resample_length": (_ll, [_ll, _i, _i]),
     "mg_resample": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _i, _p]),
-    "mg_metrics_rows": (_i, [_p, _p, _p, _i, _i, _p, _p]),
+    "mg_resample_rows": (_i, [_p, _ll, _p, _i, _ll, _p, _p, _i, _i, _i, _p, _ll, _p]),
+    "mg_rows_moments_workspace": (_sz, [_i, _ll]),
+    "mg_rows_moments": (_i, [_p, _ll, _p, _i, _ll, _p, _p, _sz, _p]),
+    "mg_add_noise_rows": (_i, [_p, _p, _ll, _p, _i, _ll, _p, _p, C.c_double, _ll, _p]),
+    "mg_metrics_rows":(_i, [_p, _p, _p, _i, _i, _p, _p]),
     "mg_stft_num_frames": (_i, [_i, _i, _i, _i]),
     "mg_stft_frames": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p]),
     "mg_lsd_frames": (_i, [_p, _p, _ll, _i, _p, _p]),

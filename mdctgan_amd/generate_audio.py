@@ -12,7 +12,8 @@ generator's batches.  Every waveform sits at an aligned start of one packed inpu
 device row tables (``mg_seg_row``: position, window) say where each batch row reads and writes: one gather launch per batch cuts
 the segments (``mg_segments_gather``), and the row-table decode (``mg_imdct4_stitched_rows``, ``mg_imdct4_pow2_stitched_rows``)
 stitches every utterance in its own window.  The launch topology does not depend on the mix of lengths, so one captured graph
-serves them all.
+serves them all.  ``super_resolve_many`` starts one step earlier, from raw files at their own sampling rates: the packed
+front end of ``resample.front_end_many`` leaves the packed input buffer that these batches read.
 """
 from __future__ import annotations
 
@@ -260,21 +261,12 @@ def _views(out, plan: UtterancePlan):
     return [out[s:s + n].view(1, -1) for s, n in zip(plan.out_start, plan.out_length)]
 
 
-def generate_many(model, waves, batch_size: int = 64, gen_overlap: int = 0, pad_batches: bool = False, segment_length=None):
-    """Whole-utterance inference over a list of low-rate waveforms ([T_u] or [1, T_u]) of any lengths, their segments sharing the
-    generator's batches -> list of stitched super-resolved waveforms [1, total_u] (views of one packed buffer), each what
-    generate(model, segment_audio(wave_u, ...), ...) stitches from the same generator outputs.  Per batch: one gather launch
-    (mg_segments_gather), model.inference, and its row-table decode that writes every utterance's window of the packed output.
-    pad_batches: every batch runs at the full batch_size (dead rows are zero segments and write nothing); otherwise the last batch
-    runs at its live size.  Codec geometries without a stitched decoder (or MG_NO_STITCHED_K2=1) decode per batch and stitch every
-    utterance with ops.stitch_segments.  segment_length: the model's --segment_length by default.
-    The factored n_fft-512 decode addresses its output with 32 bits: a packed output of 2^30 - 2^14 samples or more (about six
-    hours at 48 kHz; plan.out_total) still decodes correctly, but on the slower generic kernel (mg_mdct_last_kernel(1) names it)
-    -- split a larger corpus into several calls."""
+def _run_packed(model, packed, plan: UtterancePlan, pad_batches: bool = False):
+    """generate_many's batches over a packed input buffer and its plan: per batch one gather launch, model.inference and the
+    row-table decode -> list of stitched waveforms [1, total_u]."""
     from .mdct import seg_row_table, segments_gather
-    plan = _plan_for(model, waves, batch_size, gen_overlap, segment_length)
-    dev = next(model.netG.parameters()).device
-    packed = _pack_waves(waves, plan, dev)
+    dev = packed.device
+    gen_overlap = plan.gen_overlap
     tables = seg_row_table(np.stack([plan.in_rows, plan.out_rows]), dev).view(2, -1, 3)
     fused = _fused_many(model)
     # (zeros: the cross-fade zones are added into the buffer, and the alignment gaps between utterances are never written)
@@ -298,7 +290,43 @@ def generate_many(model, waves, batch_size: int = 64, gen_overlap: int = 0, pad_
         return _views(out, plan)
     audio = torch.cat(outs, dim=0)                      # [n_live, 1, 1, T]
     first = np.concatenate([[0], np.cumsum(plan.segments)])
-    return [ops.stitch_segments(audio[first[u]:first[u + 1]], audio.shape[-1], gen_overlap) for u in range(len(waves))]
+    return [ops.stitch_segments(audio[first[u]:first[u + 1]], audio.shape[-1], gen_overlap) for u in range(len(plan.lengths))]
+
+
+def generate_many(model, waves, batch_size: int = 64, gen_overlap: int = 0, pad_batches: bool = False, segment_length=None):
+    """Whole-utterance inference over a list of low-rate waveforms ([T_u] or [1, T_u]) of any lengths, their segments sharing the
+    generator's batches -> list of stitched super-resolved waveforms [1, total_u] (views of one packed buffer), each what
+    generate(model, segment_audio(wave_u, ...), ...) stitches from the same generator outputs.  Per batch: one gather launch
+    (mg_segments_gather), model.inference, and its row-table decode that writes every utterance's window of the packed output.
+    pad_batches: every batch runs at the full batch_size (dead rows are zero segments and write nothing); otherwise the last batch
+    runs at its live size.  Codec geometries without a stitched decoder (or MG_NO_STITCHED_K2=1) decode per batch and stitch every
+    utterance with ops.stitch_segments.  segment_length: the model's --segment_length by default.
+    The factored n_fft-512 decode addresses its output with 32 bits: a packed output of 2^30 - 2^14 samples or more (about six
+    hours at 48 kHz; plan.out_total) still decodes correctly, but on the slower generic kernel (mg_mdct_last_kernel(1) names it)
+    -- split a larger corpus into several calls."""
+    plan = _plan_for(model, waves, batch_size, gen_overlap, segment_length)
+    dev = next(model.netG.parameters()).device
+    return _run_packed(model, _pack_waves(waves, plan, dev), plan, pad_batches)
+
+
+def super_resolve_many(model, raws, rates, batch_size: int = 64, gen_overlap=None, noise=None, generator=None):
+    """From raw files to super-resolved waveforms for a whole test set: resample.front_end_many (AudioTestDataset.read_audio +
+    post_processing, data/audio_dataset.py:141-186, for all utterances in shared launches) followed by generate_many's batches
+    over the packed buffer it leaves -- no per-utterance launch, no repacking.  raws: waveforms [T_u] or [1, T_u] (host or device)
+    at sampling rates `rates`.  lr_sampling_rate, hr_sampling_rate, is_lr_input, add_noise, snr, segment_length and (unless given)
+    gen_overlap come from model.opt.  noise / generator: see front_end_many.  -> list of stitched waveforms [1, total_u], views
+    of one packed buffer, bit for bit generate_many(model, front_end_many(...)'s views)."""
+    from .resample import front_end_many
+    opt = model.opt
+    L = int(opt.segment_length)
+    ov = int(getattr(opt, "gen_overlap", 0) or 0) if gen_overlap is None else int(gen_overlap)
+    kw = dict(lr_sampling_rate=opt.lr_sampling_rate, hr_sampling_rate=opt.hr_sampling_rate,
+              is_lr_input=bool(getattr(opt, "is_lr_input", False)), add_noise=bool(getattr(opt, "add_noise", False)),
+              snr=float(getattr(opt, "snr", 55.0)), segment_length=L, gen_overlap=ov, batch_size=batch_size,
+              out_segment_length=_decoded_segment_length(model.preprocess, L))
+    dev = next(model.netG.parameters()).device
+    packed, _, plan = front_end_many(raws, rates, kw, noise=noise, generator=generator, device=dev)
+    return _run_packed(model, packed, plan.utterances)
 
 
 def make_graphed_generate_many(model, max_segments: int, max_samples: int, batch_size: int = 64, gen_overlap: int = 0,

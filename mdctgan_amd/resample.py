@@ -2,11 +2,22 @@
 device: same signature and defaults (sinc_interp_hann, lowpass_filter_width=6, rolloff=0.99), the polyphase filter bank
 built once per rate pair exactly as torchaudio's ``_get_sinc_resample_kernel`` does (float64, stored as float32), the
 convolution as one HIP launch (``mg_resample``).  torchaudio itself is not a dependency.
+
+Many utterances (``plan_front_end``, ``front_end_many``): AudioTestDataset.read_audio + post_processing (:141-186) for a whole
+test set in shared launches.  Every utterance sits at an aligned start of one packed buffer per resampling step, device row
+tables (``mg_resample_row``, ``mg_seg_row``) say where each row reads and writes, and the launch count -- one packing copy, one
+table copy, the DC mean (``mg_rows_moments``), one ``mg_resample_rows`` per distinct rate pair and step, and under ``--add_noise``
+two more moment passes and ``mg_add_noise_rows`` -- does not depend on the number of utterances.  Nothing is read back.  The final
+buffer has ``generate_audio._pack_waves``' layout, so ``generate_many``'s gather and decode tables apply to it unchanged.
 """
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
+from types import SimpleNamespace
+from typing import List
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -65,20 +76,26 @@ def seg_pad_audio(waveform: torch.Tensor, segment_length: int) -> torch.Tensor:
 
 
 def make_training_pair(waveform: torch.Tensor, orig_sample_rate: int, hr_sampling_rate: int, lr_sampling_rate: int,
-                       segment_length: int):
-    """AudioDataset.__getitem__ (data/audio_dataset.py:66-82) without the optional noise: HR = resample to hr_rate; LR =
-    resample to lr_rate and back up to hr_rate; both cropped / padded to segment_length.  [B, L] -> (lr, hr)."""
+                       segment_length: int, add_noise: bool = False, snr: float = 55.0, noise=None, generator=None):
+    """AudioDataset.__getitem__ (data/audio_dataset.py:66-82): HR = resample to hr_rate; LR = resample to lr_rate and back up to
+    hr_rate, plus the noise of :72-78 under add_noise (on the full resampled waveform, before the crop; see add_noise); both
+    cropped / padded to segment_length.  [B, L] -> (lr, hr).  The random file offset of readaudio (:43-48) is the loader's."""
     hr = resample(waveform, orig_sample_rate, hr_sampling_rate)
     lr = resample(resample(waveform, orig_sample_rate, lr_sampling_rate), lr_sampling_rate, hr_sampling_rate)
+    if add_noise:
+        lr = add_noise_rows_of(lr, snr, segment_length, noise, generator, in_place=lr.data_ptr() != waveform.data_ptr())
     return seg_pad_audio(lr, segment_length), seg_pad_audio(hr, segment_length)
 
 
 def make_test_segments(raw_audio: torch.Tensor, in_sampling_rate: int, hr_sampling_rate: int, lr_sampling_rate: int,
-                       segment_length: int, gen_overlap: int = 0, is_lr_input: bool = False):
-    """AudioTestDataset (data/audio_dataset.py:141-186; add_noise off) for one waveform [1, L] in HBM: the DC shift of
+                       segment_length: int, gen_overlap: int = 0, is_lr_input: bool = False, add_noise: bool = False,
+                       snr: float = 55.0, noise=None, generator=None):
+    """AudioTestDataset (data/audio_dataset.py:141-186) for one waveform [1, L] in HBM: the DC shift of
     read_audio (``raw += 1e-4 - mean(raw)``), then the low-rate input of the model -- a file that already IS low-rate
-    (``--is_lr_input``) is only brought up to hr_rate, anything else goes down to lr_rate and back up -- cut into segments
-    by seg_pad_audio (generate_audio.segment_audio).  -> (lr_audio [1, L'], segments [n_seg, segment_length])."""
+    (``--is_lr_input``) is only brought up to hr_rate, anything else goes down to lr_rate and back up -- plus the noise of
+    :178-184 under add_noise (see add_noise_rows_of), cut into segments
+    by seg_pad_audio (generate_audio.segment_audio).  -> (lr_audio [1, L'], segments [n_seg, segment_length]).
+    front_end_many does this for any number of waveforms in shared launches."""
     from .generate_audio import segment_audio
     raw = raw_audio.to(torch.float32)
     raw = raw + (1e-4 - raw.mean())
@@ -86,4 +103,287 @@ def make_test_segments(raw_audio: torch.Tensor, in_sampling_rate: int, hr_sampli
         lr_audio = resample(raw, in_sampling_rate, hr_sampling_rate)
     else:
         lr_audio = resample(resample(raw, in_sampling_rate, lr_sampling_rate), lr_sampling_rate, hr_sampling_rate)
+    if add_noise:
+        lr_audio = add_noise_rows_of(lr_audio, snr, segment_length, noise, generator, in_place=True)
     return lr_audio, segment_audio(lr_audio, segment_length, gen_overlap)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Row-table kernels: many utterances in shared launches
+# ---------------------------------------------------------------------------------------------------------------------
+def _table(table, cols: int, what: str):
+    if not (torch.is_tensor(table) and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == cols
+            and table.shape[0] > 0 and table.is_contiguous()):
+        raise ValueError("%s: the row table is a contiguous int64 [n, %d] tensor with at least one row" % (what, cols))
+    return table
+
+
+def resample_rows(x: torch.Tensor, table: torch.Tensor, max_out_len: int, orig_freq: int, new_freq: int, out: torch.Tensor,
+                  shift=None, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> torch.Tensor:
+    """mg_resample_rows: row u of `table` (int64 [n, 4] = in_pos, in_len, out_pos, out_len, on the device) reads its window of the
+    packed float32 buffer `x` and writes resample()'s result for it into its window of `out`; shift [n] float32 enters row u's
+    samples as x + shift[u].  Equal rates copy (a one-tap bank)."""
+    lib = _lib.load()
+    n = _table(table, 4, "resample_rows").shape[0]
+    if x.dtype != torch.float32 or out.dtype != torch.float32 or not x.is_contiguous() or not out.is_contiguous():
+        raise ValueError("resample_rows: x and out are contiguous float32 buffers")
+    if shift is not None and (shift.dtype != torch.float32 or shift.numel() != n or not shift.is_contiguous()):
+        raise ValueError("resample_rows: shift is a contiguous float32 [%d] tensor" % n)
+    if orig_freq <= 0 or new_freq <= 0:
+        raise ValueError("Original frequency and desired frequency should be positive")
+    if int(orig_freq) == int(new_freq):
+        kern, width, orig, new = _identity_kernel(x.device)
+    else:
+        kern, width, orig, new = _sinc_kernel(orig_freq, new_freq, lowpass_filter_width, rolloff, x.device)
+    _lib.check(lib.mg_resample_rows(_lib.ptr(x), x.numel(), _lib.ptr(table), n, int(max_out_len), _lib.ptr(shift), _lib.ptr(kern),
+                                    orig, new, width, _lib.ptr(out), out.numel(), _lib.stream()), "mg_resample_rows")
+    return out
+
+
+def _identity_kernel(device):
+    key = ("identity", str(device))
+    if key not in _kernels:
+        _kernels[key] = (torch.ones(1, 1, dtype=torch.float32, device=device), 0, 1, 1)
+    return _kernels[key]
+
+
+def rows_moments(x: torch.Tensor, table: torch.Tensor, max_len: int) -> torch.Tensor:
+    """mg_rows_moments: float64 [n, 2] = {sum x, sum x^2} over the window [lo, hi) of every row of `table` (int64 [n, 3] = pos, lo,
+    hi on the device) of the packed float32 buffer `x`."""
+    lib = _lib.load()
+    n = _table(table, 3, "rows_moments").shape[0]
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("rows_moments: x is a contiguous float32 buffer")
+    nbytes = lib.mg_rows_moments_workspace(n, int(max_len))
+    ws = _lib.workspace(nbytes, x.device)
+    out = torch.empty(n, 2, dtype=torch.float64, device=x.device)
+    _lib.check(lib.mg_rows_moments(_lib.ptr(x), x.numel(), _lib.ptr(table), n, int(max_len), _lib.ptr(out), _lib.ptr(ws), nbytes,
+                                   _lib.stream()), "mg_rows_moments")
+    return out
+
+
+def add_noise_rows(lr: torch.Tensor, noise: torch.Tensor, table: torch.Tensor, max_len: int, lr_moments: torch.Tensor,
+                   noise_moments: torch.Tensor, snr: float, segment_length: int) -> torch.Tensor:
+    """mg_add_noise_rows, in place on the packed buffer `lr`: every row's window [lo, hi) becomes lr + a (noise - mean(noise)),
+    a = sqrt((sum lr^2 / segment_length) / 10^(snr / 10)) / std(noise), from rows_moments(lr, ...) and rows_moments(noise, ...)."""
+    lib = _lib.load()
+    n = _table(table, 3, "add_noise_rows").shape[0]
+    if lr.dtype != torch.float32 or noise.dtype != torch.float32 or not lr.is_contiguous() or not noise.is_contiguous():
+        raise ValueError("add_noise_rows: lr and noise are contiguous float32 buffers")
+    if noise.numel() < lr.numel():
+        raise ValueError("add_noise_rows: the noise buffer has lr's layout (%d samples, got %d)" % (lr.numel(), noise.numel()))
+    for m in (lr_moments, noise_moments):
+        if m.dtype != torch.float64 or tuple(m.shape) != (n, 2) or not m.is_contiguous():
+            raise ValueError("add_noise_rows: moments are contiguous float64 [%d, 2] tensors" % n)
+    _lib.check(lib.mg_add_noise_rows(_lib.ptr(lr), _lib.ptr(noise), lr.numel(), _lib.ptr(table), n, int(max_len),
+                                     _lib.ptr(lr_moments), _lib.ptr(noise_moments), float(snr), int(segment_length),
+                                     _lib.stream()), "mg_add_noise_rows")
+    return lr
+
+
+def add_noise_rows_of(waveform: torch.Tensor, snr: float, segment_length: int, noise=None, generator=None,
+                      in_place: bool = False) -> torch.Tensor:
+    """data/audio_dataset.py:73-78 / :179-184 for every row of a [..., L] waveform on the device: ``noise = randn(size); noise -=
+    noise.mean(); lr + sqrt(sum(lr^2) / segment_length / 10^(snr / 10)) / noise.std() * noise`` (mean, power and standard
+    deviation per row, as the reference sees one file at a time).  noise: the caller's samples (same shape) instead of
+    torch.randn(..., generator=generator) on the device -- the CPU stream of the reference cannot be matched there."""
+    shape = waveform.shape
+    L = int(shape[-1])
+    if L < 2:
+        raise ValueError("add_noise: a waveform of %d sample(s) has no standard deviation" % L)
+    x = _lib.f32c(waveform.reshape(-1, L))
+    if not in_place and x.data_ptr() == waveform.data_ptr():
+        x = x.clone()
+    B = x.shape[0]
+    if noise is None:
+        z = torch.randn(B, L, dtype=torch.float32, device=x.device, generator=generator)
+    else:
+        if noise.numel() != x.numel():
+            raise ValueError("add_noise: noise has the waveform's shape %s (got %s)" % (tuple(shape), tuple(noise.shape)))
+        z = noise.to(device=x.device, dtype=torch.float32).reshape(B, L).contiguous()
+    first = np.arange(B, dtype=np.int64) * L
+    table = torch.from_numpy(np.stack([first, first, first + L], axis=1)).to(x.device, non_blocking=True)
+    flat = x.view(-1)
+    add_noise_rows(flat, z.view(-1), table, L, rows_moments(flat, table, L), rows_moments(z.view(-1), table, L), snr,
+                   segment_length)
+    return x.reshape(shape)
+
+
+@dataclass
+class ResampleGroup:
+    """The rows of one mg_resample_rows launch: utterances `index` (in table order) share the rate pair orig_freq -> new_freq."""
+    orig_freq: int
+    new_freq: int
+    index: List[int]
+    rows: np.ndarray            # int64 [n, 4] = in_pos, in_len, out_pos, out_len
+    max_out_len: int
+
+
+@dataclass
+class FrontEndPlan:
+    """plan_front_end's result.  `lengths[s]` / `starts[s]` / `totals[s]`: per-utterance lengths, aligned starts and the size of
+    the packed buffer before step s (s = 0: the raw waveforms) and after the last one (s = len(steps): the low-rate input at
+    hr_rate).  `steps[s]`: the ResampleGroups of step s, one per distinct rate pair.  `order`: the utterances in the order of the
+    first step's groups -- the row order of the DC-mean table, so that every group's shifts are contiguous.  `utterances`:
+    generate_audio.plan_utterances over the final lengths; its in_start / in_total ARE starts[-1] / totals[-1]."""
+    rates: List[int]
+    lengths: List[List[int]]
+    starts: List[List[int]]
+    totals: List[int]
+    steps: List[List[ResampleGroup]]
+    order: List[int]
+    utterances: object
+
+    @property
+    def final_lengths(self):
+        return self.lengths[-1]
+
+    @property
+    def in_rows(self):
+        return self.utterances.in_rows
+
+    @property
+    def out_rows(self):
+        return self.utterances.out_rows
+
+    @property
+    def n_launches(self) -> int:
+        """mg_resample_rows launches: one per distinct rate pair and step."""
+        return sum(len(step) for step in self.steps)
+
+
+def resample_length(length: int, orig_freq: int, new_freq: int) -> int:
+    """mg_resample_length on the gcd-reduced rates: ceil(new * L / orig), the length aF.resample returns."""
+    g = math.gcd(int(orig_freq), int(new_freq))
+    n = _lib.load().mg_resample_length(int(length), int(orig_freq) // g, int(new_freq) // g)
+    if n <= 0:
+        raise ValueError("lengths and sampling rates must be positive")
+    return int(n)
+
+
+def _aligned_starts(lengths, align):
+    starts, pos = [], 0
+    for n in lengths:
+        starts.append(pos)
+        pos = -(-(pos + n) // align) * align
+    return starts, pos
+
+
+def plan_front_end(lengths, rates, hr_rate: int, lr_rate: int, is_lr_input: bool, segment_length: int, gen_overlap: int,
+                   batch_size: int, out_segment_length=None, align: int = 64) -> FrontEndPlan:
+    """Where every utterance reads and writes in every step of AudioTestDataset.post_processing (host only: no device call).
+    Utterance u of lengths[u] samples at rates[u] Hz goes to hr_rate (is_lr_input) or down to lr_rate and back up to hr_rate;
+    each step's lengths are mg_resample_length of the step before.  Every packed buffer has generate_audio._pack_waves' layout
+    (starts rounded up to `align` samples), the last one exactly the one plan_utterances(final lengths, segment_length,
+    out_segment_length (default: segment_length), gen_overlap, batch_size) describes."""
+    from .generate_audio import plan_utterances
+    lengths, rates = [int(n) for n in lengths], [int(r) for r in rates]
+    if not lengths or len(lengths) != len(rates):
+        raise ValueError("plan_front_end needs one sampling rate per utterance, and at least one utterance")
+    if min(lengths) <= 0 or min(rates) <= 0 or int(hr_rate) <= 0 or int(lr_rate) <= 0:
+        raise ValueError("lengths and sampling rates must be positive")
+    targets = [int(hr_rate)] if is_lr_input else [int(lr_rate), int(hr_rate)]
+    all_lengths, all_starts, totals, steps = [lengths], [], [], []
+    starts, total = _aligned_starts(lengths, align)
+    all_starts.append(starts)
+    totals.append(total)
+    now = rates
+    for target in targets:
+        src_len, src_start = all_lengths[-1], all_starts[-1]
+        dst_len = [resample_length(n, r, target) for n, r in zip(src_len, now)]
+        dst_start, total = _aligned_starts(dst_len, align)
+        members = {}
+        for u, r in enumerate(now):
+            members.setdefault(r, []).append(u)
+        steps.append([ResampleGroup(r, target, idx,
+                                    np.asarray([(src_start[u], src_len[u], dst_start[u], dst_len[u]) for u in idx],
+                                               dtype=np.int64).reshape(-1, 4), max(dst_len[u] for u in idx))
+                      for r, idx in members.items()])
+        all_lengths.append(dst_len)
+        all_starts.append(dst_start)
+        totals.append(total)
+        now = [target] * len(lengths)
+    L = int(segment_length)
+    utt = plan_utterances(all_lengths[-1], L, L if out_segment_length is None else int(out_segment_length), gen_overlap, batch_size,
+                          align)
+    assert utt.in_start == all_starts[-1] and utt.in_total == totals[-1]
+    return FrontEndPlan(rates, all_lengths, all_starts, totals, steps, [u for g in steps[0] for u in g.index], utt)
+
+
+def _front_end_options(opt) -> dict:
+    """lr_sampling_rate, hr_sampling_rate and segment_length are required; is_lr_input / add_noise default to off, snr to 55,
+    gen_overlap to 0, batch_size to 64, out_segment_length to segment_length.  `opt`: an options namespace or a dict."""
+    get = (lambda k, d=None: opt.get(k, d)) if isinstance(opt, dict) else (lambda k, d=None: getattr(opt, k, d))
+    o = dict(lr_sampling_rate=get("lr_sampling_rate"), hr_sampling_rate=get("hr_sampling_rate"),
+             segment_length=get("segment_length"), is_lr_input=bool(get("is_lr_input", False)),
+             add_noise=bool(get("add_noise", False)), snr=float(get("snr", 55.0)), gen_overlap=int(get("gen_overlap", 0) or 0),
+             batch_size=int(get("batch_size", 64) or 64), out_segment_length=get("out_segment_length"))
+    for k in ("lr_sampling_rate", "hr_sampling_rate", "segment_length"):
+        if o[k] is None:
+            raise ValueError("front_end_many needs %s" % k)
+    return o
+
+
+def front_end_many(raws, rates, opt_or_kwargs, noise=None, generator=None, device=None):
+    """AudioTestDataset.read_audio + post_processing (data/audio_dataset.py:141-186) for a list of raw waveforms ([T_u] or
+    [1, T_u], on the host or the device) at sampling rates `rates` -> (packed, views, plan): the packed low-rate buffer at
+    hr_sampling_rate (float32 [plan.totals[-1]], generate_audio._pack_waves' layout, zeros in the gaps), one [1, T'_u] view of it
+    per utterance, and the FrontEndPlan (plan.utterances: the UtterancePlan generate_many's tables come from).
+    opt_or_kwargs: an options namespace or a dict (see _front_end_options).  Under add_noise, `noise` is a list of per-utterance
+    waveforms of the final lengths (for tests: the reference draws from the CPU stream, which a device cannot reproduce);
+    otherwise torch.randn(..., generator=generator) on the device.
+    Launches: one packing copy, one table copy, mg_rows_moments, a handful of element-wise launches over [U] for the shift, one
+    mg_resample_rows per distinct rate pair and step, and under add_noise two more mg_rows_moments and mg_add_noise_rows --
+    whatever the number of utterances.  No host read-back."""
+    from .generate_audio import _pack_waves
+    o = _front_end_options(opt_or_kwargs)
+    raws = list(raws)
+    if len(raws) == 0:
+        raise ValueError("no waveforms")
+    if any(w.numel() == 0 for w in raws):
+        raise ValueError("an empty waveform cannot be resampled")
+    plan = plan_front_end([w.numel() for w in raws], rates, o["hr_sampling_rate"], o["lr_sampling_rate"], o["is_lr_input"],
+                          o["segment_length"], o["gen_overlap"], o["batch_size"], o["out_segment_length"])
+    final = plan.final_lengths
+    if o["add_noise"]:
+        if min(final) < 2:
+            raise ValueError("add_noise: an utterance of fewer than 2 samples has no standard deviation")
+        if noise is not None and [z.numel() for z in noise] != final:
+            raise ValueError("add_noise: noise holds one waveform per utterance, of the lengths %s" % final)
+    if device is None:
+        device = next((w.device for w in raws if w.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
+
+    def layout(s):
+        return SimpleNamespace(in_total=plan.totals[s], in_start=plan.starts[s], lengths=plan.lengths[s])
+
+    # every table in one host array and one copy: the raw windows in group order, the final windows, then each group's rows
+    def windows(s, order):
+        first = np.asarray([plan.starts[s][u] for u in order], dtype=np.int64)
+        return np.stack([first, first, first + np.asarray([plan.lengths[s][u] for u in order], dtype=np.int64)], axis=1)
+    U = len(raws)
+    parts = [windows(0, plan.order).reshape(-1), windows(-1, range(U)).reshape(-1)]
+    parts += [g.rows.reshape(-1) for step in plan.steps for g in step]
+    tables = torch.from_numpy(np.concatenate(parts)).to(device, non_blocking=True)
+    raw_win, lr_win = tables[:3 * U].view(U, 3), tables[3 * U:6 * U].view(U, 3)
+
+    buf = _pack_waves(raws, layout(0), device)
+    mom = rows_moments(buf, raw_win, max(plan.lengths[0]))
+    shift = (1e-4 - mom[:, 0] / (raw_win[:, 2] - raw_win[:, 1]).double()).float()     # raw += 1e-4 - mean(raw), per utterance
+    at = 6 * U
+    for s, step in enumerate(plan.steps):
+        out = torch.zeros(plan.totals[s + 1], dtype=torch.float32, device=device)
+        row = 0
+        for g in step:
+            n = len(g.index)
+            resample_rows(buf, tables[at:at + 4 * n].view(n, 4), g.max_out_len, g.orig_freq, g.new_freq, out,
+                          shift=shift[row:row + n] if s == 0 else None)
+            at, row = at + 4 * n, row + n
+        buf = out
+    if o["add_noise"]:
+        if noise is None:
+            z = torch.randn(buf.numel(), dtype=torch.float32, device=device, generator=generator)
+        else:
+            z = _pack_waves(list(noise), layout(-1), device)
+        add_noise_rows(buf, z, lr_win, max(final), rows_moments(buf, lr_win, max(final)), rows_moments(z, lr_win, max(final)),
+                       o["snr"], o["segment_length"])
+    return buf, [buf[s0:s0 + n].view(1, -1) for s0, n in zip(plan.starts[-1], final)], plan
