@@ -656,3 +656,277 @@ def test_weight_streaming_gemm_equals_the_im2col_gemm(case, monkeypatch):
     monkeypatch.delenv("MG_NO_HGEMM_SA")
     assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[0])
     assert torch.equal(got[2], ref[1]) and torch.equal(got[3], ref[1] + skip)
+
+
+# ---- op-level parity of the streaming optimiser / GradScaler kernels (csrc/norm_act.hip) at their vector-body edges --------------
+# The C ABI takes the betas and eps as float32: the float64 reference uses those very values (float32(0.999) is 1.3e-5 of
+# 1 - beta2 away from 0.999).
+ADAM_LR, ADAM_B1, ADAM_B2, ADAM_EPS = 2e-4, 0.5, float(np.float32(0.999)), float(np.float32(1e-8))
+FLT_MAX = float(np.finfo(np.float32).max)
+
+
+def ulp32(t):
+    """Spacing of float32 at |t| (float64 tensor)."""
+    _, e = torch.frexp(t.abs())
+    return torch.ldexp(torch.ones_like(t), e - 24)
+
+
+def adam_ref(p, g, m, v, step, gscale=1.0):
+    """One Adam step (betas 0.5 / 0.999, eps 1e-8, bias-corrected, eps added after the correction as torch.optim.Adam) in
+    float64, and per-element bounds for a float32 evaluation that starts from the same p, m, v:
+      m: the roundings of g * gscale, g - m, its product with 1 - beta1 and the sum     -> 4 x 2^-24 (|g| + |m|)
+      v: six roundings of non-negative terms                                            -> 8 x 2^-24 v'
+      p: the update u = step_size m' / (sqrt(v') / bc2 + eps) carries v's error halved, two float32 clock values and five
+         roundings (16 x 2^-24 |u|) plus m's error through the same quotient; p - u rounds once: 1 ulp of p', the bound
+         test_dinput_pair_losses_adam states for |p| < 4, here at each element's own magnitude."""
+    gi = g * gscale
+    m2 = m + (gi - m) * (1.0 - ADAM_B1)
+    v2 = v * ADAM_B2 + (1.0 - ADAM_B2) * gi * gi
+    step_size = ADAM_LR / (1.0 - ADAM_B1 ** step)
+    denom = v2.sqrt() / np.sqrt(1.0 - ADAM_B2 ** step) + ADAM_EPS
+    u = step_size * (m2 / denom)
+    p2 = p - u
+    tol_m = 4 * 2.0 ** -24 * (gi.abs() + m.abs())
+    tol_v = 8 * 2.0 ** -24 * v2
+    tol_p = ulp32(p2) + 16 * 2.0 ** -24 * u.abs() + step_size * tol_m / denom
+    return (p2, m2, v2), (tol_p, tol_m, tol_v)
+
+
+def guarded(values, dtype=torch.float32):
+    """A device buffer holding `values` with 8 sentinel elements behind them: (the view the kernel gets, the whole buffer)."""
+    n = values.numel()
+    buf = torch.full((n + 8,), 3.25, dtype=dtype, device=DEV)
+    buf[:n] = values.to(DEV).to(dtype)
+    return buf[:n], buf
+
+
+@pytest.mark.parametrize("n", [1, 3, 5, 1023, 4097, 8 * 256 * 4096 + 6])
+def test_adam_dev_kernel_tails_against_float64(n):
+    """adam_dev_kernel behind mg_adam_step_dev / _amp (loss scale 1024 on gradients scaled by 1024) / _h (float16 shadow): n / 4
+    float4 trips plus a scalar tail that block 0 walks -- tail only, body + tail, and a second grid-stride trip + tail.  Three
+    steps on the device clock; each step is compared with a float64 Adam step from the float32 state that step started from, so
+    the bound is one step's rounding (adam_ref) and does not grow with the step count.  The shadow is p.half(), tail included,
+    and nothing is written behind element n."""
+    from mdctgan_amd import ops
+    gen = torch.Generator().manual_seed(n % 977)
+    p0 = torch.randn(n, generator=gen)
+    runs = {}
+    for kind in ("dev", "amp", "h"):
+        p, pbuf = guarded(p0)
+        m, mbuf = guarded(torch.zeros(n))
+        v, vbuf = guarded(torch.zeros(n))
+        state = torch.zeros(6, dtype=torch.float64, device=DEV)
+        state[1] = ADAM_LR
+        runs[kind] = dict(p=p, m=m, v=v, bufs=[pbuf, mbuf, vbuf], state=state)
+    p16, p16buf = guarded(torch.zeros(n), torch.float16)
+    runs["h"]["bufs"].append(p16buf)
+    scaler = torch.tensor([1024.0, 0.0, 0.0, 0.0], device=DEV)
+    worst = [0.0, 0.0, 0.0]
+    for step, gmag in ((1, 1.0), (2, 1e-4), (3, 10.0)):
+        g = torch.randn(n, generator=gen) * gmag
+        gd, g1024 = g.to(DEV), (g * 1024.0).to(DEV)
+        before = [runs["dev"][k].cpu().double() for k in ("p", "m", "v")]
+        want, tol = adam_ref(before[0], g.double(), before[1], before[2], step)
+        r = runs["dev"]
+        ops.adam_tick(r["state"], ADAM_B1, ADAM_B2)
+        ops.adam_step_dev(r["p"], gd, r["m"], r["v"], r["state"], ADAM_B1, ADAM_B2, ADAM_EPS)
+        r = runs["amp"]
+        ops.adam_tick_amp(r["state"], ADAM_B1, ADAM_B2, scaler, 0)
+        ops.adam_step_amp(r["p"], g1024, r["m"], r["v"], r["state"], ADAM_B1, ADAM_B2, ADAM_EPS, 1.0, scaler, 0)
+        r = runs["h"]
+        ops.adam_tick(r["state"], ADAM_B1, ADAM_B2)
+        ops.adam_step_h(r["p"], gd, r["m"], r["v"], p16, r["state"], ADAM_B1, ADAM_B2, ADAM_EPS, 1.0)
+        for j, k in enumerate(("p", "m", "v")):
+            err = (runs["dev"][k].cpu().double() - want[j]).abs()
+            worst[j] = max(worst[j], (err / tol[j]).max().item())
+            bad = err > tol[j]
+            assert not bad.any(), (k, step, int(bad.sum()), int(bad.nonzero()[0]), err[bad].max().item())
+        for kind, r in runs.items():
+            # unscaling by 1024 is exact and the shadow is one more store: the three entry points give the same bits, so the
+            # float64 comparison above holds for each of them (and the next step's reference serves all three)
+            assert all(torch.equal(r[k], runs["dev"][k]) for k in ("p", "m", "v")), (kind, step)
+            assert r["state"][0].item() == step
+            assert all(bool((b[n:] == 3.25).all()) for b in r["bufs"]), (kind, step)
+        assert torch.equal(p16, runs["h"]["p"].half())
+    print("adam n=%d: worst error / bound for p, m, v: %.3g %.3g %.3g" % (n, *worst))
+    assert scaler.tolist() == [1024.0, 0.0, 0.0, 0.0]
+
+
+@pytest.mark.parametrize("n", [5, 1023])
+def test_adam_amp_skips_on_found_inf(n):
+    """found_inf[slot] != 0: mg_adam_tick_amp / mg_adam_step_amp / mg_adam_step_h leave p, m, v, the shadow and the clock bit-unchanged
+    (vector body and tail); the other slot's optimiser steps."""
+    from mdctgan_amd import ops
+    gen = torch.Generator().manual_seed(n)
+    p = torch.randn(n, generator=gen).to(DEV)
+    m, v = (0.1 * torch.randn(n, generator=gen)).to(DEV), (0.01 * torch.rand(n, generator=gen)).to(DEV)
+    g = torch.randn(n, generator=gen).to(DEV)
+    p16 = p.half()
+    state = torch.zeros(6, dtype=torch.float64, device=DEV)
+    state[1] = ADAM_LR
+    ops.adam_tick(state, ADAM_B1, ADAM_B2)
+    scaler = torch.tensor([1024.0, 3.0, 0.0, 1.0], device=DEV)          # slot 1 saw an inf
+    keep = [t.clone() for t in (p, m, v, p16, state, scaler)]
+    ops.adam_tick_amp(state, ADAM_B1, ADAM_B2, scaler, 1)
+    ops.adam_step_amp(p, g, m, v, state, ADAM_B1, ADAM_B2, ADAM_EPS, 1.0, scaler, 1)
+    ops.adam_step_h(p, g, m, v, p16, state, ADAM_B1, ADAM_B2, ADAM_EPS, 1.0, scaler, 1)
+    for a, b in zip((p, m, v, p16, state, scaler), keep):
+        assert torch.equal(a, b)
+    ops.adam_tick_amp(state, ADAM_B1, ADAM_B2, scaler, 0)
+    ops.adam_step_h(p, g, m, v, p16, state, ADAM_B1, ADAM_B2, ADAM_EPS, 1.0, scaler, 0)
+    assert state[0].item() == 2.0 and bool((p != keep[0]).any()) and bool((m != keep[1]).any()) and bool((v != keep[2]).any())
+    assert torch.equal(p16, p.half()) and torch.equal(scaler, keep[5])
+
+
+def scaler_check_positions(n):
+    """Elements of an n-element buffer that scaler_check_kernel reaches differently: the first, the last of the float4 body, every
+    tail element (block 0's scalar loop), and one that the last block owns on its first trip."""
+    n4 = n // 4
+    blocks = min(4096, (n + 4095) // 4096)
+    pos = {0, n - 1} | set(range(4 * n4, n))
+    if n4:
+        pos.add(4 * n4 - 1)
+    if blocks > 1:
+        pos.add(4 * ((blocks - 1) * 256 + 3) + 2)
+    return sorted(pos)
+
+
+@pytest.mark.parametrize("n", [5, 1003, 16 * 256 * 4096 + 7])
+def test_scaler_check_finds_a_single_bad_element_anywhere(n):
+    """mg_scaler_check: a clean buffer -- FLT_MAX and denormals included -- leaves the slot at 0; one +-inf or NaN sets it wherever
+    it sits (float4 body on the first and on a later grid-stride trip, the last block, the scalar tail).  Only the slot asked for
+    is written."""
+    from mdctgan_amd import ops
+    gen = torch.Generator().manual_seed(n % 991)
+    g = torch.randn(n, generator=gen).to(DEV)
+    positions = scaler_check_positions(n)
+    scaler = torch.tensor([512.0, 7.0, 0.0, 0.0], device=DEV)
+
+    def flagged(slot=1):
+        ops.scaler_check(g, scaler, slot)
+        got = scaler.tolist()
+        assert got[:2] == [512.0, 7.0] and got[3 - slot] == 0.0 and got[2 + slot] in (0.0, 1.0), got
+        scaler[2 + slot] = 0.0
+        return got[2 + slot] == 1.0
+    assert not flagged()
+    for pos in positions:
+        old = g[pos].item()
+        for val in (FLT_MAX, -FLT_MAX, 1e-45, -1e-45, 1.1754942e-38):          # the largest finite values and denormals are numbers
+            g[pos] = val
+            assert not flagged(), (pos, val)
+        for val in (float("inf"), float("-inf"), float("nan")):
+            g[pos] = val
+            assert flagged(), (pos, val)
+            assert flagged(slot=0), (pos, val)
+        g[pos] = old
+    assert not flagged()
+    if n <= 1003:
+        g.fill_(FLT_MAX)
+        assert not flagged()
+        g.fill_(1e-45)
+        assert g[0].item() != 0.0 and not flagged()
+
+
+SEG_DTYPE = np.dtype([("off", "<i8"), ("n", "<i8"), ("mode", "<i4"), ("skip", "<i4")])          # mg_grad_seg
+
+
+def seg_table(segs):
+    rec = np.zeros(len(segs), dtype=SEG_DTYPE)
+    for j, sg in enumerate(segs):
+        rec[j] = sg
+    return torch.from_numpy(rec.view(np.uint8).copy()).to(DEV)
+
+
+def test_scaler_check_segs_overflow_criteria():
+    """mg_scaler_check_segs over three segments, one of each mode, in every order (the value under test sits in the first, second
+    and third segment in turn):
+      autocast  flagged exactly when torch's CPU float16 cast of the value is not finite: 65520 and beyond, not nextafter(65520, 0)
+      float32   the same values are numbers; inf / NaN are not
+      float16   +-inf / NaN at each of the 8 positions of a 16-byte group (low and high half of each word), 65504 is a number
+    The storage a segment does not use (g16 of a float32 segment, g of a float16 one) holds inf and is never looked at; a segment
+    with skip_check set is ignored even when it holds inf."""
+    from mdctgan_amd import _lib, ops
+    below = float(np.nextafter(np.float32(65520.0), np.float32(0.0)))
+    sizes = {_lib.GRAD_F32: 8 * 3, _lib.GRAD_AUTOCAST: 8 * 40, _lib.GRAD_F16: 8 * 300}      # one 256-thread block: groups 256..299 are a second trip
+    gen = torch.Generator().manual_seed(8)
+    orders = [(_lib.GRAD_F32, _lib.GRAD_AUTOCAST, _lib.GRAD_F16), (_lib.GRAD_F16, _lib.GRAD_F32, _lib.GRAD_AUTOCAST),
+              (_lib.GRAD_AUTOCAST, _lib.GRAD_F16, _lib.GRAD_F32)]
+    for order in orders:
+        offs, total = {}, 0
+        for mode in order:
+            offs[mode] = total
+            total += sizes[mode]
+        g = (torch.randn(total, generator=gen) * 100.0).to(DEV)
+        g16 = (torch.randn(total, generator=gen) * 100.0).half().to(DEV)
+        lo, hi = offs[_lib.GRAD_F16], offs[_lib.GRAD_F16] + sizes[_lib.GRAD_F16]
+        g[lo:hi] = float("inf")                   # unused storage
+        g16[:lo] = float("inf")
+        g16[hi:] = float("nan")
+        scaler = torch.tensor([256.0, 5.0, 0.0, 0.0], device=DEV)
+
+        def flagged(skip=()):
+            table = seg_table([(offs[mode], sizes[mode], mode, int(mode in skip)) for mode in order])
+            ops.scaler_check_segs(g, g16, table, 3, total, 4 * total, scaler, 0)
+            got = scaler.tolist()
+            assert got[:2] == [256.0, 5.0] and got[3] == 0.0 and got[2] in (0.0, 1.0), got
+            scaler[2] = 0.0
+            return got[2] == 1.0
+        assert not flagged(), order
+        for mode in (_lib.GRAD_AUTOCAST, _lib.GRAD_F32):
+            o, n = offs[mode], sizes[mode]
+            for pos in (o, o + 5, o + n - 2, o + n - 1):
+                old = g[pos].item()
+                for val in (below, -below, 65520.0, -65520.0, 65536.0, FLT_MAX, float("inf"), float("-inf"), float("nan")):
+                    g[pos] = val
+                    as_half = not bool(torch.isfinite(torch.tensor(val).half()))
+                    as_float = not np.isfinite(np.float32(val))
+                    assert flagged() == (as_half if mode == _lib.GRAD_AUTOCAST else as_float), (order, mode, pos, val)
+                g[pos] = float("inf")
+                assert not flagged(skip=(mode,)), (order, mode, pos)
+                g[pos] = old
+        assert not bool(torch.isfinite(torch.tensor(65520.0).half())) and bool(torch.isfinite(torch.tensor(below).half()))
+        o, n = offs[_lib.GRAD_F16], sizes[_lib.GRAD_F16]
+        g16[o:o + n] = 65504.0                                                # the largest finite half, everywhere
+        assert not flagged(), order
+        g16[o:o + n:2] = -65504.0
+        assert not flagged(), order
+        for group in (0, 77, 255, 256, n // 8 - 1):          # the last two on the block's second grid-stride trip
+            for j in range(8):
+                pos = o + 8 * group + j
+                old = g16[pos].item()
+                for val in (float("inf"), float("-inf"), float("nan")):
+                    g16[pos] = val
+                    assert flagged(), (order, pos, val)
+                g16[pos] = float("inf")
+                assert not flagged(skip=(_lib.GRAD_F16,)), (order, pos)
+                g16[pos] = old
+        assert not flagged(), order
+
+
+def test_scaler_update_follows_the_grad_scaler_rule():
+    """mg_scaler_update against torch.amp.GradScaler.update as documented: any found_inf -> scale *= backoff_factor, tracker = 0;
+    otherwise tracker += 1 and, when it reaches growth_interval, scale *= growth_factor, tracker = 0.  Every slot is cleared."""
+    from mdctgan_amd import ops
+    growth, backoff, interval = 2.0, 0.5, 3
+    scaler = torch.tensor([1024.0, 0.0, 0.0, 0.0], device=DEV)
+    scale, tracker = 1024.0, 0
+    # found_inf slots per iteration: growth at the interval (twice), an inf in either slot, in both, right before a growth
+    pattern = [(0, 0), (0, 0), (0, 0), (0, 0), (1, 0), (0, 0), (0, 0), (0, 1), (1, 1), (0, 0), (0, 0), (0, 0), (0, 0), (0, 0), (0, 0)]
+    for it, found in enumerate(pattern):
+        scaler[2], scaler[3] = float(found[0]), float(found[1])
+        ops.scaler_update(scaler, growth, backoff, interval)
+        if sum(found):
+            scale, tracker = scale * backoff, 0
+        else:
+            tracker += 1
+            if tracker == interval:
+                scale, tracker = scale * growth, 0
+        assert scaler.tolist() == [scale, float(tracker), 0.0, 0.0], (it, scaler.tolist(), scale, tracker)
+    assert scale == 1024.0 * 2 * 0.5 * 0.5 * 0.5 * 2 * 2
+    # other factors, interval 1: every clean iteration grows
+    scaler = torch.tensor([3.0, 0.0, 0.0, 0.0], device=DEV)
+    ops.scaler_update(scaler, 1.5, 0.25, 1)
+    assert scaler.tolist() == [4.5, 0.0, 0.0, 0.0]
+    scaler[3] = 1.0
+    ops.scaler_update(scaler, 1.5, 0.25, 1)
+    assert scaler.tolist() == [1.125, 0.0, 0.0, 0.0]

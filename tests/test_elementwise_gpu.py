@@ -189,3 +189,197 @@ def test_multi_tensor_losses_equal_the_single_tensor_calls():
         for buf, w_ in zip(bufs, wants):
             n = w_.numel()
             assert torch.equal(buf[:n], w_.reshape(-1)) and bool((buf[n:] == 0).all())
+
+
+# ---- joined gradients (mg_instnorm_bwd_add / mg_act_bwd_add), pooling edges, sign(0), mg_stats_finalize --------------------------
+ACTS = {"none": lambda t: t, "relu": torch.relu, "lrelu": lambda t: F.leaky_relu(t, 0.2), "tanh": torch.tanh}
+# (B, C, H, W) -> the generator seed of its inputs.  Chosen on the CPU so that the float64 normalised values keep clear of zero
+# (joined_norm_case checks it): a ReLU / LeakyReLU mask decided in float32 is then the float64 one.
+JOINED_NORM_SEEDS = {(1, 32, 2, 3): 0, (2, 32, 9, 17): 0, (1, 96, 16, 32): 4, (2, 64, 17, 33): 2, (2, 16, 8, 16): 0,
+                     (2, 64, 32, 64): 5, (3, 5, 7, 9): 0}          # smallest |xhat|: 9.6e-4 7.6e-5 1.9e-4 4.8e-5 1.1e-4 2.4e-5 3.2e-3
+_joined_cache = {}
+
+
+def f32_exact(t):
+    """float64 values that float32 holds exactly: the device sees the numbers the reference differentiates."""
+    return t.float().double()
+
+
+def joined_norm_inputs(shape, seed):
+    gen = torch.Generator().manual_seed(seed)
+    x = f32_exact(torch.randn(*shape, generator=gen, dtype=torch.float64) * 3 + 1.5)
+    gy = f32_exact(torch.randn(*shape, generator=gen, dtype=torch.float64))
+    gy2 = f32_exact(torch.randn(*shape, generator=gen, dtype=torch.float64) * 0.5 + 0.25)
+    return x, gy, gy2
+
+
+def joined_norm_case(shape):
+    """Inputs (NCHW float64), the smallest |xhat| of the float64 reference and, per activation, autograd's gradient of
+    act(instance_norm(x)) seeded with gy + gy2.  Computed once per shape, shared and never written."""
+    if shape not in _joined_cache:
+        x, gy, gy2 = joined_norm_inputs(shape, JOINED_NORM_SEEDS[shape])
+        want = {}
+        for act in ("none", "relu", "lrelu"):
+            xr = x.clone().requires_grad_()
+            ACTS[act](F.instance_norm(xr, eps=1e-5)).backward(gy + gy2)
+            want[act] = nhwc(xr.grad)
+        _joined_cache[shape] = (x, gy, gy2, F.instance_norm(x, eps=1e-5).abs().min().item(), want)
+    return _joined_cache[shape]
+
+
+# (route of mg_instnorm_bwd_add, shape, MG_NO_NORM_ROWS, also request dx16)
+JOINED_NORM_ROUTES = [
+    ("slab_depth4", (1, 32, 2, 3), False, False), ("slab_depth8", (2, 32, 9, 17), False, True),
+    ("slab_depth16", (1, 96, 16, 32), False, False), ("slab_depth20", (2, 64, 17, 33), False, False),
+    ("rows_hw128", (2, 16, 8, 16), False, True), ("rows_hw2048", (2, 64, 32, 64), False, False),
+    ("flat_vector_small", (2, 16, 8, 16), True, False), ("flat_vector_hw2048", (2, 64, 32, 64), True, False),
+    ("flat_scalar", (3, 5, 7, 9), False, False)]
+
+
+@pytest.mark.parametrize("route", JOINED_NORM_ROUTES, ids=lambda r: r[0])
+@pytest.mark.parametrize("act", ["none", "relu", "lrelu"])
+def test_instnorm_bwd_joined_gradient_against_float64(route, act, monkeypatch):
+    """ops.instnorm_bwd(..., dy2=gy2) on every route that threads dy2 (slab kernels at the four register depths, the rows kernel,
+    the flat vector and scalar kernels, both partial-sum kernels behind the last three) == float64 autograd seeded with gy + gy2:
+    a route that dropped dy2, or added it behind the activation mask, misses by O(1).  2e-5 of max|ref| as test_instnorm_fwd_bwd."""
+    from mdctgan_amd import ops
+    name, shape, no_rows, want16 = route
+    code = {"none": ops.ACT_NONE, "relu": ops.ACT_RELU, "lrelu": ops.ACT_LRELU02}[act]
+    x, gy, gy2, min_xhat, want = joined_norm_case(shape)
+    assert min_xhat > 1e-5, (shape, min_xhat)          # the float32 mask is the float64 mask
+    if no_rows:
+        monkeypatch.setenv("MG_NO_NORM_ROWS", "1")
+    else:
+        monkeypatch.delenv("MG_NO_NORM_ROWS", raising=False)
+    xd, gyd, gy2d = (nhwc(t).float().to(DEV) for t in (x, gy, gy2))
+    _, mean, rstd = ops.instnorm_fwd(xd, code)
+    d16 = torch.full((xd.numel(),), float("nan"), dtype=torch.float16, device=DEV) if want16 else None
+    dx = ops.instnorm_bwd(gyd, xd, mean, rstd, code, dx16=d16, dy2=gy2d)
+    err = rel_err(dx, want[act])
+    print("instnorm_bwd dy2 %s %s: rel err %.3g, min|xhat| %.3g" % (name, act, err, min_xhat))
+    assert err < 2e-5
+    if want16:
+        assert torch.equal(d16.view_as(dx), dx.half())
+    # the joined call is not the unjoined one (dy2 is far from zero)
+    assert rel_err(ops.instnorm_bwd(gyd, xd, mean, rstd, code), want[act]) > 1e-2
+
+
+def test_instnorm_bwd_refuses_an_unaligned_second_gradient():
+    """dy2 is read as float4: a view one element into its buffer is refused (MG_ERR_ARG), nothing is launched or written."""
+    from mdctgan_amd import ops
+    shape = (2, 32, 9, 17)
+    x, gy, gy2, _, _ = joined_norm_case(shape)
+    xd, gyd = nhwc(x).float().to(DEV), nhwc(gy).float().to(DEV)
+    buf = torch.zeros(xd.numel() + 4, device=DEV)
+    off = buf[1:1 + xd.numel()].view(xd.shape)
+    off.copy_(nhwc(gy2).float())
+    assert off.data_ptr() % 16 == 4 and off.is_contiguous()
+    _, mean, rstd = ops.instnorm_fwd(xd, ops.ACT_RELU)
+    out = torch.full_like(xd, 3.25)
+    with pytest.raises(ValueError):
+        ops.instnorm_bwd(gyd, xd, mean, rstd, ops.ACT_RELU, out=out, dy2=off)
+    assert bool((out == 3.25).all())
+
+
+@pytest.mark.parametrize("n", [1, 255, 1000, 4096 * 256 + 3])          # the last: one element past a full grid, a second trip
+@pytest.mark.parametrize("act", ["tanh", "lrelu", "relu"])
+def test_act_bwd_joined_gradient_against_float64(n, act):
+    """ops.act_bwd(gy, y, act, dy2=gy2) == float64 autograd of act(pre) seeded with gy + gy2 (1e-5 as the unjoined case)."""
+    from mdctgan_amd import ops
+    code = {"tanh": ops.ACT_TANH, "lrelu": ops.ACT_LRELU02, "relu": ops.ACT_RELU}[act]
+    gen = torch.Generator().manual_seed(n % 1000 + len(act))
+    pre = f32_exact(torch.randn(n, generator=gen, dtype=torch.float64)).requires_grad_()
+    gy = f32_exact(torch.randn(n, generator=gen, dtype=torch.float64))
+    gy2 = f32_exact(torch.randn(n, generator=gen, dtype=torch.float64) * 0.5 + 0.25)
+    y = ACTS[act](pre)
+    y.backward(gy + gy2)
+    assert pre.detach().abs().min().item() > 0.0
+    yd = y.detach().float().to(DEV)
+    got = ops.act_bwd(gy.float().to(DEV), yd, code, dy2=gy2.float().to(DEV))
+    err = rel_err(got, pre.grad)
+    print("act_bwd dy2 %s n=%d: rel err %.3g" % (act, n, err))
+    assert err < 1e-5
+    assert rel_err(ops.act_bwd(gy.float().to(DEV), yd, code), pre.grad) > 1e-2 or n == 1
+
+
+@pytest.mark.parametrize("shape", [(2, 64, 1, 7), (1, 3, 6, 1), (1, 1, 1, 1), (2, 130, 2, 3)])
+def test_pool_upsample_edge_shapes(shape):
+    """AvgPool2d(3, 2, 1, count_include_pad=False) and nearest 2x upsampling with H == 1 or W == 1 (both clamps of the 3x3 window
+    active at once: divisors 1, 2, 4) and at the discriminator pyramid's channel counts, against float64."""
+    from mdctgan_amd import ops
+    gen = torch.Generator().manual_seed(sum(shape))
+    x = f32_exact(torch.randn(*shape, generator=gen, dtype=torch.float64)).requires_grad_()
+    y = F.avg_pool2d(x, 3, stride=2, padding=1, count_include_pad=False)
+    gy = f32_exact(torch.randn(y.shape, generator=gen, dtype=torch.float64))
+    y.backward(gy)
+    xd = nhwc(x.detach()).float().to(DEV)
+    yd = ops.avgpool_fwd(xd)
+    assert yd.shape == nhwc(y).shape and rel_err(yd, nhwc(y.detach())) < 1e-6
+    assert rel_err(ops.avgpool_bwd(nhwc(gy).float().to(DEV), xd.shape), nhwc(x.grad)) < 1e-6
+    x.grad = None
+    u = F.interpolate(x, scale_factor=2.0, mode="nearest")
+    gu = f32_exact(torch.randn(u.shape, generator=gen, dtype=torch.float64))
+    u.backward(gu)
+    ud = ops.upsample_fwd(xd)
+    assert ud.shape == nhwc(u).shape and rel_err(ud, nhwc(u.detach())) < 1e-6
+    assert rel_err(ops.upsample_bwd(nhwc(gu).float().to(DEV)), nhwc(x.grad)) < 1e-6
+
+
+def test_sign_of_zero_is_zero_in_dinput_and_l1_backward():
+    """d|s|/ds at s == 0 and d|a - b|/da at a == b are exactly 0 (torch's sgn), also for a negative zero."""
+    from mdctgan_amd import ops
+    gen = torch.Generator().manual_seed(6)
+    lr = torch.randn(2, 8, 16, generator=gen, dtype=torch.float64)
+    s = f32_exact(torch.randn(2, 8, 16, generator=gen, dtype=torch.float64))
+    s.view(-1)[[0, 5, 100, 255]] = 0.0
+    s.view(-1)[[7, 254]] = -0.0
+    s.requires_grad_()
+    out = torch.stack((lr, s, s.abs() * 2 - 1), dim=-1)
+    go = f32_exact(torch.randn(out.shape, generator=gen, dtype=torch.float64))
+    out.backward(go)
+    zero = s.detach() == 0
+    assert int(zero.sum()) == 6
+    got = ops.dinput_bwd(go.float().to(DEV), s.detach().float().to(DEV)).cpu()
+    assert rel_err(got, s.grad) < 1e-6
+    assert torch.equal(got[zero], go[..., 1].float()[zero])          # the |s| branch contributes exactly nothing there
+    n = 1000
+    a = f32_exact(torch.randn(n, generator=gen, dtype=torch.float64))
+    b = f32_exact(torch.randn(n, generator=gen, dtype=torch.float64))
+    tie = torch.zeros(n, dtype=torch.bool)
+    tie[[0, 3, 255, 256, 999]] = True
+    b[tie] = a[tie]
+    a.requires_grad_()
+    (1.3 * F.l1_loss(a, b)).backward()
+    go1 = torch.full((1,), 2.0, device=DEV)
+    got = ops.l1_bwd(a.detach().float().to(DEV), b.float().to(DEV), 1.3, go1).cpu()
+    assert rel_err(got, 2.0 * a.grad) < 1e-6
+    assert bool((got[tie] == 0).all()) and bool((got[~tie] != 0).all())
+
+
+def test_stats_finalize_against_float64():
+    """mg_stats_finalize: {sum, sum of squares} -> (s0 / n).float(), ((s1 - s0 * s0 / n) / (n - 1)).clamp_min(0).sqrt().float();
+    a slightly negative variance gives 0, a NaN sum stays NaN.  One float32 rounding of the float64 value: 2^-23 relative."""
+    from mdctgan_amd import _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(4)
+    v = rng.standard_normal(1000) * 0.3 + 2.0
+    three = 3.0
+    cases = [((v.sum(), (v * v).sum()), 1000), ((v[:2].sum(), (v[:2] ** 2).sum()), 2),
+             ((three, np.nextafter(three, 0.0)), 3),                  # s1 just below s0^2 / n: variance -7e-17
+             ((float("nan"), 5.0), 10), ((1.0, float("nan")), 10)]
+    for (s0, s1), n in cases:
+        st = torch.tensor([s0, s1], dtype=torch.float64)
+        want = torch.stack(((st[0] / n).float(), ((st[1] - st[0] * st[0] / n) / (n - 1)).clamp_min(0).sqrt().float())).double()
+        out = torch.full((2,), 7.0, device=DEV)
+        std = st.to(DEV)
+        _lib.check(lib.mg_stats_finalize(_lib.ptr(std), n, _lib.ptr(out), _lib.stream()), "mg_stats_finalize")
+        got = out.double().cpu()
+        assert torch.equal(torch.isnan(got), torch.isnan(want)), (s0, s1, n, got, want)
+        ok = ~torch.isnan(want)
+        assert bool(((got[ok] - want[ok]).abs() <= 2.0 ** -23 * want[ok].abs()).all()), (s0, s1, n, got, want)
+    assert (cases[2][0][1] - three * three / 3) / 2 < 0                      # the clamp really is exercised ...
+    st = torch.tensor(cases[2][0], dtype=torch.float64, device=DEV)
+    out = torch.full((2,), 7.0, device=DEV)
+    _lib.check(lib.mg_stats_finalize(_lib.ptr(st), 3, _lib.ptr(out), _lib.stream()), "mg_stats_finalize")
+    assert out[1].item() == 0.0 and out[0].item() == 1.0                      # ... and gives exactly 0
+    assert lib.mg_stats_finalize(_lib.ptr(st), 1, _lib.ptr(out), _lib.stream()) == -1          # n - 1 == 0 is refused

@@ -109,3 +109,150 @@ def test_compute_matrics_against_the_reference_fixture(golden):
         assert abs(got[1] - want[1]) <= 2e-5 and abs(got[2] - want[2]) <= 2e-5                # dB
         assert abs(got[6] - want[6]) <= 1.5e-3 * want[6]
         assert abs(got[6] - exact[6]) <= 2e-4 * exact[6]
+
+
+# ---- the metrics kernels one at a time (csrc/metrics.hip) against numpy float64 restatements ------------------------------------
+def stft_frames_ref(x, window, n_fft, hop, center):
+    """[B, T] float32 -> [B, F, n_fft] float32: numpy reflect padding, framing, one float32 product per output."""
+    if center:
+        x = np.pad(x, ((0, 0), (n_fft // 2, n_fft // 2)), mode="reflect")
+    F = 1 + (x.shape[1] - n_fft) // hop
+    idx = hop * np.arange(F)[:, None] + np.arange(n_fft)[None, :]
+    out = x[:, idx] * window[None, None, :]
+    assert out.dtype == np.float32
+    return out
+
+
+def stft_lengths(n_fft, hop, center):
+    return ([n_fft // 2 + 1] if center else []) + [n_fft, n_fft + 1, 7 * hop + 5, 4000]      # n_fft / 2 + 1: the deepest legal reflection
+
+
+def device_frames(x, window, n_fft, hop, center, F):
+    from mdctgan_amd import _lib
+    lib = _lib.load()
+    B, T = x.shape
+    frames = torch.full((B * max(F, 1), n_fft), 3.25, device="cuda")
+    xd, wd = torch.from_numpy(x).cuda(), torch.from_numpy(window).cuda()
+    rc = lib.mg_stft_frames(_lib.ptr(xd), B, T, _lib.ptr(wd), n_fft, hop, int(center), _lib.ptr(frames), _lib.stream())
+    return rc, frames
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("center", [True, False])
+@pytest.mark.parametrize("n_fft,hop", [(64, 32), (64, 16), (1024, 512)])
+def test_stft_frames_bit_exact(n_fft, hop, center):
+    """mg_stft_num_frames == torch.stft's frame count, and mg_stft_frames == reflect padding + framing + a float32 multiply by the
+    window, bit for bit -- a wrong reflected sample in an edge frame cannot hide in a mean over frames.  Both rejected argument
+    sets return MG_ERR_ARG and write nothing."""
+    from mdctgan_amd import _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(n_fft + hop + center)
+    window = rng.uniform(0.1, 1.0, n_fft).astype(np.float32)
+    for T in stft_lengths(n_fft, hop, center):
+        x = rng.standard_normal((3, T)).astype(np.float32)
+        want = stft_frames_ref(x, window, n_fft, hop, center)
+        F = lib.mg_stft_num_frames(T, n_fft, hop, int(center))
+        ts = torch.stft(torch.from_numpy(x), n_fft, hop_length=hop, win_length=n_fft, window=torch.from_numpy(window), center=center,
+                        pad_mode="reflect", return_complex=True)
+        assert F == ts.shape[-1] == want.shape[1], (T, F, ts.shape, want.shape)
+        rc, frames = device_frames(x, window, n_fft, hop, center, F)
+        assert rc == 0
+        assert np.array_equal(frames.cpu().numpy().reshape(3, F, n_fft), want), T
+    T = n_fft // 2 if center else n_fft - 1                # center: the reflection would need sample T; else: not one whole frame
+    x = rng.standard_normal((3, T)).astype(np.float32)
+    if not center:
+        assert lib.mg_stft_num_frames(T, n_fft, hop, 0) == -1
+    rc, frames = device_frames(x, window, n_fft, hop, center, 1)
+    assert rc == -1 and bool((frames == 3.25).all())
+    assert lib.mg_stft_num_frames(0, n_fft, hop, int(center)) == -1 and lib.mg_stft_num_frames(T, n_fft, 0, int(center)) == -1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_fft,hop,T,center", [(64, 32, 229, True), (64, 16, 117, False), (1024, 512, 4000, True)])
+def test_power_spectra_against_rfft(n_fft, hop, T, center):
+    """metrics.power_spectra == numpy.fft.rfft (float64) of the same windowed frames, (re, im) interleaved; 3e-5 of max|ref|: an
+    exact-float32 MFMA contraction over n_fft terms (tests/test_conv_gpu.py)."""
+    from mdctgan_amd.metrics import power_spectra
+    rng = np.random.default_rng(T)
+    window = rng.uniform(0.1, 1.0, n_fft).astype(np.float32)
+    x = rng.standard_normal((3, T)).astype(np.float32)
+    frames = stft_frames_ref(x, window, n_fft, hop, center)
+    spec = np.fft.rfft(frames.astype(np.float64), axis=-1).reshape(-1, n_fft // 2 + 1)
+    want = np.stack((spec.real, spec.imag), axis=-1).reshape(spec.shape[0], -1)
+    got, F = power_spectra(torch.from_numpy(x).cuda(), n_fft, hop, torch.from_numpy(window), center)
+    assert F == frames.shape[1] and tuple(got.shape) == want.shape
+    err = np.abs(got.double().cpu().numpy() - want).max()
+    print("power_spectra n_fft=%d: err %.3g of max %.3g" % (n_fft, err, np.abs(want).max()))
+    assert err <= 3e-5 * np.abs(want).max()
+    if not center:
+        with pytest.raises(ValueError):
+            power_spectra(torch.from_numpy(x[:, :n_fft - 1]).cuda(), n_fft, hop, torch.from_numpy(window), center)
+    else:
+        with pytest.raises(ValueError):
+            power_spectra(torch.from_numpy(x[:, :n_fft // 2].copy()).cuda(), n_fft, hop, torch.from_numpy(window), center)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_frames", [1, 130])
+@pytest.mark.parametrize("n_bins", [1, 63, 64, 65, 513])
+def test_lsd_frames_against_float64(n_bins, n_frames):
+    """mg_lsd_frames on given float32 spectra == sqrt(mean_k (log10(|a_k|^2 + 1e-6) - log10(|b_k|^2 + 1e-6))^2) in float64: bin counts
+    around the 64-lane wave, frames that are all zero in one input or in both (the 1e-6 floor decides), a bin 10 orders below the
+    floor.  The kernel computes in double and rounds once to float32: 2^-22 relative."""
+    from mdctgan_amd import _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(1000 * n_bins + n_frames)
+    variants = [((3, 7), (5, 7))] if n_frames > 1 else [((), ()), ((0,), ()), ((), (0,)), ((0,), (0,))]
+    for zero_a, zero_b in variants:
+        a = (rng.standard_normal((n_frames, n_bins, 2)) * 10.0 ** rng.uniform(-3, 1, (n_frames, 1, 1))).astype(np.float32)
+        b = (rng.standard_normal((n_frames, n_bins, 2)) * 10.0 ** rng.uniform(-3, 1, (n_frames, 1, 1))).astype(np.float32)
+        if n_bins > 1:           # (a lone bin below the floor in both inputs would make the answer a difference of rounding errors)
+            a[:, min(2, n_bins - 1)] = (1e-8, -1e-8)                # power 2e-16
+            b[:, 0] = (0.0, 3e-9)
+        a[list(zero_a)] = 0.0
+        b[list(zero_b)] = 0.0
+        if n_frames > 9:
+            b[9] = a[9]                                             # identical frames: exactly 0
+        pa = (a.astype(np.float64) ** 2).sum(-1)
+        pb = (b.astype(np.float64) ** 2).sum(-1)
+        want = np.sqrt(((np.log10(pa + 1e-6) - np.log10(pb + 1e-6)) ** 2).mean(-1))
+        out = torch.full((n_frames,), -1.0, device="cuda")
+        ad, bd = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+        _lib.check(lib.mg_lsd_frames(_lib.ptr(ad), _lib.ptr(bd), n_frames, n_bins, _lib.ptr(out), _lib.stream()), "mg_lsd_frames")
+        got = out.double().cpu().numpy()
+        assert np.all(np.abs(got - want) <= 2.0 ** -22 * want), (zero_a, zero_b, np.abs(got - want).max())
+        if zero_a and zero_a == zero_b:
+            assert got[0] == 0.0
+        if n_frames > 9:
+            assert got[7] == 0.0 and got[9] == 0.0 and got[3] > 0.0 and got[5] > 0.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [1, 5])
+@pytest.mark.parametrize("T", [1, 255, 256, 257, 7001])
+def test_metrics_rows_against_float64(T, B):
+    """mg_metrics_rows == float64 numpy sums of hr^2, (sr - hr)^2, (lr - hr)^2 per row to 1e-12 (double accumulation; only the order
+    of the additions differs), lengths around the 256-thread block.  A row with sr == hr sums to exactly 0 and its SNR is inf."""
+    from mdctgan_amd import _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(10 * T + B)
+    for exact_row in (None, B - 1):
+        hr = (0.1 * rng.standard_normal((B, T))).astype(np.float32)
+        sr = (hr + 0.01 * rng.standard_normal((B, T))).astype(np.float32)
+        lr = (hr + 0.03 * rng.standard_normal((B, T))).astype(np.float32)
+        if exact_row is not None:
+            sr[exact_row] = hr[exact_row]
+        h, s, l = (t.astype(np.float64) for t in (hr, sr, lr))
+        want = np.stack(((h * h).sum(1), ((s - h) ** 2).sum(1), ((l - h) ** 2).sum(1)), axis=1)
+        sums = torch.full((B, 3), -1.0, dtype=torch.float64, device="cuda")
+        hd, ld, sd = (torch.from_numpy(t).cuda() for t in (hr, lr, sr))
+        _lib.check(lib.mg_metrics_rows(_lib.ptr(hd), _lib.ptr(ld), _lib.ptr(sd), B, T, _lib.ptr(sums), _lib.stream()), "mg_metrics_rows")
+        got = sums.cpu().numpy()
+        assert np.all(np.abs(got - want) <= 1e-12 * want), (exact_row, np.abs(got - want).max())
+        snr = (10 * torch.log10(sums[:, 0] / sums[:, 1])).cpu().numpy()          # as metrics.compute_matrics forms it
+        with np.errstate(divide="ignore"):
+            snr_want = 10 * np.log10(want[:, 0] / want[:, 1])
+        if exact_row is not None:
+            assert got[exact_row, 1] == 0.0 and snr[exact_row] == np.inf and snr_want[exact_row] == np.inf
+        fin = np.isfinite(snr_want)
+        assert np.array_equal(fin, np.isfinite(snr)) and np.all(np.abs(snr[fin] - snr_want[fin]) <= 1e-9)
