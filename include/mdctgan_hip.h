@@ -431,9 +431,15 @@ int mg_conv_wgrad_adam_w(const mg_conv_geom* g, const float* x, const float* dy,
 /* Name of the kernel instance a pass (0 fwd, 1 dgrad, 2 wgrad) launches for this geometry -- the symbol
  * rocprofv3 reports -- so bench.py can attribute event-timed launches per kernel.  out: host buffer >= 64 B. */
 int mg_conv_plan_name(int pass, const mg_conv_geom* g, char* out, int out_len);
-/* K splits of that launch where the pass takes the LDS-DMA implicit-GEMM kernels (conv_{fwd,dgrad,wgrad}_dma_kernel; 1 = unsplit),
- * 0 for every other kernel family: lets a host-only test pin the planner (workgroups = tiles x splits). */
+/* K splits of that launch where the pass takes the LDS-DMA implicit-GEMM kernels (conv_{fwd,dgrad,wgrad}_dma_kernel; 1 = unsplit)
+ * or is a Winograd layer (the splits of its batched Winograd-domain GEMM), 0 for every other kernel family: lets a host-only
+ * test pin the planner (workgroups = tiles x splits). */
 int mg_conv_plan_splits(int pass, const mg_conv_geom* g);
+/* Launch order of that kernel where the pass takes the LDS-DMA forward / data-gradient kernels, under the current environment:
+ * gm = row tiles per group of the tile order (0 = row tiles fastest over the whole split), cls_order = the stride-2 data
+ * gradient's parity-class order (1 = light and heavy classes paired, 0 = heaviest first; MG_DGRAD_CLASS_ORDER=0|1 forces one).
+ * Both 0 for every other pass and family. */
+int mg_conv_plan_order(int pass, const mg_conv_geom* g, int* gm, int* cls_order);
 /* FLOPs issued by that kernel for this geometry (direct: 2*MACs; Winograd layers: the P batched GEMMs, 2*P*T*Co*K). */
 double mg_conv_plan_flops(int pass, const mg_conv_geom* g);
 /* One-shot timing probe for bench.py: the next mg_conv_{fwd,dgrad,wgrad} call records hipEvent e0 / e1 on its launch

@@ -101,6 +101,7 @@ SIGNATURES = {
     "mg_conv_wgrad_workspace": (_sz, [_G]),
     "mg_conv_plan_name": (_i, [_i, _G, C.c_char_p, _i]),
     "mg_conv_plan_splits": (_i, [_i, _G]),
+    "mg_conv_plan_order": (_i, [_i, _G, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mg_conv_plan_flops": (C.c_double, [_i, _G]),
     "mg_probe_arm": (None, [_p, _p]),
     "mg_resample_length": (_ll, [_ll, _i, _i]),

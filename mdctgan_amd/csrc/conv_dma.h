@@ -847,19 +847,23 @@ inline int cd_half_nbuf() {
         else if (cd_half_nbuf() == 3) CD_TILE_DISPATCH(KERNEL, ALAY, BLAY, true, 3);           \
         else CD_TILE_DISPATCH(KERNEL, ALAY, BLAY, true, 2);                                    \
     } while (0)
+// Tile order of the forward launch (CdArgs.gm, cd_pick_gm): the one computation behind the launch and mg_conv_plan_order
+inline int conv_dma_fwd_gm(const mg_conv_geom* g, const CdPlan& p) {
+    const long long M = (long long)g->B * g->OH * g->OW;
+    const int tiles_m = (int)((M + p.bm - 1) / p.bm), tiles_n = g->Co / p.bn;
+    const double es = conv_dma_half(g) ? 2.0 : 4.0;
+    // a row tile's share of the input (every input pixel belongs to ~one row tile; taps re-read it from L2), a column tile's weights
+    const double a_bytes = (double)g->B * g->H * g->W * g->Ci * es / tiles_m / p.splits;
+    const double b_bytes = (double)p.bn * g->KH * g->KW * g->Ci * es / p.splits;
+    return cd_pick_gm(tiles_m, tiles_n, p.splits, a_bytes, b_bytes);
+}
 void conv_dma_fwd_launch(const mg_conv_geom* g, const CdPlan& p, const void* x, const void* w, const float* bias, float* y,
                          int act, float* part, hipStream_t st) {
     CdArgs a = cd_args(g);
     a.x = x; a.w = w; a.bias = bias; a.y = y; a.part = p.splits > 1 ? part : nullptr; a.act = act;
     const long long M = (long long)g->B * g->OH * g->OW;
     a.tiles_m = (int)((M + p.bm - 1) / p.bm); a.tiles_n = g->Co / p.bn; a.splits = p.splits; a.cps = p.cps;
-    {
-        const double es = conv_dma_half(g) ? 2.0 : 4.0;
-        // a row tile's share of the input (every input pixel belongs to ~one row tile; taps re-read it from L2), a column tile's weights
-        const double a_bytes = (double)g->B * g->H * g->W * g->Ci * es / a.tiles_m / a.splits;
-        const double b_bytes = (double)p.bn * g->KH * g->KW * g->Ci * es / a.splits;
-        a.gm = cd_pick_gm(a.tiles_m, a.tiles_n, a.splits, a_bytes, b_bytes);
-    }
+    a.gm = conv_dma_fwd_gm(g, p);
     const dim3 grid((unsigned)((long long)a.tiles_m * a.tiles_n * a.splits));
     CD_DISPATCH(conv_fwd_dma_kernel, 0, 0, conv_dma_half(g));
 }
@@ -960,28 +964,45 @@ inline CdPlan conv_dma_dgrad_plan(const mg_conv_geom* g) {
     }
     return best;
 }
+// Launch order of the data gradient (CdArgs.cls_order, CdArgs.gm): the one computation behind the launch and mg_conv_plan_order
+struct CdOrder { int gm, cls_order; };
+inline dim3 conv_dma_dgrad_grid(const mg_conv_geom* g, const CdPlan& p) {
+    const int s = g->stride;
+    const long long Mc = (long long)g->B * ((g->H + s - 1) / s) * ((g->W + s - 1) / s);
+    return dim3((unsigned)(((Mc + p.bm - 1) / p.bm) * (g->Ci / p.bn)), (unsigned)(s * s), (unsigned)p.splits);
+}
+inline CdOrder conv_dma_dgrad_order(const mg_conv_geom* g, const CdPlan& p) {
+    const int s = g->stride;
+    const long long Mc = (long long)g->B * ((g->H + s - 1) / s) * ((g->W + s - 1) / s);
+    const dim3 grid = conv_dma_dgrad_grid(g, p);
+    CdOrder o{};
+    // class order (stride 2, odd kernels: 4 / 2 / 2 / 1 taps).  All workgroups resident at once (LDS: 5 / 3 / 2 per CU for
+    // 64x64 / 64x128, 128x64 / 128x128 tiles): the round robin pairs class y with y + 2 on a CU, so (4, 2, 1, 2) balances
+    // (512 -> 1024 channels at 8x16: 107 against 119 us).  More rounds than that: heaviest first is the better list order
+    // (128 -> 256 channels at 64x128: 87 against 100 us).  MG_DGRAD_CLASS_ORDER=0|1 forces one (read per call).
+    const long long slots = 256LL * (p.bm == 64 && p.bn == 64 ? 5 : (p.bm == 128 && p.bn == 128 ? 2 : 3));
+    o.cls_order = (long long)grid.x * grid.y * grid.z <= slots ? 1 : 0;
+    if (const char* f = getenv("MG_DGRAD_CLASS_ORDER")) {
+        if (f[0] == '0' && !f[1]) o.cls_order = 0;
+        else if (f[0] == '1' && !f[1]) o.cls_order = 1;
+    }
+    // per parity class (grid.y) and K split (grid.z) the tiles of grid.x are handed to the XCDs in runs: same window model as
+    // the forward pass, with dy as the row operand (a class reads its taps' share of dy) and the weights as the column operand
+    const int tiles_m = (int)((Mc + p.bm - 1) / p.bm), tiles_n = g->Ci / p.bn;
+    const double es = conv_dma_half(g) ? 2.0 : 4.0;
+    const double a_bytes = (double)g->B * g->OH * g->OW * g->Co * es / tiles_m / p.splits;
+    const double b_bytes = (double)p.bn * g->KH * g->KW * g->Co * es / (s * s) / p.splits;
+    o.gm = cd_pick_gm(tiles_m, tiles_n, 1, a_bytes, b_bytes);
+    return o;
+}
 void conv_dma_dgrad_launch(const mg_conv_geom* g, const CdPlan& p, const void* dy, const void* w, const float* bias, float* dx,
                            int act, float* part, hipStream_t st, int round_f16) {
     CdArgs a = cd_args(g);
     a.round_f16 = round_f16;
     a.x = dy; a.w = w; a.bias = bias; a.y = dx; a.part = p.splits > 1 ? part : nullptr; a.act = act;
-    const int s = g->stride;
-    const long long Mc = (long long)g->B * ((g->H + s - 1) / s) * ((g->W + s - 1) / s);
-    const dim3 grid((unsigned)(((Mc + p.bm - 1) / p.bm) * (g->Ci / p.bn)), (unsigned)(s * s), (unsigned)p.splits);
-    // class order (stride 2, odd kernels: 4 / 2 / 2 / 1 taps).  All workgroups resident at once (LDS: 5 / 3 / 2 per CU for
-    // 64x64 / 64x128, 128x64 / 128x128 tiles): the round robin pairs class y with y + 2 on a CU, so (4, 2, 1, 2) balances
-    // (512 -> 1024 channels at 8x16: 107 against 119 us).  More rounds than that: heaviest first is the better list order
-    // (128 -> 256 channels at 64x128: 87 against 100 us).  MG_DGRAD_CLASS_ORDER=0|1 forces one.
-    const long long slots = 256LL * (p.bm == 64 && p.bn == 64 ? 5 : (p.bm == 128 && p.bn == 128 ? 2 : 3));
-    a.cls_order = (long long)grid.x * grid.y * grid.z <= slots ? 1 : 0;
-    {
-        // per parity class (grid.y) and K split (grid.z) the tiles of grid.x are handed to the XCDs in runs: same window model as
-        // the forward pass, with dy as the row operand (a class reads its taps' share of dy) and the weights as the column operand
-        const int tiles_m = (int)((Mc + p.bm - 1) / p.bm), tiles_n = g->Ci / p.bn;
-        const double es = conv_dma_half(g) ? 2.0 : 4.0;
-        const double a_bytes = (double)g->B * g->OH * g->OW * g->Co * es / tiles_m / p.splits;
-        const double b_bytes = (double)p.bn * g->KH * g->KW * g->Co * es / (s * s) / p.splits;
-        a.gm = cd_pick_gm(tiles_m, tiles_n, 1, a_bytes, b_bytes);
-    }
+    const dim3 grid = conv_dma_dgrad_grid(g, p);
+    const CdOrder o = conv_dma_dgrad_order(g, p);
+    a.cls_order = o.cls_order;
+    a.gm = o.gm;
     CD_DISPATCH(conv_dgrad_dma_kernel, 0, 1, conv_dma_half(g));
 }

@@ -1109,26 +1109,36 @@ DensePlan dense_plan(int pass, int P, long long T, int Co, int Kc, bool hp) {
     static const int split_opts[8] = {1, 2, 3, 4, 6, 8, 12, 16};
     const int chunks = (dd.K + DG_BK - 1) / DG_BK;
     int f_bm = 0, f_bn = 0, f_sp = 0;
+    if (const char* f = getenv("MG_FORCE_DENSE")) {      // tuning harness: "bm,bn,splits" (dropped where the shape does not admit it)
+        if (sscanf(f, "%d,%d,%d", &f_bm, &f_bn, &f_sp) != 3) f_bm = f_bn = f_sp = 0;
+    }
     double best = 1e300;
-    for (const Cand& c : cands) {
-        if (dd.N % c.bn != 0) continue;
-        if (!p.dma && !((c.bm == 64 && c.bn == 64) || (c.bm == 128 && c.bn == 128))) continue;   // register-path instances
-        if (f_bm && (c.bm != f_bm || c.bn != f_bn)) continue;
-        const long long w = ((dd.M + c.bm - 1) / c.bm) * (long long)(dd.N / c.bn) * P;
-        const double tile_us = 2.0 * c.bm * c.bn * DG_BK / (157.3e12 / 256.0) * 1e6 / (p.dma ? c.eff_dma : c.eff_reg);
-        for (int sp : split_opts) {
-            if (sp > 1 && chunks / sp < 8) break;
-            if (f_sp && sp != f_sp) continue;
-            const int cps = (chunks + sp - 1) / sp;
-            const int spl = (chunks + cps - 1) / cps;
-            const long long wg = w * spl;
-            double t = (double)((wg + 255) / 256) * tile_us * (cps + 1.2);
-            // forward / data gradient: 500 workgroups already count as two rounds (17x33 maps on 128x128 tiles: 110 against
-            // 125 us with the penalty); the weight gradient's short K loops keep the wider band (measured both ways)
-            if (wg < (pass == 2 ? 512 : 384)) t /= 0.85;
-            if (spl > 1) t += (double)(spl + 1) * P * (double)dd.M * dd.N * 4.0 / 4e12 * 1e6 + 3.0;
-            if (t < best) { best = t; p.bm = c.bm; p.bn = c.bn; p.splits = spl; p.cps = cps; }
+    auto search = [&]() {
+        for (const Cand& c : cands) {
+            if (dd.N % c.bn != 0) continue;
+            if (!p.dma && !((c.bm == 64 && c.bn == 64) || (c.bm == 128 && c.bn == 128))) continue;   // register-path instances
+            if (f_bm && (c.bm != f_bm || c.bn != f_bn)) continue;
+            const long long w = ((dd.M + c.bm - 1) / c.bm) * (long long)(dd.N / c.bn) * P;
+            const double tile_us = 2.0 * c.bm * c.bn * DG_BK / (157.3e12 / 256.0) * 1e6 / (p.dma ? c.eff_dma : c.eff_reg);
+            for (int sp : split_opts) {
+                if (sp > 1 && chunks / sp < 8) break;
+                if (f_sp && sp != f_sp) continue;
+                const int cps = (chunks + sp - 1) / sp;
+                const int spl = (chunks + cps - 1) / cps;
+                const long long wg = w * spl;
+                double t = (double)((wg + 255) / 256) * tile_us * (cps + 1.2);
+                // forward / data gradient: 500 workgroups already count as two rounds (17x33 maps on 128x128 tiles: 110 against
+                // 125 us with the penalty); the weight gradient's short K loops keep the wider band (measured both ways)
+                if (wg < (pass == 2 ? 512 : 384)) t /= 0.85;
+                if (spl > 1) t += (double)(spl + 1) * P * (double)dd.M * dd.N * 4.0 / 4e12 * 1e6 + 3.0;
+                if (t < best) { best = t; p.bm = c.bm; p.bn = c.bn; p.splits = spl; p.cps = cps; }
+            }
         }
+    };
+    search();
+    if (best == 1e300 && (f_bm || f_sp)) {      // a forced plan the shape does not admit is dropped, as the other hooks' are
+        f_bm = f_bn = f_sp = 0;
+        search();
     }
     if (best == 1e300) { p.ok = false; return p; }
     if (p.splits == 1) p.cps = 1 << 28;
@@ -1970,7 +1980,7 @@ double mg_conv_plan_flops(int pass, const mg_conv_geom* g) {
     }
 }
 
-// Split-K factor of the LDS-DMA kernels a pass runs (0: another family)
+// Split-K factor of the LDS-DMA kernels or of the Winograd-domain GEMM a pass runs (0: another family)
 int mg_conv_plan_splits(int pass, const mg_conv_geom* g) {
     if (!geom_ok(g) || pass < 0 || pass > 2) return 0;
     const ConvRoute r = conv_route(pass, g);
@@ -1978,8 +1988,29 @@ int mg_conv_plan_splits(int pass, const mg_conv_geom* g) {
         const mg_conv_geom gp = cd_reflect_geom(g);
         return conv_dma_dgrad_plan(&gp).splits;
     }
+    if (r == R_WINO || r == R_WINO4 || r == R_WINO42) {      // the Winograd-domain GEMM stage, on either kernel family
+        const WinoGemm s = wino_gemm_plan(wino_geo(r, g), pass, g);
+        return s.dp.ok ? s.dp.splits : s.tp.splits;
+    }
     if (r != R_DMA) return 0;
     return (pass == 0 ? conv_dma_fwd_plan(g) : pass == 1 ? conv_dma_dgrad_plan(g) : conv_dma_wgrad_plan(g)).splits;
+}
+// Launch order of the LDS-DMA forward pass / data gradient (CdArgs.gm, CdArgs.cls_order) under the current environment: what
+// conv_dma_fwd_launch / conv_dma_dgrad_launch compute for the pass's plan.  0 / 0 for every other pass and family.
+int mg_conv_plan_order(int pass, const mg_conv_geom* g, int* gm, int* cls_order) {
+    if (!geom_ok(g) || !gm || !cls_order || pass < 0 || pass > 2) return MG_ERR_ARG;
+    *gm = 0;
+    *cls_order = 0;
+    const ConvRoute r = conv_route(pass, g);
+    if (pass == 0 && r == R_DMA) {
+        *gm = conv_dma_fwd_gm(g, conv_dma_fwd_plan(g));
+    } else if (pass == 1 && (r == R_DMA || r == R_DMA_REFLECT)) {
+        const mg_conv_geom gp = r == R_DMA ? *g : cd_reflect_geom(g);
+        const CdOrder o = conv_dma_dgrad_order(&gp, conv_dma_dgrad_plan(&gp));
+        *gm = o.gm;
+        *cls_order = o.cls_order;
+    }
+    return MG_OK;
 }
 // Name of the kernel instance a pass would launch for this geometry (matches the symbol rocprofv3 reports,
 // minus the anonymous-namespace prefix).  pass: 0 fwd, 1 dgrad, 2 wgrad.
@@ -2291,12 +2322,14 @@ static int conv_fwd(const mg_conv_geom* g, const float* x, const float* w, const
         if (al && workspace_bytes >= wino_ws_bytes(r, 0, g))
             return wino_fwd(wino_geo(r, g), g, x, w, bias, y, act, (float*)workspace, st, u, v, r == R_WINO && !prec_h(g) && v_filled);
         break;
-    case R_SMALLC: {
-        probe_begin(st);
-        const int rc = smallc_fwd(g, x, w, bias, y, act, st);
-        probe_end(st);
-        return rc;
-    }
+    case R_SMALLC:
+        if ((reinterpret_cast<uintptr_t>(w) & 7) == 0) {      // conv_smallc_fwd_kernel reads its weights as float2s
+            probe_begin(st);
+            const int rc = smallc_fwd(g, x, w, bias, y, act, st);
+            probe_end(st);
+            return rc;
+        }
+        break;
     default: break;
     }
     const Geom gg = to_geom(g);
@@ -2347,7 +2380,7 @@ static int conv_fwd(const mg_conv_geom* g, const float* x, const float* w, const
     }
     const bool vec = (g->Ci % BK == 0) && aligned16(x) && aligned16(w);
     TilePlan tp = fwd_plan(g);
-    if (tp.splits > 1 && (!workspace || workspace_bytes < mg_conv_fwd_workspace(g) || !aligned16(y) ||
+    if (tp.splits > 1 && (!workspace || !aligned16(workspace) || workspace_bytes < mg_conv_fwd_workspace(g) || !aligned16(y) ||
                           (bias && !aligned16(bias)))) {
         tp.splits = 1;
         tp.cps = 1 << 30;
@@ -2459,7 +2492,7 @@ static int conv_dgrad(const mg_conv_geom* g, const float* dy, const float* w, co
     const bool veca = (g->Co % BK == 0) && aligned16(dy);
     const bool vecb = (g->Ci % 4 == 0) && aligned16(w);
     TilePlan tp = dgrad_plan(g);
-    if (tp.splits > 1 && (!workspace || workspace_bytes < mg_conv_dgrad_workspace(g) || !aligned16(dx) ||
+    if (tp.splits > 1 && (!workspace || !aligned16(workspace) || workspace_bytes < mg_conv_dgrad_workspace(g) || !aligned16(dx) ||
                           (bias && !aligned16(bias)))) {
         tp.splits = 1;
         tp.cps = 1 << 30;
@@ -2613,7 +2646,8 @@ int mg_conv_wgrad_chk(const mg_conv_geom* g, const float* x, const float* dy, fl
                               wt ? wt->md : nullptr);
         break;
     case R_SMALLC:
-        if (aligned16(dw) && aligned16(workspace)) {
+        // (conv_smallc_wgrad_mfma_kernel reads dy as float2s)
+        if (aligned16(dw) && aligned16(workspace) && (reinterpret_cast<uintptr_t>(dy) & 7) == 0) {
             probe_begin(st);
             const int rc = smallc_wgrad(g, x, dy, dw, accumulate, (float*)workspace, st);
             probe_end(st);
@@ -2662,7 +2696,11 @@ int mg_conv_wgrad_chk(const mg_conv_geom* g, const float* x, const float* dy, fl
             return mg_colsum(dy, (long long)g->B * g->OH * g->OW, g->Co, dbias, accumulate, workspace, workspace_bytes, stream);
         return MG_OK;
     }
-    const WgradPlan p = wgrad_plan(g);
+    WgradPlan p = wgrad_plan(g);
+    if (p.splits > 1 && (!aligned16(dw) || !aligned16(workspace))) {      // splitk_reduce_kernel reads the slabs and stores (accumulates into) dw as float4s
+        p.splits = 1;
+        p.cps = 1 << 30;
+    }
     const bool veca = (g->Co % 4 == 0) && aligned16(dy);
     const bool vecb = (g->Ci % 4 == 0) && aligned16(x);
     const size_t n_out = (size_t)g->Co * g->KH * g->KW * g->Ci;

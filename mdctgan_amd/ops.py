@@ -111,10 +111,10 @@ def precast_ok(pass_id: int, g: ConvGeom) -> bool:
     return hit
 
 
-def conv_fwd(g: ConvGeom, x, w, bias=None, act=ACT_NONE, u=None, v_out=None, v_filled=False):
-    """v_filled: v_out already holds float16(x) (written by x's producer; only where precast_ok(0, g))."""
+def conv_fwd(g: ConvGeom, x, w, bias=None, act=ACT_NONE, u=None, v_out=None, v_filled=False, out=None):
+    """v_filled: v_out already holds float16(x) (written by x's producer; only where precast_ok(0, g)).  out: the caller's y."""
     lib = _lib.load()
-    y = torch.empty(g.B, g.OH, g.OW, g.Co, dtype=torch.float32, device=x.device)
+    y = torch.empty(g.B, g.OH, g.OW, g.Co, dtype=torch.float32, device=x.device) if out is None else out
     ws = _ws(lib.mg_conv_fwd_workspace(g), x.device)
     if PROFILER is not None:
         PROFILER.begin(0, g)
