@@ -789,10 +789,11 @@ CdPlan conv_dma_plan(long long M, int N, int chunks, bool wgrad, int ck, int tap
         const long long w = ((M + c.bm - 1) / c.bm) * (long long)(N / c.bn);
         const double tile_us = 2.0 * c.bm * c.bn * ck / rate * 1e6 / c.eff;
         for (int sp : split_opts) {
-            if (sp > 1 && chunks / sp < 8) break;
+            // (the planner keeps 8 chunks per split; a forced count is taken up to `chunks`, as the other two models take it)
+            if (sp > 1 && (f_sp ? sp > chunks : chunks / sp < 8)) break;
             if (f_sp && sp != f_sp) continue;
             const int cps = (chunks + sp - 1) / sp;
-            const int spl = sp;                                  // (cd_split_bound: every split count up to `chunks` is exact)
+            const int spl = sp;                               // (cd_split_bound: every split count up to `chunks` is exact)
             const long long wg = w * spl;
             double t = (double)((wg + 255) / 256) * tile_us * (cps + fixed);
             if (wg < fill) t /= 0.85;

@@ -650,7 +650,7 @@ __global__ void wino_dweight_xform_kernel(const float* __restrict__ dU, int Co, 
 // dw = G^T dU G, the Adam update of (w, m, v) and the forward transform U = G w G^T of the UPDATED weights for the next
 // iteration -- what wino_dweight_xform_kernel, adam_dev_kernel and wino_weight_xform_kernel do in three passes with the
 // gradient and the weights making an HBM round trip each (467 MB -> 354 MB per 1024-channel layer).  The arithmetic is theirs,
-// operation for operation (bit-identical: tests/test_conv_gpu.py::test_wgrad_adam_fusion_is_bit_identical).  The Adam clock
+// operation for operation (bit-identical: tests/test_trunk_fused_gpu.py::test_wgrad_adam_fusion_is_bit_identical).  The Adam clock
 // has not ticked yet when this runs (backward precedes optimizer.step()): the bias corrections come from state[4], state[5],
 // which the last tick left for exactly this purpose.
 __global__ void wino_adam_kernel(const float* __restrict__ dU, int Co, int Ci, float* __restrict__ w, float* __restrict__ m,
