@@ -249,6 +249,34 @@ int mg_stft_frames(const float* x, int B, int T, const float* window, int n_fft,
                    void* stream);
 int mg_lsd_frames(const float* spec_a, const float* spec_b, long long n_frames, int n_bins, float* out, void* stream);
 
+/* The same metrics for MANY utterances in shared launches (the per-file compute_matrics of generate_audio.py:57-67 for a whole
+ * test set).  mg_metric_row (a DEVICE array, one entry per utterance): sample t < len of row u is hr[hr_pos + t], lr[lr_pos + t],
+ * sr[sr_pos + t] of three packed float32 buffers, each with its own total.  Windows are cut to their buffers (a sample that is
+ * missing from one is skipped by the sums and enters a frame as 0), a row with len <= 0 is dead, there are no atomics and every
+ * sum has one fixed order: a row has the same bits alone as inside any pack.  hr_shift [n_rows] or NULL: every hr sample of row u
+ * enters as hr[p] + hr_shift[u], one float32 add (the operand mg_resample_rows forms from its shift).  No host synchronisation;
+ * the launch count does not depend on n_rows.
+ *   mg_metrics_rows_packed   out[u] = {sum hr^2, sum (sr - hr)^2, sum (lr - hr)^2} (double, mg_metrics_rows' arithmetic): chunks of
+ *                            MG_MOMENTS_CHUNK samples counted from the row's first sample, each summed by one workgroup in a fixed
+ *                            tree, then the chunks in ascending order.  max_len: the longest row (sizes the workspace and the grid;
+ *                            longer rows lose their tail).  workspace: mg_metrics_rows_packed_workspace(n_rows, max_len) bytes.
+ *                            A dead row gives {0, 0, 0}.
+ *   mg_lsd_rows              out[frame_start[u] + f] = mg_lsd_frames' value for frame f of utterance u (float32), from the
+ *                            waveforms: frames and spectra are never written.  frame_start [n_rows + 1] (device): the prefix sums
+ *                            of mg_stft_num_frames(len_u, n_fft, hop, center), total_frames its last entry and the size of out.
+ *                            Frames are reflected at the row's own [0, len) (center != 0; the host refuses n_fft / 2 >= len) and
+ *                            multiplied by window [n_fft] as mg_stft_frames does; each spectrum is a real transform through an
+ *                            n_fft / 2-point complex float32 Stockham FFT in LDS, the same statements for hr and sr (sr == hr
+ *                            gives exactly 0).  n_fft 512, 1024 or 2048 (else MG_ERR_ARG), any hop >= 1. */
+typedef struct { long long hr_pos, lr_pos, sr_pos, len; } mg_metric_row;
+size_t mg_metrics_rows_packed_workspace(int n_rows, long long max_len);
+int mg_metrics_rows_packed(const float* hr, long long hr_total, const float* lr, long long lr_total, const float* sr,
+                           long long sr_total, const mg_metric_row* rows, int n_rows, long long max_len, const float* hr_shift,
+                           double* out, void* workspace, size_t workspace_bytes, void* stream);
+int mg_lsd_rows(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows, int n_rows,
+                const long long* frame_start, long long total_frames, const float* hr_shift, const float* window, int n_fft,
+                int hop, int center, float* out, void* stream);
+
 /* Segment stitching of generate_audio.py:40-53: seg [n_seg, seg_len] (the [n_seg,1,1,T] inference outputs) -> one
  * waveform of mg_stitch_length() samples (-1: invalid arguments; 2*overlap must be < seg_len).  overlap == 0
  * concatenates; overlap > 0 halves the first/last `overlap` samples of every segment, overlap-adds at stride

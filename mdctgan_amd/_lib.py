@@ -114,6 +114,9 @@ SIGNATURES = {
     "mg_stft_num_frames": (_i, [_i, _i, _i, _i]),
     "mg_stft_frames": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p]),
     "mg_lsd_frames": (_i, [_p, _p, _ll, _i, _p, _p]),
+    "mg_metrics_rows_packed_workspace": (_sz, [_i, _ll]),
+    "mg_metrics_rows_packed": (_i, [_p, _ll, _p, _ll, _p, _ll, _p, _i, _ll, _p, _p, _p, _sz, _p]),
+    "mg_lsd_rows": (_i, [_p, _ll, _p, _ll, _p, _i, _p, _ll, _p, _p, _i, _i, _i, _p, _p]),
     "mg_frames_window": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "mg_codec_forward": (_i, [_p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p]),
     "mg_codec_inverse": (_i, [_p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _p, _p, _p, _p]),

@@ -1,0 +1,430 @@
+// The metrics of util/util.py:132-177 (compute_matrics) for MANY utterances in shared launches: the last step of the reference's
+// generate_audio.py:57-67, which metrics.hip serves one clip at a time.  Every utterance sits at its own place of three packed
+// float32 buffers (ground truth hr, low-rate lr, super-resolved sr; each with its own total), a device row table
+// (mg_metric_row = hr_pos, lr_pos, sr_pos, len) says where: sample t < len of row u is hr[hr_pos + t], lr[lr_pos + t],
+// sr[sr_pos + t].  An optional shift [n_rows] enters every hr sample as one float32 add, hr[p] + shift[u] -- the operand
+// resample_rows_kernel<., true> forms, so the un-materialised `raw += 1e-4 - mean(raw)` of read_audio is the ground truth.
+//   metrics_rows_packed_*   per row {sum hr^2, sum (sr - hr)^2, sum (lr - hr)^2} in double (metrics_rows_kernel's arithmetic) with
+//                           the two-level sums of rows_moments_* (resample_rows.hip): chunks of MG_MOMENTS_CHUNK samples counted
+//                           from the row's first sample, one workgroup per chunk in a fixed tree, then the chunks in ascending order.
+//   lsd_rows_kernel         the per-frame log-spectral distance of every frame of every utterance, straight from the waveforms:
+//                           neither the windowed frames nor the spectra of metrics.hip's three-launch chain exist in HBM.
+// Windows are cut to their buffers (a sample outside one is not read: it is skipped by the sums and enters a frame as 0), a row
+// with len <= 0 is dead, there are no atomics, every sum has one fixed order: a row has the same bits alone as inside any pack.
+//
+// lsd_rows_kernel.  A tile is LSD_TILE / N consecutive frames of the flattened frame index (8 / 4 / 2 at N = 512 / 1024 / 2048), so
+// it may hold the end of one utterance and the start of the next; frame_start [n_rows + 1] (a device prefix array) places the
+// utterances, and one lane per frame of the tile searches it and leaves the frame's row in LDS.  Frame f of a row is
+// x[reflect(f hop + n - N/2)] window[n] (center) or x[f hop + n] window[n], reflected at the row's own [0, len), one float32
+// product as stft_frames_kernel forms it.  TWO REAL transforms per frame, each through one complex transform of M = N/2 points:
+//     z[m] = x_w[2m] + i x_w[2m+1],   Z = DFT_M(z),   E[k] = (Z[k] + conj Z[M-k]) / 2,   O[k] = (Z[k] - conj Z[M-k]) / 2i,
+//     X[k] = E[k] + exp(-2 pi i k / N) O[k],   k = 0 .. N/2   (indices of Z mod M),
+// the same statements for hr and for sr, so sr == hr gives exactly 0 and a quiet sr is as accurate as a loud one.  (One N-point
+// transform of hr_w + i sr_w costs the same and was tried first: its float32 error is relative to the LOUDER signal, and for
+// sr == hr a near-null bin of a mirror-symmetric edge frame left 1.07e-5 where the tests allow 1e-5.)
+// The DFT is mdct_pow2.hip's Stockham autosort FFT restated for M complex points per signal: plain float32 on the VALU, radix-8
+// stages with one radix-4 (N = 512) or radix-2 (N = 2048) stage first, every stage in place in LDS (all butterflies of the tile
+// are read into registers, a barrier, then written to their autosort positions: natural order out).  Roots exp(-2 pi i t / N) are
+// evaluated in double by the workgroup (sincospi of an exactly representable argument) and rounded once; the stages use the even
+// ones.  Epilogue per bin in double as lsd_frames_kernel: p = re^2 + im^2, d = log10(p_hr + 1e-6) - log10(p_sr + 1e-6), sum d^2
+// over the N/2 + 1 bins by the 256 / frames-per-tile lanes of the frame in a fixed tree, sqrt(sum / (N/2 + 1)) rounded once to
+// float32 and stored once.
+// LDS: 32 KiB of frame data + 8 N bytes of roots (4 / 8 / 16 KiB): three workgroups per CU.
+#include <limits.h>
+#include <math.h>
+
+#include "common.h"
+#include "mdctgan_hip.h"
+
+namespace {
+
+struct MetricRow { long long hr_pos, lr_pos, sr_pos, len; };
+
+constexpr int kChunk = MG_MOMENTS_CHUNK;
+constexpr long long kFar = 1LL << 62;            // positions beyond this are a broken table: the row is dead before any sum overflows
+
+// samples [lo, hi) of a row of `len` samples at `pos` exist in a buffer of `total` samples
+__device__ __forceinline__ void cut_to(long long pos, long long total, long long& lo, long long& hi) {
+    if (pos <= -kFar || pos >= total) { hi = lo; return; }
+    if (-pos > lo) lo = -pos;
+    if (total - pos < hi) hi = total - pos;
+}
+
+// One workgroup = one chunk of one row.  Thread t owns samples 4t .. 4t+3 (+ 1024 i) of the chunk, whatever the row's alignment;
+// 16-byte loads where the quad is aligned and whole in all three buffers (VEC: 16-byte aligned bases), scalar loads otherwise.
+template <bool VEC, bool SHIFT>
+__global__ __launch_bounds__(256) void metrics_rows_packed_chunks_kernel(const float* __restrict__ hr, long long hr_total,
+                                                                         const float* __restrict__ lr, long long lr_total,
+                                                                         const float* __restrict__ sr, long long sr_total,
+                                                                         const MetricRow* __restrict__ rows, int n_rows,
+                                                                         const float* __restrict__ shift, int max_chunks,
+                                                                         double* __restrict__ partial) {
+    __shared__ double red[4][3];
+    for (int r = blockIdx.y; r < n_rows; r += gridDim.y) {
+        const MetricRow rw = rows[r];
+        if (rw.len <= 0) continue;
+        long long lo = 0, hi = rw.len;
+        cut_to(rw.hr_pos, hr_total, lo, hi);
+        cut_to(rw.lr_pos, lr_total, lo, hi);
+        cut_to(rw.sr_pos, sr_total, lo, hi);
+        if (hi <= lo) continue;
+        const long long all = (rw.len + kChunk - 1) / kChunk;
+        const int n_chunks = (int)(all < max_chunks ? all : max_chunks);
+        const float s = SHIFT ? shift[r] : 0.0f;
+        for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+            const long long t0 = (long long)c * kChunk;
+            // samples [a, b) of the chunk exist in all three buffers (all of them for a sound table)
+            const int a = (int)(lo - t0 > 0 ? (lo - t0 < kChunk ? lo - t0 : kChunk) : 0);
+            const int b = (int)(hi - t0 < kChunk ? (hi - t0 > 0 ? hi - t0 : 0) : kChunk);
+            const float* h = hr + (rw.hr_pos + t0);                    // (only [a, b) of each is read)
+            const float* l = lr + (rw.lr_pos + t0);
+            const float* q = sr + (rw.sr_pos + t0);
+            const bool quads = VEC && (((rw.hr_pos + t0) | (rw.lr_pos + t0) | (rw.sr_pos + t0)) & 3) == 0;
+            double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+            for (int i = 4 * threadIdx.x; i < b; i += 4 * 256) {
+                float eh[4], el[4], es[4];
+                bool on[4];
+                if (quads && i >= a && i + 3 < b) {
+                    const float4 vh = *reinterpret_cast<const float4*>(h + i);
+                    const float4 vl = *reinterpret_cast<const float4*>(l + i);
+                    const float4 vs = *reinterpret_cast<const float4*>(q + i);
+                    eh[0] = vh.x; eh[1] = vh.y; eh[2] = vh.z; eh[3] = vh.w;
+                    el[0] = vl.x; el[1] = vl.y; el[2] = vl.z; el[3] = vl.w;
+                    es[0] = vs.x; es[1] = vs.y; es[2] = vs.z; es[3] = vs.w;
+                    on[0] = on[1] = on[2] = on[3] = true;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        on[k] = i + k >= a && i + k < b;
+                        eh[k] = on[k] ? h[i + k] : 0.0f;
+                        el[k] = on[k] ? l[i + k] : 0.0f;
+                        es[k] = on[k] ? q[i + k] : 0.0f;
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    // (a missing sample adds 0 to all three sums: its shift stays out as well)
+                    const double hv = on[k] ? (double)(SHIFT ? eh[k] + s : eh[k]) : 0.0;
+                    const double ds = (double)es[k] - hv, dl = (double)el[k] - hv;
+                    a0 += hv * hv;
+                    a1 += ds * ds;
+                    a2 += dl * dl;
+                }
+            }
+            a0 = wave_sum_d(a0); a1 = wave_sum_d(a1); a2 = wave_sum_d(a2);
+            if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = a0; red[threadIdx.x >> 6][1] = a1; red[threadIdx.x >> 6][2] = a2; }
+            __syncthreads();
+            if (threadIdx.x < 3) {
+                const int w = threadIdx.x;
+                partial[((size_t)r * max_chunks + c) * 3 + w] = ((red[0][w] + red[1][w]) + red[2][w]) + red[3][w];
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void metrics_rows_packed_final_kernel(const MetricRow* __restrict__ rows, long long hr_total,
+                                                                        long long lr_total, long long sr_total, int n_rows,
+                                                                        int max_chunks, const double* __restrict__ partial,
+                                                                        double* __restrict__ out) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    const MetricRow rw = rows[r];
+    long long lo = 0, hi = rw.len > 0 ? rw.len : 0;
+    cut_to(rw.hr_pos, hr_total, lo, hi);
+    cut_to(rw.lr_pos, lr_total, lo, hi);
+    cut_to(rw.sr_pos, sr_total, lo, hi);
+    const long long all = hi > lo ? (rw.len + kChunk - 1) / kChunk : 0;        // (the chunks the first kernel wrote)
+    const int n_chunks = (int)(all < max_chunks ? all : max_chunks);
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int c = 0; c < n_chunks; ++c) {
+        const double* p = partial + ((size_t)r * max_chunks + c) * 3;
+        s0 += p[0];
+        s1 += p[1];
+        s2 += p[2];
+    }
+    out[3 * (size_t)r] = s0;
+    out[3 * (size_t)r + 1] = s1;
+    out[3 * (size_t)r + 2] = s2;
+}
+
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// as rows_grid of resample_rows.hip: enough x blocks per row to fill the chip, few enough that thousands of rows do not launch
+// mostly empty ones
+inline dim3 rows_grid(int n_rows, long long max_len, int per_block) {
+    const unsigned gy = (unsigned)(n_rows < 65535 ? n_rows : 65535);
+    long long bx = (max_len + per_block - 1) / per_block;
+    const long long cap = 8192 / gy > 8 ? 8192 / gy : 8;
+    bx = bx < cap ? bx : cap;
+    return dim3((unsigned)(bx < 1 ? 1 : (bx > 1024 ? 1024 : bx)), gy);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// lsd_rows_kernel
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int LSD_NT = 256;
+constexpr int LSD_TILE = 4096;      // complex points of frame data per workgroup
+
+__device__ __forceinline__ float2 lsd_cmul(float2 a, float2 b) {
+    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+
+template <int R>
+__device__ __forceinline__ void lsd_butterfly(float2 (&v)[R]) {
+    if (R == 2) {
+        const float2 a = v[0], b = v[1];
+        v[0] = make_float2(a.x + b.x, a.y + b.y);
+        v[1] = make_float2(a.x - b.x, a.y - b.y);
+    } else if (R == 4) {
+        const float2 a0 = make_float2(v[0].x + v[2].x, v[0].y + v[2].y), a1 = make_float2(v[0].x - v[2].x, v[0].y - v[2].y);
+        const float2 a2 = make_float2(v[1].x + v[3].x, v[1].y + v[3].y), a3 = make_float2(v[1].x - v[3].x, v[1].y - v[3].y);
+        v[0] = make_float2(a0.x + a2.x, a0.y + a2.y);
+        v[2] = make_float2(a0.x - a2.x, a0.y - a2.y);
+        v[1] = make_float2(a1.x + a3.y, a1.y - a3.x);      // a1 - i a3
+        v[3] = make_float2(a1.x - a3.y, a1.y + a3.x);      // a1 + i a3
+    } else {
+        // 8 points: two 4-point transforms (even / odd inputs), then out[k] = E[k] + W8^k O[k], out[k + 4] = E[k] - W8^k O[k]
+        float2 e[4] = {v[0], v[2], v[4], v[6]}, o[4] = {v[1], v[3], v[5], v[7]};
+        lsd_butterfly<4>(e);
+        lsd_butterfly<4>(o);
+        constexpr float H = 0.70710678118654752440f;
+        const float2 t0 = o[0];
+        const float2 t1 = make_float2((o[1].x + o[1].y) * H, (o[1].y - o[1].x) * H);       // (1 - i) / sqrt 2
+        const float2 t2 = make_float2(o[2].y, -o[2].x);                                     // -i
+        const float2 t3 = make_float2((o[3].y - o[3].x) * H, (-o[3].x - o[3].y) * H);      // (-1 - i) / sqrt 2
+        v[0] = make_float2(e[0].x + t0.x, e[0].y + t0.y); v[4] = make_float2(e[0].x - t0.x, e[0].y - t0.y);
+        v[1] = make_float2(e[1].x + t1.x, e[1].y + t1.y); v[5] = make_float2(e[1].x - t1.x, e[1].y - t1.y);
+        v[2] = make_float2(e[2].x + t2.x, e[2].y + t2.y); v[6] = make_float2(e[2].x - t2.x, e[2].y - t2.y);
+        v[3] = make_float2(e[3].x + t3.x, e[3].y + t3.y); v[7] = make_float2(e[3].x - t3.x, e[3].y - t3.y);
+    }
+}
+
+// One Stockham stage over the LSD_TILE / P transforms of P points in the tile.  buf: [LSD_TILE / P][P] complex; NS = size of the
+// sub-transforms done so far; root[t] = exp(-2 pi i t / 2P).  Butterfly j of a transform reads points j + r P / R and writes
+// (j / NS) NS R + j % NS + r NS.  Contains both barriers: on entry every earlier write to buf must already be fenced by the
+// caller's barrier.
+template <int P, int R, int NS>
+__device__ __forceinline__ void lsd_stage(float2* __restrict__ buf, const float2* __restrict__ root, int tid) {
+    constexpr int NB = P / R, FT = LSD_TILE / P, IT = FT * NB / LSD_NT;
+    static_assert(FT * NB % LSD_NT == 0, "whole butterflies per thread");
+    float2 v[IT][R];
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        const int idx = tid + it * LSD_NT, fr = idx / NB, j = idx % NB;
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[it][r] = buf[fr * P + j + r * NB];
+        if (NS > 1) {
+            const int k = j % NS;
+#pragma unroll
+            for (int r = 1; r < R; ++r) v[it][r] = lsd_cmul(v[it][r], root[2 * (r * k * (P / (NS * R)))]);
+        }
+        lsd_butterfly<R>(v[it]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        const int idx = tid + it * LSD_NT, fr = idx / NB, j = idx % NB;
+        const int d = (j / NS) * NS * R + j % NS;
+#pragma unroll
+        for (int r = 0; r < R; ++r) buf[fr * P + d + r * NS] = v[it][r];
+    }
+    __syncthreads();
+}
+
+template <int P, int NS>
+__device__ __forceinline__ void lsd_stages8(float2* buf, const float2* root, int tid) {
+    lsd_stage<P, 8, NS>(buf, root, tid);
+    if constexpr (NS * 8 < P) lsd_stages8<P, NS * 8>(buf, root, tid);
+}
+
+constexpr int lsd_log2(int n) { int l = 0; while (n > 1) { n >>= 1; ++l; } return l; }
+
+// Stage radices: P = 256: 4 8 8;  P = 512: 8 8 8;  P = 1024: 2 8 8 8.
+template <int P>
+__device__ __forceinline__ void lsd_fft(float2* buf, const float2* root, int tid) {
+    constexpr int REM = lsd_log2(P) % 3;
+    if constexpr (REM == 0) {
+        lsd_stages8<P, 1>(buf, root, tid);
+    } else {
+        lsd_stage<P, 1 << REM, 1>(buf, root, tid);
+        lsd_stages8<P, 1 << REM>(buf, root, tid);
+    }
+}
+
+// X[k] of the real transform whose packed M-point transform is Z, k = 0 .. M; w = exp(-2 pi i k / 2M)
+template <int M>
+__device__ __forceinline__ float2 lsd_real_bin(const float2* __restrict__ Z, int k, float2 w) {
+    const float2 zk = Z[k & (M - 1)], zm = Z[(M - k) & (M - 1)];
+    const float2 e = make_float2(0.5f * (zk.x + zm.x), 0.5f * (zk.y - zm.y));          // (Z[k] + conj Z[M-k]) / 2
+    const float2 o = make_float2(0.5f * (zk.y + zm.y), 0.5f * (zm.x - zk.x));          // (Z[k] - conj Z[M-k]) / 2i
+    const float2 t = lsd_cmul(w, o);
+    return make_float2(e.x + t.x, e.y + t.y);
+}
+
+struct LsdFrame { long long hr_at, sr_at, len, first; float shift; int live; };     // `first`: sample of the row under window tap 0
+
+template <int N, bool SHIFT>
+__global__ __launch_bounds__(LSD_NT) void lsd_rows_kernel(const float* __restrict__ hr, long long hr_total,
+                                                          const float* __restrict__ sr, long long sr_total,
+                                                          const MetricRow* __restrict__ rows, int n_rows,
+                                                          const long long* __restrict__ frame_start, long long total_frames,
+                                                          const float* __restrict__ shift, const float* __restrict__ window,
+                                                          int hop, int center, long long n_tiles, float* __restrict__ out) {
+    constexpr int M = N / 2, FT = LSD_TILE / N, TPF = LSD_NT / FT, NBINS = N / 2 + 1;
+    static_assert(TPF >= 32 && M % LSD_NT == 0, "a frame's lanes fill whole half-waves, a load pass stays inside one signal of a frame");
+    __shared__ __attribute__((aligned(16))) float2 buf[LSD_TILE];          // [FT][hr, sr][M]
+    __shared__ __attribute__((aligned(16))) float2 root[N];
+    __shared__ double red[LSD_NT / 64];
+    __shared__ LsdFrame info[FT];
+    const int tid = threadIdx.x;
+    for (int t = tid; t < N; t += LSD_NT) {
+        double s, c;
+        sincospi(-2.0 * (double)t / (double)N, &s, &c);
+        root[t] = make_float2((float)c, (float)s);
+    }
+    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        // the row of every frame of the tile: the last u with frame_start[u] <= g (rows without frames share a start and lose)
+        if (tid < FT) {
+            const long long g = tile * FT + tid;
+            LsdFrame fi = {0, 0, 0, 0, 0.0f, 0};
+            if (g < total_frames) {
+                int lo = 0, hi = n_rows;                       // invariant: the answer is in [lo, hi)
+                while (hi - lo > 1) {
+                    const int mid = lo + ((hi - lo) >> 1);
+                    if (frame_start[mid] <= g) lo = mid; else hi = mid;
+                }
+                const MetricRow rw = rows[lo];
+                const long long f = g - frame_start[lo];
+                // (a table that does not agree with itself gives silent frames, never a read outside the row)
+                if (rw.len > 0 && rw.len <= INT_MAX && f >= 0 && f < frame_start[lo + 1] - frame_start[lo] && f <= INT_MAX &&
+                    rw.hr_pos > -kFar && rw.hr_pos < kFar && rw.sr_pos > -kFar && rw.sr_pos < kFar) {
+                    fi.hr_at = rw.hr_pos;
+                    fi.sr_at = rw.sr_pos;
+                    fi.len = rw.len;
+                    fi.first = f * hop - (center ? N / 2 : 0);
+                    fi.shift = SHIFT ? shift[lo] : 0.0f;
+                    fi.live = 1;
+                }
+            }
+            info[tid] = fi;
+        }
+        __syncthreads();
+        // z[m] = x_w[2m] + i x_w[2m+1] for hr, then for sr
+#pragma unroll 4
+        for (int i = tid; i < LSD_TILE; i += LSD_NT) {
+            const int fr = i / N, is_sr = (i / M) & 1, m = i % M;
+            const LsdFrame fi = info[fr];
+            const float* __restrict__ x = is_sr ? sr : hr;
+            const long long at = is_sr ? fi.sr_at : fi.hr_at, total = is_sr ? sr_total : hr_total;
+            float e[2];
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                long long t = fi.first + 2 * m + q;
+                if (center) {
+                    if (t < 0) t = -t;
+                    if (t >= fi.len) t = 2 * (fi.len - 1) - t;
+                }
+                float v = 0.0f;
+                if (fi.live && t >= 0 && t < fi.len) {
+                    const long long p = at + t;
+                    if (p >= 0 && p < total) v = (SHIFT && !is_sr) ? x[p] + fi.shift : x[p];
+                }
+                e[q] = v * window[2 * m + q];
+            }
+            buf[i] = make_float2(e[0], e[1]);
+        }
+        __syncthreads();
+        lsd_fft<M>(buf, root, tid);
+        // bins k = j, j + TPF, ... of frame fr on lane j of the frame's TPF lanes
+        const int fr = tid / TPF, j = tid % TPF;
+        const float2* Zh = buf + fr * N;
+        const float2* Zs = Zh + M;
+        double acc = 0.0;
+        for (int k = j; k < NBINS; k += TPF) {
+            const float2 w = root[k];
+            const float2 a = lsd_real_bin<M>(Zh, k, w), b = lsd_real_bin<M>(Zs, k, w);
+            const double pa = (double)a.x * a.x + (double)a.y * a.y, pb = (double)b.x * b.x + (double)b.y * b.y;
+            const double d = log10(pa + 1e-6) - log10(pb + 1e-6);
+            acc += d * d;
+        }
+#pragma unroll
+        for (int o = (TPF < 64 ? TPF : 64) / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        if (TPF > 64) {
+            if ((tid & 63) == 0) red[tid >> 6] = acc;
+            __syncthreads();
+            if (j == 0) {
+                acc = red[fr * (TPF / 64)];
+                for (int w = 1; w < TPF / 64; ++w) acc += red[fr * (TPF / 64) + w];
+            }
+        }
+        if (j == 0) {
+            const long long g = tile * FT + fr;
+            if (g < total_frames) out[g] = info[fr].live ? (float)sqrt(acc / NBINS) : 0.0f;
+        }
+        __syncthreads();                                    // buf, info and red are free for the next tile
+    }
+}
+
+inline bool lsd_size_ok(int n_fft) { return n_fft == 512 || n_fft == 1024 || n_fft == 2048; }
+
+}  // namespace
+
+extern "C" {
+
+// See include/mdctgan_hip.h.
+size_t mg_metrics_rows_packed_workspace(int n_rows, long long max_len) {
+    if (n_rows <= 0 || max_len <= 0) return 0;
+    return (size_t)n_rows * (size_t)((max_len + kChunk - 1) / kChunk) * 3 * sizeof(double);
+}
+
+int mg_metrics_rows_packed(const float* hr, long long hr_total, const float* lr, long long lr_total, const float* sr,
+                           long long sr_total, const mg_metric_row* rows, int n_rows, long long max_len, const float* hr_shift,
+                           double* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!hr || !lr || !sr || !rows || !out || !workspace || n_rows <= 0 || max_len <= 0) return MG_ERR_ARG;
+    if (hr_total <= 0 || lr_total <= 0 || sr_total <= 0) return MG_ERR_ARG;
+    const long long max_chunks = (max_len + kChunk - 1) / kChunk;
+    if (max_chunks > INT_MAX || workspace_bytes < mg_metrics_rows_packed_workspace(n_rows, max_len)) return MG_ERR_ARG;
+    const MetricRow* rt = reinterpret_cast<const MetricRow*>(rows);
+    double* partial = static_cast<double*>(workspace);
+    const dim3 grid = rows_grid(n_rows, max_len, kChunk);
+    hipStream_t st = (hipStream_t)stream;
+#define MG_MRP_LAUNCH(V, S)                                                                                                       \
+    hipLaunchKernelGGL((metrics_rows_packed_chunks_kernel<V, S>), grid, dim3(256), 0, st, hr, hr_total, lr, lr_total, sr, sr_total, \
+                       rt, n_rows, hr_shift, (int)max_chunks, partial)
+    if (al16(hr) && al16(lr) && al16(sr)) {
+        if (hr_shift) MG_MRP_LAUNCH(true, true); else MG_MRP_LAUNCH(true, false);
+    } else {
+        if (hr_shift) MG_MRP_LAUNCH(false, true); else MG_MRP_LAUNCH(false, false);
+    }
+#undef MG_MRP_LAUNCH
+    MG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(metrics_rows_packed_final_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, rt, hr_total,
+                       lr_total, sr_total, n_rows, (int)max_chunks, partial, out);
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+}
+
+int mg_lsd_rows(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows, int n_rows,
+                const long long* frame_start, long long total_frames, const float* hr_shift, const float* window, int n_fft,
+                int hop, int center, float* out, void* stream) {
+    if (!hr || !sr || !rows || !frame_start || !window || !out || n_rows <= 0 || total_frames <= 0) return MG_ERR_ARG;
+    if (hr_total <= 0 || sr_total <= 0 || hop <= 0 || !lsd_size_ok(n_fft)) return MG_ERR_ARG;
+    const MetricRow* rt = reinterpret_cast<const MetricRow*>(rows);
+    const long long ft = LSD_TILE / n_fft, n_tiles = (total_frames + ft - 1) / ft;
+    const unsigned blocks = (unsigned)(n_tiles < 3 * 256 * 4 ? n_tiles : 3 * 256 * 4);    // a few waves of three workgroups per CU
+    hipStream_t st = (hipStream_t)stream;
+#define MG_LSD_LAUNCH(NN, S)                                                                                                  \
+    hipLaunchKernelGGL((lsd_rows_kernel<NN, S>), dim3(blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rt, n_rows,   \
+                       frame_start, total_frames, hr_shift, window, hop, center != 0, n_tiles, out)
+#define MG_LSD_SIZE(NN) do { if (hr_shift) MG_LSD_LAUNCH(NN, true); else MG_LSD_LAUNCH(NN, false); } while (0)
+    if (n_fft == 512) MG_LSD_SIZE(512);
+    else if (n_fft == 1024) MG_LSD_SIZE(1024);
+    else MG_LSD_SIZE(2048);
+#undef MG_LSD_SIZE
+#undef MG_LSD_LAUNCH
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+}
+
+}  // extern "C"

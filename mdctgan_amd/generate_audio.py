@@ -261,9 +261,10 @@ def _views(out, plan: UtterancePlan):
     return [out[s:s + n].view(1, -1) for s, n in zip(plan.out_start, plan.out_length)]
 
 
-def _run_packed(model, packed, plan: UtterancePlan, pad_batches: bool = False):
+def _run_packed(model, packed, plan: UtterancePlan, pad_batches: bool = False, with_buffer: bool = False):
     """generate_many's batches over a packed input buffer and its plan: per batch one gather launch, model.inference and the
-    row-table decode -> list of stitched waveforms [1, total_u]."""
+    row-table decode -> list of stitched waveforms [1, total_u].  with_buffer: -> (list, packed output buffer of which the
+    waveforms are views at plan.out_start, or None without a stitched decoder)."""
     from .mdct import seg_row_table, segments_gather
     dev = packed.device
     gen_overlap = plan.gen_overlap
@@ -287,10 +288,11 @@ def _run_packed(model, packed, plan: UtterancePlan, pad_batches: bool = False):
     finally:
         model.train(was_training)
     if fused:
-        return _views(out, plan)
+        return (_views(out, plan), out) if with_buffer else _views(out, plan)
     audio = torch.cat(outs, dim=0)                      # [n_live, 1, 1, T]
     first = np.concatenate([[0], np.cumsum(plan.segments)])
-    return [ops.stitch_segments(audio[first[u]:first[u + 1]], audio.shape[-1], gen_overlap) for u in range(len(plan.lengths))]
+    waves = [ops.stitch_segments(audio[first[u]:first[u + 1]], audio.shape[-1], gen_overlap) for u in range(len(plan.lengths))]
+    return (waves, None) if with_buffer else waves
 
 
 def generate_many(model, waves, batch_size: int = 64, gen_overlap: int = 0, pad_batches: bool = False, segment_length=None):
@@ -317,16 +319,53 @@ def super_resolve_many(model, raws, rates, batch_size: int = 64, gen_overlap=Non
     gen_overlap come from model.opt.  noise / generator: see front_end_many.  -> list of stitched waveforms [1, total_u], views
     of one packed buffer, bit for bit generate_many(model, front_end_many(...)'s views)."""
     from .resample import front_end_many
+    dev = next(model.netG.parameters()).device
+    packed, _, plan = front_end_many(raws, rates, _front_end_kwargs(model, batch_size, gen_overlap), noise=noise,
+                                     generator=generator, device=dev)
+    return _run_packed(model, packed, plan.utterances)
+
+
+def _front_end_kwargs(model, batch_size, gen_overlap) -> dict:
     opt = model.opt
     L = int(opt.segment_length)
     ov = int(getattr(opt, "gen_overlap", 0) or 0) if gen_overlap is None else int(gen_overlap)
-    kw = dict(lr_sampling_rate=opt.lr_sampling_rate, hr_sampling_rate=opt.hr_sampling_rate,
-              is_lr_input=bool(getattr(opt, "is_lr_input", False)), add_noise=bool(getattr(opt, "add_noise", False)),
-              snr=float(getattr(opt, "snr", 55.0)), segment_length=L, gen_overlap=ov, batch_size=batch_size,
-              out_segment_length=_decoded_segment_length(model.preprocess, L))
+    return dict(lr_sampling_rate=opt.lr_sampling_rate, hr_sampling_rate=opt.hr_sampling_rate,
+                is_lr_input=bool(getattr(opt, "is_lr_input", False)), add_noise=bool(getattr(opt, "add_noise", False)),
+                snr=float(getattr(opt, "snr", 55.0)), segment_length=L, gen_overlap=ov, batch_size=batch_size,
+                out_segment_length=_decoded_segment_length(model.preprocess, L))
+
+
+def evaluate_many(model, raws, rates, batch_size: int = 64, gen_overlap=None, noise=None, generator=None, metric_path=None):
+    """generate_audio.py:22-88 for a whole test set of files at hr_sampling_rate: super_resolve_many, then every utterance scored
+    against its own ground truth by metrics.compute_matrics_many -- front end, generator batches and metrics over the same packed
+    buffers, the host never waiting.  The ground truth is read_audio's waveform, the packed raw buffer plus the per-utterance DC
+    shift (added inside the metric kernels, never materialised); the low-rate and the stitched waveform are cropped to its length
+    (`lr_audio[..., :audio_len]`, :58-59).  Every rates[u] must be opt.hr_sampling_rate (ValueError): the reference compares
+    raw_audio with the model's output sample by sample, which means something only then.
+    -> (waveforms, scores): super_resolve_many's list, and a float64 device tensor [U, 7] = (mse, snr_sr, snr_lr, 0, 0, 0, lsd) per
+    utterance.  metric_path: one `MSE,SNR_SR,LSD` line per utterance is appended (:86-88) -- the only read-back, after everything
+    is queued."""
+    from .metrics import compute_matrics_many
+    from .resample import front_end_many
+    opt = model.opt
+    rates = [int(r) for r in rates]
+    for u, r in enumerate(rates):
+        if r != int(opt.hr_sampling_rate):
+            raise ValueError("utterance %d: %d Hz is not hr_sampling_rate (%d Hz): it cannot be scored against its own file"
+                             % (u, r, int(opt.hr_sampling_rate)))
     dev = next(model.netG.parameters()).device
-    packed, _, plan = front_end_many(raws, rates, kw, noise=noise, generator=generator, device=dev)
-    return _run_packed(model, packed, plan.utterances)
+    packed, _, plan = front_end_many(raws, rates, _front_end_kwargs(model, batch_size, gen_overlap), noise=noise,
+                                     generator=generator, device=dev, keep_raw=True)
+    utt = plan.utterances
+    waves, out = _run_packed(model, packed, utt, with_buffer=True)
+    srs = (out, utt.out_start, utt.out_length) if out is not None else waves
+    scores = compute_matrics_many((plan.raw.buffer, plan.raw.starts, plan.raw.lengths), (packed, utt.in_start, utt.lengths), srs,
+                                  opt, hr_shift=plan.raw.shift)
+    if metric_path:
+        with open(metric_path, "a") as f:
+            for mse, snr_sr, _, _, _, _, lsd in scores.tolist():
+                f.write("%f,%f,%f\n" % (mse, snr_sr, lsd))
+    return waves, scores
 
 
 def make_graphed_generate_many(model, max_segments: int, max_samples: int, batch_size: int = 64, gen_overlap: int = 0,

@@ -7,7 +7,11 @@ power=2)`` as windowed reflect-padded frames times a dense DFT table on the f32 
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
+from types import SimpleNamespace
+from typing import List
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -71,6 +75,161 @@ def compute_matrics(hr_audio, lr_audio, sr_audio, opt):
                                  _lib.stream()), "mg_lsd_frames")
     lsd = per_frame.double().mean().item()
     return mse, snr_sr, snr_lr, 0, 0, 0, lsd
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Many utterances in shared launches
+# ---------------------------------------------------------------------------------------------------------------------
+LSD_ROWS_N_FFT = (512, 1024, 2048)         # the transform sizes of mg_lsd_rows (csrc/metrics_rows.hip)
+
+
+@dataclass
+class MetricsPlan:
+    """plan_metrics' result: `frames[u]` = mg_stft_num_frames(lengths[u], n_fft, hop, center), `frame_start` its prefix sums
+    (U + 1 entries: utterance u's per-frame values are [frame_start[u], frame_start[u + 1]) of the packed per-frame array)."""
+    lengths: List[int]
+    n_fft: int
+    hop: int
+    center: bool
+    frames: List[int]
+    frame_start: List[int]
+
+    @property
+    def total_frames(self) -> int:
+        return self.frame_start[-1]
+
+
+def plan_metrics(lengths, n_fft: int, hop: int, center: bool) -> MetricsPlan:
+    """How many STFT frames every utterance has and where they sit in the packed per-frame array (host only: no device call).
+    n_fft / hop: the transform's, i.e. 2 * opt.n_fft / 2 * opt.hop_length.  ValueError (naming the utterance) where mg_stft_frames
+    refuses: a length without a frame, or a centred transform whose reflection (n_fft / 2 samples) does not fit the utterance."""
+    n_fft, hop, center = int(n_fft), int(hop), bool(center)
+    lengths = [int(n) for n in lengths]
+    if not lengths:
+        raise ValueError("plan_metrics needs at least one utterance")
+    if n_fft <= 0 or hop <= 0:
+        raise ValueError("n_fft and hop must be positive")
+    frames, start = [], [0]
+    for u, n in enumerate(lengths):
+        padded = n + 2 * (n_fft // 2) if center else n
+        if n <= 0 or padded < n_fft:
+            raise ValueError("utterance %d: %d samples are too short for n_fft=%d" % (u, n, n_fft))
+        if center and n_fft // 2 >= n:
+            raise ValueError("utterance %d: %d samples cannot be reflect-padded by n_fft / 2 = %d" % (u, n, n_fft // 2))
+        frames.append(1 + (padded - n_fft) // hop)
+        start.append(start[-1] + frames[-1])
+    return MetricsPlan(lengths, n_fft, hop, center, frames, start)
+
+
+def _packed_operand(x, what: str):
+    """A list of waveforms ([T_u] or [1, T_u]) -> (None, waves, lengths available); a packed `(buffer, starts)` or `(buffer,
+    starts, lengths)` tuple -> (buffer, starts, lengths available).  Without lengths, an utterance of a packed buffer is taken to
+    reach the next start (the end of the buffer for the last one)."""
+    if isinstance(x, tuple) and len(x) in (2, 3) and torch.is_tensor(x[0]) and not torch.is_tensor(x[1]):
+        buf, starts = x[0], [int(s) for s in x[1]]
+        if buf.dim() != 1 or buf.dtype != torch.float32 or not buf.is_contiguous() or not buf.is_cuda:
+            raise ValueError("%s: a packed operand is a contiguous float32 [total] device buffer" % what)
+        if len(x) == 3:
+            avail = [int(n) for n in x[2]]
+            if len(avail) != len(starts):
+                raise ValueError("%s: one length per start" % what)
+        else:
+            avail = [b - a for a, b in zip(starts, starts[1:] + [buf.numel()])]
+        if any(s < 0 or n < 0 or s + n > buf.numel() for s, n in zip(starts, avail)):
+            raise ValueError("%s: an utterance lies outside its packed buffer" % what)
+        return buf, starts, avail
+    waves = list(x)
+    return None, waves, [int(w.numel()) for w in waves]
+
+
+def compute_matrics_many(hrs, lrs, srs, opt, hr_shift=None):
+    """``compute_matrics`` for every utterance of a test set on its own (generate_audio.py:57-67), in shared launches.
+    hrs / lrs / srs: lists of waveforms ([T_u] or [1, T_u], host or device; packed here with _pack_waves' layout), or packed
+    operands that are read where they lie -- ``(buffer, starts, lengths)`` (hrs), ``(buffer, starts)`` or ``(buffer, starts,
+    lengths)`` (lrs, srs) with a contiguous float32 device buffer and host lists, as front_end_many and generate_many leave them.
+    Utterance u is scored over len_u = len(hr_u) samples; lr_u and sr_u are cropped to that and must not be shorter (ValueError).
+    hr_shift: float32 [U] on the device; every ground-truth sample enters as hr + hr_shift[u] (one float32 add) -- read_audio's
+    un-materialised DC shift.  -> float64 device tensor [U, 7], row u = (mse, snr_sr, snr_lr, 0, 0, 0, lsd) of utterance u alone,
+    with the same bits whatever else shares the call.  Launches: one table copy (plus one packing copy per operand given as a
+    list), mg_metrics_rows_packed, mg_lsd_rows, mg_rows_moments and a few element-wise launches over [U], whatever U is; nothing
+    is read back."""
+    from .generate_audio import _pack_waves
+    from .resample import _aligned_starts, rows_moments
+    n_fft, hop, win = 2 * int(opt.n_fft), 2 * int(opt.hop_length), 2 * int(opt.win_length)
+    if win != n_fft:
+        raise NotImplementedError("win_length != n_fft")
+    if n_fft not in LSD_ROWS_N_FFT:
+        raise NotImplementedError("mg_lsd_rows serves n_fft in %s (got %d)" % (LSD_ROWS_N_FFT, n_fft))
+    ops_ = [_packed_operand(x, name) for x, name in ((hrs, "hrs"), (lrs, "lrs"), (srs, "srs"))]
+    if isinstance(hrs, tuple) and ops_[0][0] is not None and len(hrs) != 3:
+        raise ValueError("hrs: a packed ground truth names its lengths: (buffer, starts, lengths)")
+    lengths = ops_[0][2]
+    U = len(lengths)
+    if U == 0:
+        raise ValueError("no waveforms")
+    for (_, _, avail), name in zip(ops_[1:], ("lr", "sr")):
+        if len(avail) != U:
+            raise ValueError("%d hr waveforms but %d %s waveforms" % (U, len(avail), name))
+        for u in range(U):
+            if avail[u] < lengths[u]:
+                raise ValueError("utterance %d: %s has %d samples, fewer than hr's %d" % (u, name, avail[u], lengths[u]))
+    plan = plan_metrics(lengths, n_fft, hop, bool(opt.center))
+
+    device = next((t.device for buf, ws, _ in ops_ for t in ([buf] if buf is not None else ws) if t.is_cuda), None)
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    bufs, starts = [], []
+    for buf, ws, avail in ops_:
+        if buf is None:
+            st, total = _aligned_starts(avail, 64)
+            buf = _pack_waves(ws, SimpleNamespace(in_total=total, in_start=st, lengths=avail), device)
+            ws = st
+        bufs.append(buf)
+        starts.append(ws)
+    hr, lr, sr = bufs
+    if hr_shift is not None and (not hr_shift.is_cuda or hr_shift.dtype != torch.float32 or hr_shift.numel() != U
+                                 or not hr_shift.is_contiguous()):
+        raise ValueError("hr_shift is a contiguous float32 [%d] device tensor" % U)
+
+    # every table in one host array and one copy: the metric rows, frame_start, and the windows of the per-frame array
+    fs = np.asarray(plan.frame_start, dtype=np.int64)
+    rows = np.stack([np.asarray(starts[0], dtype=np.int64), np.asarray(starts[1], dtype=np.int64),
+                     np.asarray(starts[2], dtype=np.int64), np.asarray(lengths, dtype=np.int64)], axis=1)
+    frame_rows = np.stack([fs[:-1], fs[:-1], fs[1:]], axis=1)
+    tables = torch.from_numpy(np.concatenate([rows.reshape(-1), fs, frame_rows.reshape(-1)])).to(device, non_blocking=True)
+    row_t, fs_t, frame_t = tables[:4 * U].view(U, 4), tables[4 * U:5 * U + 1], tables[5 * U + 1:].view(U, 3)
+
+    lib = _lib.load()
+    max_len = max(lengths)
+    nbytes = lib.mg_metrics_rows_packed_workspace(U, max_len)
+    ws = _lib.workspace(nbytes, device)
+    sums = torch.empty(U, 3, dtype=torch.float64, device=device)
+    _lib.check(lib.mg_metrics_rows_packed(_lib.ptr(hr), hr.numel(), _lib.ptr(lr), lr.numel(), _lib.ptr(sr), sr.numel(),
+                                          _lib.ptr(row_t), U, max_len, _lib.ptr(hr_shift), _lib.ptr(sums), _lib.ptr(ws), nbytes,
+                                          _lib.stream()), "mg_metrics_rows_packed")
+    window = _window(win, device)
+    per_frame = torch.empty(plan.total_frames, dtype=torch.float32, device=device)
+    _lib.check(lib.mg_lsd_rows(_lib.ptr(hr), hr.numel(), _lib.ptr(sr), sr.numel(), _lib.ptr(row_t), U, _lib.ptr(fs_t),
+                               plan.total_frames, _lib.ptr(hr_shift), _lib.ptr(window), n_fft, hop, int(bool(opt.center)),
+                               _lib.ptr(per_frame), _lib.stream()), "mg_lsd_rows")
+    lsd_sum = rows_moments(per_frame, frame_t, max(plan.frames))[:, 0]
+
+    out = torch.zeros(U, 7, dtype=torch.float64, device=device)
+    out[:, 0] = sums[:, 1] / row_t[:, 3].double()
+    out[:, 1] = 10 * torch.log10(sums[:, 0] / sums[:, 1])
+    out[:, 2] = 10 * torch.log10(sums[:, 0] / sums[:, 2])
+    out[:, 6] = lsd_sum / (frame_t[:, 2] - frame_t[:, 1]).double()
+    return out
+
+
+_windows = {}
+
+
+def _window(win: int, device):
+    key = (win, str(device))
+    if key not in _windows:
+        _windows[key] = kbdwin(win).to(device=device, dtype=torch.float32).contiguous()
+    return _windows[key]
 
 
 def eval_model(model, eval_batches, opt, eval_path=None):

@@ -225,7 +225,10 @@ class FrontEndPlan:
     the packed buffer before step s (s = 0: the raw waveforms) and after the last one (s = len(steps): the low-rate input at
     hr_rate).  `steps[s]`: the ResampleGroups of step s, one per distinct rate pair.  `order`: the utterances in the order of the
     first step's groups -- the row order of the DC-mean table, so that every group's shifts are contiguous.  `utterances`:
-    generate_audio.plan_utterances over the final lengths; its in_start / in_total ARE starts[-1] / totals[-1]."""
+    generate_audio.plan_utterances over the final lengths; its in_start / in_total ARE starts[-1] / totals[-1].  `raw`: None, or
+    under front_end_many(keep_raw=True) a namespace of the packed raw buffer (`buffer`, float32 [totals[0]]; utterance u at
+    starts[0][u], lengths[0][u] samples) and the DC shift per utterance (`shift`, float32 [U] on the device, in UTTERANCE order):
+    raw + shift is read_audio's waveform, the ground truth of metrics.compute_matrics_many."""
     rates: List[int]
     lengths: List[List[int]]
     starts: List[List[int]]
@@ -233,6 +236,7 @@ class FrontEndPlan:
     steps: List[List[ResampleGroup]]
     order: List[int]
     utterances: object
+    raw: object = None
 
     @property
     def final_lengths(self):
@@ -324,7 +328,7 @@ def _front_end_options(opt) -> dict:
     return o
 
 
-def front_end_many(raws, rates, opt_or_kwargs, noise=None, generator=None, device=None):
+def front_end_many(raws, rates, opt_or_kwargs, noise=None, generator=None, device=None, keep_raw=False):
     """AudioTestDataset.read_audio + post_processing (data/audio_dataset.py:141-186) for a list of raw waveforms ([T_u] or
     [1, T_u], on the host or the device) at sampling rates `rates` -> (packed, views, plan): the packed low-rate buffer at
     hr_sampling_rate (float32 [plan.totals[-1]], generate_audio._pack_waves' layout, zeros in the gaps), one [1, T'_u] view of it
@@ -334,7 +338,9 @@ def front_end_many(raws, rates, opt_or_kwargs, noise=None, generator=None, devic
     otherwise torch.randn(..., generator=generator) on the device.
     Launches: one packing copy, one table copy, mg_rows_moments, a handful of element-wise launches over [U] for the shift, one
     mg_resample_rows per distinct rate pair and step, and under add_noise two more mg_rows_moments and mg_add_noise_rows --
-    whatever the number of utterances.  No host read-back."""
+    whatever the number of utterances.  No host read-back.
+    keep_raw: plan.raw keeps the packed raw buffer and the shift in utterance order (see FrontEndPlan; one more element-wise launch
+    when the rates differ); nothing else changes."""
     from .generate_audio import _pack_waves
     o = _front_end_options(opt_or_kwargs)
     raws = list(raws)
@@ -363,12 +369,18 @@ def front_end_many(raws, rates, opt_or_kwargs, noise=None, generator=None, devic
     U = len(raws)
     parts = [windows(0, plan.order).reshape(-1), windows(-1, range(U)).reshape(-1)]
     parts += [g.rows.reshape(-1) for step in plan.steps for g in step]
+    reorder = keep_raw and plan.order != list(range(U))
+    if reorder:                                                 # (where utterance u sits in plan.order)
+        parts.append(np.argsort(np.asarray(plan.order, dtype=np.int64), kind="stable"))
     tables = torch.from_numpy(np.concatenate(parts)).to(device, non_blocking=True)
     raw_win, lr_win = tables[:3 * U].view(U, 3), tables[3 * U:6 * U].view(U, 3)
 
     buf = _pack_waves(raws, layout(0), device)
     mom = rows_moments(buf, raw_win, max(plan.lengths[0]))
     shift = (1e-4 - mom[:, 0] / (raw_win[:, 2] - raw_win[:, 1]).double()).float()     # raw += 1e-4 - mean(raw), per utterance
+    if keep_raw:
+        plan.raw = SimpleNamespace(buffer=buf, shift=shift[tables[-U:]].contiguous() if reorder else shift,
+                                   starts=plan.starts[0], lengths=plan.lengths[0])
     at = 6 * U
     for s, step in enumerate(plan.steps):
         out = torch.zeros(plan.totals[s + 1], dtype=torch.float32, device=device)
