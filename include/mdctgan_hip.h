@@ -236,6 +236,39 @@ int mg_rows_moments(const float* x, long long total, const mg_seg_row* rows, int
 int mg_add_noise_rows(float* lr, const float* noise, long long total, const mg_seg_row* rows, int n_rows, long long max_len,
                       const double* lr_moments, const double* noise_moments, double snr, long long segment_length, void* stream);
 
+/* The TRAINING side of that data path (data/audio_dataset.py:34-82, AudioDataset.readaudio + __getitem__) for a whole batch in shared
+ * launches (csrc/train_rows.hip): the corpus sits packed in one float32 device buffer, a device row table (one mg_train_row per batch
+ * row) names the window every row loads, and (LR_audio, HR_audio) come out as two dense [out_rows, seg_len] tensors.
+ *   mg_resample_bank    one polyphase filter bank as mg_resample takes it (kern [new_, 2*width + orig], gcd-reduced rates);
+ *                       kern == NULL: equal rates, the step is a copy (orig / new_ / width are not read).
+ *   mg_train_row        the row loads corpus[in_pos, in_pos + in_len) -- torchaudio.load(frame_offset, num_frames) -- and writes row
+ *                       out_row of lr and hr; in_len == 0 marks a dead row, which writes nothing.  full_pos / full_len are read only
+ *                       with lr_full.  The window is the WHOLE signal in both legs: taps outside it contribute nothing, whatever
+ *                       the corpus holds next to it (another file's samples, or the same file's).
+ *   mg_train_pair_rows  hr[out_row][t] = resample(window, to_hr)[t] for t < min(seg_len, ceil(hr L / fs)), zero after;
+ *                       lr[out_row][t] = resample(resample(window, to_lr), lr_to_hr)[t] for t < min(seg_len, ceil(hr M / lr)),
+ *                       M = ceil(lr L / fs), zero after (seg_pad_audio, :102-110; the two lengths differ in general).  Two launches,
+ *                       whatever n_rows is: the hr leg, and the lr leg as ONE kernel -- a workgroup computes the lr-rate samples
+ *                       its tile of outputs touches into LDS (each rounded to float32 once, as the tensor between the two
+ *                       aF.resample calls; none beyond M) and runs the second chain from there.  Every chain is mg_resample's fmaf
+ *                       chain in ascending tap order: a row has the bits of mg_resample (twice) on its window alone, whatever else
+ *                       shares the launch.  Banks of more than 2048 floats are read from global memory; LDS is static (32 KB), so
+ *                       nothing is configured before a graph capture.  No atomics, no host synchronisation.
+ *                       lr_full != NULL (--add_noise, whose power and standard deviation run over the signal BEFORE the crop,
+ *                       :72-78): the lr leg writes the whole low-rate signal of row u to lr_full[full_pos, full_pos + full_len)
+ *                       (full_len = ceil(hr M / lr), the host builds the table so; max_full_len, the longest, sizes the grid) and
+ *                       leaves lr alone (it may be NULL); mg_rows_moments, mg_add_noise_rows and mg_segments_gather finish the batch.
+ *                       Windows that stick out of the corpus are cut to it; rows whose out_row or lr_full window lies outside
+ *                       their buffers, or longer than 2^30 samples, are dropped.  MG_ERR_ARG: a null pointer, n_rows, seg_len,
+ *                       corpus_total or out_rows <= 0, a malformed bank.  MG_ERR_UNSUPPORTED: an lr_to_hr bank whose taps of one
+ *                       output sample do not fit the 4096 intermediates a tile holds. */
+typedef struct { const float* kern; int orig, new_, width; } mg_resample_bank;
+typedef struct { long long in_pos, in_len, out_row, full_pos, full_len; } mg_train_row;
+int mg_train_pair_rows(const float* corpus, long long corpus_total, const mg_train_row* rows, int n_rows, int seg_len,
+                       const mg_resample_bank* to_hr, const mg_resample_bank* to_lr, const mg_resample_bank* lr_to_hr, float* lr,
+                       float* hr, long long out_rows, float* lr_full, long long lr_full_total, long long max_full_len,
+                       void* stream);
+
 /* F2  util/util.py:132-177 compute_matrics on the device (train.py:104-134 eval_model, generate_audio.py:60).
  *   mg_metrics_rows   out[b] = {sum hr^2, sum (sr - hr)^2, sum (lr - hr)^2} (double) for clips [B, T]  -> MSE / SNR
  *   mg_stft_frames    reflect-padded (center != 0), windowed frames [B * F, n_fft], F = mg_stft_num_frames(): the A

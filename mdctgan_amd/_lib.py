@@ -54,6 +54,14 @@ class WinoAdam(C.Structure):
 
 _WA = C.POINTER(WinoAdam)
 
+
+class ResampleBank(C.Structure):
+    """mg_resample_bank: one polyphase filter bank (kern NULL: equal rates, a copy)."""
+    _fields_ = [("kern", C.c_void_p), ("orig", C.c_int), ("new_", C.c_int), ("width", C.c_int)]
+
+
+_RB = C.POINTER(ResampleBank)
+
 # name -> (restype, argtypes); must list every symbol include/mdctgan_hip.h declares
 SIGNATURES = {
     "mg_abi_version": (_i, []),
@@ -110,6 +118,7 @@ SIGNATURES = {
     "mg_rows_moments_workspace": (_sz, [_i, _ll]),
     "mg_rows_moments": (_i, [_p, _ll, _p, _i, _ll, _p, _p, _sz, _p]),
     "mg_add_noise_rows": (_i, [_p, _p, _ll, _p, _i, _ll, _p, _p, C.c_double, _ll, _p]),
+    "mg_train_pair_rows": (_i, [_p, _ll, _p, _i, _i, _RB, _RB, _RB, _p, _p, _ll, _p, _ll, _ll, _p]),
     "mg_metrics_rows":(_i, [_p, _p, _p, _i, _i, _p, _p]),
     "mg_stft_num_frames": (_i, [_i, _i, _i, _i]),
     "mg_stft_frames": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p]),

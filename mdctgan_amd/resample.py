@@ -79,7 +79,8 @@ def make_training_pair(waveform: torch.Tensor, orig_sample_rate: int, hr_samplin
                        segment_length: int, add_noise: bool = False, snr: float = 55.0, noise=None, generator=None):
     """AudioDataset.__getitem__ (data/audio_dataset.py:66-82): HR = resample to hr_rate; LR = resample to lr_rate and back up to
     hr_rate, plus the noise of :72-78 under add_noise (on the full resampled waveform, before the crop; see add_noise); both
-    cropped / padded to segment_length.  [B, L] -> (lr, hr).  The random file offset of readaudio (:43-48) is the loader's."""
+    cropped / padded to segment_length.  [B, L] -> (lr, hr).  The random file offset of readaudio (:43-48) and whole batches cut
+    from a corpus in HBM in shared launches: train_data.draw_windows / training_batch_many."""
     hr = resample(waveform, orig_sample_rate, hr_sampling_rate)
     lr = resample(resample(waveform, orig_sample_rate, lr_sampling_rate), lr_sampling_rate, hr_sampling_rate)
     if add_noise:
