@@ -33,15 +33,9 @@
 #include <limits.h>
 #include <math.h>
 
-#include "common.h"
-#include "mdctgan_hip.h"
+#include "rows.h"
 
 namespace {
-
-struct MetricRow { long long hr_pos, lr_pos, sr_pos, len; };
-
-constexpr int kChunk = MG_MOMENTS_CHUNK;
-constexpr long long kFar = 1LL << 62;            // positions beyond this are a broken table: the row is dead before any sum overflows
 
 // samples [lo, hi) of a row of `len` samples at `pos` exist in a buffer of `total` samples
 __device__ __forceinline__ void cut_to(long long pos, long long total, long long& lo, long long& hi) {
@@ -56,20 +50,19 @@ template <bool VEC, bool SHIFT>
 __global__ __launch_bounds__(256) void metrics_rows_packed_chunks_kernel(const float* __restrict__ hr, long long hr_total,
                                                                          const float* __restrict__ lr, long long lr_total,
                                                                          const float* __restrict__ sr, long long sr_total,
-                                                                         const MetricRow* __restrict__ rows, int n_rows,
+                                                                         const mg_metric_row* __restrict__ rows, int n_rows,
                                                                          const float* __restrict__ shift, int max_chunks,
                                                                          double* __restrict__ partial) {
     __shared__ double red[4][3];
     for (int r = blockIdx.y; r < n_rows; r += gridDim.y) {
-        const MetricRow rw = rows[r];
+        const mg_metric_row rw = rows[r];
         if (rw.len <= 0) continue;
         long long lo = 0, hi = rw.len;
         cut_to(rw.hr_pos, hr_total, lo, hi);
         cut_to(rw.lr_pos, lr_total, lo, hi);
         cut_to(rw.sr_pos, sr_total, lo, hi);
         if (hi <= lo) continue;
-        const long long all = (rw.len + kChunk - 1) / kChunk;
-        const int n_chunks = (int)(all < max_chunks ? all : max_chunks);
+        const int n_chunks = row_chunks(rw.len, max_chunks);
         const float s = SHIFT ? shift[r] : 0.0f;
         for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
             const long long t0 = (long long)c * kChunk;
@@ -80,7 +73,7 @@ __global__ __launch_bounds__(256) void metrics_rows_packed_chunks_kernel(const f
             const float* l = lr + (rw.lr_pos + t0);
             const float* q = sr + (rw.sr_pos + t0);
             const bool quads = VEC && (((rw.hr_pos + t0) | (rw.lr_pos + t0) | (rw.sr_pos + t0)) & 3) == 0;
-            double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+            double acc[3] = {0.0, 0.0, 0.0};                              // sum hr^2, sum (sr - hr)^2, sum (lr - hr)^2
             for (int i = 4 * threadIdx.x; i < b; i += 4 * 256) {
                 float eh[4], el[4], es[4];
                 bool on[4];
@@ -106,58 +99,29 @@ __global__ __launch_bounds__(256) void metrics_rows_packed_chunks_kernel(const f
                     // (a missing sample adds 0 to all three sums: its shift stays out as well)
                     const double hv = on[k] ? (double)(SHIFT ? eh[k] + s : eh[k]) : 0.0;
                     const double ds = (double)es[k] - hv, dl = (double)el[k] - hv;
-                    a0 += hv * hv;
-                    a1 += ds * ds;
-                    a2 += dl * dl;
+                    acc[0] += hv * hv;
+                    acc[1] += ds * ds;
+                    acc[2] += dl * dl;
                 }
             }
-            a0 = wave_sum_d(a0); a1 = wave_sum_d(a1); a2 = wave_sum_d(a2);
-            if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = a0; red[threadIdx.x >> 6][1] = a1; red[threadIdx.x >> 6][2] = a2; }
-            __syncthreads();
-            if (threadIdx.x < 3) {
-                const int w = threadIdx.x;
-                partial[((size_t)r * max_chunks + c) * 3 + w] = ((red[0][w] + red[1][w]) + red[2][w]) + red[3][w];
-            }
-            __syncthreads();
+            block_sum_store<3>(acc, red, partial + ((size_t)r * max_chunks + c) * 3);
         }
     }
 }
 
-__global__ __launch_bounds__(256) void metrics_rows_packed_final_kernel(const MetricRow* __restrict__ rows, long long hr_total,
+__global__ __launch_bounds__(256) void metrics_rows_packed_final_kernel(const mg_metric_row* __restrict__ rows, long long hr_total,
                                                                         long long lr_total, long long sr_total, int n_rows,
                                                                         int max_chunks, const double* __restrict__ partial,
                                                                         double* __restrict__ out) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rows) return;
-    const MetricRow rw = rows[r];
+    const mg_metric_row rw = rows[r];
     long long lo = 0, hi = rw.len > 0 ? rw.len : 0;
     cut_to(rw.hr_pos, hr_total, lo, hi);
     cut_to(rw.lr_pos, lr_total, lo, hi);
     cut_to(rw.sr_pos, sr_total, lo, hi);
-    const long long all = hi > lo ? (rw.len + kChunk - 1) / kChunk : 0;        // (the chunks the first kernel wrote)
-    const int n_chunks = (int)(all < max_chunks ? all : max_chunks);
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int c = 0; c < n_chunks; ++c) {
-        const double* p = partial + ((size_t)r * max_chunks + c) * 3;
-        s0 += p[0];
-        s1 += p[1];
-        s2 += p[2];
-    }
-    out[3 * (size_t)r] = s0;
-    out[3 * (size_t)r + 1] = s1;
-    out[3 * (size_t)r + 2] = s2;
-}
-
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// as rows_grid of resample_rows.hip: enough x blocks per row to fill the chip, few enough that thousands of rows do not launch
-// mostly empty ones
-inline dim3 rows_grid(int n_rows, long long max_len, int per_block) {
-    const unsigned gy = (unsigned)(n_rows < 65535 ? n_rows : 65535);
-    long long bx = (max_len + per_block - 1) / per_block;
-    const long long cap = 8192 / gy > 8 ? 8192 / gy : 8;
-    bx = bx < cap ? bx : cap;
-    return dim3((unsigned)(bx < 1 ? 1 : (bx > 1024 ? 1024 : bx)), gy);
+    const int n_chunks = row_chunks(hi > lo ? rw.len : 0, max_chunks);         // (the chunks the first kernel wrote)
+    sum_chunks<3>(partial + (size_t)r * max_chunks * 3, n_chunks, out + 3 * (size_t)r);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -267,7 +231,7 @@ struct LsdFrame { long long hr_at, sr_at, len, first; float shift; int live; }; 
 template <int N, bool SHIFT>
 __global__ __launch_bounds__(LSD_NT) void lsd_rows_kernel(const float* __restrict__ hr, long long hr_total,
                                                           const float* __restrict__ sr, long long sr_total,
-                                                          const MetricRow* __restrict__ rows, int n_rows,
+                                                          const mg_metric_row* __restrict__ rows, int n_rows,
                                                           const long long* __restrict__ frame_start, long long total_frames,
                                                           const float* __restrict__ shift, const float* __restrict__ window,
                                                           int hop, int center, long long n_tiles, float* __restrict__ out) {
@@ -294,7 +258,7 @@ __global__ __launch_bounds__(LSD_NT) void lsd_rows_kernel(const float* __restric
                     const int mid = lo + ((hi - lo) >> 1);
                     if (frame_start[mid] <= g) lo = mid; else hi = mid;
                 }
-                const MetricRow rw = rows[lo];
+                const mg_metric_row rw = rows[lo];
                 const long long f = g - frame_start[lo];
                 // (a table that does not agree with itself gives silent frames, never a read outside the row)
                 if (rw.len > 0 && rw.len <= INT_MAX && f >= 0 && f < frame_start[lo + 1] - frame_start[lo] && f <= INT_MAX &&
@@ -385,13 +349,12 @@ int mg_metrics_rows_packed(const float* hr, long long hr_total, const float* lr,
     if (hr_total <= 0 || lr_total <= 0 || sr_total <= 0) return MG_ERR_ARG;
     const long long max_chunks = (max_len + kChunk - 1) / kChunk;
     if (max_chunks > INT_MAX || workspace_bytes < mg_metrics_rows_packed_workspace(n_rows, max_len)) return MG_ERR_ARG;
-    const MetricRow* rt = reinterpret_cast<const MetricRow*>(rows);
     double* partial = static_cast<double*>(workspace);
     const dim3 grid = rows_grid(n_rows, max_len, kChunk);
     hipStream_t st = (hipStream_t)stream;
 #define MG_MRP_LAUNCH(V, S)                                                                                                       \
     hipLaunchKernelGGL((metrics_rows_packed_chunks_kernel<V, S>), grid, dim3(256), 0, st, hr, hr_total, lr, lr_total, sr, sr_total, \
-                       rt, n_rows, hr_shift, (int)max_chunks, partial)
+                       rows, n_rows, hr_shift, (int)max_chunks, partial)
     if (al16(hr) && al16(lr) && al16(sr)) {
         if (hr_shift) MG_MRP_LAUNCH(true, true); else MG_MRP_LAUNCH(true, false);
     } else {
@@ -399,7 +362,7 @@ int mg_metrics_rows_packed(const float* hr, long long hr_total, const float* lr,
     }
 #undef MG_MRP_LAUNCH
     MG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(metrics_rows_packed_final_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, rt, hr_total,
+    hipLaunchKernelGGL(metrics_rows_packed_final_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, rows, hr_total,
                        lr_total, sr_total, n_rows, (int)max_chunks, partial, out);
     MG_CHECK_LAUNCH();
     return MG_OK;
@@ -410,12 +373,11 @@ int mg_lsd_rows(const float* hr, long long hr_total, const float* sr, long long 
                 int hop, int center, float* out, void* stream) {
     if (!hr || !sr || !rows || !frame_start || !window || !out || n_rows <= 0 || total_frames <= 0) return MG_ERR_ARG;
     if (hr_total <= 0 || sr_total <= 0 || hop <= 0 || !lsd_size_ok(n_fft)) return MG_ERR_ARG;
-    const MetricRow* rt = reinterpret_cast<const MetricRow*>(rows);
     const long long ft = LSD_TILE / n_fft, n_tiles = (total_frames + ft - 1) / ft;
     const unsigned blocks = (unsigned)(n_tiles < 3 * 256 * 4 ? n_tiles : 3 * 256 * 4);    // a few waves of three workgroups per CU
     hipStream_t st = (hipStream_t)stream;
 #define MG_LSD_LAUNCH(NN, S)                                                                                                  \
-    hipLaunchKernelGGL((lsd_rows_kernel<NN, S>), dim3(blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rt, n_rows,   \
+    hipLaunchKernelGGL((lsd_rows_kernel<NN, S>), dim3(blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rows, n_rows, \
                        frame_start, total_frames, hr_shift, window, hop, center != 0, n_tiles, out)
 #define MG_LSD_SIZE(NN) do { if (hr_shift) MG_LSD_LAUNCH(NN, true); else MG_LSD_LAUNCH(NN, false); } while (0)
     if (n_fft == 512) MG_LSD_SIZE(512);

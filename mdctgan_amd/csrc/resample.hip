@@ -5,8 +5,7 @@
 //   k in [0, 2 * width + orig), p in [0, new), cropped to out_len = ceil(new * L / orig).
 // HBM-bound: one thread per output sample, the (<= few KB) filter bank in LDS, input reads coalesced along n for the
 // down-sampling case and broadcast within a phase group for the up-sampling case.
-#include "common.h"
-#include "mdctgan_hip.h"
+#include "rows.h"
 
 namespace {
 
@@ -26,12 +25,9 @@ __global__ __launch_bounds__(256) void resample_kernel(const float* __restrict__
     for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < out_len; o += gridDim.x * blockDim.x) {
         const int n = o / new_, p = o - n * new_;
         const int t0 = n * orig - width;           // sample index of tap 0
-        const float* kp = kl + p * K;
-        float acc = 0.0f;
-        const int k_lo = t0 < 0 ? -t0 : 0;
-        const int k_hi = (t0 + K > L) ? L - t0 : K;
-        for (int k = k_lo; k < k_hi; ++k) acc = fmaf(xb[t0 + k], kp[k], acc);
-        out[(size_t)b * out_len + o] = acc;
+        int k_lo, k_hi;
+        tap_range(0, L, t0, K, k_lo, k_hi);
+        out[(size_t)b * out_len + o] = fir_chain<false>(xb + t0, kl + p * K, k_lo, k_hi, 0.0f);
     }
 }
 

@@ -12,19 +12,13 @@
 #include <limits.h>
 #include <math.h>
 
-#include "common.h"
-#include "mdctgan_hip.h"
+#include "rows.h"
 
 namespace {
 
-struct ResRow { long long in_pos, in_len, out_pos, out_len; };
-
-constexpr int kChunk = MG_MOMENTS_CHUNK;
-constexpr long long kFar = 1LL << 62;            // positions beyond this are a broken table: the row is dropped before any sum overflows
-
 template <bool BANK_IN_LDS, bool SHIFT>
 __global__ __launch_bounds__(256) void resample_rows_kernel(const float* __restrict__ x, long long x_total,
-                                                            const ResRow* __restrict__ rows, int n_rows,
+                                                            const mg_resample_row* __restrict__ rows, int n_rows,
                                                             const float* __restrict__ shift, const float* __restrict__ kern,
                                                             int orig, int new_, int width, float* __restrict__ out,
                                                             long long out_total) {
@@ -36,7 +30,7 @@ __global__ __launch_bounds__(256) void resample_rows_kernel(const float* __restr
     }
     const float* kl = BANK_IN_LDS ? kl_s : kern;
     for (int r = blockIdx.y; r < n_rows; r += gridDim.y) {
-        const ResRow rw = rows[r];
+        const mg_resample_row rw = rows[r];
         if (rw.in_len <= 0 || rw.out_len <= 0 || rw.in_len > INT_MAX || rw.out_len > INT_MAX) continue;
         if (rw.in_pos <= -kFar || rw.in_pos >= x_total || rw.out_pos <= -kFar || rw.out_pos >= out_total) continue;
         // samples [j_lo, j_hi) of the row exist in x, samples [o_lo, o_hi) of its output in out (all of them for a sound table)
@@ -48,13 +42,9 @@ __global__ __launch_bounds__(256) void resample_rows_kernel(const float* __restr
         for (long long o = o_lo + blockIdx.x * blockDim.x + threadIdx.x; o < o_hi; o += (long long)gridDim.x * blockDim.x) {
             const int n = (int)o / new_, p = (int)o - n * new_;
             const long long t0 = (long long)n * orig - width;          // sample index of tap 0
-            const float* kp = kl + p * K;
-            float acc = 0.0f;
-            const int k_lo = (int)(j_lo - t0 > 0 ? (j_lo - t0 < K ? j_lo - t0 : K) : 0);
-            const int k_hi = (int)(j_hi - t0 < K ? (j_hi - t0 > 0 ? j_hi - t0 : 0) : K);
-            const float* xt = x + (rw.in_pos + t0);                     // (only [k_lo, k_hi) of it is read)
-            for (int k = k_lo; k < k_hi; ++k) acc = fmaf(SHIFT ? xt[k] + s : xt[k], kp[k], acc);
-            out[rw.out_pos + o] = acc;
+            int k_lo, k_hi;
+            tap_range(j_lo, j_hi, t0, K, k_lo, k_hi);
+            out[rw.out_pos + o] = fir_chain<SHIFT>(x + (rw.in_pos + t0), kl + p * K, k_lo, k_hi, s);
         }
     }
 }
@@ -70,12 +60,11 @@ __global__ __launch_bounds__(256) void rows_moments_chunks_kernel(const float* _
         const SegRow rw = seg_row_clamped(rows, r, total);
         const long long len = rw.hi - rw.lo;
         if (len <= 0) continue;
-        const long long all = (len + kChunk - 1) / kChunk;
-        const int n_chunks = (int)(all < max_chunks ? all : max_chunks);
+        const int n_chunks = row_chunks(len, max_chunks);
         for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
             const long long base = rw.lo + (long long)c * kChunk;
             const int n = (int)(rw.hi - base < kChunk ? rw.hi - base : kChunk);
-            double s1 = 0.0, s2 = 0.0;
+            double acc[2] = {0.0, 0.0};                                  // sum x, sum x^2
             for (int i = 4 * threadIdx.x; i < n; i += 4 * 256) {
                 float e[4] = {0.0f, 0.0f, 0.0f, 0.0f};
                 if (VEC && ((base + i) & 3) == 0 && i + 3 < n) {
@@ -86,17 +75,9 @@ __global__ __launch_bounds__(256) void rows_moments_chunks_kernel(const float* _
                     for (int k = 0; k < 4; ++k) if (i + k < n) e[k] = x[base + i + k];
                 }
 #pragma unroll
-                for (int k = 0; k < 4; ++k) { const double d = (double)e[k]; s1 += d; s2 += d * d; }    // (a missing sample adds 0)
+                for (int k = 0; k < 4; ++k) { const double d = (double)e[k]; acc[0] += d; acc[1] += d * d; }   // (missing: adds 0)
             }
-            s1 = wave_sum_d(s1);
-            s2 = wave_sum_d(s2);
-            if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = s1; red[threadIdx.x >> 6][1] = s2; }
-            __syncthreads();
-            if (threadIdx.x < 2) {
-                const int w = threadIdx.x;
-                partial[((size_t)r * max_chunks + c) * 2 + w] = ((red[0][w] + red[1][w]) + red[2][w]) + red[3][w];
-            }
-            __syncthreads();
+            block_sum_store<2>(acc, red, partial + ((size_t)r * max_chunks + c) * 2);
         }
     }
 }
@@ -107,16 +88,7 @@ __global__ __launch_bounds__(256) void rows_moments_final_kernel(const SegRow* _
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rows) return;
     const SegRow rw = seg_row_clamped(rows, r, total);
-    const long long len = rw.hi - rw.lo;
-    const long long all = len > 0 ? (len + kChunk - 1) / kChunk : 0;
-    const int n_chunks = (int)(all < max_chunks ? all : max_chunks);
-    double s1 = 0.0, s2 = 0.0;
-    for (int c = 0; c < n_chunks; ++c) {
-        s1 += partial[((size_t)r * max_chunks + c) * 2];
-        s2 += partial[((size_t)r * max_chunks + c) * 2 + 1];
-    }
-    out[2 * (size_t)r] = s1;
-    out[2 * (size_t)r + 1] = s2;
+    sum_chunks<2>(partial + (size_t)r * max_chunks * 2, row_chunks(rw.hi - rw.lo, max_chunks), out + 2 * (size_t)r);
 }
 
 template <bool VEC>
@@ -153,18 +125,6 @@ __global__ __launch_bounds__(256) void add_noise_rows_kernel(float* __restrict__
     }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// x blocks per row for a launch over n_rows rows of at most max_len samples, `per_block` samples per block and pass: enough
-// blocks to fill the chip, few enough that a table of thousands of rows does not launch mostly empty ones
-inline dim3 rows_grid(int n_rows, long long max_len, int per_block) {
-    const unsigned gy = (unsigned)(n_rows < 65535 ? n_rows : 65535);
-    long long bx = (max_len + per_block - 1) / per_block;
-    const long long cap = 8192 / gy > 8 ? 8192 / gy : 8;
-    bx = bx < cap ? bx : cap;
-    return dim3((unsigned)(bx < 1 ? 1 : (bx > 1024 ? 1024 : bx)), gy);
-}
-
 }  // namespace
 
 extern "C" {
@@ -178,10 +138,9 @@ int mg_resample_rows(const float* x, long long x_total, const mg_resample_row* r
     if ((long long)new_ * (2LL * width + orig) > INT_MAX / 4) return MG_ERR_ARG;
     const size_t lds = (size_t)new_ * (2 * width + orig) * sizeof(float);
     const dim3 grid = rows_grid(n_rows, max_out_len, 256);
-    const ResRow* rt = reinterpret_cast<const ResRow*>(rows);
     hipStream_t st = (hipStream_t)stream;
 #define MG_RR_LAUNCH(LDS, SH, BYTES)                                                                                          \
-    hipLaunchKernelGGL((resample_rows_kernel<LDS, SH>), grid, dim3(256), BYTES, st, x, x_total, rt, n_rows, shift, kern, orig, \
+    hipLaunchKernelGGL((resample_rows_kernel<LDS, SH>), grid, dim3(256), BYTES, st, x, x_total, rows, n_rows, shift, kern, orig, \
                        new_, width, out, out_total)
     if (lds <= 48 * 1024) {
         if (shift) MG_RR_LAUNCH(true, true, lds); else MG_RR_LAUNCH(true, false, lds);

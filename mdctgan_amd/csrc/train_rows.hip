@@ -14,19 +14,16 @@
 // make_training_pair on its window alone.  No atomics; every store is guarded; the loops a workgroup runs depend on its row alone.
 #include <limits.h>
 
-#include "common.h"
-#include "mdctgan_hip.h"
+#include "rows.h"
 
 namespace {
 
-struct TrainRow { long long in_pos, in_len, out_row, full_pos, full_len; };
 struct Bank { const float* kern; int orig, new_, width; };          // kern == nullptr: equal rates, the step is a copy
 
 constexpr int kThreads = 256;
 constexpr int kTile = 1024;                      // output samples of one workgroup pass (the host may shrink it, see tile_for)
 constexpr int kMidCap = 4096;                    // lr-rate intermediates of one tile held in LDS
 constexpr int kBankCap = 2048;                   // floats of one filter bank held in LDS (rows padded to an odd stride)
-constexpr long long kFar = 1LL << 62;
 constexpr int kMaxLen = 1 << 30;                 // rows of more output samples are refused / dropped: every index below stays an int
 
 __host__ __device__ inline int bank_stride(int K) { return K | 1; }       // odd: the phases of neighbouring outputs sit on different banks
@@ -39,23 +36,19 @@ __device__ __forceinline__ void stage_bank(float* dst, const Bank& b) {
     for (int i = threadIdx.x; i < b.new_ * K; i += kThreads) dst[(i / K) * S + (i % K)] = b.kern[i];
 }
 
-// Sample o of resample(window) for the bank (kl, stride S): the window is x[pos + j], j in [j_lo, j_hi) (already cut to the buffer)
-__device__ __forceinline__ float chain_global(const float* __restrict__ x, long long pos, long long j_lo, long long j_hi,
-                                              const float* kl, int S, int orig, int new_, int width, int o) {
-    const int K = 2 * width + orig;
+// Sample o of resample(window) for the bank (kl, stride S): sample j of the window is x[pos + j] and exists for j in [j_lo, j_hi)
+// -- the row's samples already cut to the corpus, or the intermediates a tile holds in LDS
+__device__ __forceinline__ float chain_at(const float* x, long long pos, long long j_lo, long long j_hi, const float* kl, int S,
+                                          int orig, int new_, int width, int o) {
     const int n = o / new_, p = o - n * new_;
     const long long t0 = (long long)n * orig - width;                      // sample index of tap 0
-    const float* kp = kl + p * S;
-    const int k_lo = (int)(j_lo - t0 > 0 ? (j_lo - t0 < K ? j_lo - t0 : K) : 0);
-    const int k_hi = (int)(j_hi - t0 < K ? (j_hi - t0 > 0 ? j_hi - t0 : 0) : K);
-    const float* xt = x + (pos + t0);                                       // (only [k_lo, k_hi) of it is read)
-    float acc = 0.0f;
-    for (int k = k_lo; k < k_hi; ++k) acc = fmaf(xt[k], kp[k], acc);
-    return acc;
+    int k_lo, k_hi;
+    tap_range(j_lo, j_hi, t0, 2 * width + orig, k_lo, k_hi);
+    return fir_chain<false>(x + (pos + t0), kl + p * S, k_lo, k_hi, 0.0f);
 }
 
 // The window of a row cut to the corpus; false: a dead or broken row
-__device__ __forceinline__ bool row_window(const TrainRow& rw, long long x_total, long long* j_lo, long long* j_hi) {
+__device__ __forceinline__ bool row_window(const mg_train_row& rw, long long x_total, long long* j_lo, long long* j_hi) {
     if (rw.in_len <= 0 || rw.in_len > INT_MAX || rw.in_pos <= -kFar || rw.in_pos >= x_total) return false;
     *j_lo = rw.in_pos < 0 ? -rw.in_pos : 0;
     *j_hi = rw.in_len < x_total - rw.in_pos ? rw.in_len : x_total - rw.in_pos;
@@ -64,7 +57,7 @@ __device__ __forceinline__ bool row_window(const TrainRow& rw, long long x_total
 
 template <bool BANK_IN_LDS>
 __global__ __launch_bounds__(kThreads) void train_hr_rows_kernel(const float* __restrict__ x, long long x_total,
-                                                                 const TrainRow* __restrict__ rows, int n_rows, int seg_len,
+                                                                 const mg_train_row* __restrict__ rows, int n_rows, int seg_len,
                                                                  Bank bank, float* __restrict__ hr, long long out_rows) {
     __shared__ float bank_s[kBankCap];
     if (BANK_IN_LDS) {
@@ -75,7 +68,7 @@ __global__ __launch_bounds__(kThreads) void train_hr_rows_kernel(const float* __
     const float* kl = BANK_IN_LDS ? bank_s : bank.kern;
     const int S = BANK_IN_LDS ? bank_stride(K) : K;
     for (int r = blockIdx.y; r < n_rows; r += gridDim.y) {
-        const TrainRow rw = rows[r];
+        const mg_train_row rw = rows[r];
         long long j_lo, j_hi;
         if (!row_window(rw, x_total, &j_lo, &j_hi) || rw.out_row < 0 || rw.out_row >= out_rows) continue;
         const long long len = bank.kern ? ((long long)bank.new_ * rw.in_len + bank.orig - 1) / bank.orig : rw.in_len;
@@ -84,7 +77,7 @@ __global__ __launch_bounds__(kThreads) void train_hr_rows_kernel(const float* __
         for (int o = blockIdx.x * kThreads + threadIdx.x; o < seg_len; o += gridDim.x * kThreads) {
             float v = 0.0f;
             if (o < n_sig) {
-                if (bank.kern) v = chain_global(x, rw.in_pos, j_lo, j_hi, kl, S, bank.orig, bank.new_, bank.width, o);
+                if (bank.kern) v = chain_at(x, rw.in_pos, j_lo, j_hi, kl, S, bank.orig, bank.new_, bank.width, o);
                 else if (o >= j_lo && o < j_hi) v = x[rw.in_pos + o];
             }
             dst[o] = v;
@@ -94,7 +87,7 @@ __global__ __launch_bounds__(kThreads) void train_hr_rows_kernel(const float* __
 
 template <bool DOWN_IN_LDS, bool UP_IN_LDS, bool FULL>
 __global__ __launch_bounds__(kThreads) void train_lr_rows_kernel(const float* __restrict__ x, long long x_total,
-                                                                 const TrainRow* __restrict__ rows, int n_rows, int seg_len,
+                                                                 const mg_train_row* __restrict__ rows, int n_rows, int seg_len,
                                                                  Bank down, Bank up, int tile_len, float* __restrict__ lr,
                                                                  long long out_rows, float* __restrict__ lr_full,
                                                                  long long full_total) {
@@ -110,7 +103,7 @@ __global__ __launch_bounds__(kThreads) void train_lr_rows_kernel(const float* __
     const int Sd = DOWN_IN_LDS ? bank_stride(Kd) : Kd, Su = UP_IN_LDS ? bank_stride(Ku) : Ku;
 
     for (int r = blockIdx.y; r < n_rows; r += gridDim.y) {
-        const TrainRow rw = rows[r];
+        const mg_train_row rw = rows[r];
         long long j_lo, j_hi;
         if (!row_window(rw, x_total, &j_lo, &j_hi)) continue;
         // the intermediate exists for 0 <= i < mid_len, the low-rate signal for 0 <= o < lr_len
@@ -143,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void train_lr_rows_kernel(const float* __
                 c_hi = c_hi > mid_len ? mid_len : c_hi;
                 if (c_hi - c_lo > kMidCap) continue;                        // (the host's tile_len rules this out)
                 for (long long i = c_lo + threadIdx.x; i < c_hi; i += kThreads)
-                    mid_s[i - c_lo] = down.kern ? chain_global(x, rw.in_pos, j_lo, j_hi, kd, Sd, down.orig, down.new_, down.width, (int)i)
+                    mid_s[i - c_lo] = down.kern ? chain_at(x, rw.in_pos, j_lo, j_hi, kd, Sd, down.orig, down.new_, down.width, (int)i)
                                                 : (i >= j_lo && i < j_hi ? x[rw.in_pos + i] : 0.0f);
             }
             __syncthreads();
@@ -151,15 +144,9 @@ __global__ __launch_bounds__(kThreads) void train_lr_rows_kernel(const float* __
                 float v = 0.0f;
                 if (o < s1) {
                     if (up.kern) {
-                        const int n = o / up.new_, p = o - n * up.new_;
-                        const long long t0 = (long long)n * up.orig - up.width;
-                        const float* kp = ku + p * Su;
-                        const int k_lo = (int)(c_lo - t0 > 0 ? (c_lo - t0 < Ku ? c_lo - t0 : Ku) : 0);
-                        const int k_hi = (int)(c_hi - t0 < Ku ? (c_hi - t0 > 0 ? c_hi - t0 : 0) : Ku);
-                        const float* mt = mid_s + (t0 - c_lo);             // (only [k_lo, k_hi) of it is read)
-                        for (int k = k_lo; k < k_hi; ++k) v = fmaf(mt[k], kp[k], v);
+                        v = chain_at(mid_s, -c_lo, c_lo, c_hi, ku, Su, up.orig, up.new_, up.width, o);
                     } else if (down.kern) {
-                        v = chain_global(x, rw.in_pos, j_lo, j_hi, kd, Sd, down.orig, down.new_, down.width, o);
+                        v = chain_at(x, rw.in_pos, j_lo, j_hi, kd, Sd, down.orig, down.new_, down.width, o);
                     } else if (o >= j_lo && o < j_hi) {
                         v = x[rw.in_pos + o];
                     }
@@ -188,14 +175,6 @@ inline int tile_for(const Bank& up) {
     return (int)(t < kTile ? t : kTile);
 }
 
-inline dim3 train_grid(int n_rows, long long max_len, int per_block) {
-    const unsigned gy = (unsigned)(n_rows < 65535 ? n_rows : 65535);
-    long long bx = (max_len + per_block - 1) / per_block;
-    const long long cap = 8192 / gy > 8 ? 8192 / gy : 8;
-    bx = bx < cap ? bx : cap;
-    return dim3((unsigned)(bx < 1 ? 1 : (bx > 1024 ? 1024 : bx)), gy);
-}
-
 }  // namespace
 
 extern "C" {
@@ -213,21 +192,20 @@ int mg_train_pair_rows(const float* corpus, long long corpus_total, const mg_tra
     const Bank bh = bank_of(to_hr), bd = bank_of(to_lr), bu = bank_of(lr_to_hr);
     const int tile_len = tile_for(bu);
     if (tile_len <= 0) return MG_ERR_UNSUPPORTED;
-    const TrainRow* rt = reinterpret_cast<const TrainRow*>(rows);
     hipStream_t st = (hipStream_t)stream;
 
-    const dim3 gh = train_grid(n_rows, seg_len, kThreads);
+    const dim3 gh = rows_grid(n_rows, seg_len, kThreads);
     if (bank_fits(bh))
-        hipLaunchKernelGGL(train_hr_rows_kernel<true>, gh, dim3(kThreads), 0, st, corpus, corpus_total, rt, n_rows, seg_len, bh, hr,
+        hipLaunchKernelGGL(train_hr_rows_kernel<true>, gh, dim3(kThreads), 0, st, corpus, corpus_total, rows, n_rows, seg_len, bh, hr,
                            out_rows);
     else
-        hipLaunchKernelGGL(train_hr_rows_kernel<false>, gh, dim3(kThreads), 0, st, corpus, corpus_total, rt, n_rows, seg_len, bh, hr,
+        hipLaunchKernelGGL(train_hr_rows_kernel<false>, gh, dim3(kThreads), 0, st, corpus, corpus_total, rows, n_rows, seg_len, bh, hr,
                            out_rows);
     MG_CHECK_LAUNCH();
 
-    const dim3 gl = train_grid(n_rows, lr_full ? max_full_len : (long long)seg_len, tile_len);
+    const dim3 gl = rows_grid(n_rows, lr_full ? max_full_len : (long long)seg_len, tile_len);
 #define MG_TL_LAUNCH(D, U, F)                                                                                                     \
-    hipLaunchKernelGGL((train_lr_rows_kernel<D, U, F>), gl, dim3(kThreads), 0, st, corpus, corpus_total, rt, n_rows, seg_len, bd, \
+    hipLaunchKernelGGL((train_lr_rows_kernel<D, U, F>), gl, dim3(kThreads), 0, st, corpus, corpus_total, rows, n_rows, seg_len, bd, \
                        bu, tile_len, lr, out_rows, lr_full, lr_full_total)
 #define MG_TL_FULL(D, U) do { if (lr_full) MG_TL_LAUNCH(D, U, true); else MG_TL_LAUNCH(D, U, false); } while (0)
     if (bank_fits(bd)) {

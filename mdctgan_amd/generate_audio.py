@@ -27,6 +27,7 @@ import torch
 from . import _lib
 from . import functional as Fh
 from . import ops
+from .packed import PackedLayout, aligned_layout, pack_waves
 
 
 def segment_audio(audio: torch.Tensor, segment_length: int, gen_overlap: int = 0) -> torch.Tensor:
@@ -145,6 +146,11 @@ class UtterancePlan:
     n_live: int
 
     @property
+    def in_layout(self) -> PackedLayout:
+        """The packed input buffer, as packed.pack_waves lays it out."""
+        return PackedLayout(self.in_start, self.lengths, self.in_total)
+
+    @property
     def n_batches(self) -> int:
         return self.in_rows.shape[0] // self.batch_size
 
@@ -177,31 +183,25 @@ def plan_utterances(lengths, segment_length: int, out_segment_length: int, gen_o
         raise ValueError("gen_overlap must be in [0, segment_length) and below half a decoded segment")
     if not lengths or min(lengths) <= 0:
         raise ValueError("plan_utterances needs at least one utterance, each of at least one sample")
-    up = lambda n: -(-n // align) * align
-    segments, in_start, out_start, out_length, in_rows, out_rows = [], [], [], [], [], []
-    in_pos = out_pos = 0
+    segments, out_length = [], []
     for n in lengths:
-        if n >= L:
-            n_seg = (-(-n // L) * L + 2 * ov - L) // (L - ov) + 1
-            front = ov
-        else:
-            n_seg, front = 1, 0                 # (the short waveform is padded behind only)
-        total = stitch_length(n_seg, Lo, ov)
+        n_seg = (-(-n // L) * L + 2 * ov - L) // (L - ov) + 1 if n >= L else 1
         segments.append(n_seg)
-        in_start.append(in_pos)
-        out_start.append(out_pos)
-        out_length.append(total)
+        out_length.append(stitch_length(n_seg, Lo, ov))
+    ins, outs = aligned_layout(lengths, align), aligned_layout(out_length, align)
+    in_rows, out_rows = [], []
+    for n, n_seg, total, in_pos, out_pos in zip(lengths, segments, out_length, ins.starts, outs.starts):
+        front = ov if n >= L else 0             # (the short waveform is padded behind only)
         for k in range(n_seg):
             in_rows.append((in_pos + k * (L - ov) - front, in_pos, in_pos + n))
             out_rows.append((out_pos + k * (Lo - ov) - ov, out_pos, out_pos + total))
-        in_pos, out_pos = up(in_pos + n), up(out_pos + total)
     n_live = len(in_rows)
     dead = -n_live % bs
     in_rows += [(0, 0, 0)] * dead
     out_rows += [(0, 0, 0)] * dead
-    return UtterancePlan(L, Lo, ov, bs, lengths, segments, in_start, out_start, out_length,
+    return UtterancePlan(L, Lo, ov, bs, lengths, segments, ins.starts, outs.starts, out_length,
                          np.asarray(in_rows, dtype=np.int64).reshape(-1, 3), np.asarray(out_rows, dtype=np.int64).reshape(-1, 3),
-                         in_pos, out_pos, n_live)
+                         ins.total, outs.total, n_live)
 
 
 def check_capacity(plan: UtterancePlan, max_segments: int, max_samples: int) -> None:
@@ -222,30 +222,6 @@ def _decoded_segment_length(pre, segment_length: int) -> int:
 
 def _fused_many(model) -> bool:
     return bool(getattr(model.preprocess, "has_stitched_decoder", False)) and os.environ.get("MG_NO_STITCHED_K2") != "1"
-
-
-def _pack_waves(waves, plan: UtterancePlan, device, out=None) -> torch.Tensor:
-    """The packed input buffer: every waveform at its aligned start, written once -- one concatenation straight into `out`
-    (a device buffer of at least plan.in_total samples; default: a new one).  A list of host waveforms is concatenated on the
-    host and travels in one copy; a list that mixes devices is moved to `device` waveform by waveform."""
-    device = torch.device(device)
-    buf = torch.empty(plan.in_total, dtype=torch.float32, device=device) if out is None else out[:plan.in_total]
-    flat = [w.reshape(-1) for w in waves]
-    on_host = all(w.device.type == "cpu" for w in flat)
-    where = torch.device("cpu") if on_host else device
-    gap = torch.zeros(max(int(s1 - s0 - n) for s0, s1, n in
-                          zip(plan.in_start, plan.in_start[1:] + [plan.in_total], plan.lengths)) or 1,
-                      dtype=torch.float32, device=where)
-    parts = []
-    for w, s0, s1 in zip(flat, plan.in_start, plan.in_start[1:] + [plan.in_total]):
-        parts.append(w.to(device=where, dtype=torch.float32))
-        if s1 - s0 > w.numel():
-            parts.append(gap[:s1 - s0 - w.numel()])
-    if on_host and device.type != "cpu":
-        buf.copy_(torch.cat(parts), non_blocking=True)
-    else:
-        torch.cat(parts, out=buf)
-    return buf
 
 
 def _plan_for(model, waves, batch_size, gen_overlap, segment_length):
@@ -308,7 +284,7 @@ def generate_many(model, waves, batch_size: int = 64, gen_overlap: int = 0, pad_
     -- split a larger corpus into several calls."""
     plan = _plan_for(model, waves, batch_size, gen_overlap, segment_length)
     dev = next(model.netG.parameters()).device
-    return _run_packed(model, _pack_waves(waves, plan, dev), plan, pad_batches)
+    return _run_packed(model, pack_waves(waves, plan.in_layout, dev), plan, pad_batches)
 
 
 def super_resolve_many(model, raws, rates, batch_size: int = 64, gen_overlap=None, noise=None, generator=None):
@@ -433,7 +409,7 @@ def make_graphed_generate_many(model, max_segments: int, max_samples: int, batch
         check_capacity(plan, max_segments, max_samples)
         rows = np.zeros((2, n_rows, 3), dtype=np.int64)
         rows[0, :plan.in_rows.shape[0]], rows[1, :plan.out_rows.shape[0]] = plan.in_rows, plan.out_rows
-        _pack_waves(waves, plan, dev, out=static_in)
+        pack_waves(waves, plan.in_layout, dev, out=static_in)
         static_rows.copy_(seg_row_table(rows).view(2, n_rows, 3), non_blocking=True)
         graph.replay()
         run.last = _views(static_out, plan)

@@ -8,7 +8,6 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from types import SimpleNamespace
 from typing import List
 
 import numpy as np
@@ -16,6 +15,7 @@ import torch
 
 from . import _lib, ops
 from .mdct import kbdwin
+from .packed import aligned_layout, pack_waves, rows_moments, upload_tables, window_table
 
 _tables = {}
 
@@ -144,7 +144,7 @@ def _packed_operand(x, what: str):
 
 def compute_matrics_many(hrs, lrs, srs, opt, hr_shift=None):
     """``compute_matrics`` for every utterance of a test set on its own (generate_audio.py:57-67), in shared launches.
-    hrs / lrs / srs: lists of waveforms ([T_u] or [1, T_u], host or device; packed here with _pack_waves' layout), or packed
+    hrs / lrs / srs: lists of waveforms ([T_u] or [1, T_u], host or device; packed here with packed.aligned_layout's layout), or packed
     operands that are read where they lie -- ``(buffer, starts, lengths)`` (hrs), ``(buffer, starts)`` or ``(buffer, starts,
     lengths)`` (lrs, srs) with a contiguous float32 device buffer and host lists, as front_end_many and generate_many leave them.
     Utterance u is scored over len_u = len(hr_u) samples; lr_u and sr_u are cropped to that and must not be shorter (ValueError).
@@ -153,8 +153,6 @@ def compute_matrics_many(hrs, lrs, srs, opt, hr_shift=None):
     with the same bits whatever else shares the call.  Launches: one table copy (plus one packing copy per operand given as a
     list), mg_metrics_rows_packed, mg_lsd_rows, mg_rows_moments and a few element-wise launches over [U], whatever U is; nothing
     is read back."""
-    from .generate_audio import _pack_waves
-    from .resample import _aligned_starts, rows_moments
     n_fft, hop, win = 2 * int(opt.n_fft), 2 * int(opt.hop_length), 2 * int(opt.win_length)
     if win != n_fft:
         raise NotImplementedError("win_length != n_fft")
@@ -181,9 +179,8 @@ def compute_matrics_many(hrs, lrs, srs, opt, hr_shift=None):
     bufs, starts = [], []
     for buf, ws, avail in ops_:
         if buf is None:
-            st, total = _aligned_starts(avail, 64)
-            buf = _pack_waves(ws, SimpleNamespace(in_total=total, in_start=st, lengths=avail), device)
-            ws = st
+            layout = aligned_layout(avail)
+            buf, ws = pack_waves(ws, layout, device), layout.starts
         bufs.append(buf)
         starts.append(ws)
     hr, lr, sr = bufs
@@ -191,13 +188,9 @@ def compute_matrics_many(hrs, lrs, srs, opt, hr_shift=None):
                                  or not hr_shift.is_contiguous()):
         raise ValueError("hr_shift is a contiguous float32 [%d] device tensor" % U)
 
-    # every table in one host array and one copy: the metric rows, frame_start, and the windows of the per-frame array
-    fs = np.asarray(plan.frame_start, dtype=np.int64)
-    rows = np.stack([np.asarray(starts[0], dtype=np.int64), np.asarray(starts[1], dtype=np.int64),
-                     np.asarray(starts[2], dtype=np.int64), np.asarray(lengths, dtype=np.int64)], axis=1)
-    frame_rows = np.stack([fs[:-1], fs[:-1], fs[1:]], axis=1)
-    tables = torch.from_numpy(np.concatenate([rows.reshape(-1), fs, frame_rows.reshape(-1)])).to(device, non_blocking=True)
-    row_t, fs_t, frame_t = tables[:4 * U].view(U, 4), tables[4 * U:5 * U + 1], tables[5 * U + 1:].view(U, 3)
+    # every table in one copy: the metric rows, frame_start, and the windows of the per-frame array
+    rows = np.stack([np.asarray(t, dtype=np.int64) for t in (*starts, lengths)], axis=1)
+    row_t, fs_t, frame_t = upload_tables([rows, plan.frame_start, window_table(plan.frame_start[:-1], plan.frames)], device)
 
     lib = _lib.load()
     max_len = max(lengths)

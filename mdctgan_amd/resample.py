@@ -8,7 +8,7 @@ test set in shared launches.  Every utterance sits at an aligned start of one pa
 tables (``mg_resample_row``, ``mg_seg_row``) say where each row reads and writes, and the launch count -- one packing copy, one
 table copy, the DC mean (``mg_rows_moments``), one ``mg_resample_rows`` per distinct rate pair and step, and under ``--add_noise``
 two more moment passes and ``mg_add_noise_rows`` -- does not depend on the number of utterances.  Nothing is read back.  The final
-buffer has ``generate_audio._pack_waves``' layout, so ``generate_many``'s gather and decode tables apply to it unchanged.
+buffer has ``packed.pack_waves``' layout, so ``generate_many``'s gather and decode tables apply to it unchanged.
 """
 from __future__ import annotations
 
@@ -21,6 +21,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from .packed import (PackedLayout, add_noise_packed, add_noise_rows, aligned_layout, check_table, noise_buffer,  # noqa: F401
+                     pack_waves, rows_moments, upload_tables, window_table)
 
 _kernels = {}
 
@@ -47,6 +49,25 @@ def _sinc_kernel(orig_freq: int, new_freq: int, lowpass_filter_width: int, rollo
     return _kernels[key]
 
 
+def filter_bank(orig_freq: int, new_freq: int, device, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """(kern [new, 2 * width + orig] float32 on `device`, width, orig, new) of one resampling step, on the gcd-reduced rates and
+    cached for the life of the process; equal rates: the one-tap identity bank (ones [1, 1], 0, 1, 1), a copy."""
+    if int(orig_freq) != int(new_freq):
+        return _sinc_kernel(orig_freq, new_freq, lowpass_filter_width, rolloff, device)
+    key = ("identity", str(device))
+    if key not in _kernels:
+        _kernels[key] = (torch.ones(1, 1, dtype=torch.float32, device=device), 0, 1, 1)
+    return _kernels[key]
+
+
+def resample_length(length: int, orig_freq: int, new_freq: int) -> int:
+    """mg_resample_length on the gcd-reduced rates, on the host: ceil(new * L / orig), the length aF.resample returns."""
+    if int(length) <= 0 or int(orig_freq) <= 0 or int(new_freq) <= 0:
+        raise ValueError("lengths and sampling rates must be positive")
+    g = math.gcd(int(orig_freq), int(new_freq))
+    return -(-(int(new_freq) // g) * int(length) // (int(orig_freq) // g))
+
+
 def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6,
              rolloff: float = 0.99, resampling_method: str = "sinc_interp_hann") -> torch.Tensor:
     """waveform [..., L] (device) -> [..., ceil(new_freq * L / orig_freq)]."""
@@ -57,7 +78,7 @@ def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filt
     if int(orig_freq) == int(new_freq):
         return waveform
     lib = _lib.load()
-    kern, width, orig, new = _sinc_kernel(orig_freq, new_freq, lowpass_filter_width, rolloff, waveform.device)
+    kern, width, orig, new = filter_bank(orig_freq, new_freq, waveform.device, lowpass_filter_width, rolloff)
     shape = waveform.shape
     x = _lib.f32c(waveform.reshape(-1, shape[-1]))
     n_out = lib.mg_resample_length(shape[-1], orig, new)
@@ -112,74 +133,23 @@ def make_test_segments(raw_audio: torch.Tensor, in_sampling_rate: int, hr_sampli
 # ---------------------------------------------------------------------------------------------------------------------
 # Row-table kernels: many utterances in shared launches
 # ---------------------------------------------------------------------------------------------------------------------
-def _table(table, cols: int, what: str):
-    if not (torch.is_tensor(table) and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == cols
-            and table.shape[0] > 0 and table.is_contiguous()):
-        raise ValueError("%s: the row table is a contiguous int64 [n, %d] tensor with at least one row" % (what, cols))
-    return table
-
-
 def resample_rows(x: torch.Tensor, table: torch.Tensor, max_out_len: int, orig_freq: int, new_freq: int, out: torch.Tensor,
                   shift=None, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> torch.Tensor:
     """mg_resample_rows: row u of `table` (int64 [n, 4] = in_pos, in_len, out_pos, out_len, on the device) reads its window of the
     packed float32 buffer `x` and writes resample()'s result for it into its window of `out`; shift [n] float32 enters row u's
     samples as x + shift[u].  Equal rates copy (a one-tap bank)."""
     lib = _lib.load()
-    n = _table(table, 4, "resample_rows").shape[0]
+    n = check_table(table, 4, "resample_rows").shape[0]
     if x.dtype != torch.float32 or out.dtype != torch.float32 or not x.is_contiguous() or not out.is_contiguous():
         raise ValueError("resample_rows: x and out are contiguous float32 buffers")
     if shift is not None and (shift.dtype != torch.float32 or shift.numel() != n or not shift.is_contiguous()):
         raise ValueError("resample_rows: shift is a contiguous float32 [%d] tensor" % n)
     if orig_freq <= 0 or new_freq <= 0:
         raise ValueError("Original frequency and desired frequency should be positive")
-    if int(orig_freq) == int(new_freq):
-        kern, width, orig, new = _identity_kernel(x.device)
-    else:
-        kern, width, orig, new = _sinc_kernel(orig_freq, new_freq, lowpass_filter_width, rolloff, x.device)
+    kern, width, orig, new = filter_bank(orig_freq, new_freq, x.device, lowpass_filter_width, rolloff)
     _lib.check(lib.mg_resample_rows(_lib.ptr(x), x.numel(), _lib.ptr(table), n, int(max_out_len), _lib.ptr(shift), _lib.ptr(kern),
                                     orig, new, width, _lib.ptr(out), out.numel(), _lib.stream()), "mg_resample_rows")
     return out
-
-
-def _identity_kernel(device):
-    key = ("identity", str(device))
-    if key not in _kernels:
-        _kernels[key] = (torch.ones(1, 1, dtype=torch.float32, device=device), 0, 1, 1)
-    return _kernels[key]
-
-
-def rows_moments(x: torch.Tensor, table: torch.Tensor, max_len: int) -> torch.Tensor:
-    """mg_rows_moments: float64 [n, 2] = {sum x, sum x^2} over the window [lo, hi) of every row of `table` (int64 [n, 3] = pos, lo,
-    hi on the device) of the packed float32 buffer `x`."""
-    lib = _lib.load()
-    n = _table(table, 3, "rows_moments").shape[0]
-    if x.dtype != torch.float32 or not x.is_contiguous():
-        raise ValueError("rows_moments: x is a contiguous float32 buffer")
-    nbytes = lib.mg_rows_moments_workspace(n, int(max_len))
-    ws = _lib.workspace(nbytes, x.device)
-    out = torch.empty(n, 2, dtype=torch.float64, device=x.device)
-    _lib.check(lib.mg_rows_moments(_lib.ptr(x), x.numel(), _lib.ptr(table), n, int(max_len), _lib.ptr(out), _lib.ptr(ws), nbytes,
-                                   _lib.stream()), "mg_rows_moments")
-    return out
-
-
-def add_noise_rows(lr: torch.Tensor, noise: torch.Tensor, table: torch.Tensor, max_len: int, lr_moments: torch.Tensor,
-                   noise_moments: torch.Tensor, snr: float, segment_length: int) -> torch.Tensor:
-    """mg_add_noise_rows, in place on the packed buffer `lr`: every row's window [lo, hi) becomes lr + a (noise - mean(noise)),
-    a = sqrt((sum lr^2 / segment_length) / 10^(snr / 10)) / std(noise), from rows_moments(lr, ...) and rows_moments(noise, ...)."""
-    lib = _lib.load()
-    n = _table(table, 3, "add_noise_rows").shape[0]
-    if lr.dtype != torch.float32 or noise.dtype != torch.float32 or not lr.is_contiguous() or not noise.is_contiguous():
-        raise ValueError("add_noise_rows: lr and noise are contiguous float32 buffers")
-    if noise.numel() < lr.numel():
-        raise ValueError("add_noise_rows: the noise buffer has lr's layout (%d samples, got %d)" % (lr.numel(), noise.numel()))
-    for m in (lr_moments, noise_moments):
-        if m.dtype != torch.float64 or tuple(m.shape) != (n, 2) or not m.is_contiguous():
-            raise ValueError("add_noise_rows: moments are contiguous float64 [%d, 2] tensors" % n)
-    _lib.check(lib.mg_add_noise_rows(_lib.ptr(lr), _lib.ptr(noise), lr.numel(), _lib.ptr(table), n, int(max_len),
-                                     _lib.ptr(lr_moments), _lib.ptr(noise_moments), float(snr), int(segment_length),
-                                     _lib.stream()), "mg_add_noise_rows")
-    return lr
 
 
 def add_noise_rows_of(waveform: torch.Tensor, snr: float, segment_length: int, noise=None, generator=None,
@@ -202,11 +172,8 @@ def add_noise_rows_of(waveform: torch.Tensor, snr: float, segment_length: int, n
         if noise.numel() != x.numel():
             raise ValueError("add_noise: noise has the waveform's shape %s (got %s)" % (tuple(shape), tuple(noise.shape)))
         z = noise.to(device=x.device, dtype=torch.float32).reshape(B, L).contiguous()
-    first = np.arange(B, dtype=np.int64) * L
-    table = torch.from_numpy(np.stack([first, first, first + L], axis=1)).to(x.device, non_blocking=True)
-    flat = x.view(-1)
-    add_noise_rows(flat, z.view(-1), table, L, rows_moments(flat, table, L), rows_moments(z.view(-1), table, L), snr,
-                   segment_length)
+    table, = upload_tables([window_table(np.arange(B, dtype=np.int64) * L, [L] * B)], x.device)
+    add_noise_packed(x.view(-1), table, L, snr, segment_length, z.view(-1))
     return x.reshape(shape)
 
 
@@ -226,7 +193,7 @@ class FrontEndPlan:
     the packed buffer before step s (s = 0: the raw waveforms) and after the last one (s = len(steps): the low-rate input at
     hr_rate).  `steps[s]`: the ResampleGroups of step s, one per distinct rate pair.  `order`: the utterances in the order of the
     first step's groups -- the row order of the DC-mean table, so that every group's shifts are contiguous.  `utterances`:
-    generate_audio.plan_utterances over the final lengths; its in_start / in_total ARE starts[-1] / totals[-1].  `raw`: None, or
+    generate_audio.plan_utterances over the final lengths; its in_layout IS starts[-1] / lengths[-1] / totals[-1].  `raw`: None, or
     under front_end_many(keep_raw=True) a namespace of the packed raw buffer (`buffer`, float32 [totals[0]]; utterance u at
     starts[0][u], lengths[0][u] samples) and the DC shift per utterance (`shift`, float32 [U] on the device, in UTTERANCE order):
     raw + shift is read_audio's waveform, the ground truth of metrics.compute_matrics_many."""
@@ -257,28 +224,11 @@ class FrontEndPlan:
         return sum(len(step) for step in self.steps)
 
 
-def resample_length(length: int, orig_freq: int, new_freq: int) -> int:
-    """mg_resample_length on the gcd-reduced rates: ceil(new * L / orig), the length aF.resample returns."""
-    g = math.gcd(int(orig_freq), int(new_freq))
-    n = _lib.load().mg_resample_length(int(length), int(orig_freq) // g, int(new_freq) // g)
-    if n <= 0:
-        raise ValueError("lengths and sampling rates must be positive")
-    return int(n)
-
-
-def _aligned_starts(lengths, align):
-    starts, pos = [], 0
-    for n in lengths:
-        starts.append(pos)
-        pos = -(-(pos + n) // align) * align
-    return starts, pos
-
-
 def plan_front_end(lengths, rates, hr_rate: int, lr_rate: int, is_lr_input: bool, segment_length: int, gen_overlap: int,
                    batch_size: int, out_segment_length=None, align: int = 64) -> FrontEndPlan:
     """Where every utterance reads and writes in every step of AudioTestDataset.post_processing (host only: no device call).
     Utterance u of lengths[u] samples at rates[u] Hz goes to hr_rate (is_lr_input) or down to lr_rate and back up to hr_rate;
-    each step's lengths are mg_resample_length of the step before.  Every packed buffer has generate_audio._pack_waves' layout
+    each step's lengths are resample_length of the step before.  Every packed buffer has packed.aligned_layout's layout
     (starts rounded up to `align` samples), the last one exactly the one plan_utterances(final lengths, segment_length,
     out_segment_length (default: segment_length), gen_overlap, batch_size) describes."""
     from .generate_audio import plan_utterances
@@ -288,15 +238,12 @@ def plan_front_end(lengths, rates, hr_rate: int, lr_rate: int, is_lr_input: bool
     if min(lengths) <= 0 or min(rates) <= 0 or int(hr_rate) <= 0 or int(lr_rate) <= 0:
         raise ValueError("lengths and sampling rates must be positive")
     targets = [int(hr_rate)] if is_lr_input else [int(lr_rate), int(hr_rate)]
-    all_lengths, all_starts, totals, steps = [lengths], [], [], []
-    starts, total = _aligned_starts(lengths, align)
-    all_starts.append(starts)
-    totals.append(total)
-    now = rates
+    layouts, steps, now = [aligned_layout(lengths, align)], [], rates
     for target in targets:
-        src_len, src_start = all_lengths[-1], all_starts[-1]
+        src_len, src_start = layouts[-1].lengths, layouts[-1].starts
         dst_len = [resample_length(n, r, target) for n, r in zip(src_len, now)]
-        dst_start, total = _aligned_starts(dst_len, align)
+        layouts.append(aligned_layout(dst_len, align))
+        dst_start = layouts[-1].starts
         members = {}
         for u, r in enumerate(now):
             members.setdefault(r, []).append(u)
@@ -304,18 +251,16 @@ def plan_front_end(lengths, rates, hr_rate: int, lr_rate: int, is_lr_input: bool
                                     np.asarray([(src_start[u], src_len[u], dst_start[u], dst_len[u]) for u in idx],
                                                dtype=np.int64).reshape(-1, 4), max(dst_len[u] for u in idx))
                       for r, idx in members.items()])
-        all_lengths.append(dst_len)
-        all_starts.append(dst_start)
-        totals.append(total)
         now = [target] * len(lengths)
     L = int(segment_length)
-    utt = plan_utterances(all_lengths[-1], L, L if out_segment_length is None else int(out_segment_length), gen_overlap, batch_size,
-                          align)
-    assert utt.in_start == all_starts[-1] and utt.in_total == totals[-1]
-    return FrontEndPlan(rates, all_lengths, all_starts, totals, steps, [u for g in steps[0] for u in g.index], utt)
+    utt = plan_utterances(layouts[-1].lengths, L, L if out_segment_length is None else int(out_segment_length), gen_overlap,
+                          batch_size, align)
+    assert utt.in_layout == layouts[-1]                         # (both come from aligned_layout)
+    return FrontEndPlan(rates, [p.lengths for p in layouts], [p.starts for p in layouts], [p.total for p in layouts], steps,
+                        [u for g in steps[0] for u in g.index], utt)
 
 
-def _front_end_options(opt) -> dict:
+def data_options(opt) -> dict:
     """lr_sampling_rate, hr_sampling_rate and segment_length are required; is_lr_input / add_noise default to off, snr to 55,
     gen_overlap to 0, batch_size to 64, out_segment_length to segment_length.  `opt`: an options namespace or a dict."""
     get = (lambda k, d=None: opt.get(k, d)) if isinstance(opt, dict) else (lambda k, d=None: getattr(opt, k, d))
@@ -332,9 +277,9 @@ def _front_end_options(opt) -> dict:
 def front_end_many(raws, rates, opt_or_kwargs, noise=None, generator=None, device=None, keep_raw=False):
     """AudioTestDataset.read_audio + post_processing (data/audio_dataset.py:141-186) for a list of raw waveforms ([T_u] or
     [1, T_u], on the host or the device) at sampling rates `rates` -> (packed, views, plan): the packed low-rate buffer at
-    hr_sampling_rate (float32 [plan.totals[-1]], generate_audio._pack_waves' layout, zeros in the gaps), one [1, T'_u] view of it
+    hr_sampling_rate (float32 [plan.totals[-1]], packed.pack_waves' layout, zeros in the gaps), one [1, T'_u] view of it
     per utterance, and the FrontEndPlan (plan.utterances: the UtterancePlan generate_many's tables come from).
-    opt_or_kwargs: an options namespace or a dict (see _front_end_options).  Under add_noise, `noise` is a list of per-utterance
+    opt_or_kwargs: an options namespace or a dict (see data_options).  Under add_noise, `noise` is a list of per-utterance
     waveforms of the final lengths (for tests: the reference draws from the CPU stream, which a device cannot reproduce);
     otherwise torch.randn(..., generator=generator) on the device.
     Launches: one packing copy, one table copy, mg_rows_moments, a handful of element-wise launches over [U] for the shift, one
@@ -342,8 +287,7 @@ def front_end_many(raws, rates, opt_or_kwargs, noise=None, generator=None, devic
     whatever the number of utterances.  No host read-back.
     keep_raw: plan.raw keeps the packed raw buffer and the shift in utterance order (see FrontEndPlan; one more element-wise launch
     when the rates differ); nothing else changes."""
-    from .generate_audio import _pack_waves
-    o = _front_end_options(opt_or_kwargs)
+    o = data_options(opt_or_kwargs)
     raws = list(raws)
     if len(raws) == 0:
         raise ValueError("no waveforms")
@@ -360,43 +304,33 @@ def front_end_many(raws, rates, opt_or_kwargs, noise=None, generator=None, devic
     if device is None:
         device = next((w.device for w in raws if w.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
 
-    def layout(s):
-        return SimpleNamespace(in_total=plan.totals[s], in_start=plan.starts[s], lengths=plan.lengths[s])
-
-    # every table in one host array and one copy: the raw windows in group order, the final windows, then each group's rows
-    def windows(s, order):
-        first = np.asarray([plan.starts[s][u] for u in order], dtype=np.int64)
-        return np.stack([first, first, first + np.asarray([plan.lengths[s][u] for u in order], dtype=np.int64)], axis=1)
+    # every table in one copy: the raw windows in group order, the final windows, each group's rows, then where utterance u sits in
+    # plan.order
     U = len(raws)
-    parts = [windows(0, plan.order).reshape(-1), windows(-1, range(U)).reshape(-1)]
-    parts += [g.rows.reshape(-1) for step in plan.steps for g in step]
     reorder = keep_raw and plan.order != list(range(U))
-    if reorder:                                                 # (where utterance u sits in plan.order)
-        parts.append(np.argsort(np.asarray(plan.order, dtype=np.int64), kind="stable"))
-    tables = torch.from_numpy(np.concatenate(parts)).to(device, non_blocking=True)
-    raw_win, lr_win = tables[:3 * U].view(U, 3), tables[3 * U:6 * U].view(U, 3)
+    raw_win, lr_win, *group_rows = upload_tables(
+        [window_table(plan.starts[0], plan.lengths[0], plan.order), window_table(plan.starts[-1], final)]
+        + [g.rows for step in plan.steps for g in step]
+        + ([np.argsort(np.asarray(plan.order, dtype=np.int64), kind="stable")] if reorder else []), device)
+    place = group_rows.pop() if reorder else None
 
-    buf = _pack_waves(raws, layout(0), device)
+    buf = pack_waves(raws, PackedLayout(plan.starts[0], plan.lengths[0], plan.totals[0]), device)
     mom = rows_moments(buf, raw_win, max(plan.lengths[0]))
     shift = (1e-4 - mom[:, 0] / (raw_win[:, 2] - raw_win[:, 1]).double()).float()     # raw += 1e-4 - mean(raw), per utterance
     if keep_raw:
-        plan.raw = SimpleNamespace(buffer=buf, shift=shift[tables[-U:]].contiguous() if reorder else shift,
+        plan.raw = SimpleNamespace(buffer=buf, shift=shift[place].contiguous() if reorder else shift,
                                    starts=plan.starts[0], lengths=plan.lengths[0])
-    at = 6 * U
+    tables = iter(group_rows)
     for s, step in enumerate(plan.steps):
         out = torch.zeros(plan.totals[s + 1], dtype=torch.float32, device=device)
         row = 0
         for g in step:
             n = len(g.index)
-            resample_rows(buf, tables[at:at + 4 * n].view(n, 4), g.max_out_len, g.orig_freq, g.new_freq, out,
+            resample_rows(buf, next(tables), g.max_out_len, g.orig_freq, g.new_freq, out,
                           shift=shift[row:row + n] if s == 0 else None)
-            at, row = at + 4 * n, row + n
+            row += n
         buf = out
     if o["add_noise"]:
-        if noise is None:
-            z = torch.randn(buf.numel(), dtype=torch.float32, device=device, generator=generator)
-        else:
-            z = _pack_waves(list(noise), layout(-1), device)
-        add_noise_rows(buf, z, lr_win, max(final), rows_moments(buf, lr_win, max(final)), rows_moments(z, lr_win, max(final)),
-                       o["snr"], o["segment_length"])
+        z = noise_buffer(noise, plan.utterances.in_layout, device, generator)
+        add_noise_packed(buf, lr_win, max(final), o["snr"], o["segment_length"], z)
     return buf, [buf[s0:s0 + n].view(1, -1) for s0, n in zip(plan.starts[-1], final)], plan

@@ -13,17 +13,16 @@ Decoding files stays outside: the caller hands over loaded
 """
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass, field
-from types import SimpleNamespace
 from typing import List
 
 import numpy as np
 import torch
 
 from . import _lib
-from .resample import (_aligned_starts, _front_end_options, _sinc_kernel, _table, add_noise_rows, make_training_pair, resample,
-                       rows_moments)
+from .packed import (PackedLayout, add_noise_packed, aligned_layout, check_table, noise_buffer, pack_waves, upload_tables,
+                     window_table)
+from .resample import data_options, filter_bank, make_training_pair, resample, resample_length
 
 __all__ = ["TrainingCorpus", "TrainingBatchPlan", "pack_corpus", "crop_window", "draw_windows", "windows_at", "pair_lengths",
            "plan_training_batch", "train_pair_rows", "training_batch_many", "make_graphed_training_batch",
@@ -51,7 +50,6 @@ class TrainingCorpus:
 
 def pack_corpus(waveforms, rates, device, align: int = 64) -> TrainingCorpus:
     """Loaded waveforms ([T] or [1, T], on the host or the device) at `rates` Hz -> one packed float32 buffer on `device`."""
-    from .generate_audio import _pack_waves
     waveforms = list(waveforms)
     rates = [int(r) for r in rates]
     if not waveforms or len(waveforms) != len(rates):
@@ -59,9 +57,8 @@ def pack_corpus(waveforms, rates, device, align: int = 64) -> TrainingCorpus:
     lengths = [int(w.numel()) for w in waveforms]
     if min(lengths) <= 0 or min(rates) <= 0:
         raise ValueError("lengths and sampling rates must be positive")
-    starts, total = _aligned_starts(lengths, int(align))
-    buf = _pack_waves(waveforms, SimpleNamespace(in_total=total, in_start=starts, lengths=lengths), device)
-    return TrainingCorpus(buf, starts, lengths, rates)
+    layout = aligned_layout(lengths, align)
+    return TrainingCorpus(pack_waves(waveforms, layout, device), layout.starts, lengths, rates)
 
 
 def crop_window(audio_length: int, fs: int, segment_length: int, hr_rate: int) -> int:
@@ -118,16 +115,11 @@ def windows_at(corpus: TrainingCorpus, indices, offsets, segment_length: int, hr
     return torch.tensor(out_off, dtype=torch.int64), torch.tensor(out_len, dtype=torch.int64)
 
 
-def _resampled(length: int, orig_freq: int, new_freq: int) -> int:
-    g = math.gcd(int(orig_freq), int(new_freq))
-    return -(-(int(new_freq) // g) * int(length) // (int(orig_freq) // g))
-
-
 def pair_lengths(length: int, fs: int, hr_rate: int, lr_rate: int):
     """(hr_len, mid_len, lr_len) of a window of `length` samples at fs Hz: ceil(hr L / fs), mid_len = ceil(lr L / fs) and
     ceil(hr mid_len / lr) -- the lengths aF.resample returns in :66-71.  The first and the last differ in general."""
-    mid = _resampled(length, fs, lr_rate)
-    return _resampled(length, fs, hr_rate), mid, _resampled(mid, lr_rate, hr_rate)
+    mid = resample_length(length, fs, lr_rate)
+    return resample_length(length, fs, hr_rate), mid, resample_length(mid, lr_rate, hr_rate)
 
 
 @dataclass
@@ -185,7 +177,8 @@ def plan_training_batch(corpus: TrainingCorpus, indices, offsets, lengths, segme
         raise ValueError("pad_to is at least the batch (%d) and not for add_noise" % B)
     trio = [pair_lengths(n, corpus.rates[i], hr_rate, lr_rate) for i, n in zip(idx, lens)]
     hr_len, mid_len, lr_len = ([t[k] for t in trio] for k in range(3))
-    full_start, full_total = _aligned_starts(lr_len, int(align)) if add_noise else ([0] * B, 0)
+    full = aligned_layout(lr_len, align) if add_noise else PackedLayout([0] * B, lr_len, 0)
+    full_start, full_total = full.starts, full.total
     members = {}
     for b, i in enumerate(idx):
         members.setdefault(corpus.rates[i], []).append(b)
@@ -203,12 +196,9 @@ def plan_training_batch(corpus: TrainingCorpus, indices, offsets, lengths, segme
 
 
 def _bank(orig_freq: int, new_freq: int, device):
-    """mg_resample_bank of one step (the filter is resample._sinc_kernel's, cached for the life of the process); equal rates: the
-    copy bank."""
-    if int(orig_freq) == int(new_freq):
-        return _lib.ResampleBank(None, 1, 1, 0)
-    kern, width, orig, new = _sinc_kernel(orig_freq, new_freq, 6, 0.99, device)
-    return _lib.ResampleBank(kern.data_ptr(), orig, new, width)
+    """mg_resample_bank of one step, from resample.filter_bank; its identity bank (equal rates) travels as the copy bank."""
+    kern, width, orig, new = filter_bank(orig_freq, new_freq, device)
+    return _lib.ResampleBank(kern.data_ptr() if (orig, new) != (1, 1) else None, orig, new, width)
 
 
 def train_pair_rows(corpus_buffer: torch.Tensor, table: torch.Tensor, segment_length: int, file_rate: int, hr_rate: int,
@@ -217,7 +207,7 @@ def train_pair_rows(corpus_buffer: torch.Tensor, table: torch.Tensor, segment_le
     window of the packed corpus and writes row out_row of hr and lr ([rows, segment_length] float32) -- or, with lr_full (a packed
     float32 buffer), its whole low-rate signal to lr_full[full_pos : full_pos + full_len] in place of lr."""
     lib = _lib.load()
-    n = _table(table, ROW_COLS, "train_pair_rows").shape[0]
+    n = check_table(table, ROW_COLS, "train_pair_rows").shape[0]
     L = int(segment_length)
     if corpus_buffer.dtype != torch.float32 or not corpus_buffer.is_contiguous():
         raise ValueError("train_pair_rows: the corpus is a contiguous float32 buffer")
@@ -276,7 +266,7 @@ def training_batch_many(corpus: TrainingCorpus, indices, opt_or_kwargs, offsets=
     Launches: one table copy and mg_train_pair_rows per distinct file rate; under add_noise also two mg_rows_moments,
     mg_add_noise_rows and mg_segments_gather -- whatever the batch size.  Nothing is read back."""
     from .mdct import segments_gather
-    o = _front_end_options(opt_or_kwargs)
+    o = data_options(opt_or_kwargs)
     L, hr_rate, lr_rate = int(o["segment_length"]), int(o["hr_sampling_rate"]), int(o["lr_sampling_rate"])
     idx = _indices(corpus, indices)
     offsets, lengths = _windows(corpus, idx, o, offsets, lengths, generator)
@@ -291,28 +281,16 @@ def training_batch_many(corpus: TrainingCorpus, indices, opt_or_kwargs, offsets=
         raise ValueError("noise= is for add_noise")
     lr, hr = _out_pair(out, B, L, dev)
 
-    # every table in one host array and one copy: each group's rows, then under add_noise the windows of lr_full in batch order
-    parts = [plan.table().reshape(-1)]
+    # every table in one copy: each group's rows, then under add_noise the windows of lr_full in batch order
+    full = PackedLayout(plan.full_start, plan.lr_len, plan.full_total)
+    *group_rows, win = upload_tables([g.rows for g in plan.groups]
+                                     + [window_table(full.starts, full.lengths) if o["add_noise"] else []], dev)
+    lr_full = torch.empty(full.total, dtype=torch.float32, device=dev) if o["add_noise"] else None
+    for g, rows in zip(plan.groups, group_rows):
+        train_pair_rows(corpus.buffer, rows, L, g.file_rate, hr_rate, lr_rate, hr, None if o["add_noise"] else lr, lr_full,
+                        g.max_full_len)
     if o["add_noise"]:
-        first = np.asarray(plan.full_start, dtype=np.int64)
-        parts.append(np.stack([first, first, first + np.asarray(plan.lr_len, dtype=np.int64)], axis=1).reshape(-1))
-    tables = torch.from_numpy(np.concatenate(parts)).to(dev, non_blocking=True)
-    lr_full = torch.empty(plan.full_total, dtype=torch.float32, device=dev) if o["add_noise"] else None
-    at = 0
-    for g in plan.groups:
-        n = g.rows.shape[0]
-        train_pair_rows(corpus.buffer, tables[at:at + ROW_COLS * n].view(n, ROW_COLS), L, g.file_rate, hr_rate, lr_rate, hr,
-                        None if o["add_noise"] else lr, lr_full, g.max_full_len)
-        at += ROW_COLS * n
-    if o["add_noise"]:
-        from .generate_audio import _pack_waves
-        win, longest = tables[at:].view(B, 3), max(plan.lr_len)
-        if noise is None:
-            z = torch.randn(plan.full_total, dtype=torch.float32, device=dev, generator=noise_generator)
-        else:
-            z = _pack_waves(list(noise), SimpleNamespace(in_total=plan.full_total, in_start=plan.full_start, lengths=plan.lr_len),
-                            dev)
-        add_noise_rows(lr_full, z, win, longest, rows_moments(lr_full, win, longest), rows_moments(z, win, longest), o["snr"], L)
+        add_noise_packed(lr_full, win, max(plan.lr_len), o["snr"], L, noise_buffer(noise, full, dev, noise_generator))
         segments_gather(lr_full, win, L, out=lr)
     return lr, hr
 
@@ -324,7 +302,7 @@ def make_graphed_training_batch(corpus: TrainingCorpus, batch: int, opt_or_kwarg
     leave the remaining rows dead (they keep what they held).  The graph is a plain chain of two kernels.
     Defined for a corpus with ONE file rate (the launches of a capture are fixed; the row grouping of mixed rates is not);
     add_noise draws from a random stream inside the capture, which is out of scope."""
-    o = _front_end_options(opt_or_kwargs)
+    o = data_options(opt_or_kwargs)
     if len(corpus.distinct_rates) != 1:
         raise ValueError("make_graphed_training_batch needs a corpus with one file rate, this one has %s" % corpus.distinct_rates)
     if o["add_noise"]:

@@ -66,10 +66,9 @@ def main():
     args = ap.parse_args()
     dev = "cuda:0"
     from mdctgan_amd import _lib
-    from mdctgan_amd.generate_audio import _pack_waves
     from mdctgan_amd.mdct import kbdwin
     from mdctgan_amd.metrics import compute_matrics, compute_matrics_many, plan_metrics, power_spectra
-    from mdctgan_amd.resample import _aligned_starts
+    from mdctgan_amd.packed import aligned_layout, pack_waves
 
     opt = types.SimpleNamespace(n_fft=512, hop_length=256, win_length=512, center=True)
     hrs = corpus(args.utterances, args.seed, dev)
@@ -78,9 +77,8 @@ def main():
     lrs = [h + 0.015 * torch.randn(h.numel(), device=dev, generator=gen) for h in hrs]
     lengths = [h.numel() for h in hrs]
     real_seconds = sum(lengths) / RATE
-    starts, total = _aligned_starts(lengths, 64)
-    layout = types.SimpleNamespace(in_total=total, in_start=starts, lengths=lengths)
-    packed = [(_pack_waves(ws, layout, dev), starts, lengths) for ws in (hrs, lrs, srs)]
+    layout = aligned_layout(lengths, 64)
+    packed = [(pack_waves(ws, layout, dev), layout.starts, lengths) for ws in (hrs, lrs, srs)]
 
     def per_utterance():
         return [compute_matrics(h, l, s, opt) for h, l, s in zip(hrs, lrs, srs)]

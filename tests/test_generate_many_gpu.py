@@ -57,12 +57,13 @@ def test_segments_gather_equals_segment_audio(overlap, align):
     """One launch cuts the segments of five utterances (shorter than a segment, exactly one, one sample more, 20000, 4 L + 123)
     as segment_audio cuts each alone; dead rows are zeros; nothing is written behind the last row.  align 1 packs the waveforms
     back to back, so most rows start at positions that are no multiple of 4 (the scalar loads)."""
-    from mdctgan_amd.generate_audio import _pack_waves, plan_utterances, segment_audio
+    from mdctgan_amd.generate_audio import plan_utterances, segment_audio
+    from mdctgan_amd.packed import pack_waves
     from mdctgan_amd.mdct import seg_row_table, segments_gather
     waves = _waves(LENGTHS)
     plan = plan_utterances(LENGTHS, SEG, SEG, overlap, 5, align=align)
     assert plan.n_live == 12 and plan.in_rows.shape[0] == 15
-    packed = _pack_waves(waves, plan, DEV)
+    packed = pack_waves(waves, plan.in_layout, DEV)
     assert packed.numel() == plan.in_total
     table = seg_row_table(plan.in_rows, DEV)
     guard = 512
@@ -295,14 +296,15 @@ def test_generate_is_untouched_by_generate_many():
 
 def test_waveforms_may_live_on_the_host_or_on_both_sides():
     """The packed input is the same whether the list holds device tensors, host tensors or a mix of them."""
-    from mdctgan_amd.generate_audio import _pack_waves, plan_utterances
+    from mdctgan_amd.generate_audio import plan_utterances
+    from mdctgan_amd.packed import pack_waves
     waves = _waves(LENGTHS)
     plan = plan_utterances(LENGTHS, SEG, SEG, 100, 5)
-    want = _pack_waves(waves, plan, DEV)
+    want = pack_waves(waves, plan.in_layout, DEV)
     for u, w in enumerate(waves):
         assert torch.equal(want[plan.in_start[u]:plan.in_start[u] + w.numel()], w)
-    assert torch.equal(_pack_waves([w.cpu() for w in waves], plan, DEV), want)
-    assert torch.equal(_pack_waves([w.cpu() if u % 2 else w for u, w in enumerate(waves)], plan, DEV), want)
+    assert torch.equal(pack_waves([w.cpu() for w in waves], plan.in_layout, DEV), want)
+    assert torch.equal(pack_waves([w.cpu() if u % 2 else w for u, w in enumerate(waves)], plan.in_layout, DEV), want)
     static = torch.full((plan.in_total + 64,), SENTINEL, device=DEV)
-    assert _pack_waves(waves, plan, DEV, out=static).data_ptr() == static.data_ptr()
+    assert pack_waves(waves, plan.in_layout, DEV, out=static).data_ptr() == static.data_ptr()
     assert torch.equal(static[:plan.in_total], want) and (static[plan.in_total:] == SENTINEL).all()
