@@ -310,6 +310,23 @@ int mg_lsd_rows(const float* hr, long long hr_total, const float* sr, long long 
                 const long long* frame_start, long long total_frames, const float* hr_shift, const float* window, int n_fft,
                 int hop, int center, float* out, void* stream);
 
+/* The backward pass of mg_lsd_rows with respect to sr (hr is a constant), csrc/lsd_rows_grad.hip: with L_f the value mg_lsd_rows
+ * stores for frame f of row u, grad_sr = d (sum_u sum_f grad_rows[u] L_f) / d sr.  The arguments up to `center` are mg_lsd_rows'
+ * own and follow its rules.  grad_rows: float32 [n_rows], the gradient of row u's mean ALREADY divided by the row's frame count.
+ * grad_sr: float32 [sr_total]; sample t < len of a live row is written once, at grad_sr[sr_pos + t], and nothing else is (the
+ * caller zero-fills what it wants defined between the rows).  A frame with L_f == 0 (sr == hr, silence) contributes exactly 0,
+ * where the formula has 0 / 0.  Two launches whatever n_rows is, no atomics, every sum in one fixed order: a row has the same
+ * gradient bits alone as inside any pack.  workspace: mg_lsd_rows_backward_workspace(total_frames, n_fft) bytes, 16-byte aligned
+ * (one window-weighted float32 gradient frame of n_fft samples per frame; 0: invalid arguments).  MG_ERR_ARG before any launch
+ * for a null pointer (hr_shift may be NULL), n_fft outside {512, 1024, 2048}, a non-positive count, total or hop, a short or
+ * misaligned workspace.  Precondition of a centred transform: len > n_fft / 2 (one reflection per end, what plan_metrics and
+ * mg_stft_frames accept); a shorter live row is treated as dead here -- nothing of it is written. */
+size_t mg_lsd_rows_backward_workspace(long long total_frames, int n_fft);
+int mg_lsd_rows_backward(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows,
+                         int n_rows, const long long* frame_start, long long total_frames, const float* hr_shift,
+                         const float* window, int n_fft, int hop, int center, const float* grad_rows, float* grad_sr,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Segment stitching of generate_audio.py:40-53: seg [n_seg, seg_len] (the [n_seg,1,1,T] inference outputs) -> one
  * waveform of mg_stitch_length() samples (-1: invalid arguments; 2*overlap must be < seg_len).  overlap == 0
  * concatenates; overlap > 0 halves the first/last `overlap` samples of every segment, overlap-adds at stride

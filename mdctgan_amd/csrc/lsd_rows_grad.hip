@@ -1,0 +1,220 @@
+// The backward pass of lsd_rows_kernel (metrics_rows.hip): the gradient of every utterance's log-spectral distance with respect to
+// its super-resolved waveform sr, for any pack of utterances, in two launches without atomics.  hr is a constant.
+//
+// For one frame, with NB = N/2 + 1 bins, p = |X|^2, d_k = log10(p_hr[k] + 1e-6) - log10(p_sr[k] + 1e-6), L = sqrt(sum d_k^2 / NB)
+// and the upstream g (the row's gradient, already divided by the row's frame count):
+//     dL/dx_w[n] = sum_k c_k 2 Re(X_sr[k] exp(+2 pi i k n / N)),   c_k = -g d_k / (L NB ln 10 (p_sr[k] + 1e-6)),
+// i.e. y = Re sum_{k=0..N/2} G_k exp(+2 pi i k n / N) with G_k = 2 c_k X_sr[k]: the unnormalised inverse real transform of the
+// Hermitian spectrum H_k = G_k / 2 (0 < k < N/2), Re G_k (k = 0, N/2).  A frame with L == 0 (sr == hr, silence) contributes 0
+// by definition.  Then dL/dx = the adjoint of framing and reflection applied to y[n] window[n].
+//
+//   lsd_rows_grad_frames_kernel   the forward's tile, row search, staging and Stockham stages (lsd_fft.h); the epilogue in double
+//       as the forward's: pass one keeps d_k / (p_sr[k] + 1e-6) and X_sr[k] of the lane's 9 bins in registers and sums d_k^2 in
+//       the forward's tree (every lane of the frame ends with the sum); pass two writes H_k, k = 0 .. N/2, over the frame's own
+//       LDS region (after a barrier: lsd_real_bin read Z[k] and Z[M-k] from other lanes).  The inverse real transform is the
+//       adjoint of the forward's pack-and-split, M = N/2:
+//           A_k = H_k + conj H_{M-k},   B_k = (H_k - conj H_{M-k}) exp(+2 pi i k / N),   Zt_k = A_k + i B_k,   k = 0 .. M-1,
+//           y[2m] + i y[2m+1] = sum_k Zt_k exp(+2 pi i k m / M) = conj DFT_M(conj Zt)[m],
+//       so the forward stages run once more, on conj Zt, over the half tile that the Zt of all frames fill when packed densely.
+//       y[n] window[n] goes to the workspace [total_frames][N] (float32) in 16-byte stores.
+//       LDS: the forward's 32 KiB of frame data + 8 N bytes of roots, which would admit three workgroups per CU; the 206-232
+//       VGPRs (no scratch) admit two.
+//   lsd_rows_grad_gather_kernel   one thread per sample slot; row u owns the slots [S_u, S_u + frames_u hop + N), S_u =
+//       frame_start[u] hop + u N (its len never exceeds that), found by binary search.  Sample t sums the workspace taps that
+//       framing mapped to it -- the direct position t, on a centred transform the left reflection -t (1 <= t <= N/2) and the
+//       right reflection 2 (len - 1) - t (t < len - 1, inside the right padding); for each, every frame whose span covers the
+//       position, ascending -- in double in that order, rounds once and stores once to grad_sr[sr_pos + t].  Samples outside the
+//       rows, dead rows, samples outside the sr buffer and centred rows of at most N/2 samples (the forward's staging would
+//       reflect them twice; plan_metrics refuses them) are never written.
+// Neither kernel's arithmetic for a row depends on where the row sits: a row has the same gradient bits alone and in any pack.
+#include <math.h>
+
+#include "lsd_fft.h"
+
+namespace {
+
+template <int N, bool SHIFT>
+__global__ __launch_bounds__(LSD_NT) void lsd_rows_grad_frames_kernel(const float* __restrict__ hr, long long hr_total,
+                                                                      const float* __restrict__ sr, long long sr_total,
+                                                                      const mg_metric_row* __restrict__ rows, int n_rows,
+                                                                      const long long* __restrict__ frame_start,
+                                                                      long long total_frames, const float* __restrict__ shift,
+                                                                      const float* __restrict__ window,
+                                                                      const float* __restrict__ grad_rows, int hop, int center,
+                                                                      long long n_tiles, float* __restrict__ frames_out) {
+    constexpr int M = N / 2, FT = LSD_TILE / N, TPF = LSD_NT / FT, NBINS = N / 2 + 1, BPL = (NBINS + TPF - 1) / TPF;
+    constexpr int HALF = LSD_TILE / 2;                                      // the Zt of the tile's frames, densely: [FT][M]
+    static_assert(TPF >= 32 && M % LSD_NT == 0, "a frame's lanes fill whole half-waves, a load pass stays inside one signal of a frame");
+    static_assert(HALF % LSD_NT == 0 && (HALF / 2) % LSD_NT == 0 && M % 2 == 0, "whole points and whole point pairs per thread");
+    __shared__ __attribute__((aligned(16))) float2 buf[LSD_TILE];          // [FT][hr, sr][M], then [FT][H: M + 1], then [FT][M]
+    __shared__ __attribute__((aligned(16))) float2 root[N];
+    __shared__ double red[LSD_NT / 64];
+    __shared__ LsdFrame info[FT];
+    __shared__ float upstream[FT];
+    const int tid = threadIdx.x;
+    lsd_roots<N>(root, tid);
+    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        if (tid < FT) {
+            int row;
+            const LsdFrame fi = lsd_locate<SHIFT>(tile * FT + tid, rows, n_rows, frame_start, total_frames, shift, N, hop, center, row);
+            info[tid] = fi;
+            upstream[tid] = fi.live ? grad_rows[row] : 0.0f;
+        }
+        __syncthreads();
+        lsd_load_tile<N, SHIFT>(buf, info, hr, hr_total, sr, sr_total, window, center, tid);
+        __syncthreads();
+        lsd_fft<M>(buf, root, tid);
+        // pass one: bins k = j, j + TPF, ... of frame fr on lane j of the frame's TPF lanes
+        const int fr = tid / TPF, j = tid % TPF;
+        float2* Zh = buf + fr * N;
+        const float2* Zs = Zh + M;
+        double e[BPL];                                      // d_k / (p_sr[k] + 1e-6)
+        float2 xs[BPL];                                     // X_sr[k]
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < BPL; ++i) {
+            const int k = j + i * TPF;
+            e[i] = 0.0;
+            xs[i] = make_float2(0.0f, 0.0f);
+            if (k < NBINS) {
+                const float2 w = root[k];
+                const float2 a = lsd_real_bin<M>(Zh, k, w), b = lsd_real_bin<M>(Zs, k, w);
+                const double pa = (double)a.x * a.x + (double)a.y * a.y, pb = (double)b.x * b.x + (double)b.y * b.y;
+                const double d = log10(pa + 1e-6) - log10(pb + 1e-6);
+                acc += d * d;
+                e[i] = d / (pb + 1e-6);
+                xs[i] = b;
+            }
+        }
+#pragma unroll
+        for (int o = (TPF < 64 ? TPF : 64) / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        if (TPF > 64) {
+            if ((tid & 63) == 0) red[tid >> 6] = acc;
+            __syncthreads();
+            acc = red[fr * (TPF / 64)];
+            for (int w = 1; w < TPF / 64; ++w) acc += red[fr * (TPF / 64) + w];
+        }
+        __syncthreads();                                    // every lane has read its Z[k] and Z[M-k]
+        // pass two: H_k over the frame's region, k = 0 .. M (one point into the sr half)
+        const double L = sqrt(acc / NBINS);
+        const double scale = (info[fr].live && acc > 0.0) ? -2.0 * (double)upstream[fr] / (L * NBINS * 2.302585092994045684) : 0.0;
+#pragma unroll
+        for (int i = 0; i < BPL; ++i) {
+            const int k = j + i * TPF;
+            if (k < NBINS) {
+                const double c = scale * e[i];
+                Zh[k] = (k == 0 || k == M) ? make_float2((float)(c * (double)xs[i].x), 0.0f)
+                                           : make_float2((float)(0.5 * c * (double)xs[i].x), (float)(0.5 * c * (double)xs[i].y));
+            }
+        }
+        __syncthreads();
+        // conj Zt of every frame, held in registers until all H are read, then packed densely
+        float2 zt[HALF / LSD_NT];
+#pragma unroll
+        for (int it = 0; it < HALF / LSD_NT; ++it) {
+            const int idx = tid + it * LSD_NT, f2 = idx / M, k = idx % M;
+            const float2 h1 = buf[f2 * N + k], h2 = buf[f2 * N + M - k], w = root[k];
+            const float2 a = make_float2(h1.x + h2.x, h1.y - h2.y);                         // H_k + conj H_{M-k}
+            const float2 b = lsd_cmul(make_float2(h1.x - h2.x, h1.y + h2.y), make_float2(w.x, -w.y));
+            zt[it] = make_float2(a.x - b.y, -(a.y + b.x));                                  // conj (a + i b)
+        }
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < HALF / LSD_NT; ++it) buf[tid + it * LSD_NT] = zt[it];
+        __syncthreads();
+        lsd_fft<M, HALF>(buf, root, tid);
+        // y[2m] = Re, y[2m+1] = -Im of the transform; two points = four samples per store
+#pragma unroll
+        for (int it = 0; it < HALF / 2 / LSD_NT; ++it) {
+            const int idx = tid + it * LSD_NT, f2 = idx / (M / 2), n = 4 * (idx % (M / 2));
+            const long long g = tile * FT + f2;
+            if (g < total_frames) {
+                const float4 v = *reinterpret_cast<const float4*>(buf + f2 * M + n / 2);
+                *reinterpret_cast<float4*>(frames_out + g * N + n) =
+                    make_float4(v.x * window[n], -v.y * window[n + 1], v.z * window[n + 2], -v.w * window[n + 3]);
+            }
+        }
+        __syncthreads();                                    // buf, info, upstream and red are free for the next tile
+    }
+}
+
+__global__ __launch_bounds__(256) void lsd_rows_grad_gather_kernel(const float* __restrict__ frames, const mg_metric_row* __restrict__ rows,
+                                                                   int n_rows, const long long* __restrict__ frame_start,
+                                                                   long long total_frames, int n_fft, int hop, int center,
+                                                                   long long sr_total, long long n_slots,
+                                                                   float* __restrict__ grad_sr) {
+    const long long N = n_fft, H = hop, off = center ? N / 2 : 0;
+    for (long long s = (long long)blockIdx.x * 256 + threadIdx.x; s < n_slots; s += (long long)gridDim.x * 256) {
+        int lo = 0, hi = n_rows;                           // the last u with S_u <= s
+        while (hi - lo > 1) {
+            const int mid = lo + ((hi - lo) >> 1);
+            if (frame_start[mid] * H + mid * N <= s) lo = mid; else hi = mid;
+        }
+        const mg_metric_row rw = rows[lo];
+        const long long f0 = frame_start[lo], nf = frame_start[lo + 1] - f0, t = s - (f0 * H + lo * N);
+        // (the frames kernel's rules: a table that does not agree with itself loses samples, it reads nothing outside the workspace)
+        if (!lsd_row_ok(rw) || f0 < 0 || nf <= 0 || nf - 1 > INT_MAX || f0 + nf > total_frames || t < 0 || t >= rw.len) continue;
+        // a centred row of at most N/2 samples is reflected twice by the staging (the planner refuses it): it gets no gradient
+        if (center && rw.len <= N / 2) continue;
+        const long long p = rw.sr_pos + t;
+        if (p < 0 || p >= sr_total) continue;
+        double acc = 0.0;
+        // the taps at position q of the padded row (tap 0 of frame 0 = position 0), frames ascending
+        auto take = [&](long long q) {
+            const long long f_lo = q - N + 1 <= 0 ? 0 : (q - N + H) / H;
+            const long long f_hi = q / H < nf - 1 ? q / H : nf - 1;
+            for (long long f = f_lo; f <= f_hi; ++f) acc += (double)frames[(f0 + f) * N + (q - f * H)];
+        };
+        take(t + off);
+        if (center) {
+            if (t >= 1 && t <= N / 2) take(off - t);
+            const long long r = 2 * (rw.len - 1) - t;
+            if (t < rw.len - 1 && r <= rw.len - 1 + N / 2) take(r + off);
+        }
+        grad_sr[p] = (float)acc;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// See include/mdctgan_hip.h.
+size_t mg_lsd_rows_backward_workspace(long long total_frames, int n_fft) {
+    if (total_frames <= 0 || !lsd_size_ok(n_fft) || total_frames > kFar / (n_fft * (long long)sizeof(float))) return 0;
+    return (size_t)total_frames * (size_t)n_fft * sizeof(float);
+}
+
+int mg_lsd_rows_backward(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows,
+                         int n_rows, const long long* frame_start, long long total_frames, const float* hr_shift,
+                         const float* window, int n_fft, int hop, int center, const float* grad_rows, float* grad_sr,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    if (!hr || !sr || !rows || !frame_start || !window || !grad_rows || !grad_sr || !workspace) return MG_ERR_ARG;
+    if (n_rows <= 0 || total_frames <= 0 || hr_total <= 0 || sr_total <= 0 || hop <= 0 || !lsd_size_ok(n_fft)) return MG_ERR_ARG;
+    const size_t need = mg_lsd_rows_backward_workspace(total_frames, n_fft);
+    if (need == 0 || workspace_bytes < need || !al16(workspace)) return MG_ERR_ARG;
+    if (total_frames > (kFar - (long long)n_rows * n_fft) / hop) return MG_ERR_ARG;          // the gather's slot count
+    float* frames = static_cast<float*>(workspace);
+    const long long ft = LSD_TILE / n_fft, n_tiles = (total_frames + ft - 1) / ft;
+    const unsigned blocks = (unsigned)(n_tiles < 2 * 256 * 4 ? n_tiles : 2 * 256 * 4);    // a few waves of two workgroups per CU (VGPR-bound)
+    hipStream_t st = (hipStream_t)stream;
+#define MG_LSDG_LAUNCH(NN, S)                                                                                                    \
+    hipLaunchKernelGGL((lsd_rows_grad_frames_kernel<NN, S>), dim3(blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rows, \
+                       n_rows, frame_start, total_frames, hr_shift, window, grad_rows, hop, center != 0, n_tiles, frames)
+#define MG_LSDG_SIZE(NN) do { if (hr_shift) MG_LSDG_LAUNCH(NN, true); else MG_LSDG_LAUNCH(NN, false); } while (0)
+    if (n_fft == 512) MG_LSDG_SIZE(512);
+    else if (n_fft == 1024) MG_LSDG_SIZE(1024);
+    else MG_LSDG_SIZE(2048);
+#undef MG_LSDG_SIZE
+#undef MG_LSDG_LAUNCH
+    MG_CHECK_LAUNCH();
+    const long long n_slots = total_frames * hop + (long long)n_rows * n_fft;
+    const long long want = (n_slots + 255) / 256;
+    const unsigned gblocks = (unsigned)(want < 256 * 64 ? want : 256 * 64);
+    hipLaunchKernelGGL(lsd_rows_grad_gather_kernel, dim3(gblocks), dim3(256), 0, st, frames, rows, n_rows, frame_start, total_frames,
+                       n_fft, hop, center != 0, sr_total, n_slots, grad_sr);
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+}
+
+}  // extern "C"

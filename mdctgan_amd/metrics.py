@@ -142,30 +142,28 @@ def _packed_operand(x, what: str):
     return None, waves, [int(w.numel()) for w in waves]
 
 
-def compute_matrics_many(hrs, lrs, srs, opt, hr_shift=None):
-    """``compute_matrics`` for every utterance of a test set on its own (generate_audio.py:57-67), in shared launches.
-    hrs / lrs / srs: lists of waveforms ([T_u] or [1, T_u], host or device; packed here with packed.aligned_layout's layout), or packed
-    operands that are read where they lie -- ``(buffer, starts, lengths)`` (hrs), ``(buffer, starts)`` or ``(buffer, starts,
-    lengths)`` (lrs, srs) with a contiguous float32 device buffer and host lists, as front_end_many and generate_many leave them.
-    Utterance u is scored over len_u = len(hr_u) samples; lr_u and sr_u are cropped to that and must not be shorter (ValueError).
-    hr_shift: float32 [U] on the device; every ground-truth sample enters as hr + hr_shift[u] (one float32 add) -- read_audio's
-    un-materialised DC shift.  -> float64 device tensor [U, 7], row u = (mse, snr_sr, snr_lr, 0, 0, 0, lsd) of utterance u alone,
-    with the same bits whatever else shares the call.  Launches: one table copy (plus one packing copy per operand given as a
-    list), mg_metrics_rows_packed, mg_lsd_rows, mg_rows_moments and a few element-wise launches over [U], whatever U is; nothing
-    is read back."""
+def _metric_operands(operands, opt, hr_shift, differentiable=False):
+    """What compute_matrics_many and the LSD loss do before their launches, stated once so that the two stay in step.  operands:
+    ((hrs, "hrs"), ..., (srs, "srs")), the ground truth first; every other one is cropped to its lengths and must not be shorter.
+    Checks the transform (2 * opt.n_fft in LSD_ROWS_N_FFT, win_length == n_fft), the operand forms, the counts, the lengths and
+    hr_shift, plans the frames, and packs what came as a list (packed.aligned_layout's layout; `differentiable`: a list with an
+    entry that requires grad is packed by one differentiable concatenation).
+    -> (n_fft, hop, win, plan, device, buffers, starts), buffers / starts in the operands' order."""
     n_fft, hop, win = 2 * int(opt.n_fft), 2 * int(opt.hop_length), 2 * int(opt.win_length)
     if win != n_fft:
         raise NotImplementedError("win_length != n_fft")
     if n_fft not in LSD_ROWS_N_FFT:
         raise NotImplementedError("mg_lsd_rows serves n_fft in %s (got %d)" % (LSD_ROWS_N_FFT, n_fft))
-    ops_ = [_packed_operand(x, name) for x, name in ((hrs, "hrs"), (lrs, "lrs"), (srs, "srs"))]
+    ops_ = [_packed_operand(x, name) for x, name in operands]
+    hrs = operands[0][0]
     if isinstance(hrs, tuple) and ops_[0][0] is not None and len(hrs) != 3:
         raise ValueError("hrs: a packed ground truth names its lengths: (buffer, starts, lengths)")
     lengths = ops_[0][2]
     U = len(lengths)
     if U == 0:
         raise ValueError("no waveforms")
-    for (_, _, avail), name in zip(ops_[1:], ("lr", "sr")):
+    for (_, _, avail), (_, name) in zip(ops_[1:], operands[1:]):
+        name = name[:-1]
         if len(avail) != U:
             raise ValueError("%d hr waveforms but %d %s waveforms" % (U, len(avail), name))
         for u in range(U):
@@ -180,13 +178,31 @@ def compute_matrics_many(hrs, lrs, srs, opt, hr_shift=None):
     for buf, ws, avail in ops_:
         if buf is None:
             layout = aligned_layout(avail)
-            buf, ws = pack_waves(ws, layout, device), layout.starts
+            with_grad = differentiable and torch.is_grad_enabled() and any(w.requires_grad for w in ws)
+            buf, ws = (_pack_with_grad if with_grad else pack_waves)(ws, layout, device), layout.starts
         bufs.append(buf)
         starts.append(ws)
-    hr, lr, sr = bufs
     if hr_shift is not None and (not hr_shift.is_cuda or hr_shift.dtype != torch.float32 or hr_shift.numel() != U
                                  or not hr_shift.is_contiguous()):
         raise ValueError("hr_shift is a contiguous float32 [%d] device tensor" % U)
+    return n_fft, hop, win, plan, device, bufs, starts
+
+
+def compute_matrics_many(hrs, lrs, srs, opt, hr_shift=None):
+    """``compute_matrics`` for every utterance of a test set on its own (generate_audio.py:57-67), in shared launches.
+    hrs / lrs / srs: lists of waveforms ([T_u] or [1, T_u], host or device; packed here with packed.aligned_layout's layout), or packed
+    operands that are read where they lie -- ``(buffer, starts, lengths)`` (hrs), ``(buffer, starts)`` or ``(buffer, starts,
+    lengths)`` (lrs, srs) with a contiguous float32 device buffer and host lists, as front_end_many and generate_many leave them.
+    Utterance u is scored over len_u = len(hr_u) samples; lr_u and sr_u are cropped to that and must not be shorter (ValueError).
+    hr_shift: float32 [U] on the device; every ground-truth sample enters as hr + hr_shift[u] (one float32 add) -- read_audio's
+    un-materialised DC shift.  -> float64 device tensor [U, 7], row u = (mse, snr_sr, snr_lr, 0, 0, 0, lsd) of utterance u alone,
+    with the same bits whatever else shares the call.  Launches: one table copy (plus one packing copy per operand given as a
+    list), mg_metrics_rows_packed, mg_lsd_rows, mg_rows_moments and a few element-wise launches over [U], whatever U is; nothing
+    is read back."""
+    n_fft, hop, win, plan, device, (hr, lr, sr), starts = _metric_operands(((hrs, "hrs"), (lrs, "lrs"), (srs, "srs")), opt,
+                                                                           hr_shift)
+    lengths = plan.lengths
+    U = len(lengths)
 
     # every table in one copy: the metric rows, frame_start, and the windows of the per-frame array
     rows = np.stack([np.asarray(t, dtype=np.int64) for t in (*starts, lengths)], axis=1)
@@ -223,6 +239,111 @@ def _window(win: int, device):
     if key not in _windows:
         _windows[key] = kbdwin(win).to(device=device, dtype=torch.float32).contiguous()
     return _windows[key]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The log-spectral distance as a loss: mg_lsd_rows forward, mg_lsd_rows_backward (csrc/lsd_rows_grad.hip) backward
+# ---------------------------------------------------------------------------------------------------------------------
+class _LsdRows(torch.autograd.Function):
+    """Per-utterance LSD [U] (float64) of a packed sr buffer against a packed, constant hr buffer.  Forward: mg_lsd_rows and
+    rows_moments, compute_matrics_many's statements.  Backward: the upstream gradient divided by every row's frame count, then
+    mg_lsd_rows_backward into a zero-filled buffer of sr's size."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, row_t, fs_t, frame_t, hr_shift, window, geom):
+        n_fft, hop, center, total_frames, max_frames = geom
+        lib = _lib.load()
+        per_frame = torch.empty(total_frames, dtype=torch.float32, device=sr.device)
+        _lib.check(lib.mg_lsd_rows(_lib.ptr(hr), hr.numel(), _lib.ptr(sr), sr.numel(), _lib.ptr(row_t), row_t.shape[0],
+                                   _lib.ptr(fs_t), total_frames, _lib.ptr(hr_shift), _lib.ptr(window), n_fft, hop, int(center),
+                                   _lib.ptr(per_frame), _lib.stream()), "mg_lsd_rows")
+        lsd_sum = rows_moments(per_frame, frame_t, max_frames)[:, 0]
+        ctx.save_for_backward(sr, hr, row_t, fs_t, frame_t, hr_shift, window)
+        ctx.geom = geom
+        return lsd_sum / (frame_t[:, 2] - frame_t[:, 1]).double()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        sr, hr, row_t, fs_t, frame_t, hr_shift, window = ctx.saved_tensors
+        n_fft, hop, center, total_frames, _ = ctx.geom
+        lib = _lib.load()
+        grad_rows = (grad.double() / (frame_t[:, 2] - frame_t[:, 1]).double()).float().contiguous()
+        grad_sr = torch.zeros_like(sr)
+        nbytes = lib.mg_lsd_rows_backward_workspace(total_frames, n_fft)
+        ws = _lib.workspace(nbytes, sr.device)
+        _lib.check(lib.mg_lsd_rows_backward(_lib.ptr(hr), hr.numel(), _lib.ptr(sr), sr.numel(), _lib.ptr(row_t), row_t.shape[0],
+                                            _lib.ptr(fs_t), total_frames, _lib.ptr(hr_shift), _lib.ptr(window), n_fft, hop,
+                                            int(center), _lib.ptr(grad_rows), _lib.ptr(grad_sr), _lib.ptr(ws), nbytes,
+                                            _lib.stream()), "mg_lsd_rows_backward")
+        return grad_sr, None, None, None, None, None, None, None
+
+
+def _pack_with_grad(waves, layout, device):
+    """pack_waves' buffer as one differentiable concatenation (the gradient of the packed buffer is cut back to the waveforms)."""
+    gap = torch.zeros(max(layout.total - sum(layout.lengths), 1), dtype=torch.float32, device=device)
+    parts = []
+    for w, s0, s1 in zip(waves, layout.starts, layout.starts[1:] + [layout.total]):
+        parts.append(w.reshape(-1).to(device=device, dtype=torch.float32))
+        if s1 - s0 > w.numel():
+            parts.append(gap[:s1 - s0 - w.numel()])
+    return torch.cat(parts)
+
+
+_lsd_tables = {}            # lsd_loss: the row tables of a dense geometry (B, T, n_fft, hop, center, device), uploaded once
+
+
+def _lsd_rows(hrs, srs, opt, hr_shift, table_key=None):
+    hr_op = _packed_operand(hrs, "hrs")
+    if any(t.requires_grad for t in ([hr_op[0]] if hr_op[0] is not None else hr_op[1])):
+        raise NotImplementedError("the LSD has no gradient with respect to hr: detach the ground truth")
+    n_fft, hop, win, plan, device, (hr, sr), starts = _metric_operands(((hrs, "hrs"), (srs, "srs")), opt, hr_shift,
+                                                                       differentiable=True)
+    lengths, center = plan.lengths, plan.center
+    U = len(lengths)
+
+    # compute_matrics_many's tables (no lr column), in one copy; a caller that names its geometry finds them again
+    tables = _lsd_tables.get(table_key) if table_key is not None else None
+    if tables is None:
+        rows = np.stack([np.asarray(t, dtype=np.int64) for t in (starts[0], [0] * U, starts[1], lengths)], axis=1)
+        tables = upload_tables([rows, plan.frame_start, window_table(plan.frame_start[:-1], plan.frames)], device)
+        if table_key is not None:
+            _lsd_tables[table_key] = tables
+    row_t, fs_t, frame_t = tables
+    geom = (n_fft, hop, center, plan.total_frames, max(plan.frames))
+    return _LsdRows.apply(sr, hr, row_t, fs_t, frame_t, hr_shift, _window(win, device), geom)
+
+
+def lsd_many(hrs, srs, opt, hr_shift=None):
+    """The log-spectral distance of every utterance on its own, differentiable in sr -> float64 device tensor [U]: column 6 of
+    ``compute_matrics_many`` bit for bit, from the same operand forms (lists of waveforms, or packed ``(buffer, starts,
+    lengths)`` / ``(buffer, starts[, lengths])`` read where they lie), the same ``plan_metrics`` table and the same launches
+    (mg_lsd_rows, mg_rows_moments).  The gradient reaches a packed sr buffer that requires grad, or the list entries that do
+    (packed then by one differentiable concatenation); it is mg_lsd_rows_backward's: two launches whatever U is, deterministic,
+    exactly 0 on frames whose distance is 0 (sr == hr, silence), where autograd through torch.stft has NaN.  hr is a constant:
+    a ground truth that requires grad raises NotImplementedError.  Nothing is read back."""
+    return _lsd_rows(hrs, srs, opt, hr_shift)
+
+
+def lsd_loss(sr_audio, hr_audio, opt):
+    """The reference's ``lsd`` (util/util.py:171-175: the mean over all frames of a batch of equal-length clips) as a training
+    loss -> 0-dim float64 tensor, differentiable in sr_audio.  sr_audio / hr_audio: dense float32 device tensors [B, T], [B, 1,
+    T] or [B, 1, 1, T] -- what ``Audio2MDCT.to_audio`` returns -- read in place as a pack with starts b * T (no packing copy).
+    Nothing is read back and the row tables of a geometry are uploaded once and kept, so forward + backward capture into a
+    graph on one stream after one eager call.  As for any autograd capture: no graph built on another stream from the same
+    leaf may still be alive (detach or drop earlier losses), or the engine synchronises the capture with that stream."""
+    flat = []
+    for x, what in ((sr_audio, "sr_audio"), (hr_audio, "hr_audio")):
+        if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() not in (2, 3, 4) \
+                or any(n != 1 for n in x.shape[1:-1]):
+            raise ValueError("%s is a float32 device tensor [B, T], [B, 1, T] or [B, 1, 1, T]" % what)
+        flat.append((x if x.is_contiguous() else x.contiguous()).reshape(-1))
+    B, T = int(sr_audio.shape[0]), int(sr_audio.shape[-1])
+    if (int(hr_audio.shape[0]), int(hr_audio.shape[-1])) != (B, T):
+        raise ValueError("sr_audio holds %d clips of %d samples, hr_audio %d of %d" % (B, T, hr_audio.shape[0], hr_audio.shape[-1]))
+    starts, lengths = [b * T for b in range(B)], [T] * B
+    key = (B, T, int(opt.n_fft), int(opt.hop_length), bool(opt.center), str(sr_audio.device))
+    return _lsd_rows((flat[1], starts, lengths), (flat[0], starts, lengths), opt, None, table_key=key).mean()
 
 
 def eval_model(model, eval_batches, opt, eval_path=None):
