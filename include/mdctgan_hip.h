@@ -626,6 +626,8 @@ int mg_stats_finalize(const double* stats, long long n, float* mean_std, void* s
  *   fwd: loss[0] (+)= scale * mean((pred - target)^2)   |   scale * mean(|a - b|)
  *        (two-stage fixed-order reduction in double: deterministic; workspace >= mg_loss_workspace()).
  *   bwd: grad = d loss / d pred (resp. a) * grad_out[0]  (grad_out: device scalar, nullable == 1).
+ *   Each of these single-tensor calls is mg_loss_multi_{fwd,bwd} below on a list of one item (the same kernels, the same bits);
+ *   one item has at most 1024 partials, so mg_loss_workspace() bytes serve it.
  */
 size_t mg_loss_workspace(void);
 int mg_mse_const_fwd(const float* pred, long long n, float target, float scale, float* loss, int accumulate,
@@ -647,8 +649,9 @@ int mg_l1_bwd(const float* a, const float* b, long long n, float scale, const fl
 /* The same three losses over a LIST of tensors, one launch per stage (kind 0: mean((a - target)^2), 1: mean(|a - b|), 2: BCE against
  * the constant label `target`): loss (+)= sum_i scale * loss_i -- the feature-matching sum over the discriminators' intermediate
  * layers (models/pix2pixHD_model.py:440-449) and the per-scale GAN terms.  Bit-identical to the accumulate-in-place sequence of
- * the single-tensor calls in list order.  Backward: grad[i][0..n) = d(scale * loss_i)/da_i * grad_out[0]; additionally
- * grad[i][n .. n + zero_tail) = 0 (the other half of a stacked [fake; real] batch).  items: HOST array, count <= MG_LOSS_MAX_ITEMS. */
+ * one-item calls in list order (every item keeps the partial blocks and the grid stride it has alone).
+ * Backward: grad[i][0..n) = d(scale * loss_i)/da_i * grad_out[0]; additionally grad[i][n .. n + zero_tail) = 0 (the other half of
+ * a stacked [fake; real] batch).  items: HOST array, count <= MG_LOSS_MAX_ITEMS. */
 #define MG_LOSS_MAX_ITEMS 16
 typedef struct {
     const float* a;

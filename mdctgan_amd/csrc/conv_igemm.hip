@@ -1042,7 +1042,7 @@ __global__ void colsum_partial_kernel(const float* __restrict__ a, long long M, 
 }  // namespace
 
 extern "C" __attribute__((visibility("hidden"))) int mg_conv_rowdot_kq(const mg_conv_geom* g);       // conv_rowdot.hip (library-internal)
-extern "C" __attribute__((visibility("hidden"))) int mg_instnorm_slab_ok(int HW, int C);              // norm_act.hip (library-internal)
+extern "C" __attribute__((visibility("hidden"))) int mg_instnorm_slab_ok(int HW, int C);              // instnorm.hip (library-internal)
 extern "C" __attribute__((visibility("hidden"))) int mg_instnorm_fwd_slabs(const float* part, int S, const float* bias, int round_f16,
                                                                           float* x_out, int B, int HW, int C, float eps, int act,
                                                                           const float* residual, float* y, float* mean, float* rstd,
@@ -1242,7 +1242,7 @@ inline size_t slab_count(int old_splits, int dense) {      // split-K slabs a wo
 }
 
 // A forward convolution whose caller normalises the result right away (mg_conv_fwd_instnorm_*) may leave its split-K slabs
-// unreduced: the InstanceNorm slab kernel sums them itself (norm_act.hip: mg_instnorm_fwd_slabs) -- one launch fewer per layer.
+// unreduced: the InstanceNorm slab kernel sums them itself (instnorm.hip: mg_instnorm_fwd_slabs) -- one launch fewer per layer.
 // The caller passes a FwdDefer; a path that can oblige fills it INSTEAD of launching splitk_epilogue_kernel.
 struct FwdDefer { const float* part; int splits; const float* bias; int round_f16; bool filled; };
 #include "dense_gemm_h.h"

@@ -13,8 +13,6 @@
 constexpr int kChunk = MG_MOMENTS_CHUNK;
 constexpr long long kFar = 1LL << 62;            // positions beyond this are a broken table: the row is dropped before any sum overflows
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // x blocks per row for a launch over n_rows rows of at most max_len samples, `per_block` samples per block and pass: enough
 // blocks to fill the chip, few enough that a table of thousands of rows does not launch mostly empty ones
 inline dim3 rows_grid(int n_rows, long long max_len, int per_block) {

@@ -11,6 +11,7 @@
 // the implicit-GEMM kernels with a 1x1 geometry (conv_igemm.hip); everything here is the HBM-bound transforms.
 // Layouts: V / M: [16][T][C] (T = B * TH * TW tiles), U: [16][Co][Ci].
 #pragma once
+#include "adam.h"
 
 namespace {
 
@@ -684,7 +685,7 @@ __global__ void wino_adam_kernel(const float* __restrict__ dU, int Co, int Ci, f
                 g[r][2] = f4add(f4add(h1, h2), tmp[r][3]);
             }
         }
-        // adam_dev_kernel on the nine taps
+        // the Adam update (adam.h: what adam_dev_kernel applies) on the nine taps
 #pragma unroll
         for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -694,13 +695,7 @@ __global__ void wino_adam_kernel(const float* __restrict__ dU, int Co, int Ci, f
                 float* pp = reinterpret_cast<float*>(&pv); float* mm = reinterpret_cast<float*>(&mv);
                 float* vp = reinterpret_cast<float*>(&vv); const float* gg = reinterpret_cast<const float*>(&g[r][c]);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float gi = gg[j] * gscale;
-                    const float mi = mm[j] + (gi - mm[j]) * (1.0f - b1);
-                    const float vi = vp[j] * b2 + (1.0f - b2) * gi * gi;
-                    mm[j] = mi; vp[j] = vi;
-                    pp[j] = pp[j] - step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-                }
+                for (int j = 0; j < 4; ++j) adam_update(pp[j], mm[j], vp[j], gg[j], gscale, step_size, bc2_sqrt, b1, b2, eps);
                 *reinterpret_cast<float4*>(w + o) = pv;
                 *reinterpret_cast<float4*>(m + o) = mv;
                 *reinterpret_cast<float4*>(v + o) = vv;

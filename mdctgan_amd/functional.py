@@ -1045,121 +1045,72 @@ def g_input(spectro, nr0):
 # ------------------------------------------------------------------------------------------------
 # losses
 # ------------------------------------------------------------------------------------------------
-class _MseConstFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, pred, target, scale):
-        pred = pred.contiguous(memory_format=CL) if pred.dim() == 4 else pred.contiguous()
-        loss = torch.empty(1, dtype=torch.float32, device=pred.device)
-        ops.mse_const_fwd(pred, target, scale, loss, False)
-        ctx.target, ctx.scale = target, scale
-        ctx.save_for_backward(pred)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, go):
-        (pred,) = ctx.saved_tensors
-        go = go.reshape(1).float().contiguous()
-        return ops.mse_const_bwd(pred, ctx.target, ctx.scale, go), None, None
-
-
-class _MseConstPairFn(torch.autograd.Function):
-    """(mean((pred[:B] - t0)^2), mean((pred[B:] - t1)^2)) of a batch-stacked prediction; one gradient buffer."""
-
-    @staticmethod
-    def forward(ctx, pred, t0, t1):
-        pred = pred.contiguous(memory_format=CL) if pred.dim() == 4 else pred.contiguous()
-        B = pred.shape[0] // 2
-        l0 = torch.empty(1, dtype=torch.float32, device=pred.device)
-        l1 = torch.empty(1, dtype=torch.float32, device=pred.device)
-        ops.mse_const_fwd(pred[:B], t0, 1.0, l0, False)
-        ops.mse_const_fwd(pred[B:], t1, 1.0, l1, False)
-        ctx.targets = (t0, t1)
-        ctx.save_for_backward(pred)
-        return l0.reshape(()), l1.reshape(())
-
-    @staticmethod
-    def backward(ctx, g0, g1):
-        (pred,) = ctx.saved_tensors
-        B = pred.shape[0] // 2
-        g = torch.empty_like(pred)
-        ops.mse_const_bwd(pred[:B], ctx.targets[0], 1.0, g0.reshape(1).float().contiguous(), out=g[:B])
-        ops.mse_const_bwd(pred[B:], ctx.targets[1], 1.0, g1.reshape(1).float().contiguous(), out=g[B:])
-        return g, None, None
-
-
-def mse_const_pair_loss(pred, target_first: float, target_second: float):
-    """The two LSGAN terms of a prediction whose batch stacks two passes (first half / second half)."""
-    assert pred.shape[0] % 2 == 0
-    return _MseConstPairFn.apply(pred, float(target_first), float(target_second))
-
-
-class _MseConstFirstHalfFn(torch.autograd.Function):
-    """mean((pred[:B] - t)^2) of a batch-stacked prediction; the gradient buffer has the stacked shape, second half
-    unwritten (consumed by pass "G" only, which never reads it)."""
-
-    @staticmethod
-    def forward(ctx, pred, target):
-        pred = pred.contiguous(memory_format=CL) if pred.dim() == 4 else pred.contiguous()
-        B = pred.shape[0] // 2
-        loss = torch.empty(1, dtype=torch.float32, device=pred.device)
-        ops.mse_const_fwd(pred[:B], target, 1.0, loss, False)
-        ctx.target = target
-        ctx.save_for_backward(pred)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, go):
-        (pred,) = ctx.saved_tensors
-        B = pred.shape[0] // 2
-        g = torch.empty_like(pred)
-        if _BackwardPass.kind != "G":
-            g[B:].zero_()
-        ops.mse_const_bwd(pred[:B], ctx.target, 1.0, go.reshape(1).float().contiguous(), out=g[:B])
-        return g, None
-
-
-def mse_const_first_half_loss(pred, target: float):
-    assert pred.shape[0] % 2 == 0
-    return _MseConstFirstHalfFn.apply(pred, float(target))
-
-
-class _L1HalvesFn(torch.autograd.Function):
-    """scale * mean(|t[:B] - t[B:].detach()|): the feature-matching term of a batch-stacked [fake, real] feature map."""
-
-    @staticmethod
-    def forward(ctx, t, scale):
-        t = t.contiguous(memory_format=CL) if t.dim() == 4 else t.contiguous()
-        B = t.shape[0] // 2
-        loss = torch.empty(1, dtype=torch.float32, device=t.device)
-        ops.l1_fwd(t[:B], t[B:], scale, loss, False)
-        ctx.scale = scale
-        ctx.save_for_backward(t)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, go):
-        (t,) = ctx.saved_tensors
-        B = t.shape[0] // 2
-        g = torch.empty_like(t)
-        if _BackwardPass.kind != "G":
-            g[B:].zero_()
-        ops.l1_bwd(t[:B], t[B:], ctx.scale, go.reshape(1).float().contiguous(), out=g[:B])
-        return g, None
-
-
-def l1_halves_loss(t, scale: float = 1.0):
-    assert t.shape[0] % 2 == 0
-    return _L1HalvesFn.apply(t, float(scale))
-
-
-# Sums of such terms over the discriminator scales / layers as ONE autograd node each: the kernels accumulate into the
-# loss scalar (mg_*_fwd's accumulate flag, the same float32 additions in the same order as `loss = loss + term`), so the
-# step launches no at::native add for them.
 def _cl(t):
     return t.contiguous(memory_format=CL) if t.dim() == 4 else t.contiguous()
 
 
+class _LossFn(torch.autograd.Function):
+    """scale * loss_kind(a, b | target): one tensor is a list of one row for the list kernels (ops.loss_multi_*).  b (L1 only) gets
+    the mirrored gradient where it needs one."""
+
+    @staticmethod
+    def forward(ctx, kind, a, b, target, scale):
+        a, b = _cl(a), None if b is None else _cl(b)
+        loss = torch.empty(1, dtype=torch.float32, device=a.device)
+        ops.loss_multi_fwd(kind, [(a, b, None, 0)], target, scale, loss)
+        ctx.kind, ctx.target, ctx.scale = kind, target, scale
+        ctx.save_for_backward(a, b)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, go):
+        a, b = ctx.saved_tensors
+        go = go.reshape(1).float().contiguous()
+
+        def grad(x, y):
+            g = torch.empty_like(x)
+            ops.loss_multi_bwd(ctx.kind, [(x, y, g, 0)], ctx.target, ctx.scale, go)
+            return g
+        ga = grad(a, b) if ctx.needs_input_grad[1] else None
+        gb = grad(b, a) if b is not None and ctx.needs_input_grad[2] else None
+        return None, ga, gb, None, None
+
+
+def mse_const_loss(pred, target: float, scale: float = 1.0):
+    """scale * mean((pred - target)^2)  == nn.MSELoss()(pred, full_like(pred, target)) * scale."""
+    return _LossFn.apply(ops.LOSS_MSE_CONST, pred, None, float(target), float(scale))
+
+
+def bce_const_loss(pred, target: float, scale: float = 1.0):
+    """scale * nn.BCELoss()(pred, full_like(pred, target)) (networks.py:106-109 with use_lsgan=False)."""
+    return _LossFn.apply(ops.LOSS_BCE_CONST, pred, None, float(target), float(scale))
+
+
+def l1_loss(a, b, scale: float = 1.0):
+    """scale * mean(|a - b|) == nn.L1Loss()(a, b) * scale."""
+    return _LossFn.apply(ops.LOSS_L1, a, b, 0.0, float(scale))
+
+
+# Sums of such terms over the discriminator scales / layers, each tensor a batch-stacked [first pass; second pass], as ONE autograd
+# node each: the kernels accumulate into the loss scalar (the same float32 additions in the same order as `loss = loss + term`), so
+# the step launches no at::native add for them.
+def _half_rows(ts, half=0, other=False, grads=None, clear=False):
+    """The rows of ops.loss_multi_* over batch-stacked tensors: (this half, the other half | None, this half of the tensor's
+    gradient buffer | None, elements behind it to clear).  clear: the loss gives the second half no gradient and the same launch
+    zeroes it -- except in pass "G", which never reads it."""
+    rows = []
+    for i, t in enumerate(ts):
+        B = t.shape[0] // 2
+        hs = (t[:B], t[B:])
+        g = None if grads is None else (grads[i][:B], grads[i][B:])[half]
+        tail = hs[1].numel() if clear and _BackwardPass.kind != "G" else 0
+        rows.append((hs[half], hs[1 - half] if other else None, g, tail))
+    return rows
+
+
 class _L1HalvesSumFn(torch.autograd.Function):
+    """sum_i scale * mean(|t_i[:B] - t_i[B:].detach()|): the feature-matching terms of batch-stacked [fake, real] feature maps."""
+
     @staticmethod
     def forward(ctx, scale, *ts):
         ctx.holders = [getattr(t, "_mg_extra", None) for t in ts]      # where the producers take a second gradient (ExtraGrad)
@@ -1168,7 +1119,7 @@ class _L1HalvesSumFn(torch.autograd.Function):
             TAP.append(("l1_sign", [torch.sign(t[:t.shape[0] // 2].detach() - t[t.shape[0] // 2:].detach()) for t in ts]))
         loss = torch.empty(1, dtype=torch.float32, device=ts[0].device)
         # all layers in one partial + one final launch (mg_loss_multi_fwd): same blocks, same order of additions
-        ops.loss_multi_fwd(ops.LOSS_L1, [(t[:t.shape[0] // 2], t[t.shape[0] // 2:], None, 0) for t in ts], 0.0, scale, loss)
+        ops.loss_multi_fwd(ops.LOSS_L1, _half_rows(ts, other=True), 0.0, scale, loss)
         ctx.scale = scale
         ctx.save_for_backward(*ts)
         return loss.reshape(())
@@ -1176,14 +1127,8 @@ class _L1HalvesSumFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, go):
         go = go.reshape(1).float().contiguous()
-        grads, rows = [], []
-        for t in ctx.saved_tensors:
-            B = t.shape[0] // 2
-            g = torch.empty_like(t)
-            # the real half gets no gradient from this loss: cleared by the same launch (pass "G" never reads it)
-            rows.append((t[:B], t[B:], g, (t.numel() - t[:B].numel()) if _BackwardPass.kind != "G" else 0))
-            grads.append(g)
-        ops.loss_multi_bwd(ops.LOSS_L1, rows, 0.0, ctx.scale, go)
+        grads = [torch.empty_like(t) for t in ctx.saved_tensors]
+        ops.loss_multi_bwd(ops.LOSS_L1, _half_rows(ctx.saved_tensors, other=True, grads=grads, clear=True), 0.0, ctx.scale, go)
         if _BackwardPass.kind == "G":
             # optimize_parameters' generator pass: every map's producer runs later in this pass (reached through the next layer) and
             # adds the parked gradient inside its own kernel -- no accumulation launch
@@ -1195,18 +1140,19 @@ class _L1HalvesSumFn(torch.autograd.Function):
 
 
 def l1_halves_loss_sum(ts, scale: float = 1.0):
-    """sum_i l1_halves_loss(ts[i], scale), one node."""
     ts = list(ts)
     assert ts and all(t.shape[0] % 2 == 0 for t in ts)
     return _L1HalvesSumFn.apply(float(scale), *ts)
 
 
 class _MseConstFirstHalfSumFn(torch.autograd.Function):
+    """sum_i mean((pred_i[:B] - target)^2) of batch-stacked predictions; the gradient buffers have the stacked shape."""
+
     @staticmethod
     def forward(ctx, target, *preds):
         preds = [_cl(t) for t in preds]
         loss = torch.empty(1, dtype=torch.float32, device=preds[0].device)
-        ops.loss_multi_fwd(ops.LOSS_MSE_CONST, [(t[:t.shape[0] // 2], None, None, 0) for t in preds], target, 1.0, loss)
+        ops.loss_multi_fwd(ops.LOSS_MSE_CONST, _half_rows(preds), target, 1.0, loss)
         ctx.target = target
         ctx.save_for_backward(*preds)
         return loss.reshape(())
@@ -1214,31 +1160,27 @@ class _MseConstFirstHalfSumFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, go):
         go = go.reshape(1).float().contiguous()
-        grads, rows = [], []
-        for t in ctx.saved_tensors:
-            B = t.shape[0] // 2
-            g = torch.empty_like(t)
-            rows.append((t[:B], None, g, (t.numel() - t[:B].numel()) if _BackwardPass.kind != "G" else 0))
-            grads.append(g)
-        ops.loss_multi_bwd(ops.LOSS_MSE_CONST, rows, ctx.target, 1.0, go)
+        grads = [torch.empty_like(t) for t in ctx.saved_tensors]
+        ops.loss_multi_bwd(ops.LOSS_MSE_CONST, _half_rows(ctx.saved_tensors, grads=grads, clear=True), ctx.target, 1.0, go)
         return (None, *grads)
 
 
 def mse_const_first_half_loss_sum(preds, target: float):
-    """sum_i mse_const_first_half_loss(preds[i], target), one node."""
     preds = list(preds)
     assert preds and all(t.shape[0] % 2 == 0 for t in preds)
     return _MseConstFirstHalfSumFn.apply(float(target), *preds)
 
 
 class _MseConstPairSumFn(torch.autograd.Function):
+    """(sum_i mean((pred_i[:B] - t0)^2), sum_i mean((pred_i[B:] - t1)^2)) of batch-stacked predictions; one gradient buffer each."""
+
     @staticmethod
     def forward(ctx, t0, t1, *preds):
         preds = [_cl(t) for t in preds]
         l0 = torch.empty(1, dtype=torch.float32, device=preds[0].device)
         l1 = torch.empty(1, dtype=torch.float32, device=preds[0].device)
-        ops.loss_multi_fwd(ops.LOSS_MSE_CONST, [(t[:t.shape[0] // 2], None, None, 0) for t in preds], t0, 1.0, l0)
-        ops.loss_multi_fwd(ops.LOSS_MSE_CONST, [(t[t.shape[0] // 2:], None, None, 0) for t in preds], t1, 1.0, l1)
+        ops.loss_multi_fwd(ops.LOSS_MSE_CONST, _half_rows(preds), t0, 1.0, l0)
+        ops.loss_multi_fwd(ops.LOSS_MSE_CONST, _half_rows(preds, half=1), t1, 1.0, l1)
         ctx.targets = (t0, t1)
         ctx.save_for_backward(*preds)
         return l0.reshape(()), l1.reshape(())
@@ -1247,54 +1189,22 @@ class _MseConstPairSumFn(torch.autograd.Function):
     def backward(ctx, g0, g1):
         g0 = g0.reshape(1).float().contiguous()
         g1 = g1.reshape(1).float().contiguous()
-        grads, rows0, rows1 = [], [], []
-        for t in ctx.saved_tensors:
-            B = t.shape[0] // 2
-            g = torch.empty_like(t)
-            rows0.append((t[:B], None, g[:B], 0))
-            rows1.append((t[B:], None, g[B:], 0))
-            grads.append(g)
-        ops.loss_multi_bwd(ops.LOSS_MSE_CONST, rows0, ctx.targets[0], 1.0, g0)
-        ops.loss_multi_bwd(ops.LOSS_MSE_CONST, rows1, ctx.targets[1], 1.0, g1)
+        grads = [torch.empty_like(t) for t in ctx.saved_tensors]
+        ops.loss_multi_bwd(ops.LOSS_MSE_CONST, _half_rows(ctx.saved_tensors, grads=grads), ctx.targets[0], 1.0, g0)
+        ops.loss_multi_bwd(ops.LOSS_MSE_CONST, _half_rows(ctx.saved_tensors, half=1, grads=grads), ctx.targets[1], 1.0, g1)
         return (None, None, *grads)
 
 
 def mse_const_pair_loss_sum(preds, target_first: float, target_second: float):
-    """(sum_i first-half term, sum_i second-half term) of mse_const_pair_loss over preds, one node."""
+    """The two LSGAN terms of predictions whose batch stacks two passes (first half / second half), each summed over preds."""
     preds = list(preds)
     assert preds and all(t.shape[0] % 2 == 0 for t in preds)
     return _MseConstPairSumFn.apply(float(target_first), float(target_second), *preds)
 
 
-class _BceConstFn(torch.autograd.Function):
-    """scale * nn.BCELoss()(pred, full_like(pred, target)) (networks.py:106-109 with use_lsgan=False)."""
-
-    @staticmethod
-    def forward(ctx, pred, target, scale):
-        from . import _lib
-        pred = pred.contiguous(memory_format=CL) if pred.dim() == 4 else pred.contiguous()
-        loss = torch.empty(1, dtype=torch.float32, device=pred.device)
-        lib = _lib.load()
-        ws = _lib.workspace(lib.mg_loss_workspace(), pred.device)
-        _lib.check(lib.mg_bce_const_fwd(_lib.ptr(pred), pred.numel(), target, scale, _lib.ptr(loss), 0, _lib.ptr(ws), _lib.stream()),
-                   "mg_bce_const_fwd")
-        ctx.target, ctx.scale = target, scale
-        ctx.save_for_backward(pred)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, go):
-        from . import _lib
-        (pred,) = ctx.saved_tensors
-        go = go.reshape(1).float().contiguous()
-        g = torch.empty_like(pred)
-        _lib.check(_lib.load().mg_bce_const_bwd(_lib.ptr(pred), pred.numel(), ctx.target, ctx.scale, _lib.ptr(go), _lib.ptr(g),
-                                                _lib.stream()), "mg_bce_const_bwd")
-        return g, None, None
-
-
-def bce_const_loss(pred, target: float, scale: float = 1.0):
-    return _BceConstFn.apply(pred, float(target), float(scale))
+def mse_const_pair_loss(pred, target_first: float, target_second: float):
+    """The same pair of terms for one prediction."""
+    return mse_const_pair_loss_sum([pred], target_first, target_second)
 
 
 class _SigmoidFn(torch.autograd.Function):
@@ -1319,35 +1229,3 @@ class _SigmoidFn(torch.autograd.Function):
 
 def sigmoid(x):
     return _SigmoidFn.apply(x)
-
-
-def mse_const_loss(pred, target: float, scale: float = 1.0):
-    """scale * mean((pred - target)^2)  == nn.MSELoss()(pred, full_like(pred, target)) * scale."""
-    return _MseConstFn.apply(pred, float(target), float(scale))
-
-
-class _L1Fn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, a, b, scale):
-        fmt = CL if a.dim() == 4 else torch.contiguous_format
-        a, b = a.contiguous(memory_format=fmt), b.contiguous(memory_format=fmt)
-        loss = torch.empty(1, dtype=torch.float32, device=a.device)
-        ops.l1_fwd(a, b, scale, loss, False)
-        ctx.scale = scale
-        ctx.save_for_backward(a, b)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, go):
-        a, b = ctx.saved_tensors
-        go = go.reshape(1).float().contiguous()
-        ga = ops.l1_bwd(a, b, ctx.scale, go) if ctx.needs_input_grad[0] else None
-        gb = None
-        if ctx.needs_input_grad[1]:
-            gb = ops.l1_bwd(b, a, ctx.scale, go)
-        return ga, gb, None
-
-
-def l1_loss(a, b, scale: float = 1.0):
-    """scale * mean(|a - b|) == nn.L1Loss()(a, b) * scale."""
-    return _L1Fn.apply(a, b, float(scale))

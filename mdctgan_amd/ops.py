@@ -412,8 +412,8 @@ def _loss_items(rows):
 
 
 def loss_multi_fwd(kind, rows, target, scale, loss, accumulate=False):
-    """loss (+)= sum_i scale * loss_kind(rows[i]) in one partial + one final launch (mg_loss_multi_fwd); bit-identical to the
-    single-tensor calls accumulated in list order."""
+    """loss (+)= sum_i scale * loss_kind(rows[i]) in one partial + one final launch (mg_loss_multi_fwd); bit-identical to one-row
+    calls accumulated in list order (the single-tensor entry points are such calls)."""
     lib = _lib.load()
     ws = _ws(lib.mg_loss_multi_workspace(), loss.device)
     for lo in range(0, len(rows), LOSS_MAX_ITEMS):

@@ -1,4 +1,4 @@
-// Streaming-rate harness for the fused Adam update (mdctgan_amd/csrc/norm_act.hip::adam_dev_kernel): 16 B read + 12 B written per parameter.
+// Streaming-rate harness for the fused Adam update (mdctgan_amd/csrc/optim.hip::adam_dev_kernel): 16 B read + 12 B written per parameter.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 scripts/ubench/adam_bench.hip -o scripts/ubench/adam_bench
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -658,7 +658,7 @@ def test_weight_streaming_gemm_equals_the_im2col_gemm(case, monkeypatch):
     assert torch.equal(got[2], ref[1]) and torch.equal(got[3], ref[1] + skip)
 
 
-# ---- op-level parity of the streaming optimiser / GradScaler kernels (csrc/norm_act.hip) at their vector-body edges --------------
+# ---- op-level parity of the streaming optimiser / GradScaler kernels (csrc/optim.hip) at their vector-body edges --------------
 # The C ABI takes the betas and eps as float32: the float64 reference uses those very values (float32(0.999) is 1.3e-5 of
 # 1 - beta2 away from 0.999).
 ADAM_LR, ADAM_B1, ADAM_B2, ADAM_EPS = 2e-4, 0.5, float(np.float32(0.999)), float(np.float32(1e-8))
@@ -835,6 +835,31 @@ def seg_table(segs):
     for j, sg in enumerate(segs):
         rec[j] = sg
     return torch.from_numpy(rec.view(np.uint8).copy()).to(DEV)
+
+
+@pytest.mark.parametrize("n", [8, 4104])          # two float4 groups; 1026 groups: three blocks and a second grid-stride trip, in both kernels
+def test_adam_update_is_one_expression_across_entry_points(n):
+    """The Adam update is one expression (csrc/adam.h) whichever kernel applies it: mg_adam_step_dev (adam_dev_kernel) and
+    mg_adam_step_segs over one MG_GRAD_F32 segment without scaler or shadow (adam_seg_kernel) leave the same bits in p, m and v after
+    three steps from the same state, on the same device clock and with the same grad_scale."""
+    from mdctgan_amd import _lib, ops
+    gen = torch.Generator().manual_seed(n)
+    p0 = torch.randn(n, generator=gen)
+    m0, v0 = 0.1 * torch.randn(n, generator=gen), 0.01 * torch.rand(n, generator=gen)
+    dev = [t.clone().to(DEV) for t in (p0, m0, v0)]
+    seg = [t.clone().to(DEV) for t in (p0, m0, v0)]
+    table = seg_table([(0, n, _lib.GRAD_F32, 0)])
+    state = torch.zeros(6, dtype=torch.float64, device=DEV)
+    state[1] = ADAM_LR
+    grad_scale = 0.3
+    for gmag in (1.0, 1e-4, 10.0):
+        g = (torch.randn(n, generator=gen) * gmag).to(DEV)
+        ops.adam_tick(state, ADAM_B1, ADAM_B2)
+        ops.adam_step_dev(dev[0], g, dev[1], dev[2], state, ADAM_B1, ADAM_B2, ADAM_EPS, grad_scale)
+        ops.adam_step_segs(seg[0], g, None, seg[1], seg[2], None, table, 1, n, 28 * n, state, ADAM_B1, ADAM_B2, ADAM_EPS, grad_scale)
+    assert state[0].item() == 3.0 and bool((dev[0].cpu() != p0).any())
+    for name, a, b in zip("pmv", dev, seg):
+        assert torch.equal(a, b), (name, int((a != b).sum()))
 
 
 def test_scaler_check_segs_overflow_criteria():

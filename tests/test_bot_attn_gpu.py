@@ -495,7 +495,7 @@ def test_batchnorm_channel_vectors_stay_inside_their_buffers():
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# mg_cat2_fwd / mg_cat2_bwd (csrc/norm_act.hip): torch.cat((a, b), -1) of NHWC tensors and its split
+# mg_cat2_fwd / mg_cat2_bwd (csrc/elementwise.hip): torch.cat((a, b), -1) of NHWC tensors and its split
 # ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", [(7, 1, 2), (1000, 3, 5), (33, 64, 1)], ids=lambda s: "n%d_%d+%d" % s)
 def test_cat2_fwd_bwd(shape):

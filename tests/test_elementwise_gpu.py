@@ -1,4 +1,4 @@
-"""K5/K7/K8/K9/K11/K12 kernels (csrc/norm_act.hip) against plain PyTorch float64 CPU references."""
+"""K5/K7/K8/K9/K11/K12 kernels (csrc/instnorm.hip, elementwise.hip, loss.hip, optim.hip) against plain PyTorch float64 CPU references."""
 import numpy as np
 import pytest
 import torch
@@ -189,6 +189,68 @@ def test_multi_tensor_losses_equal_the_single_tensor_calls():
         for buf, w_ in zip(bufs, wants):
             n = w_.numel()
             assert torch.equal(buf[:n], w_.reshape(-1)) and bool((buf[n:] == 0).all())
+
+
+# ---- the list loss kernels against float64 (the single-tensor entry points are lists of one: the test above compares the list
+# kernels with themselves, this one is their independent reference) ---------------------------------------------------------------
+# An item has min(ceil(n / 1024), 1024) partial blocks: one block with one element, one block with a ragged last wave, exactly one
+# full block, a second block with one element, and the first size past the cap (every block makes a second grid-stride trip).
+LOSS_SIZES = [1, 1023, 1024, 1025, 1024 * 1024 + 5]
+LOSS_LIST = (1025, 1, 1024 * 1024 + 5)            # one list of three unequal items
+LOSS_CASES = {"mse": (0, 1.0, 0.7), "l1": (1, 0.0, 1.3), "bce_real": (2, 1.0, 0.7), "bce_fake": (2, 0.0, 0.7)}      # kind, target, scale
+_loss_cache = {}
+
+
+def loss_inputs(n):
+    """(a, b) float32 on the CPU, in (0.01, 0.99) as the test above draws them (BCE's logarithms stay clear of the clamp), and no
+    a - b is zero: |a - b| >= 0.01 by construction, so the float32 and the float64 sign agree."""
+    if n not in _loss_cache:
+        gen = torch.Generator().manual_seed(1000 + n % 997)
+        a = torch.rand(n, generator=gen) * 0.98 + 0.01
+        b = torch.rand(n, generator=gen) * 0.98 + 0.01
+        b = torch.where((a - b).abs() < 0.01, 1.0 - a, b)           # |a - (1 - a)| < 0.01 only for a in (0.495, 0.505) ...
+        b = torch.where((a - b).abs() < 0.01, a + 0.25, b)          # ... where a + 0.25 stays inside (0.01, 0.99)
+        assert bool(((a.double() - b.double()).abs() >= 0.0099).all()) and 0.01 <= min(a.min(), b.min()) and max(a.max(), b.max()) <= 0.99
+        _loss_cache[n] = (a, b)
+    return _loss_cache[n]
+
+
+def loss_ref(kind, a, b, target):
+    """float64: (mean loss, its gradient with respect to a)."""
+    n = a.numel()
+    if kind == 0:
+        return ((a - target) ** 2).mean().item(), 2.0 * (a - target) / n
+    if kind == 1:
+        return (a - b).abs().mean().item(), torch.sign(a - b) / n
+    return (-(target * a.log() + (1.0 - target) * (1.0 - a).log())).mean().item(), (a - target) / ((1.0 - a) * a) / n
+
+
+@pytest.mark.parametrize("sizes", [(n,) for n in LOSS_SIZES] + [LOSS_LIST], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("case", sorted(LOSS_CASES))
+def test_list_losses_against_float64(case, sizes):
+    """mg_loss_multi_fwd / mg_loss_multi_bwd against a CPU float64 evaluation: every block-count edge as a list of one, and one list
+    of three; forward into a fresh scalar and accumulated onto one, backward under a grad_out tensor.  Bounds: those of
+    test_dinput_pair_losses_adam (loss 1e-5 relative, gradients rel_err < 1e-5)."""
+    from mdctgan_amd import ops
+    kind, target, scale = LOSS_CASES[case]
+    host = [loss_inputs(n) for n in sizes]
+    refs = [loss_ref(kind, a.double(), b.double(), target) for a, b in host]
+    want = scale * sum(r[0] for r in refs)
+    dev = [(a.to(DEV), b.to(DEV) if kind == ops.LOSS_L1 else None) for a, b in host]
+    fresh = torch.full((1,), float("nan"), device=DEV)
+    ops.loss_multi_fwd(kind, [(a, b, None, 0) for a, b in dev], target, scale, fresh)
+    onto = torch.full((1,), 3.25, device=DEV)
+    ops.loss_multi_fwd(kind, [(a, b, None, 0) for a, b in dev], target, scale, onto, True)
+    print("%s %s: loss %.9g / %.9g, accumulated %.9g / %.9g" % (case, sizes, fresh.item(), want, onto.item(), 3.25 + want))
+    assert abs(fresh.item() - want) < 1e-5 * abs(want)
+    assert abs(onto.item() - (3.25 + want)) < 1e-5 * abs(3.25 + want)
+    go = torch.full((1,), 0.37, device=DEV)
+    grads = [torch.full_like(a, float("nan")) for a, _ in dev]
+    ops.loss_multi_bwd(kind, [(a, b, g, 0) for (a, b), g in zip(dev, grads)], target, scale, go)
+    for n, g, r in zip(sizes, grads, refs):
+        err = rel_err(g, 0.37 * scale * r[1])
+        print("  n=%d gradient rel_err %.3g" % (n, err))
+        assert err < 1e-5
 
 
 # ---- joined gradients (mg_instnorm_bwd_add / mg_act_bwd_add), pooling edges, sign(0), mg_stats_finalize --------------------------

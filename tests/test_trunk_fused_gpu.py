@@ -1,4 +1,4 @@
-"""The fused one-workgroup-per-slab kernels of the ResnetBlock trunk (csrc/wino.h, csrc/norm_act.hip) against plain float64
+"""The fused one-workgroup-per-slab kernels of the ResnetBlock trunk (csrc/wino.h, csrc/instnorm.hip) against plain float64
 evaluations of the same operations, at every register depth NT they are instantiated for and at the tile counts next to each
 depth's and each eligibility limit:
 
