@@ -327,6 +327,26 @@ int mg_lsd_rows_backward(const float* hr, long long hr_total, const float* sr, l
                          const float* window, int n_fft, int hop, int center, const float* grad_rows, float* grad_sr,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* The LSD of a dense training batch as a loss node of the step's convention (float32 [1] losses, constant factors in the node, the
+ * upstream gradient read on the device); Python: metrics.lsd_loss_term.
+ *   mg_lsd_mean_loss             loss[0] = float32(scale * (sum_f per_frame[f]) / total_frames) over mg_lsd_rows' per-frame array:
+ *                                for equal-length clips the reference's .mean() (util/util.py:175).  One workgroup; the sum runs
+ *                                in double, tiles of 256 consecutive frames in a fixed tree, then the tiles in ascending order,
+ *                                rounded once: no atomics, bit-identical reruns, any total_frames >= 1.  per_frame is only read.
+ *                                MG_ERR_ARG before the launch for a null pointer or total_frames <= 0.
+ *   mg_lsd_rows_backward_seeded  mg_lsd_rows_backward -- its two launches, workspace, argument rules and guarantees -- with row u's
+ *                                upstream gradient formed on the device instead of read from grad_rows: in double,
+ *                                ((go[0] * scale) / n_rows) / frames_u with frames_u = frame_start[u + 1] - frame_start[u], rounded
+ *                                to float32 once.  That is d (scale * mean_u mean_f L_f) / d sr times go[0] in the arithmetic
+ *                                autograd performs around mg_lsd_rows_backward, so a power-of-two scale gives its bits.  go:
+ *                                float32 [1] on the device, read when the kernel runs (a captured step follows a loss scale that
+ *                                changes between replays); NULL is MG_ERR_ARG. */
+int mg_lsd_mean_loss(const float* per_frame, long long total_frames, double scale, float* loss, void* stream);
+int mg_lsd_rows_backward_seeded(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows,
+                                int n_rows, const long long* frame_start, long long total_frames, const float* hr_shift,
+                                const float* window, int n_fft, int hop, int center, const float* go, double scale, float* grad_sr,
+                                void* workspace, size_t workspace_bytes, void* stream);
+
 /* Segment stitching of generate_audio.py:40-53: seg [n_seg, seg_len] (the [n_seg,1,1,T] inference outputs) -> one
  * waveform of mg_stitch_length() samples (-1: invalid arguments; 2*overlap must be < seg_len).  overlap == 0
  * concatenates; overlap > 0 halves the first/last `overlap` samples of every segment, overlap-adds at stride

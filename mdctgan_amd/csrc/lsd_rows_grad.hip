@@ -27,21 +27,27 @@
 //       rows, dead rows, samples outside the sr buffer and centred rows of at most N/2 samples (the forward's staging would
 //       reflect them twice; plan_metrics refuses them) are never written.
 // Neither kernel's arithmetic for a row depends on where the row sits: a row has the same gradient bits alone and in any pack.
+// mg_lsd_rows_backward_seeded is the same two launches for the loss node of a training step (metrics.lsd_loss_term): phase one
+// forms every row's upstream gradient itself from the node's upstream scalar on the device (SEEDED below).
 #include <math.h>
 
 #include "lsd_fft.h"
 
 namespace {
 
-template <int N, bool SHIFT>
+// SEEDED: `up` is not the per-row gradient but the loss node's upstream scalar go [1], and row u's gradient is formed here, in double,
+// as ((go[0] * up_scale) / n_rows) / frames_u, rounded to float32 once -- the statements autograd runs around the unseeded entry
+// point for scale * mean_u(row u's mean), so a power-of-two scale gives that path's bits, and a captured step reads go at run time.
+template <int N, bool SHIFT, bool SEEDED>
 __global__ __launch_bounds__(LSD_NT) void lsd_rows_grad_frames_kernel(const float* __restrict__ hr, long long hr_total,
                                                                       const float* __restrict__ sr, long long sr_total,
                                                                       const mg_metric_row* __restrict__ rows, int n_rows,
                                                                       const long long* __restrict__ frame_start,
                                                                       long long total_frames, const float* __restrict__ shift,
                                                                       const float* __restrict__ window,
-                                                                      const float* __restrict__ grad_rows, int hop, int center,
-                                                                      long long n_tiles, float* __restrict__ frames_out) {
+                                                                      const float* __restrict__ up, double up_scale, int hop,
+                                                                      int center, long long n_tiles,
+                                                                      float* __restrict__ frames_out) {
     constexpr int M = N / 2, FT = LSD_TILE / N, TPF = LSD_NT / FT, NBINS = N / 2 + 1, BPL = (NBINS + TPF - 1) / TPF;
     constexpr int HALF = LSD_TILE / 2;                                      // the Zt of the tile's frames, densely: [FT][M]
     static_assert(TPF >= 32 && M % LSD_NT == 0, "a frame's lanes fill whole half-waves, a load pass stays inside one signal of a frame");
@@ -58,7 +64,12 @@ __global__ __launch_bounds__(LSD_NT) void lsd_rows_grad_frames_kernel(const floa
             int row;
             const LsdFrame fi = lsd_locate<SHIFT>(tile * FT + tid, rows, n_rows, frame_start, total_frames, shift, N, hop, center, row);
             info[tid] = fi;
-            upstream[tid] = fi.live ? grad_rows[row] : 0.0f;
+            float g = 0.0f;
+            if (fi.live) {
+                if (SEEDED) g = (float)((((double)up[0] * up_scale) / (double)n_rows) / (double)(frame_start[row + 1] - frame_start[row]));
+                else g = up[row];
+            }
+            upstream[tid] = g;
         }
         __syncthreads();
         lsd_load_tile<N, SHIFT>(buf, info, hr, hr_total, sr, sr_total, window, center, tid);
@@ -185,11 +196,16 @@ size_t mg_lsd_rows_backward_workspace(long long total_frames, int n_fft) {
     return (size_t)total_frames * (size_t)n_fft * sizeof(float);
 }
 
-int mg_lsd_rows_backward(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows,
-                         int n_rows, const long long* frame_start, long long total_frames, const float* hr_shift,
-                         const float* window, int n_fft, int hop, int center, const float* grad_rows, float* grad_sr,
-                         void* workspace, size_t workspace_bytes, void* stream) {
-    if (!hr || !sr || !rows || !frame_start || !window || !grad_rows || !grad_sr || !workspace) return MG_ERR_ARG;
+}  // extern "C"
+
+namespace {
+
+// both entry points: `up` is grad_rows [n_rows] (seeded == false) or go [1] with up_scale
+int lsd_rows_backward(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows,
+                      int n_rows, const long long* frame_start, long long total_frames, const float* hr_shift,
+                      const float* window, int n_fft, int hop, int center, const float* up, double up_scale, bool seeded,
+                      float* grad_sr, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!hr || !sr || !rows || !frame_start || !window || !up || !grad_sr || !workspace) return MG_ERR_ARG;
     if (n_rows <= 0 || total_frames <= 0 || hr_total <= 0 || sr_total <= 0 || hop <= 0 || !lsd_size_ok(n_fft)) return MG_ERR_ARG;
     const size_t need = mg_lsd_rows_backward_workspace(total_frames, n_fft);
     if (need == 0 || workspace_bytes < need || !al16(workspace)) return MG_ERR_ARG;
@@ -198,14 +214,16 @@ int mg_lsd_rows_backward(const float* hr, long long hr_total, const float* sr, l
     const long long ft = LSD_TILE / n_fft, n_tiles = (total_frames + ft - 1) / ft;
     const unsigned blocks = (unsigned)(n_tiles < 2 * 256 * 4 ? n_tiles : 2 * 256 * 4);    // a few waves of two workgroups per CU (VGPR-bound)
     hipStream_t st = (hipStream_t)stream;
-#define MG_LSDG_LAUNCH(NN, S)                                                                                                    \
-    hipLaunchKernelGGL((lsd_rows_grad_frames_kernel<NN, S>), dim3(blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rows, \
-                       n_rows, frame_start, total_frames, hr_shift, window, grad_rows, hop, center != 0, n_tiles, frames)
-#define MG_LSDG_SIZE(NN) do { if (hr_shift) MG_LSDG_LAUNCH(NN, true); else MG_LSDG_LAUNCH(NN, false); } while (0)
+#define MG_LSDG_LAUNCH(NN, S, G)                                                                                                    \
+    hipLaunchKernelGGL((lsd_rows_grad_frames_kernel<NN, S, G>), dim3(blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rows, \
+                       n_rows, frame_start, total_frames, hr_shift, window, up, up_scale, hop, center != 0, n_tiles, frames)
+#define MG_LSDG_SHIFT(NN, G) do { if (hr_shift) MG_LSDG_LAUNCH(NN, true, G); else MG_LSDG_LAUNCH(NN, false, G); } while (0)
+#define MG_LSDG_SIZE(NN) do { if (seeded) MG_LSDG_SHIFT(NN, true); else MG_LSDG_SHIFT(NN, false); } while (0)
     if (n_fft == 512) MG_LSDG_SIZE(512);
     else if (n_fft == 1024) MG_LSDG_SIZE(1024);
     else MG_LSDG_SIZE(2048);
 #undef MG_LSDG_SIZE
+#undef MG_LSDG_SHIFT
 #undef MG_LSDG_LAUNCH
     MG_CHECK_LAUNCH();
     const long long n_slots = total_frames * hop + (long long)n_rows * n_fft;
@@ -215,6 +233,26 @@ int mg_lsd_rows_backward(const float* hr, long long hr_total, const float* sr, l
                        n_fft, hop, center != 0, sr_total, n_slots, grad_sr);
     MG_CHECK_LAUNCH();
     return MG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mg_lsd_rows_backward(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows,
+                         int n_rows, const long long* frame_start, long long total_frames, const float* hr_shift,
+                         const float* window, int n_fft, int hop, int center, const float* grad_rows, float* grad_sr,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    return lsd_rows_backward(hr, hr_total, sr, sr_total, rows, n_rows, frame_start, total_frames, hr_shift, window, n_fft, hop, center,
+                             grad_rows, 0.0, false, grad_sr, workspace, workspace_bytes, stream);
+}
+
+int mg_lsd_rows_backward_seeded(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows,
+                                int n_rows, const long long* frame_start, long long total_frames, const float* hr_shift,
+                                const float* window, int n_fft, int hop, int center, const float* go, double scale, float* grad_sr,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    return lsd_rows_backward(hr, hr_total, sr, sr_total, rows, n_rows, frame_start, total_frames, hr_shift, window, n_fft, hop, center,
+                             go, scale, true, grad_sr, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

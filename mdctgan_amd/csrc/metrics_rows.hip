@@ -9,6 +9,7 @@
 //                           from the row's first sample, one workgroup per chunk in a fixed tree, then the chunks in ascending order.
 //   lsd_rows_kernel         the per-frame log-spectral distance of every frame of every utterance, straight from the waveforms:
 //                           neither the windowed frames nor the spectra of metrics.hip's three-launch chain exist in HBM.
+//   lsd_mean_loss_kernel    scale * the mean of that per-frame array as a float32 [1] loss (the training term of --lambda_lsd).
 // Windows are cut to their buffers (a sample outside one is not read: it is skipped by the sums and enters a frame as 0), a row
 // with len <= 0 is dead, there are no atomics, every sum has one fixed order: a row has the same bits alone as inside any pack.
 //
@@ -181,6 +182,25 @@ __global__ __launch_bounds__(LSD_NT) void lsd_rows_kernel(const float* __restric
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// lsd_mean_loss_kernel: the loss node's reduction over lsd_rows_kernel's per-frame array, one workgroup.  Tiles of 256 consecutive
+// frames, one per thread; a tile is summed in block_sum_store's tree (rows.h), the tiles are added in ascending order by thread 0;
+// loss[0] = float32(scale * sum / total_frames), rounded once.  A training batch has a few hundred frames: one or two tiles.
+// ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void lsd_mean_loss_kernel(const float* __restrict__ per_frame, long long total_frames, double scale,
+                                                            float* __restrict__ loss) {
+    __shared__ double red[4][1];
+    __shared__ double tile_sum[1];
+    double sum = 0.0;                                       // (thread 0's)
+    for (long long base = 0; base < total_frames; base += 256) {
+        const long long i = base + threadIdx.x;
+        const double acc[1] = {i < total_frames ? (double)per_frame[i] : 0.0};
+        block_sum_store<1>(acc, red, tile_sum);             // (both barriers inside: tile_sum is thread 0's to read and to rewrite)
+        if (threadIdx.x == 0) sum += tile_sum[0];
+    }
+    if (threadIdx.x == 0) loss[0] = (float)(scale * sum / (double)total_frames);
+}
+
 }  // namespace
 
 extern "C" {
@@ -234,6 +254,13 @@ int mg_lsd_rows(const float* hr, long long hr_total, const float* sr, long long 
     else MG_LSD_SIZE(2048);
 #undef MG_LSD_SIZE
 #undef MG_LSD_LAUNCH
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+}
+
+int mg_lsd_mean_loss(const float* per_frame, long long total_frames, double scale, float* loss, void* stream) {
+    if (!per_frame || !loss || total_frames <= 0) return MG_ERR_ARG;
+    hipLaunchKernelGGL(lsd_mean_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, per_frame, total_frames, scale, loss);
     MG_CHECK_LAUNCH();
     return MG_OK;
 }

@@ -293,7 +293,8 @@ def _pack_with_grad(waves, layout, device):
 _lsd_tables = {}            # lsd_loss: the row tables of a dense geometry (B, T, n_fft, hop, center, device), uploaded once
 
 
-def _lsd_rows(hrs, srs, opt, hr_shift, table_key=None):
+def _lsd_operands(hrs, srs, opt, hr_shift, table_key=None):
+    """What every LSD loss node is applied to: -> (sr, hr, row_t, fs_t, frame_t, hr_shift, window, geom)."""
     hr_op = _packed_operand(hrs, "hrs")
     if any(t.requires_grad for t in ([hr_op[0]] if hr_op[0] is not None else hr_op[1])):
         raise NotImplementedError("the LSD has no gradient with respect to hr: detach the ground truth")
@@ -311,7 +312,11 @@ def _lsd_rows(hrs, srs, opt, hr_shift, table_key=None):
             _lsd_tables[table_key] = tables
     row_t, fs_t, frame_t = tables
     geom = (n_fft, hop, center, plan.total_frames, max(plan.frames))
-    return _LsdRows.apply(sr, hr, row_t, fs_t, frame_t, hr_shift, _window(win, device), geom)
+    return sr, hr, row_t, fs_t, frame_t, hr_shift, _window(win, device), geom
+
+
+def _lsd_rows(hrs, srs, opt, hr_shift, table_key=None):
+    return _LsdRows.apply(*_lsd_operands(hrs, srs, opt, hr_shift, table_key))
 
 
 def lsd_many(hrs, srs, opt, hr_shift=None):
@@ -332,6 +337,11 @@ def lsd_loss(sr_audio, hr_audio, opt):
     Nothing is read back and the row tables of a geometry are uploaded once and kept, so forward + backward capture into a
     graph on one stream after one eager call.  As for any autograd capture: no graph built on another stream from the same
     leaf may still be alive (detach or drop earlier losses), or the engine synchronises the capture with that stream."""
+    return _lsd_rows(*_dense_batch(sr_audio, hr_audio, opt)).mean()
+
+
+def _dense_batch(sr_audio, hr_audio, opt):
+    """lsd_loss's and lsd_loss_term's operand checks -> the arguments of _lsd_operands: both batches as packs read in place."""
     flat = []
     for x, what in ((sr_audio, "sr_audio"), (hr_audio, "hr_audio")):
         if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() not in (2, 3, 4) \
@@ -343,7 +353,60 @@ def lsd_loss(sr_audio, hr_audio, opt):
         raise ValueError("sr_audio holds %d clips of %d samples, hr_audio %d of %d" % (B, T, hr_audio.shape[0], hr_audio.shape[-1]))
     starts, lengths = [b * T for b in range(B)], [T] * B
     key = (B, T, int(opt.n_fft), int(opt.hop_length), bool(opt.center), str(sr_audio.device))
-    return _lsd_rows((flat[1], starts, lengths), (flat[0], starts, lengths), opt, None, table_key=key).mean()
+    return (flat[1], starts, lengths), (flat[0], starts, lengths), opt, None, key
+
+
+class _LsdMeanLoss(torch.autograd.Function):
+    """scale * the mean over all frames of a pack's per-frame LSD, as a node of the training step's loss family (functional._LossFn):
+    a float32 [1] loss, the constant factor inside, the upstream gradient read on the device.  Forward: mg_lsd_rows and
+    mg_lsd_mean_loss.  Backward: mg_lsd_rows_backward_seeded into an uninitialised buffer of sr's size -- the caller's pack is dense
+    (every sample belongs to a live row, and the gather writes every sample of a live row), so there is nothing to zero-fill."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, row_t, fs_t, window, geom, scale):
+        n_fft, hop, center, total_frames, _ = geom
+        lib = _lib.load()
+        per_frame = torch.empty(total_frames, dtype=torch.float32, device=sr.device)
+        _lib.check(lib.mg_lsd_rows(_lib.ptr(hr), hr.numel(), _lib.ptr(sr), sr.numel(), _lib.ptr(row_t), row_t.shape[0],
+                                   _lib.ptr(fs_t), total_frames, None, _lib.ptr(window), n_fft, hop, int(center),
+                                   _lib.ptr(per_frame), _lib.stream()), "mg_lsd_rows")
+        loss = torch.empty(1, dtype=torch.float32, device=sr.device)
+        _lib.check(lib.mg_lsd_mean_loss(_lib.ptr(per_frame), total_frames, scale, _lib.ptr(loss), _lib.stream()), "mg_lsd_mean_loss")
+        ctx.save_for_backward(sr, hr, row_t, fs_t, window)
+        ctx.geom, ctx.scale = geom, scale
+        return loss.reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        sr, hr, row_t, fs_t, window = ctx.saved_tensors
+        n_fft, hop, center, total_frames, _ = ctx.geom
+        lib = _lib.load()
+        go = go.reshape(1).float().contiguous()
+        grad_sr = torch.empty_like(sr)
+        nbytes = lib.mg_lsd_rows_backward_workspace(total_frames, n_fft)
+        ws = _lib.workspace(nbytes, sr.device)
+        _lib.check(lib.mg_lsd_rows_backward_seeded(_lib.ptr(hr), hr.numel(), _lib.ptr(sr), sr.numel(), _lib.ptr(row_t),
+                                                   row_t.shape[0], _lib.ptr(fs_t), total_frames, None, _lib.ptr(window), n_fft, hop,
+                                                   int(center), _lib.ptr(go), ctx.scale, _lib.ptr(grad_sr), _lib.ptr(ws), nbytes,
+                                                   _lib.stream()), "mg_lsd_rows_backward_seeded")
+        return grad_sr, None, None, None, None, None, None
+
+
+def lsd_loss_term(sr_audio, hr_audio, opt, scale):
+    """``scale * lsd_loss(sr_audio, hr_audio, opt)`` as a term of the training step -> 0-dim float32 tensor, differentiable in
+    sr_audio: lsd_loss's operand forms, checks and cached row tables, but one autograd node in the step's loss convention
+    (functional._LossFn) instead of a float64 composition.  Forward is mg_lsd_rows plus one reduction launch (the mean over all
+    frames: for the equal-length clips of a dense batch, lsd_loss's mean of per-clip means up to float64 rounding); backward is
+    mg_lsd_rows_backward_seeded, which forms every clip's upstream gradient on the device from the upstream scalar -- in the
+    arithmetic autograd performs for ``scale * lsd_loss``, so a power-of-two scale gives that gradient bit for bit -- and writes
+    every sample, so no buffer is zero-filled.  The upstream gradient (the GradScaler's loss scale in a --fp16 step) stays on the
+    device and is read when the kernel runs: a captured step follows it.  Capturable after one eager call, like lsd_loss."""
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError("scale must be finite")
+    sr, hr, row_t, fs_t, _, _, window, geom = _lsd_operands(*_dense_batch(sr_audio, hr_audio, opt))
+    return _LsdMeanLoss.apply(sr, hr, row_t, fs_t, window, geom, scale)
 
 
 def eval_model(model, eval_batches, opt, eval_path=None):

@@ -73,6 +73,8 @@ _FLAGS = [
     ("num_D", dict(type=int, default=2)), ("n_layers_D", dict(type=int, default=3)),
     ("ndf", dict(type=int, default=64)), ("no_ganFeat_loss", True), ("lambda_feat", dict(type=float, default=10.0)),
     ("no_lsgan", True), ("pool_size", dict(type=int, default=0)),
+    # the log-spectral distance of to_audio(sr) as a generator loss (not in the reference: metrics.lsd_loss_term); 0: off
+    ("lambda_lsd", dict(type=float, default=0.0)),
     # transform
     ("lr_sampling_rate", dict(type=int, default=LR_SAMPLE_RATE)),
     ("hr_sampling_rate", dict(type=int, default=HR_SAMPLE_RATE)),

@@ -18,7 +18,7 @@ import torch
 from . import _lib, networks
 from . import amp
 from . import functional as Fh
-from .mdct import RAW, Codec, CodecGrad, Transform, codec_inverse, kbdwin, wants_grad
+from .mdct import RAW, Codec, CodecGrad, Transform, codec_inverse, kbdwin, num_frames, wants_grad
 from .optim import FusedAdam
 
 
@@ -224,6 +224,10 @@ class Audio2MDCT(torch.nn.Module):
             audio, _ = self.transform.synthesis(raw, RAW)
         return audio if dest else audio[:, None, None, :]
 
+    def audio_length(self, T: int) -> int:
+        """Samples per clip of to_audio(to_spectro(x)) for a T-sample x (win_length == n_fft)."""
+        return (num_frames(int(T), self.win_length, self.hop_length, True) - 1) * self.hop_length
+
     def forward(self, lr_audio: torch.Tensor):
         with torch.no_grad():
             return self.to_spectro(lr_audio, mask=self.mask)
@@ -299,6 +303,7 @@ class Pix2PixHDModel(BaseModel):
         input_nc = opt.label_nc if opt.label_nc != 0 else opt.input_nc
         self.preprocess = Audio2MDCT(opt)
         self.preprocess.return_stats = False
+        self.lambda_lsd = self._check_lambda_lsd(opt) if self.isTrain else 0.0
         self.freeze = opt.freeze_g_d or opt.freeze_g_u or opt.freeze_l_d or opt.freeze_l_u
         self.netG = networks.define_G(
             input_nc, opt.output_nc, opt.ngf, opt.netG, opt.n_downsample_global, opt.n_blocks_global,
@@ -325,7 +330,8 @@ class Pix2PixHDModel(BaseModel):
             self.old_lr = opt.lr
             self.limit_aux_loss = False
             self.criterionGAN = networks.GANLoss(use_lsgan=not opt.no_lsgan, device=self.device)
-            self.loss_names = ["G_GAN"] + ([] if opt.no_ganFeat_loss else ["G_GAN_Feat"]) + ["D_real", "D_fake"]
+            self.loss_names = (["G_GAN"] + ([] if opt.no_ganFeat_loss else ["G_GAN_Feat"]) + (["G_lsd"] if self.lambda_lsd > 0 else [])
+                               + ["D_real", "D_fake"])
             if opt.niter_fix_global > 0:
                 params = [v for k, v in self.netG.named_parameters()
                           if k.startswith("model" + str(opt.n_local_enhancers))]
@@ -346,10 +352,30 @@ class Pix2PixHDModel(BaseModel):
         self._shared_rows = 0
         self.current_lable = self.current_generated = self.current_real = None
 
-    def loss_filter(self, g_gan, g_gan_feat, d_real, d_fake):
+    def _check_lambda_lsd(self, opt) -> float:
+        """--lambda_lsd: what the term cannot serve is refused here, not at the first backward pass."""
+        from .metrics import LSD_ROWS_N_FFT
+        lam = float(getattr(opt, "lambda_lsd", 0.0))
+        if not lam >= 0.0:
+            raise ValueError("--lambda_lsd must not be negative (got %r)" % lam)
+        if lam == 0.0:
+            return 0.0
+        if not self.preprocess._in_kernel:
+            raise NotImplementedError("--lambda_lsd: to_audio has no backward for the dB and explicit-encoding codecs "
+                                      "(train with --arcsinh_transform or --raw_mdct)")
+        if opt.win_length != opt.n_fft:
+            raise NotImplementedError("--lambda_lsd needs win_length == n_fft (got %d and %d)" % (opt.win_length, opt.n_fft))
+        if 2 * opt.n_fft not in LSD_ROWS_N_FFT:
+            raise NotImplementedError("--lambda_lsd: the LSD kernels serve transforms of %s samples, i.e. --n_fft in %s (got %d)"
+                                      % (LSD_ROWS_N_FFT, tuple(n // 2 for n in LSD_ROWS_N_FFT), opt.n_fft))
+        return lam
+
+    def loss_filter(self, g_gan, g_gan_feat, d_real, d_fake, g_lsd=None):
         out = [g_gan]
         if not self.no_ganFeat_loss:
             out.append(g_gan_feat)
+        if g_lsd is not None:
+            out.append(g_lsd)
         return out + [d_real, d_fake]
 
     # -- forward --------------------------------------------------------------------------------
@@ -376,9 +402,15 @@ class Pix2PixHDModel(BaseModel):
         return Fh.cat_channels(lr_spectro, x_spectro)        # pix2pixHD_model.py:425-427, 440: sr_input = sr_spectro
 
     def _forward(self, lr_audio, hr_audio, infer=False, share_d_pass=False):
-        """pix2pixHD_model.py:416-616: the four live losses [G_GAN, G_GAN_Feat, D_real, D_fake].  share_d_pass: the
+        """pix2pixHD_model.py:416-616: the live losses [G_GAN, G_GAN_Feat, (G_lsd,) D_real, D_fake].  share_d_pass: the
         caller backpropagates the two losses under Fh.backward_pass (optimize_parameters does); otherwise every loss
-        keeps its own discriminator pass and plain loss.backward() calls work as in train.py."""
+        keeps its own discriminator pass and plain loss.backward() calls work as in train.py.  --lambda_lsd > 0 adds G_lsd, the
+        log-spectral distance of to_audio(sr_spectro, lr_norm_param) to hr_audio times lambda_lsd (metrics.lsd_loss_term): the
+        place of the reference's commented-out audio-domain terms (pix2pixHD_model.py:453-498)."""
+        lsd = self.isTrain and self.lambda_lsd > 0
+        if lsd and int(hr_audio.shape[-1]) != self.preprocess.audio_length(lr_audio.shape[-1]):
+            raise ValueError("--lambda_lsd: hr_audio has %d samples per clip, to_audio returns %d for this lr_audio"
+                             % (hr_audio.shape[-1], self.preprocess.audio_length(lr_audio.shape[-1])))
         sr_spectro, _, hr_spectro, _, hr_norm_param, lr_spectro, _, lr_norm_param = self.forward(lr_audio, hr_audio)
         pooled = self.isTrain and getattr(self.opt, "pool_size", 0) > 0     # the fake pass of the D loss sees the history
         stacked = (self.stack_d_loss_passes and self.abs_spectro and self.arcsinh_transform and not pooled
@@ -428,9 +460,16 @@ class Pix2PixHDModel(BaseModel):
                     for j in range(len(pred_fake[i]) - 1):
                         loss_G_GAN_Feat = loss_G_GAN_Feat + Fh.l1_loss(
                             pred_fake[i][j], pred_real[i][j].detach(), D_weights * feat_weights * self.lambda_feat)
+        loss_G_lsd = None
+        if lsd:
+            from .metrics import lsd_loss_term
+            # (the generator's output is float32 under --fp16 as well: autocast changes the convolutions' arithmetic, not the tensors)
+            spec = sr_spectro if sr_spectro.dtype == torch.float32 and sr_spectro.is_contiguous() else sr_spectro.float().contiguous()
+            sr_audio = self.preprocess.to_audio(spec, lr_norm_param)
+            loss_G_lsd = lsd_loss_term(sr_audio, hr_audio.detach(), self.opt, self.lambda_lsd)
         # visuals are materialised lazily (the reference copies three tensors to the host every step)
         self._visual_src = (lr_spectro, sr_spectro.detach(), hr_spectro, lr_norm_param, hr_norm_param)
-        return [self.loss_filter(loss_G_GAN, loss_G_GAN_Feat, loss_D_real, loss_D_fake),
+        return [self.loss_filter(loss_G_GAN, loss_G_GAN_Feat, loss_D_real, loss_D_fake, loss_G_lsd),
                 torch.empty if not infer else sr_spectro]
 
     def optimize_parameters(self, lr_audio, hr_audio):
@@ -446,6 +485,8 @@ class Pix2PixHDModel(BaseModel):
         # 2 ones_like fills per iteration)
         loss_D = loss_dict["D_fake"] + loss_dict["D_real"]
         loss_G = loss_dict["G_GAN"] + loss_dict["G_GAN_Feat"] if "G_GAN_Feat" in loss_dict else loss_dict["G_GAN"]
+        if "G_lsd" in loss_dict:      # its gradient joins the discriminator's at sr_spectro by autograd's accumulation: one float32 add
+            loss_G = loss_G + loss_dict["G_lsd"]
         red = getattr(self, "reducers", None)      # data-parallel gradient reducers (mdctgan_amd.ddp.attach)
         sc = self.scaler                           # train.py:183-199: one GradScaler, updated once per iteration
         seed_G, seed_D = self._backward_seeds(sc, loss_D.device)
