@@ -347,6 +347,58 @@ int mg_lsd_rows_backward_seeded(const float* hr, long long hr_total, const float
                                 const float* window, int n_fft, int hop, int center, const float* go, double scale, float* grad_sr,
                                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* The multi-resolution STFT loss (spectral convergence + log-magnitude L1) of many utterances in shared launches,
+ * csrc/stft_loss_rows.hip; Python: metrics.mrstft_many / mrstft_loss / mrstft_loss_term.  ONE resolution per call; the caller loops
+ * over its resolutions on one stream.  hr, sr, rows, n_rows, frame_start, total_frames, n_fft, hop and center are mg_lsd_rows' own and
+ * follow its rules (lr_pos of a row is not read; there is no hr_shift); window [n_fft] is the resolution's window (the Python side
+ * passes the periodic Hann window, evaluated in float64 and rounded once).  With K = n_fft / 2 + 1, F_u the frames of row u, p = re^2
+ * + im^2 of the float32 spectrum (the transform of the exact sample-times-window products runs in double and every bin is rounded
+ * to float32 once, so the sign and clamp decisions below are float64's wherever two bins differ by more than float32 rounding; p
+ * is formed in double) and m = sqrt(max(p, 1e-7)), everything after the spectrum in double:
+ *     A_u = sum_{f,k} (m_hr - m_sr)^2,   B_u = sum_{f,k} m_hr^2,   C_u = sum_{f,k} |ln m_hr - ln m_sr|,
+ *     loss_u = sqrt(A_u / B_u) + C_u / (F_u K).
+ * Conventions at the non-smooth points: A_u == 0 makes the first term exactly 0, in value and gradient; a bin with ln m_hr ==
+ * ln m_sr contributes 0 to the gradient (sign(0) = 0), and so does a bin with p_sr < 1e-7 (the clamp).  So sr == hr and silence
+ * against silence give loss exactly 0 and gradient exactly 0, an all-zero sr a finite loss and gradient exactly 0.
+ *   mg_stft_loss_rows   row_out[u] = {A_u, B_u, C_u, loss_u} (double [n_rows][4]; a dead row: four zeros).  Two launches whatever
+ *                       n_rows is: every frame's three sums (a fixed tree over the frame's bins) into workspace, then each row's
+ *                       frames in ascending order.  Frames and spectra are never written.  workspace:
+ *                       mg_stft_loss_rows_workspace(total_frames) bytes (three doubles per frame; 0: invalid), 16-byte aligned.
+ *   mg_stft_loss_rows_backward   grad_sr = d (sum_u grad_rows[u] loss_u) / d sr, hr constant.  row_sums: the row_out that
+ *                       mg_stft_loss_rows wrote for the same operands and resolution (only read).  grad_rows: float32 [n_rows].
+ *                       grad_sr: float32 [sr_total]; sample t < len of a live row is written once at grad_sr[sr_pos + t]
+ *                       (accumulate == 0) or the rounded sum is added to what is there by the one thread that owns the sample
+ *                       (accumulate != 0: the second and later resolutions, so that a multi-resolution gradient is the float32 sum
+ *                       of the per-resolution ones in call order); nothing else is touched.  Two launches (the second is
+ *                       mg_lsd_rows_backward's gather), no atomics, every sum in one fixed order.  workspace:
+ *                       mg_stft_loss_rows_backward_workspace(total_frames, n_fft) bytes, 16-byte aligned (one float32 frame of
+ *                       n_fft samples per frame).  A centred row with len <= n_fft / 2 is treated as dead, as in mg_lsd_rows_backward.
+ *   mg_stft_loss_rows_backward_seeded   the same two launches for a loss node of the step's convention: every row's upstream
+ *                       gradient is formed on the device, in double, as ((go[0] * scale) / n_rows) / n_res -- d (scale * mean_u
+ *                       mean_r loss_{r,u}) times go[0].  go: float32 [1] on the device, read when the kernel runs (a captured
+ *                       step follows a loss scale that changes between replays).  n_res: the number of resolutions of the mean.
+ *   mg_stft_loss_mean   loss[0] = float32(scale * (sum_u (sum_r loss_{r,u}) / n_res) / n_rows) from row_out [n_res][n_rows][4] (the
+ *                       row_out of n_res mg_stft_loss_rows calls, one after the other in one buffer): one workgroup, double, a
+ *                       row's resolutions ascending, tiles of 256 rows in a fixed tree, the tiles ascending, rounded once.
+ * A row has the same value and gradient bits alone as inside any pack.  No host synchronisation, static LDS only.  MG_ERR_ARG
+ * before any launch for a null pointer, a non-positive count, total, hop or n_res, n_fft outside {512, 1024, 2048}, a short or
+ * misaligned workspace. */
+size_t mg_stft_loss_rows_workspace(long long total_frames);
+int mg_stft_loss_rows(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows, int n_rows,
+                      const long long* frame_start, long long total_frames, const float* window, int n_fft, int hop, int center,
+                      double* row_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t mg_stft_loss_rows_backward_workspace(long long total_frames, int n_fft);
+int mg_stft_loss_rows_backward(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows,
+                               int n_rows, const long long* frame_start, long long total_frames, const float* window, int n_fft,
+                               int hop, int center, const double* row_sums, const float* grad_rows, int accumulate, float* grad_sr,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int mg_stft_loss_rows_backward_seeded(const float* hr, long long hr_total, const float* sr, long long sr_total,
+                                      const mg_metric_row* rows, int n_rows, const long long* frame_start, long long total_frames,
+                                      const float* window, int n_fft, int hop, int center, const double* row_sums, const float* go,
+                                      double scale, int n_res, int accumulate, float* grad_sr, void* workspace, size_t workspace_bytes,
+                                      void* stream);
+int mg_stft_loss_mean(const double* row_out, int n_rows, int n_res, double scale, float* loss, void* stream);
+
 /* Segment stitching of generate_audio.py:40-53: seg [n_seg, seg_len] (the [n_seg,1,1,T] inference outputs) -> one
  * waveform of mg_stitch_length() samples (-1: invalid arguments; 2*overlap must be < seg_len).  overlap == 0
  * concatenates; overlap > 0 halves the first/last `overlap` samples of every segment, overlap-adds at stride

@@ -1,7 +1,10 @@
-// What lsd_rows_kernel (metrics_rows.hip) and its backward (lsd_rows_grad.hip) share: the tile of LSD_TILE complex points per
+// What lsd_rows_kernel (metrics_rows.hip), its backward (lsd_rows_grad.hip) and the STFT loss (stft_loss_rows.hip) share: the tile of LSD_TILE complex points per
 // workgroup of LSD_NT threads, the search of a frame's row, the staging of the windowed, reflected frames as packed complex
 // points, the Stockham stages in LDS and the split of a packed transform into the bins of the real one.  The comments at the
-// head of metrics_rows.hip describe all of it; each statement stands here once so that the two kernels cannot drift apart.
+// head of metrics_rows.hip describe all of it; each statement stands here once so that the kernels cannot drift apart.
+// ONE restated copy exists: stft_loss_rows.hip needs these stages, the split and the staging for double2 on a smaller tile (its sign
+// and clamp decisions want a spectrum that is accurate per bin) and keeps them as sd_* templates beside its kernels, so that
+// nothing here -- and no bit of the LSD -- changes.  A change to the statements below belongs there as well.
 #pragma once
 #include <limits.h>
 

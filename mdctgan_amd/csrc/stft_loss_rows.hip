@@ -1,0 +1,520 @@
+// The multi-resolution STFT loss of many utterances in shared launches (Python: metrics.mrstft_many / mrstft_loss /
+// mrstft_loss_term; the training term of --lambda_mrstft), on the frame machinery of lsd_fft.h: the row search, the staging with
+// the reflection at the row's own ends, the Stockham stages and the split of lsd_rows_kernel (metrics_rows.hip).  The FORWARD
+// transform runs in double (sd_* below: lsd_fft.h's statements for double2, on a tile of 2048 points) and every bin is rounded to
+// float32 once: the sign of ln m_hr - ln m_sr and the clamp are DECISIONS, each weighted with 1/m^2 in the gradient, and a float32
+// transform errs relative to the frame's largest bin -- on a tone whose peak lies eleven decades of power above the clamp that is
+// percents of a bin near the clamp, so a float32 transform (this one or a CPU's) takes some of those decisions differently from
+// float64 and from one build to the next.  A spectrum that is accurate per bin takes them as float64 does wherever the bins are
+// 1e-6 apart.  The inverse transform of the gradient has no decisions and stays in float32.
+//
+// One resolution r = (N, hop), window [N] (the host passes the periodic Hann window), K = N/2 + 1 bins, F_u frames of row u.  With
+// p = re^2 + im^2 of the float32 spectrum (the double transform rounded once; p formed in double) and m = sqrt(max(p, 1e-7)):
+//     A_u = sum_{f,k} (m_hr - m_sr)^2     B_u = sum_{f,k} m_hr^2     C_u = sum_{f,k} |ln m_hr - ln m_sr|
+//     loss_u = sqrt(A_u / B_u) + C_u / (F_u K)                (spectral convergence + log-magnitude L1, per utterance)
+// Gradient with respect to sr only.  At the non-smooth points, by definition: A_u == 0 gives a spectral-convergence term of exactly
+// 0 (value and gradient), a bin with ln m_hr == ln m_sr contributes 0 (sign(0) = 0), a bin with p_sr < 1e-7 contributes 0 (the
+// clamp); B_u >= F_u K 1e-7 > 0 for a live row.  So silence against silence, an all-zero sr and sr == hr (the same statements on
+// both operands) have gradient exactly 0, and the first and last have loss exactly 0.
+//
+//   stft_loss_frames_kernel   forward, one launch over all frames of the pack: lsd_rows_kernel up to the split, then per bin in
+//       double d = m_hr - m_sr; the lanes of a frame sum {d^2, m_hr^2, |ln m_hr - ln m_sr|} in lsd_rows_kernel's tree and lane 0
+//       stores the three doubles of the frame to partial [total_frames][3] (a frame outside every live row: zeros).  Frames and
+//       spectra are never written.  LDS: 32 KiB of frame data (4 / 2 / 1 frames per workgroup at N = 512 / 1024 / 2048) + 8 N bytes
+//       of roots (the half circle in double).
+//   stft_loss_finish_kernel   one thread per row: the row's frames in ascending order in double -> row_out[u] = {A_u, B_u, C_u,
+//       loss_u}; a dead row (or one whose frame range does not fit the table) gives four zeros.
+//   stft_loss_grad_frames_kernel   backward, phase one: the two spectra of every frame again, then per bin, in double, from the
+//       row's A_u, B_u, F_u (row_out) and the row's upstream gradient g_u
+//           c_k = (g_u (m_sr - m_hr) / sqrt(A_u B_u) - g_u sign(ln m_hr - ln m_sr) / (F_u K m_sr)) / m_sr     (0 where clamped;
+//                                                                                     the first term 0 where A_u == 0)
+//       i.e. G_k = (dL/dm_k / m_k) X_sr[k] and y = Re sum_{k=0..N/2} G_k exp(+2 pi i k n / N): the Hermitian spectrum H_k = G_k / 2
+//       (0 < k < N/2), Re G_k (k = 0, N/2) is rounded to float32, kept in registers until every lane has read its bins (a barrier),
+//       written as float2 over the dead doubles and inverted in float32 through lsd_rows_grad_frames_kernel's adjoint of the
+//       pack-and-split and the forward stages.  y[n] window[n] goes to the workspace [total_frames][N] (float32) in 16-byte stores.  No reduction:
+//       the row sums come from the forward.
+//   lsd_rows_grad_gather_kernel   phase two, lsd_gather.h (shared with the LSD backward): every sample of a live row sums its taps
+//       in double in one fixed order and is written (ACC == false) or added to (ACC == true: the second and later resolutions) by
+//       exactly one thread.
+//   stft_loss_mean_kernel   the dense batch's loss node: loss[0] = float32(scale * mean_u mean_r loss_{r,u}), one workgroup, double.
+// Static LDS only, no atomics, no host read-back, launch counts independent of the number of rows; no arithmetic for a row depends
+// on where the row sits, so a row has the same value and gradient bits alone and in any pack.  Tables that do not agree with
+// themselves lose samples; nothing is read or written outside a buffer, and only samples of live rows are written.
+#include <math.h>
+
+#include "lsd_gather.h"
+
+namespace {
+
+constexpr double kStftClamp = 1e-7;
+constexpr int SD_TILE = 2048;       // complex double points of frame data per workgroup: 32 KiB
+
+// ---- the transform of lsd_fft.h restated for a vector type V (double2 forward, float2 for the inverse): the same Stockham stages,
+// split and roots; a stage may have fewer butterflies than the workgroup has threads, and the roots exp(-2 pi i t / N) are kept
+// as doubles for t < N/2 only (root[t + N/2] = -root[t]), rounded to float32 once where the float32 inverse reads them ----
+__device__ __forceinline__ float2 sd_mk(float a, float b) { return make_float2(a, b); }
+__device__ __forceinline__ double2 sd_mk(double a, double b) { return make_double2(a, b); }
+__device__ __forceinline__ void sd_cvt(double2 a, double2& o) { o = a; }
+__device__ __forceinline__ void sd_cvt(double2 a, float2& o) { o = make_float2((float)a.x, (float)a.y); }
+
+template <typename V>
+__device__ __forceinline__ V sd_cmul(V a, V b) { return sd_mk(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+
+template <int N, typename V>
+__device__ __forceinline__ V sd_root(const double2* __restrict__ root, int t) {
+    const double2 r = root[t & (N / 2 - 1)];
+    V o;
+    sd_cvt((t & (N / 2)) ? make_double2(-r.x, -r.y) : r, o);
+    return o;
+}
+
+template <int N>
+__device__ __forceinline__ void sd_roots(double2* __restrict__ root, int tid) {
+    for (int t = tid; t < N / 2; t += LSD_NT) {
+        double sn, cs;
+        sincospi(-2.0 * (double)t / (double)N, &sn, &cs);
+        root[t] = make_double2(cs, sn);
+    }
+}
+
+template <int R, typename V>
+__device__ __forceinline__ void sd_butterfly(V (&v)[R]) {
+    if (R == 2) {
+        const V a = v[0], b = v[1];
+        v[0] = sd_mk(a.x + b.x, a.y + b.y);
+        v[1] = sd_mk(a.x - b.x, a.y - b.y);
+    } else if (R == 4) {
+        const V a0 = sd_mk(v[0].x + v[2].x, v[0].y + v[2].y), a1 = sd_mk(v[0].x - v[2].x, v[0].y - v[2].y);
+        const V a2 = sd_mk(v[1].x + v[3].x, v[1].y + v[3].y), a3 = sd_mk(v[1].x - v[3].x, v[1].y - v[3].y);
+        v[0] = sd_mk(a0.x + a2.x, a0.y + a2.y);
+        v[2] = sd_mk(a0.x - a2.x, a0.y - a2.y);
+        v[1] = sd_mk(a1.x + a3.y, a1.y - a3.x);      // a1 - i a3
+        v[3] = sd_mk(a1.x - a3.y, a1.y + a3.x);      // a1 + i a3
+    } else {
+        V e[4] = {v[0], v[2], v[4], v[6]}, o[4] = {v[1], v[3], v[5], v[7]};
+        sd_butterfly<4>(e);
+        sd_butterfly<4>(o);
+        const decltype(v[0].x) H = (decltype(v[0].x))0.70710678118654752440;
+        const V t0 = o[0];
+        const V t1 = sd_mk((o[1].x + o[1].y) * H, (o[1].y - o[1].x) * H);        // (1 - i) / sqrt 2
+        const V t2 = sd_mk(o[2].y, -o[2].x);                                      // -i
+        const V t3 = sd_mk((o[3].y - o[3].x) * H, (-o[3].x - o[3].y) * H);       // (-1 - i) / sqrt 2
+        v[0] = sd_mk(e[0].x + t0.x, e[0].y + t0.y); v[4] = sd_mk(e[0].x - t0.x, e[0].y - t0.y);
+        v[1] = sd_mk(e[1].x + t1.x, e[1].y + t1.y); v[5] = sd_mk(e[1].x - t1.x, e[1].y - t1.y);
+        v[2] = sd_mk(e[2].x + t2.x, e[2].y + t2.y); v[6] = sd_mk(e[2].x - t2.x, e[2].y - t2.y);
+        v[3] = sd_mk(e[3].x + t3.x, e[3].y + t3.y); v[7] = sd_mk(e[3].x - t3.x, e[3].y - t3.y);
+    }
+}
+
+// lsd_stage over the TILE / P transforms of P points in buf; root: the half table of N = 2 P.  Both barriers inside.
+template <int P, int R, int NS, int TILE, typename V>
+__device__ __forceinline__ void sd_stage(V* __restrict__ buf, const double2* __restrict__ root, int tid) {
+    constexpr int NB = P / R, TOT = (TILE / P) * NB, IT = (TOT + LSD_NT - 1) / LSD_NT;
+    V v[IT][R];
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        const int idx = tid + it * LSD_NT, fr = idx / NB, j = idx % NB;
+        if (idx < TOT) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) v[it][r] = buf[fr * P + j + r * NB];
+            if (NS > 1) {
+                const int k = j % NS;
+#pragma unroll
+                for (int r = 1; r < R; ++r) v[it][r] = sd_cmul(v[it][r], sd_root<2 * P, V>(root, 2 * (r * k * (P / (NS * R)))));
+            }
+            sd_butterfly<R>(v[it]);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        const int idx = tid + it * LSD_NT, fr = idx / NB, j = idx % NB;
+        const int d = (j / NS) * NS * R + j % NS;
+        if (idx < TOT) {
+#pragma unroll
+            for (int r = 0; r < R; ++r) buf[fr * P + d + r * NS] = v[it][r];
+        }
+    }
+    __syncthreads();
+}
+
+template <int P, int NS, int TILE, typename V>
+__device__ __forceinline__ void sd_stages8(V* buf, const double2* root, int tid) {
+    sd_stage<P, 8, NS, TILE>(buf, root, tid);
+    if constexpr (NS * 8 < P) sd_stages8<P, NS * 8, TILE>(buf, root, tid);
+}
+
+// Stage radices as lsd_fft: P = 256: 4 8 8;  P = 512: 8 8 8;  P = 1024: 2 8 8 8.
+template <int P, int TILE, typename V>
+__device__ __forceinline__ void sd_fft(V* buf, const double2* root, int tid) {
+    constexpr int REM = lsd_log2(P) % 3;
+    if constexpr (REM == 0) {
+        sd_stages8<P, 1, TILE>(buf, root, tid);
+    } else {
+        sd_stage<P, 1 << REM, 1, TILE>(buf, root, tid);
+        sd_stages8<P, 1 << REM, TILE>(buf, root, tid);
+    }
+}
+
+// lsd_real_bin in double, rounded to float32 once: THE float32 spectrum of the definition
+template <int M>
+__device__ __forceinline__ float2 sd_real_bin(const double2* __restrict__ Z, int k, const double2* __restrict__ root) {
+    const double2 zk = Z[k & (M - 1)], zm = Z[(M - k) & (M - 1)], w = sd_root<2 * M, double2>(root, k);
+    const double2 e = make_double2(0.5 * (zk.x + zm.x), 0.5 * (zk.y - zm.y));          // (Z[k] + conj Z[M-k]) / 2
+    const double2 o = make_double2(0.5 * (zk.y + zm.y), 0.5 * (zm.x - zk.x));          // (Z[k] - conj Z[M-k]) / 2i
+    const double2 t = sd_cmul(w, o);
+    return make_float2((float)(e.x + t.x), (float)(e.y + t.y));
+}
+
+// lsd_load_tile for SD_TILE points in double: the product of the float32 sample and the float32 window is exact
+template <int N>
+__device__ __forceinline__ void sd_load_tile(double2* __restrict__ buf, const LsdFrame* __restrict__ info,
+                                             const float* __restrict__ hr, long long hr_total, const float* __restrict__ sr,
+                                             long long sr_total, const float* __restrict__ window, int center, int tid) {
+    constexpr int M = N / 2;
+#pragma unroll 4
+    for (int i = tid; i < SD_TILE; i += LSD_NT) {
+        const int fr = i / N, is_sr = (i / M) & 1, m = i % M;
+        const LsdFrame fi = info[fr];
+        const float* __restrict__ x = is_sr ? sr : hr;
+        const long long at = is_sr ? fi.sr_at : fi.hr_at, total = is_sr ? sr_total : hr_total;
+        double e[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            long long t = fi.first + 2 * m + q;
+            if (center) {
+                if (t < 0) t = -t;
+                if (t >= fi.len) t = 2 * (fi.len - 1) - t;
+            }
+            float v = 0.0f;
+            if (fi.live && t >= 0 && t < fi.len) {
+                const long long p = at + t;
+                if (p >= 0 && p < total) v = x[p];
+            }
+            e[q] = (double)v * (double)window[2 * m + q];
+        }
+        buf[i] = make_double2(e[0], e[1]);
+    }
+}
+
+template <int N>
+__global__ __launch_bounds__(LSD_NT) void stft_loss_frames_kernel(const float* __restrict__ hr, long long hr_total,
+                                                                  const float* __restrict__ sr, long long sr_total,
+                                                                  const mg_metric_row* __restrict__ rows, int n_rows,
+                                                                  const long long* __restrict__ frame_start, long long total_frames,
+                                                                  const float* __restrict__ window, int hop, int center,
+                                                                  long long n_tiles, double* __restrict__ partial) {
+    constexpr int M = N / 2, FT = SD_TILE / N, TPF = LSD_NT / FT, NBINS = N / 2 + 1;
+    static_assert(TPF >= 64 && M % LSD_NT == 0, "a frame's lanes fill whole waves, a load pass stays inside one signal of a frame");
+    __shared__ __attribute__((aligned(16))) double2 buf[SD_TILE];          // [FT][hr, sr][M]
+    __shared__ __attribute__((aligned(16))) double2 root[N / 2];
+    __shared__ double red[LSD_NT / 64][3];
+    __shared__ LsdFrame info[FT];
+    const int tid = threadIdx.x;
+    sd_roots<N>(root, tid);
+    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        if (tid < FT) {
+            int row;
+            info[tid] = lsd_locate<false>(tile * FT + tid, rows, n_rows, frame_start, total_frames, nullptr, N, hop, center, row);
+        }
+        __syncthreads();
+        sd_load_tile<N>(buf, info, hr, hr_total, sr, sr_total, window, center, tid);
+        __syncthreads();
+        sd_fft<M, SD_TILE>(buf, root, tid);
+        // bins k = j, j + TPF, ... of frame fr on lane j of the frame's TPF lanes
+        const int fr = tid / TPF, j = tid % TPF;
+        const double2* Zh = buf + fr * N;
+        const double2* Zs = Zh + M;
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (int k = j; k < NBINS; k += TPF) {
+            const float2 a = sd_real_bin<M>(Zh, k, root), b = sd_real_bin<M>(Zs, k, root);
+            const double pa = fmax((double)a.x * a.x + (double)a.y * a.y, kStftClamp);
+            const double pb = fmax((double)b.x * b.x + (double)b.y * b.y, kStftClamp);
+            const double d = sqrt(pa) - sqrt(pb);
+            acc[0] += d * d;
+            acc[1] += pa;
+            acc[2] += fabs(0.5 * (log(pa) - log(pb)));
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) acc[q] = wave_sum_d(acc[q]);
+        if (TPF > 64) {
+            if ((tid & 63) == 0) {
+#pragma unroll
+                for (int q = 0; q < 3; ++q) red[tid >> 6][q] = acc[q];
+            }
+            __syncthreads();
+            if (j == 0) {
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    acc[q] = red[fr * (TPF / 64)][q];
+                    for (int w = 1; w < TPF / 64; ++w) acc[q] += red[fr * (TPF / 64) + w][q];
+                }
+            }
+        }
+        if (j == 0) {
+            const long long g = tile * FT + fr;
+            if (g < total_frames) {
+                const bool live = info[fr].live != 0;
+#pragma unroll
+                for (int q = 0; q < 3; ++q) partial[g * 3 + q] = live ? acc[q] : 0.0;
+            }
+        }
+        __syncthreads();                                    // buf, info and red are free for the next tile
+    }
+}
+
+// a row whose frames [f0, f0 + nf) the frame kernels served
+__device__ __forceinline__ bool stft_row_frames(const mg_metric_row* __restrict__ rows, const long long* __restrict__ frame_start,
+                                                long long total_frames, int u, long long& f0, long long& nf) {
+    f0 = frame_start[u];
+    nf = frame_start[u + 1] - f0;
+    return lsd_row_ok(rows[u]) && f0 >= 0 && nf > 0 && nf - 1 <= INT_MAX && f0 + nf <= total_frames;
+}
+
+__global__ __launch_bounds__(256) void stft_loss_finish_kernel(const double* __restrict__ partial, const mg_metric_row* __restrict__ rows,
+                                                               int n_rows, const long long* __restrict__ frame_start,
+                                                               long long total_frames, int n_bins, double* __restrict__ row_out) {
+    for (long long u = (long long)blockIdx.x * 256 + threadIdx.x; u < n_rows; u += (long long)gridDim.x * 256) {
+        long long f0, nf;
+        double s[3] = {0.0, 0.0, 0.0}, loss = 0.0;
+        if (stft_row_frames(rows, frame_start, total_frames, (int)u, f0, nf)) {
+            for (long long f = f0; f < f0 + nf; ++f) {
+#pragma unroll
+                for (int q = 0; q < 3; ++q) s[q] += partial[f * 3 + q];
+            }
+            loss = ((s[0] > 0.0 && s[1] > 0.0) ? sqrt(s[0] / s[1]) : 0.0) + s[2] / ((double)nf * (double)n_bins);
+        }
+        row_out[u * 4 + 0] = s[0];
+        row_out[u * 4 + 1] = s[1];
+        row_out[u * 4 + 2] = s[2];
+        row_out[u * 4 + 3] = loss;
+    }
+}
+
+// SEEDED: `up` is not the per-row gradient but the loss node's upstream scalar go [1], and every row's gradient is formed here, in
+// double, as ((go[0] * up_scale) / n_rows) / n_res -- d (scale * mean_u mean_r loss_{r,u}) / d loss_{r,u} times go[0] -- when the
+// kernel runs, so a captured step follows a loss scale that changes between replays.
+template <int N, bool SEEDED>
+__global__ __launch_bounds__(LSD_NT) void stft_loss_grad_frames_kernel(const float* __restrict__ hr, long long hr_total,
+                                                                       const float* __restrict__ sr, long long sr_total,
+                                                                       const mg_metric_row* __restrict__ rows, int n_rows,
+                                                                       const long long* __restrict__ frame_start,
+                                                                       long long total_frames, const float* __restrict__ window,
+                                                                       const double* __restrict__ row_sums,
+                                                                       const float* __restrict__ up, double up_scale, int n_res,
+                                                                       int hop, int center, long long n_tiles,
+                                                                       float* __restrict__ frames_out) {
+    constexpr int M = N / 2, FT = SD_TILE / N, TPF = LSD_NT / FT, NBINS = N / 2 + 1, BPL = (NBINS + TPF - 1) / TPF;
+    constexpr int HALF = SD_TILE / 2;                                       // the Zt of the tile's frames, densely: [FT][M]
+    static_assert(TPF >= 64 && M % LSD_NT == 0, "a frame's lanes fill whole waves, a load pass stays inside one signal of a frame");
+    static_assert(HALF % LSD_NT == 0 && (HALF / 2) % LSD_NT == 0 && M % 2 == 0, "whole points and whole point pairs per thread");
+    __shared__ __attribute__((aligned(16))) double2 buf[SD_TILE];          // [FT][hr, sr][M] double; then, as float2: [FT][N] holding
+    __shared__ __attribute__((aligned(16))) double2 root[N / 2];           //   H_k, k = 0 .. M, of every frame; then [FT][M]
+    __shared__ LsdFrame info[FT];
+    __shared__ double coef[FT][2];                                         // g / sqrt(A B) (0: A == 0),  g / (F K)
+    float2* fbuf = reinterpret_cast<float2*>(buf);
+    const int tid = threadIdx.x;
+    sd_roots<N>(root, tid);
+    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        if (tid < FT) {
+            int row;
+            const LsdFrame fi = lsd_locate<false>(tile * FT + tid, rows, n_rows, frame_start, total_frames, nullptr, N, hop, center, row);
+            info[tid] = fi;
+            double c_sc = 0.0, c_l1 = 0.0;
+            if (fi.live) {
+                const double g = SEEDED ? (((double)up[0] * up_scale) / (double)n_rows) / (double)n_res : (double)up[row];
+                const double A = row_sums[(long long)row * 4], B = row_sums[(long long)row * 4 + 1];
+                if (A > 0.0 && B > 0.0) c_sc = g / sqrt(A * B);
+                c_l1 = g / ((double)(frame_start[row + 1] - frame_start[row]) * (double)NBINS);
+            }
+            coef[tid][0] = c_sc;
+            coef[tid][1] = c_l1;
+        }
+        __syncthreads();
+        sd_load_tile<N>(buf, info, hr, hr_total, sr, sr_total, window, center, tid);
+        __syncthreads();
+        sd_fft<M, SD_TILE>(buf, root, tid);
+        // pass one: H_k of bins k = j, j + TPF, ... of frame fr on lane j of the frame's TPF lanes, in registers
+        const int fr = tid / TPF, j = tid % TPF;
+        const double2* Zh = buf + fr * N;
+        const double2* Zs = Zh + M;
+        const double c_sc = coef[fr][0], c_l1 = coef[fr][1];
+        float2 h[BPL];
+#pragma unroll
+        for (int i = 0; i < BPL; ++i) {
+            const int k = j + i * TPF;
+            h[i] = make_float2(0.0f, 0.0f);
+            if (k < NBINS) {
+                const float2 a = sd_real_bin<M>(Zh, k, root), b = sd_real_bin<M>(Zs, k, root);
+                const double pa = fmax((double)a.x * a.x + (double)a.y * a.y, kStftClamp);
+                const double pb = (double)b.x * b.x + (double)b.y * b.y;
+                if (pb >= kStftClamp) {
+                    const double ma = sqrt(pa), mb = sqrt(pb), dl = log(pa) - log(pb);
+                    const double sg = dl > 0.0 ? 1.0 : (dl < 0.0 ? -1.0 : 0.0);
+                    const double c = (c_sc * (mb - ma) - c_l1 * sg / mb) / mb;
+                    h[i] = (k == 0 || k == M) ? make_float2((float)(c * (double)b.x), 0.0f)
+                                              : make_float2((float)(0.5 * c * (double)b.x), (float)(0.5 * c * (double)b.y));
+                }
+            }
+        }
+        __syncthreads();                                    // every lane has read its Z[k] and Z[M-k]: the doubles are dead
+        // pass two: H_k, k = 0 .. M, of frame fr at fbuf[fr N + k] (float2: the frames' regions fill half of buf)
+#pragma unroll
+        for (int i = 0; i < BPL; ++i) {
+            const int k = j + i * TPF;
+            if (k < NBINS) fbuf[fr * N + k] = h[i];
+        }
+        __syncthreads();
+        // conj Zt of every frame, held in registers until all H are read, then packed densely
+        float2 zt[HALF / LSD_NT];
+#pragma unroll
+        for (int it = 0; it < HALF / LSD_NT; ++it) {
+            const int idx = tid + it * LSD_NT, f2 = idx / M, k = idx % M;
+            const float2 h1 = fbuf[f2 * N + k], h2 = fbuf[f2 * N + M - k], w = sd_root<N, float2>(root, k);
+            const float2 a = make_float2(h1.x + h2.x, h1.y - h2.y);                         // H_k + conj H_{M-k}
+            const float2 b = lsd_cmul(make_float2(h1.x - h2.x, h1.y + h2.y), make_float2(w.x, -w.y));
+            zt[it] = make_float2(a.x - b.y, -(a.y + b.x));                                  // conj (a + i b)
+        }
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < HALF / LSD_NT; ++it) fbuf[tid + it * LSD_NT] = zt[it];
+        __syncthreads();
+        sd_fft<M, HALF>(fbuf, root, tid);
+        // y[2m] = Re, y[2m+1] = -Im of the transform; two points = four samples per store
+#pragma unroll
+        for (int it = 0; it < HALF / 2 / LSD_NT; ++it) {
+            const int idx = tid + it * LSD_NT, f2 = idx / (M / 2), n = 4 * (idx % (M / 2));
+            const long long g = tile * FT + f2;
+            if (g < total_frames) {
+                const float4 v = *reinterpret_cast<const float4*>(fbuf + f2 * M + n / 2);
+                *reinterpret_cast<float4*>(frames_out + g * N + n) =
+                    make_float4(v.x * window[n], -v.y * window[n + 1], v.z * window[n + 2], -v.w * window[n + 3]);
+            }
+        }
+        __syncthreads();                                    // buf, info and coef are free for the next tile
+    }
+}
+
+// One workgroup.  Tiles of 256 consecutive rows, one per thread: a row's losses are added in resolution order and divided by n_res,
+// a tile is summed in block_sum_store's tree (rows.h), the tiles are added in ascending order by thread 0.
+__global__ __launch_bounds__(256) void stft_loss_mean_kernel(const double* __restrict__ row_out, int n_rows, int n_res, double scale,
+                                                             float* __restrict__ loss) {
+    __shared__ double red[4][1];
+    __shared__ double tile_sum[1];
+    double sum = 0.0;                                       // (thread 0's)
+    for (long long base = 0; base < n_rows; base += 256) {
+        const long long u = base + threadIdx.x;
+        double v = 0.0;
+        if (u < n_rows) {
+            for (int r = 0; r < n_res; ++r) v += row_out[((long long)r * n_rows + u) * 4 + 3];
+            v /= (double)n_res;
+        }
+        const double acc[1] = {v};
+        block_sum_store<1>(acc, red, tile_sum);             // (both barriers inside: tile_sum is thread 0's to read and to rewrite)
+        if (threadIdx.x == 0) sum += tile_sum[0];
+    }
+    if (threadIdx.x == 0) loss[0] = (float)(scale * sum / (double)n_rows);
+}
+
+}  // namespace
+
+extern "C" {
+
+// See include/mdctgan_hip.h.
+size_t mg_stft_loss_rows_workspace(long long total_frames) {
+    if (total_frames <= 0 || total_frames > kFar / (3 * (long long)sizeof(double))) return 0;
+    return (size_t)total_frames * 3 * sizeof(double);
+}
+
+size_t mg_stft_loss_rows_backward_workspace(long long total_frames, int n_fft) {
+    if (total_frames <= 0 || !lsd_size_ok(n_fft) || total_frames > kFar / (n_fft * (long long)sizeof(float))) return 0;
+    return (size_t)total_frames * (size_t)n_fft * sizeof(float);
+}
+
+int mg_stft_loss_rows(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows, int n_rows,
+                      const long long* frame_start, long long total_frames, const float* window, int n_fft, int hop, int center,
+                      double* row_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!hr || !sr || !rows || !frame_start || !window || !row_out || !workspace) return MG_ERR_ARG;
+    if (n_rows <= 0 || total_frames <= 0 || hr_total <= 0 || sr_total <= 0 || hop <= 0 || !lsd_size_ok(n_fft)) return MG_ERR_ARG;
+    const size_t need = mg_stft_loss_rows_workspace(total_frames);
+    if (need == 0 || workspace_bytes < need || !al16(workspace)) return MG_ERR_ARG;
+    double* partial = static_cast<double*>(workspace);
+    const long long ft = SD_TILE / n_fft, n_tiles = (total_frames + ft - 1) / ft;
+    const unsigned blocks = (unsigned)(n_tiles < 3 * 256 * 4 ? n_tiles : 3 * 256 * 4);    // a few waves of three workgroups per CU
+    hipStream_t st = (hipStream_t)stream;
+#define MG_STFT_LAUNCH(NN)                                                                                                          \
+    hipLaunchKernelGGL((stft_loss_frames_kernel<NN>), dim3(blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rows, n_rows, \
+                       frame_start, total_frames, window, hop, center != 0, n_tiles, partial)
+    if (n_fft == 512) MG_STFT_LAUNCH(512);
+    else if (n_fft == 1024) MG_STFT_LAUNCH(1024);
+    else MG_STFT_LAUNCH(2048);
+#undef MG_STFT_LAUNCH
+    MG_CHECK_LAUNCH();
+    const unsigned fblocks = (unsigned)((n_rows + 255) / 256 < 1024 ? (n_rows + 255) / 256 : 1024);
+    hipLaunchKernelGGL(stft_loss_finish_kernel, dim3(fblocks), dim3(256), 0, st, partial, rows, n_rows, frame_start, total_frames,
+                       n_fft / 2 + 1, row_out);
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// both entry points: `up` is grad_rows [n_rows] (seeded == false) or go [1] with up_scale and n_res
+int stft_loss_rows_backward(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows,
+                            int n_rows, const long long* frame_start, long long total_frames, const float* window, int n_fft, int hop,
+                            int center, const double* row_sums, const float* up, double up_scale, int n_res, bool seeded,
+                            int accumulate, float* grad_sr, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!hr || !sr || !rows || !frame_start || !window || !row_sums || !up || !grad_sr || !workspace) return MG_ERR_ARG;
+    if (n_rows <= 0 || total_frames <= 0 || hr_total <= 0 || sr_total <= 0 || hop <= 0 || n_res <= 0 || !lsd_size_ok(n_fft))
+        return MG_ERR_ARG;
+    const size_t need = mg_stft_loss_rows_backward_workspace(total_frames, n_fft);
+    if (need == 0 || workspace_bytes < need || !al16(workspace)) return MG_ERR_ARG;
+    if (total_frames > (kFar - (long long)n_rows * n_fft) / hop) return MG_ERR_ARG;          // the gather's slot count
+    float* frames = static_cast<float*>(workspace);
+    const long long ft = SD_TILE / n_fft, n_tiles = (total_frames + ft - 1) / ft;
+    const unsigned blocks = (unsigned)(n_tiles < 3 * 256 * 4 ? n_tiles : 3 * 256 * 4);
+    hipStream_t st = (hipStream_t)stream;
+#define MG_STFTG_LAUNCH(NN, G)                                                                                                        \
+    hipLaunchKernelGGL((stft_loss_grad_frames_kernel<NN, G>), dim3(blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rows,    \
+                       n_rows, frame_start, total_frames, window, row_sums, up, up_scale, n_res, hop, center != 0, n_tiles, frames)
+#define MG_STFTG_SIZE(NN) do { if (seeded) MG_STFTG_LAUNCH(NN, true); else MG_STFTG_LAUNCH(NN, false); } while (0)
+    if (n_fft == 512) MG_STFTG_SIZE(512);
+    else if (n_fft == 1024) MG_STFTG_SIZE(1024);
+    else MG_STFTG_SIZE(2048);
+#undef MG_STFTG_SIZE
+#undef MG_STFTG_LAUNCH
+    MG_CHECK_LAUNCH();
+    return lsd_launch_gather(frames, rows, n_rows, frame_start, total_frames, n_fft, hop, center, sr_total, accumulate != 0, grad_sr, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mg_stft_loss_rows_backward(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows,
+                               int n_rows, const long long* frame_start, long long total_frames, const float* window, int n_fft,
+                               int hop, int center, const double* row_sums, const float* grad_rows, int accumulate, float* grad_sr,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    return stft_loss_rows_backward(hr, hr_total, sr, sr_total, rows, n_rows, frame_start, total_frames, window, n_fft, hop, center,
+                                   row_sums, grad_rows, 0.0, 1, false, accumulate, grad_sr, workspace, workspace_bytes, stream);
+}
+
+int mg_stft_loss_rows_backward_seeded(const float* hr, long long hr_total, const float* sr, long long sr_total,
+                                      const mg_metric_row* rows, int n_rows, const long long* frame_start, long long total_frames,
+                                      const float* window, int n_fft, int hop, int center, const double* row_sums, const float* go,
+                                      double scale, int n_res, int accumulate, float* grad_sr, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    return stft_loss_rows_backward(hr, hr_total, sr, sr_total, rows, n_rows, frame_start, total_frames, window, n_fft, hop, center,
+                                   row_sums, go, scale, n_res, true, accumulate, grad_sr, workspace, workspace_bytes, stream);
+}
+
+int mg_stft_loss_mean(const double* row_out, int n_rows, int n_res, double scale, float* loss, void* stream) {
+    if (!row_out || !loss || n_rows <= 0 || n_res <= 0) return MG_ERR_ARG;
+    hipLaunchKernelGGL(stft_loss_mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, row_out, n_rows, n_res, scale, loss);
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+}
+
+}  // extern "C"

@@ -142,18 +142,8 @@ def _packed_operand(x, what: str):
     return None, waves, [int(w.numel()) for w in waves]
 
 
-def _metric_operands(operands, opt, hr_shift, differentiable=False):
-    """What compute_matrics_many and the LSD loss do before their launches, stated once so that the two stay in step.  operands:
-    ((hrs, "hrs"), ..., (srs, "srs")), the ground truth first; every other one is cropped to its lengths and must not be shorter.
-    Checks the transform (2 * opt.n_fft in LSD_ROWS_N_FFT, win_length == n_fft), the operand forms, the counts, the lengths and
-    hr_shift, plans the frames, and packs what came as a list (packed.aligned_layout's layout; `differentiable`: a list with an
-    entry that requires grad is packed by one differentiable concatenation).
-    -> (n_fft, hop, win, plan, device, buffers, starts), buffers / starts in the operands' order."""
-    n_fft, hop, win = 2 * int(opt.n_fft), 2 * int(opt.hop_length), 2 * int(opt.win_length)
-    if win != n_fft:
-        raise NotImplementedError("win_length != n_fft")
-    if n_fft not in LSD_ROWS_N_FFT:
-        raise NotImplementedError("mg_lsd_rows serves n_fft in %s (got %d)" % (LSD_ROWS_N_FFT, n_fft))
+def _checked_operands(operands):
+    """The operand forms, counts and lengths of ((hrs, "hrs"), ..., (srs, "srs")) -> (_packed_operand of each, hr's lengths)."""
     ops_ = [_packed_operand(x, name) for x, name in operands]
     hrs = operands[0][0]
     if isinstance(hrs, tuple) and ops_[0][0] is not None and len(hrs) != 3:
@@ -169,8 +159,11 @@ def _metric_operands(operands, opt, hr_shift, differentiable=False):
         for u in range(U):
             if avail[u] < lengths[u]:
                 raise ValueError("utterance %d: %s has %d samples, fewer than hr's %d" % (u, name, avail[u], lengths[u]))
-    plan = plan_metrics(lengths, n_fft, hop, bool(opt.center))
+    return ops_, lengths
 
+
+def _pack_operands(ops_, differentiable):
+    """Packs what came as a list (packed.aligned_layout's layout) -> (device, buffers, starts) in the operands' order."""
     device = next((t.device for buf, ws, _ in ops_ for t in ([buf] if buf is not None else ws) if t.is_cuda), None)
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
@@ -182,6 +175,25 @@ def _metric_operands(operands, opt, hr_shift, differentiable=False):
             buf, ws = (_pack_with_grad if with_grad else pack_waves)(ws, layout, device), layout.starts
         bufs.append(buf)
         starts.append(ws)
+    return device, bufs, starts
+
+
+def _metric_operands(operands, opt, hr_shift, differentiable=False):
+    """What compute_matrics_many and the LSD loss do before their launches, stated once so that the two stay in step.  operands:
+    ((hrs, "hrs"), ..., (srs, "srs")), the ground truth first; every other one is cropped to its lengths and must not be shorter.
+    Checks the transform (2 * opt.n_fft in LSD_ROWS_N_FFT, win_length == n_fft), the operand forms, the counts, the lengths and
+    hr_shift, plans the frames, and packs what came as a list (packed.aligned_layout's layout; `differentiable`: a list with an
+    entry that requires grad is packed by one differentiable concatenation).
+    -> (n_fft, hop, win, plan, device, buffers, starts), buffers / starts in the operands' order."""
+    n_fft, hop, win = 2 * int(opt.n_fft), 2 * int(opt.hop_length), 2 * int(opt.win_length)
+    if win != n_fft:
+        raise NotImplementedError("win_length != n_fft")
+    if n_fft not in LSD_ROWS_N_FFT:
+        raise NotImplementedError("mg_lsd_rows serves n_fft in %s (got %d)" % (LSD_ROWS_N_FFT, n_fft))
+    ops_, lengths = _checked_operands(operands)
+    U = len(lengths)
+    plan = plan_metrics(lengths, n_fft, hop, bool(opt.center))
+    device, bufs, starts = _pack_operands(ops_, differentiable)
     if hr_shift is not None and (not hr_shift.is_cuda or hr_shift.dtype != torch.float32 or hr_shift.numel() != U
                                  or not hr_shift.is_contiguous()):
         raise ValueError("hr_shift is a contiguous float32 [%d] device tensor" % U)
@@ -340,8 +352,8 @@ def lsd_loss(sr_audio, hr_audio, opt):
     return _lsd_rows(*_dense_batch(sr_audio, hr_audio, opt)).mean()
 
 
-def _dense_batch(sr_audio, hr_audio, opt):
-    """lsd_loss's and lsd_loss_term's operand checks -> the arguments of _lsd_operands: both batches as packs read in place."""
+def _dense_pack(sr_audio, hr_audio):
+    """The operand checks of the dense-batch losses -> (hrs, srs, B, T): both batches as packs read in place."""
     flat = []
     for x, what in ((sr_audio, "sr_audio"), (hr_audio, "hr_audio")):
         if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.float32 or x.dim() not in (2, 3, 4) \
@@ -352,8 +364,14 @@ def _dense_batch(sr_audio, hr_audio, opt):
     if (int(hr_audio.shape[0]), int(hr_audio.shape[-1])) != (B, T):
         raise ValueError("sr_audio holds %d clips of %d samples, hr_audio %d of %d" % (B, T, hr_audio.shape[0], hr_audio.shape[-1]))
     starts, lengths = [b * T for b in range(B)], [T] * B
+    return (flat[1], starts, lengths), (flat[0], starts, lengths), B, T
+
+
+def _dense_batch(sr_audio, hr_audio, opt):
+    """lsd_loss's and lsd_loss_term's operand checks -> the arguments of _lsd_operands: both batches as packs read in place."""
+    hrs, srs, B, T = _dense_pack(sr_audio, hr_audio)
     key = (B, T, int(opt.n_fft), int(opt.hop_length), bool(opt.center), str(sr_audio.device))
-    return (flat[1], starts, lengths), (flat[0], starts, lengths), opt, None, key
+    return hrs, srs, opt, None, key
 
 
 class _LsdMeanLoss(torch.autograd.Function):
@@ -407,6 +425,196 @@ def lsd_loss_term(sr_audio, hr_audio, opt, scale):
         raise ValueError("scale must be finite")
     sr, hr, row_t, fs_t, _, _, window, geom = _lsd_operands(*_dense_batch(sr_audio, hr_audio, opt))
     return _LsdMeanLoss.apply(sr, hr, row_t, fs_t, window, geom, scale)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The multi-resolution STFT loss (spectral convergence + log-magnitude L1): csrc/stft_loss_rows.hip
+# ---------------------------------------------------------------------------------------------------------------------
+STFT_RESOLUTIONS = ((512, 128), (1024, 256), (2048, 512))       # (n_fft, hop) of the default loss
+STFT_CLAMP = 1e-7                                               # m = sqrt(max(re^2 + im^2, STFT_CLAMP))
+
+_mrstft_tables = {}         # mrstft_loss: the tables of a dense geometry (B, T, resolutions, center, device), uploaded once
+
+
+def _hann(n_fft: int, device):
+    """The periodic Hann window of n_fft samples, evaluated in float64 and rounded to float32 once."""
+    key = ("hann", n_fft, str(device))
+    if key not in _windows:
+        _windows[key] = torch.hann_window(n_fft, periodic=True, dtype=torch.float64).to(torch.float32).to(device).contiguous()
+    return _windows[key]
+
+
+def _resolutions(resolutions):
+    try:
+        res = tuple((int(n), int(h)) for n, h in resolutions)
+    except (TypeError, ValueError):
+        raise ValueError("resolutions: a sequence of (n_fft, hop) pairs") from None
+    if not res:
+        raise ValueError("resolutions: at least one (n_fft, hop) pair")
+    for n, h in res:
+        if n not in LSD_ROWS_N_FFT:
+            raise NotImplementedError("the STFT loss kernels serve n_fft in %s (got %d)" % (LSD_ROWS_N_FFT, n))
+        if h < 1:
+            raise ValueError("resolution (%d, %d): the hop must be at least 1" % (n, h))
+    return res
+
+
+def plan_mrstft(lengths, resolutions=STFT_RESOLUTIONS, center: bool = True):
+    """plan_metrics for every resolution (host only) -> [MetricsPlan]; ValueError naming the utterance AND the resolution where an
+    utterance has no frame or (centred) cannot be reflected: len <= n_fft / 2."""
+    plans = []
+    for n, h in _resolutions(resolutions):
+        try:
+            plans.append(plan_metrics(lengths, n, h, center))
+        except ValueError as e:
+            raise ValueError("resolution (%d, %d): %s" % (n, h, e)) from None
+    return plans
+
+
+def _mrstft_operands(hrs, srs, resolutions, center, table_key=None):
+    """What every MR-STFT node is applied to -> (sr, hr, row_t, tabs); tabs = (frame_start tables, windows, geometries (n_fft,
+    hop, center, total_frames)), one entry per resolution."""
+    res, center = _resolutions(resolutions), bool(center)
+    ops_, lengths = _checked_operands(((hrs, "hrs"), (srs, "srs")))
+    if any(t.requires_grad for t in ([ops_[0][0]] if ops_[0][0] is not None else ops_[0][1])):
+        raise NotImplementedError("the MR-STFT loss has no gradient with respect to hr: detach the ground truth")
+    plans = plan_mrstft(lengths, res, center)
+    device, (hr, sr), starts = _pack_operands(ops_, True)
+    U = len(lengths)
+    tables = _mrstft_tables.get(table_key) if table_key is not None else None
+    if tables is None:
+        rows = np.stack([np.asarray(t, dtype=np.int64) for t in (starts[0], [0] * U, starts[1], lengths)], axis=1)
+        tables = upload_tables([rows] + [p.frame_start for p in plans], device)
+        if table_key is not None:
+            if len(_mrstft_tables) >= 64:       # a training run has one geometry; a sweep over many must not pile tables up
+                _mrstft_tables.clear()
+            _mrstft_tables[table_key] = tables
+    geoms = tuple((p.n_fft, p.hop, center, p.total_frames) for p in plans)
+    return sr, hr, tables[0], (tuple(tables[1:]), tuple(_hann(n, device) for n, _ in res), geoms)
+
+
+def _mrstft_forward(sr, hr, row_t, tabs):
+    """mg_stft_loss_rows for every resolution -> row_out float64 [R, U, 4] = {A, B, C, loss}."""
+    fs_ts, windows, geoms = tabs
+    lib = _lib.load()
+    U = row_t.shape[0]
+    row_out = torch.empty(len(geoms), U, 4, dtype=torch.float64, device=sr.device)
+    for r, (fs_t, window, (n_fft, hop, center, total_frames)) in enumerate(zip(fs_ts, windows, geoms)):
+        nbytes = lib.mg_stft_loss_rows_workspace(total_frames)
+        ws = _lib.workspace(nbytes, sr.device)
+        _lib.check(lib.mg_stft_loss_rows(_lib.ptr(hr), hr.numel(), _lib.ptr(sr), sr.numel(), _lib.ptr(row_t), U, _lib.ptr(fs_t),
+                                         total_frames, _lib.ptr(window), n_fft, hop, int(center), _lib.ptr(row_out[r]), _lib.ptr(ws),
+                                         nbytes, _lib.stream()), "mg_stft_loss_rows")
+    return row_out
+
+
+def _mrstft_backward(sr, hr, row_t, tabs, row_out, grad_sr, grad_rows=None, go=None, scale=0.0):
+    """mg_stft_loss_rows_backward (grad_rows [U]) or its seeded form (go [1], scale) for every resolution, in resolution order: the
+    first writes every sample of the live rows of grad_sr, the later ones add to it."""
+    fs_ts, windows, geoms = tabs
+    lib = _lib.load()
+    U, R = row_t.shape[0], len(geoms)
+    for r, (fs_t, window, (n_fft, hop, center, total_frames)) in enumerate(zip(fs_ts, windows, geoms)):
+        nbytes = lib.mg_stft_loss_rows_backward_workspace(total_frames, n_fft)
+        ws = _lib.workspace(nbytes, sr.device)
+        head = (_lib.ptr(hr), hr.numel(), _lib.ptr(sr), sr.numel(), _lib.ptr(row_t), U, _lib.ptr(fs_t), total_frames, _lib.ptr(window),
+                n_fft, hop, int(center), _lib.ptr(row_out[r]))
+        tail = (int(r > 0), _lib.ptr(grad_sr), _lib.ptr(ws), nbytes, _lib.stream())
+        if go is None:
+            _lib.check(lib.mg_stft_loss_rows_backward(*head, _lib.ptr(grad_rows), *tail), "mg_stft_loss_rows_backward")
+        else:
+            _lib.check(lib.mg_stft_loss_rows_backward_seeded(*head, _lib.ptr(go), scale, R, *tail),
+                       "mg_stft_loss_rows_backward_seeded")
+    return grad_sr
+
+
+class _MrStftRows(torch.autograd.Function):
+    """Per-utterance MR-STFT loss [U] (float64) of a packed sr buffer against a packed, constant hr buffer: the losses of the
+    resolutions added in resolution order and divided by their number.  Backward: into a zero-filled buffer of sr's size."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, row_t, tabs):
+        row_out = _mrstft_forward(sr, hr, row_t, tabs)
+        ctx.save_for_backward(sr, hr, row_t, row_out)
+        ctx.tabs = tabs
+        total = row_out[0, :, 3].clone()
+        for r in range(1, row_out.shape[0]):
+            total = total + row_out[r, :, 3]
+        return total / row_out.shape[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        sr, hr, row_t, row_out = ctx.saved_tensors
+        grad_rows = (grad.double() / row_out.shape[0]).float().contiguous()
+        return _mrstft_backward(sr, hr, row_t, ctx.tabs, row_out, torch.zeros_like(sr), grad_rows=grad_rows), None, None, None
+
+
+def mrstft_many(hrs, srs, resolutions=STFT_RESOLUTIONS, center=True):
+    """The multi-resolution STFT loss of every utterance on its own, differentiable in sr -> float64 device tensor [U].  For one
+    resolution (n_fft, hop) -- periodic Hann window of n_fft samples, centred frames reflected at the utterance's own ends, K =
+    n_fft / 2 + 1 bins, F_u frames, m = sqrt(max(re^2 + im^2, 1e-7)) --
+        loss_u = sqrt(sum (m_hr - m_sr)^2 / sum m_hr^2) + sum |ln m_hr - ln m_sr| / (F_u K)
+    with the sums over all frames and bins of utterance u, and the result is the mean over the resolutions.  Operand forms as for
+    ``lsd_many``: lists of waveforms, or packed ``(buffer, starts, lengths)`` / ``(buffer, starts[, lengths])`` read where they
+    lie.  Two library launches per resolution forward and two backward, whatever U is (csrc/stft_loss_rows.hip), plus the
+    element-wise launches on [U] that join the resolutions (a copy, R - 1 adds, a divide; backward: a divide, a cast and the zero
+    fill); deterministic; nothing is read back.  The gradient is exactly 0 where autograd through torch.stft has NaN or Inf: sr == hr, silence, clamped bins.  hr
+    is a constant: a ground truth that requires grad raises NotImplementedError.  ValueError (naming utterance and resolution)
+    for an utterance that cannot be reflected at a resolution, len <= n_fft / 2."""
+    return _MrStftRows.apply(*_mrstft_operands(hrs, srs, resolutions, center))
+
+
+def _mrstft_dense(sr_audio, hr_audio, resolutions):
+    hrs, srs, B, T = _dense_pack(sr_audio, hr_audio)
+    res = _resolutions(resolutions)
+    return _mrstft_operands(hrs, srs, res, True, (B, T, res, True, str(sr_audio.device)))
+
+
+def mrstft_loss(sr_audio, hr_audio, resolutions=STFT_RESOLUTIONS):
+    """``mrstft_many`` of a dense batch as a training loss -> 0-dim float64 tensor, the mean over the clips, differentiable in
+    sr_audio.  sr_audio / hr_audio: float32 device tensors [B, T], [B, 1, T] or [B, 1, 1, T], read in place (no packing copy).
+    The tables of a geometry are uploaded once and kept, so forward + backward capture into a graph on one stream after one
+    eager call (lsd_loss's note on live graphs from other streams applies)."""
+    return _MrStftRows.apply(*_mrstft_dense(sr_audio, hr_audio, resolutions)).mean()
+
+
+class _MrStftMeanLoss(torch.autograd.Function):
+    """scale * the mean over the clips of the MR-STFT loss as a node of the training step's loss family: a float32 [1] loss, the
+    constant factor inside, the upstream gradient read on the device.  Forward: mg_stft_loss_rows per resolution and
+    mg_stft_loss_mean.  Backward: mg_stft_loss_rows_backward_seeded per resolution into an uninitialised buffer of sr's size -- the
+    pack is dense and every row is live at every resolution, so the first resolution writes every sample."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, row_t, tabs, scale):
+        row_out = _mrstft_forward(sr, hr, row_t, tabs)
+        loss = torch.empty(1, dtype=torch.float32, device=sr.device)
+        _lib.check(_lib.load().mg_stft_loss_mean(_lib.ptr(row_out), row_out.shape[1], row_out.shape[0], scale, _lib.ptr(loss),
+                                                 _lib.stream()), "mg_stft_loss_mean")
+        ctx.save_for_backward(sr, hr, row_t, row_out)
+        ctx.tabs, ctx.scale = tabs, scale
+        return loss.reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        sr, hr, row_t, row_out = ctx.saved_tensors
+        go = go.reshape(1).float().contiguous()
+        return _mrstft_backward(sr, hr, row_t, ctx.tabs, row_out, torch.empty_like(sr), go=go, scale=ctx.scale), None, None, None, None
+
+
+def mrstft_loss_term(sr_audio, hr_audio, scale, resolutions=STFT_RESOLUTIONS):
+    """``scale * mrstft_loss(sr_audio, hr_audio, resolutions)`` as a term of the training step -> 0-dim float32 tensor,
+    differentiable in sr_audio: mrstft_loss's operand forms, checks and cached tables, but one autograd node in the step's loss
+    convention (functional._LossFn).  Forward is mg_stft_loss_rows per resolution plus one reduction launch; backward is
+    mg_stft_loss_rows_backward_seeded per resolution, which forms every clip's upstream gradient in the kernel, in double, from the
+    upstream scalar -- the GradScaler's loss scale in a --fp16 step stays on the device and is read when the kernel runs, so a
+    captured step follows it -- and writes every sample, so no buffer is zero-filled.  Capturable after one eager call."""
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError("scale must be finite")
+    sr, hr, row_t, tabs = _mrstft_dense(sr_audio, hr_audio, resolutions)
+    return _MrStftMeanLoss.apply(sr, hr, row_t, tabs, scale)
 
 
 def eval_model(model, eval_batches, opt, eval_path=None):

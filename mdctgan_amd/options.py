@@ -75,6 +75,8 @@ _FLAGS = [
     ("no_lsgan", True), ("pool_size", dict(type=int, default=0)),
     # the log-spectral distance of to_audio(sr) as a generator loss (not in the reference: metrics.lsd_loss_term); 0: off
     ("lambda_lsd", dict(type=float, default=0.0)),
+    # the multi-resolution STFT loss of to_audio(sr) as a generator loss (not in the reference: metrics.mrstft_loss_term); 0: off
+    ("lambda_mrstft", dict(type=float, default=0.0)),
     # transform
     ("lr_sampling_rate", dict(type=int, default=LR_SAMPLE_RATE)),
     ("hr_sampling_rate", dict(type=int, default=HR_SAMPLE_RATE)),
