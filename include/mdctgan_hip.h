@@ -399,6 +399,56 @@ int mg_stft_loss_rows_backward_seeded(const float* hr, long long hr_total, const
                                       void* stream);
 int mg_stft_loss_mean(const double* row_out, int n_rows, int n_res, double scale, float* loss, void* stream);
 
+/* The multi-scale mel-spectrogram L1 loss of many utterances in shared launches, csrc/mel_loss_rows.hip; Python: metrics.mel_many /
+ * mel_loss / mel_loss_term.  ONE resolution (n_fft, hop, n_mels) per call; the caller loops over its resolutions on one stream.  hr,
+ * sr, rows, n_rows, frame_start, total_frames, window, n_fft, hop and center are mg_stft_loss_rows' own and follow its rules, and so
+ * does everything up to the magnitudes: K = n_fft / 2 + 1 bins, p = re^2 + im^2 of the float32 spectrum (the transform runs in
+ * double and every bin is rounded to float32 once; p is formed in double), m = sqrt(max(p, 1e-7)).  The filterbank operand:
+ *   fbank   float32 [n_mels][K], dense (the Python side passes metrics.mel_fbank: HTK triangles without area normalisation,
+ *           evaluated in float64 and rounded once); widened to double where it is read;
+ *   band_k  int32 [n_mels][2]: filter j is non-zero on the bins [band_k[j][0], band_k[j][1]) only;
+ *   band_j  int32 [K][2]: bin k lies in the filters [band_j[k][0], band_j[k][1]) only;
+ *   n_mels  1 .. 256.
+ * fbank is read inside those bands only and the kernels clip every band to the matrix: tables that do not agree with fbank lose
+ * terms, nothing is read outside a buffer.  Per frame f and filter j, in double,
+ *     E_j = sum_k fbank[j][k] m_k  (k ascending),   l_j = ln max(E_j, 1e-5),   loss_u = sum_{f,j} |l_hr - l_sr| / (F_u n_mels).
+ * Conventions at the non-smooth points: a filter with l_hr == l_sr contributes 0 to the gradient (sign(0) = 0), and so do a filter
+ * with E_sr <= 1e-5 (the floor of the logarithm) and a bin with p_sr < 1e-7 (the clamp).  So sr == hr and silence against silence
+ * give loss exactly 0 and gradient exactly 0, an all-zero sr a finite loss and gradient exactly 0.
+ *   mg_mel_loss_rows    row_out[u] = {sum_{f,j} |l_hr - l_sr|, 0, 0, loss_u} (double [n_rows][4], mg_stft_loss_rows' layout, so that
+ *                       mg_stft_loss_mean over [n_res][n_rows][4] is the float32 loss of a dense batch; a dead row: four zeros).
+ *                       Two launches whatever n_rows is: every frame's sum (a fixed tree over the frame's filters) into workspace,
+ *                       then each row's frames in ascending order.  workspace: mg_mel_loss_rows_workspace(total_frames) bytes (one
+ *                       double per frame; 0: invalid), 16-byte aligned.
+ *   mg_mel_loss_rows_backward   grad_sr = d (sum_u grad_rows[u] loss_u) / d sr, hr constant: both spectra and both E again (nothing
+ *                       is kept from the forward), dE_j = -grad_rows[u] sign(l_hr - l_sr) / (F_u n_mels E_sr), dm_k = sum_j
+ *                       fbank[j][k] dE_j (j ascending), G_k = (dm_k / m_sr) X_sr[k], all in double; from G_k on
+ *                       mg_stft_loss_rows_backward's float32 inverse, window product and gather, with its grad_rows, accumulate,
+ *                       grad_sr and workspace (mg_mel_loss_rows_backward_workspace(total_frames, n_fft) bytes, 16-byte aligned).
+ *   mg_mel_loss_rows_backward_seeded   the same two launches for a loss node of the step's convention: every row's upstream gradient
+ *                       is formed on the device as float32(((go[0] * scale) / n_rows) / n_res), the quotient in double -- the row
+ *                       gradient autograd hands the unseeded form for scale * mean_u mean_r loss_{r,u}.  go: float32 [1] on the
+ *                       device, read when the kernel runs.
+ * A row has the same value and gradient bits alone as inside any pack.  No host synchronisation, static LDS only, no atomics.
+ * MG_ERR_ARG before any launch for a null or misaligned pointer, a non-positive count, total, hop or n_res, n_fft outside {512, 1024,
+ * 2048}, n_mels outside 1 .. 256, a short or misaligned workspace. */
+size_t mg_mel_loss_rows_workspace(long long total_frames);
+int mg_mel_loss_rows(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows, int n_rows,
+                     const long long* frame_start, long long total_frames, const float* window, int n_fft, int hop, int center,
+                     const float* fbank, const int* band_k, const int* band_j, int n_mels, double* row_out, void* workspace,
+                     size_t workspace_bytes, void* stream);
+size_t mg_mel_loss_rows_backward_workspace(long long total_frames, int n_fft);
+int mg_mel_loss_rows_backward(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows,
+                              int n_rows, const long long* frame_start, long long total_frames, const float* window, int n_fft,
+                              int hop, int center, const float* fbank, const int* band_k, const int* band_j, int n_mels,
+                              const float* grad_rows, int accumulate, float* grad_sr, void* workspace, size_t workspace_bytes,
+                              void* stream);
+int mg_mel_loss_rows_backward_seeded(const float* hr, long long hr_total, const float* sr, long long sr_total,
+                                     const mg_metric_row* rows, int n_rows, const long long* frame_start, long long total_frames,
+                                     const float* window, int n_fft, int hop, int center, const float* fbank, const int* band_k,
+                                     const int* band_j, int n_mels, const float* go, double scale, int n_res, int accumulate,
+                                     float* grad_sr, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Segment stitching of generate_audio.py:40-53: seg [n_seg, seg_len] (the [n_seg,1,1,T] inference outputs) -> one
  * waveform of mg_stitch_length() samples (-1: invalid arguments; 2*overlap must be < seg_len).  overlap == 0
  * concatenates; overlap > 0 halves the first/last `overlap` samples of every segment, overlap-adds at stride

@@ -137,6 +137,12 @@ SIGNATURES = {
     "mg_stft_loss_rows_backward_seeded": (_i, [_p, _ll, _p, _ll, _p, _i, _p, _ll, _p, _i, _i, _i, _p, _p, C.c_double, _i, _i, _p, _p,
                                                _sz, _p]),
     "mg_stft_loss_mean": (_i, [_p, _i, _i, C.c_double, _p, _p]),
+    "mg_mel_loss_rows_workspace": (_sz, [_ll]),
+    "mg_mel_loss_rows": (_i, [_p, _ll, _p, _ll, _p, _i, _p, _ll, _p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _sz, _p]),
+    "mg_mel_loss_rows_backward_workspace": (_sz, [_ll, _i]),
+    "mg_mel_loss_rows_backward": (_i, [_p, _ll, _p, _ll, _p, _i, _p, _ll, _p, _i, _i, _i, _p, _p, _p, _i, _p, _i, _p, _p, _sz, _p]),
+    "mg_mel_loss_rows_backward_seeded": (_i, [_p, _ll, _p, _ll, _p, _i, _p, _ll, _p, _i, _i, _i, _p, _p, _p, _i, _p, C.c_double, _i, _i,
+                                              _p, _p, _sz, _p]),
     "mg_frames_window": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "mg_codec_forward": (_i, [_p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p, _p, _p, _p]),
     "mg_codec_inverse": (_i, [_p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _p, _p, _p, _p]),

@@ -2,8 +2,9 @@
 // workgroup of LSD_NT threads, the search of a frame's row, the staging of the windowed, reflected frames as packed complex
 // points, the Stockham stages in LDS and the split of a packed transform into the bins of the real one.  The comments at the
 // head of metrics_rows.hip describe all of it; each statement stands here once so that the kernels cannot drift apart.
-// ONE restated copy exists: stft_loss_rows.hip needs these stages, the split and the staging for double2 on a smaller tile (its sign
-// and clamp decisions want a spectrum that is accurate per bin) and keeps them as sd_* templates beside its kernels, so that
+// ONE restated copy exists: stft_loss_rows.hip and mel_loss_rows.hip need these stages, the split and the staging for double2 on a
+// smaller tile (their sign and clamp decisions want a spectrum that is accurate per bin) and share them as the sd_* templates of
+// stft_frames.h, so that
 // nothing here -- and no bit of the LSD -- changes.  A change to the statements below belongs there as well.
 #pragma once
 #include <limits.h>

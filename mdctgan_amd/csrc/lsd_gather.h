@@ -1,6 +1,6 @@
 // The adjoint of framing and reflection, shared by every backward pass that leaves one window-weighted float32 gradient frame per
-// STFT frame in a workspace [total_frames][N]: lsd_rows_grad.hip (the log-spectral distance) and stft_loss_rows.hip (the
-// multi-resolution STFT loss).  Stated once so that the two cannot drift apart.
+// STFT frame in a workspace [total_frames][N]: lsd_rows_grad.hip (the log-spectral distance), stft_loss_rows.hip (the
+// multi-resolution STFT loss) and mel_loss_rows.hip (the mel-spectrogram loss).  Stated once so that they cannot drift apart.
 //   lsd_rows_grad_gather_kernel   one thread per sample slot; row u owns the slots [S_u, S_u + frames_u hop + N), S_u =
 //       frame_start[u] hop + u N (its len never exceeds that), found by binary search.  Sample t sums the workspace taps that
 //       framing mapped to it -- the direct position t, on a centred transform the left reflection -t (1 <= t <= N/2) and the

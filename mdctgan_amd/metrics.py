@@ -617,6 +617,272 @@ def mrstft_loss_term(sr_audio, hr_audio, scale, resolutions=STFT_RESOLUTIONS):
     return _MrStftMeanLoss.apply(sr, hr, row_t, tabs, scale)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The multi-scale mel-spectrogram L1 loss: csrc/mel_loss_rows.hip
+# ---------------------------------------------------------------------------------------------------------------------
+MEL_RESOLUTIONS = ((512, 128, 40), (1024, 256, 80), (2048, 512, 160))       # (n_fft, hop, n_mels) of the default loss
+MEL_FLOOR = 1e-5                                                            # l = ln(max(E, MEL_FLOOR))
+MEL_MAX_FILTERS = 256                                                       # the kernels' limit on n_mels
+
+_mel_tables = {}            # mel_loss: the tables of a dense geometry (B, T, resolutions, center, device), uploaded once
+_mel_fbanks = {}            # (sample_rate, n_fft, n_mels, f_min, f_max, device) -> (W, band_k, band_j) on the device
+
+
+def mel_fbank(sample_rate, n_fft: int, n_mels: int, f_min: float = 0.0, f_max=None):
+    """The HTK triangular mel filterbank without area normalisation -> float32 host tensor [n_mels, n_fft / 2 + 1], evaluated in
+    float64 and rounded once: mel(f) = 2595 log10(1 + f / 700); n_mels + 2 equally spaced mel points from f_min to f_max (default
+    sample_rate / 2) mapped back to Hz, h_0 .. h_{n_mels + 1}; with f_k = k sample_rate / n_fft,
+        W[j][k] = max(0, min((f_k - h_j) / (h_{j+1} - h_j), (h_{j+2} - f_k) / (h_{j+2} - h_{j+1})))."""
+    n_fft, n_mels = int(n_fft), int(n_mels)
+    sample_rate, f_min = float(sample_rate), float(f_min)
+    f_max = sample_rate / 2.0 if f_max is None else float(f_max)
+    if n_fft < 2 or n_mels < 1 or not sample_rate > 0.0:
+        raise ValueError("mel_fbank: n_fft >= 2, n_mels >= 1 and a positive sample rate")
+    if not 0.0 <= f_min < f_max <= sample_rate / 2.0:
+        raise ValueError("mel_fbank: 0 <= f_min < f_max <= sample_rate / 2 (got %r, %r)" % (f_min, f_max))
+    mel_lo, mel_hi = (2595.0 * np.log10(1.0 + f / 700.0) for f in (f_min, f_max))
+    h = 700.0 * (10.0 ** (np.linspace(mel_lo, mel_hi, n_mels + 2, dtype=np.float64) / 2595.0) - 1.0)
+    f = np.arange(n_fft // 2 + 1, dtype=np.float64) * (sample_rate / n_fft)
+    up = (f[None, :] - h[:-2, None]) / (h[1:-1] - h[:-2])[:, None]
+    down = (h[2:, None] - f[None, :]) / (h[2:] - h[1:-1])[:, None]
+    return torch.from_numpy(np.maximum(0.0, np.minimum(up, down)).astype(np.float32))
+
+
+def mel_band_tables(fbank):
+    """The two tables the kernels walk a filterbank with, derived from W [J, K] (host) -> int32 numpy (band_k [J, 2], band_j [K, 2]):
+    filter j is non-zero exactly on the bins [band_k[j, 0], band_k[j, 1]), bin k lies exactly in the filters [band_j[k, 0],
+    band_j[k, 1]) (a bin in no filter: an empty range).  ValueError for a W that is not a finite float32 matrix of 1 .. 256 rows,
+    an empty filter (an all-zero row, named), a support or a bin's set of filters that is not one contiguous run, or tables that
+    are not monotone (the ends of the non-empty ranges must not decrease)."""
+    W = fbank.detach().cpu().numpy() if torch.is_tensor(fbank) else np.asarray(fbank)
+    if W.ndim != 2 or W.dtype != np.float32 or not 1 <= W.shape[0] <= MEL_MAX_FILTERS or not np.all(np.isfinite(W)):
+        raise ValueError("a filterbank is a finite float32 matrix [n_mels, bins] with 1 <= n_mels <= %d" % MEL_MAX_FILTERS)
+    nz = W != 0.0
+    tables = []
+    for what, mask in (("filter", nz), ("bin", nz.T)):
+        table = np.zeros((mask.shape[0], 2), dtype=np.int32)
+        last = (0, 0)
+        for i, row in enumerate(mask):
+            at = np.flatnonzero(row)
+            if at.size == 0:
+                if what == "filter":
+                    raise ValueError("filter %d is empty (an all-zero row of the filterbank)" % i)
+                continue
+            lo, hi = int(at[0]), int(at[-1]) + 1
+            if hi - lo != at.size:
+                raise ValueError("%s %d: its %s are not one contiguous run" % (what, i, "bins" if what == "filter" else "filters"))
+            if lo < last[0] or hi < last[1]:
+                raise ValueError("%s %d: the band tables are not monotone" % (what, i))
+            table[i] = last = (lo, hi)
+        tables.append(table)
+    return tables[0], tables[1]
+
+
+def _mel_resolutions(resolutions):
+    try:
+        res = tuple((int(n), int(h), int(j)) for n, h, j in resolutions)
+    except (TypeError, ValueError):
+        raise ValueError("resolutions: a sequence of (n_fft, hop, n_mels) triples") from None
+    if not res:
+        raise ValueError("resolutions: at least one (n_fft, hop, n_mels) triple")
+    for n, h, j in res:
+        if n not in LSD_ROWS_N_FFT:
+            raise NotImplementedError("the mel loss kernels serve n_fft in %s (got %d)" % (LSD_ROWS_N_FFT, n))
+        if h < 1:
+            raise ValueError("resolution (%d, %d, %d): the hop must be at least 1" % (n, h, j))
+        if not 1 <= j <= MEL_MAX_FILTERS:
+            raise ValueError("resolution (%d, %d, %d): the mel loss kernels serve 1 to %d filters" % (n, h, j, MEL_MAX_FILTERS))
+    return res
+
+
+def plan_mel(lengths, resolutions=MEL_RESOLUTIONS, center: bool = True):
+    """plan_metrics for every resolution (n_fft, hop, n_mels) (host only) -> [MetricsPlan]; ValueError naming the utterance AND the
+    resolution where an utterance has no frame or (centred) cannot be reflected: len <= n_fft / 2."""
+    plans = []
+    for n, h, j in _mel_resolutions(resolutions):
+        try:
+            plans.append(plan_metrics(lengths, n, h, center))
+        except ValueError as e:
+            raise ValueError("resolution (%d, %d, %d): %s" % (n, h, j, e)) from None
+    return plans
+
+
+def _mel_bank(sample_rate, n_fft, n_mels, f_min, f_max, device=None):
+    """mel_fbank and its band tables, checked; device None: the host check alone, else the three tensors on the device (built once
+    per (sample_rate, n_fft, n_mels, f_min, f_max, device) and kept).  ValueError naming the filter for an empty one."""
+    key = (float(sample_rate), n_fft, n_mels, float(f_min), None if f_max is None else float(f_max))
+    bank = _mel_fbanks.get(key + (str(device),))
+    if bank is None:
+        host = _mel_fbanks.get(key + ("None",))
+        if host is None:
+            W = mel_fbank(sample_rate, n_fft, n_mels, f_min, f_max)
+            host = _mel_fbanks[key + ("None",)] = (W,) + tuple(torch.from_numpy(t) for t in mel_band_tables(W))
+        bank = host if device is None else tuple(t.to(device).contiguous() for t in host)
+        _mel_fbanks[key + (str(device),)] = bank
+    return bank
+
+
+def _mel_banks(res, sample_rate, f_min, f_max, device=None):
+    banks = []
+    for n, h, j in res:
+        try:
+            banks.append(_mel_bank(sample_rate, n, j, f_min, f_max, device))
+        except ValueError as e:
+            raise ValueError("resolution (%d, %d, %d) at %g Hz: %s" % (n, h, j, float(sample_rate), e)) from None
+    return tuple(banks)
+
+
+def _mel_operands(hrs, srs, sample_rate, resolutions, center, f_min, f_max, table_key=None):
+    """What every mel-loss node is applied to -> (sr, hr, row_t, tabs); tabs = (frame_start tables, windows, filterbanks (W, band_k,
+    band_j), geometries (n_fft, hop, center, total_frames, n_mels)), one entry per resolution."""
+    res, center = _mel_resolutions(resolutions), bool(center)
+    ops_, lengths = _checked_operands(((hrs, "hrs"), (srs, "srs")))
+    if any(t.requires_grad for t in ([ops_[0][0]] if ops_[0][0] is not None else ops_[0][1])):
+        raise NotImplementedError("the mel loss has no gradient with respect to hr: detach the ground truth")
+    plans = plan_mel(lengths, res, center)
+    _mel_banks(res, sample_rate, f_min, f_max)          # (refusals before anything is packed or uploaded)
+    device, (hr, sr), starts = _pack_operands(ops_, True)
+    banks = _mel_banks(res, sample_rate, f_min, f_max, device)
+    U = len(lengths)
+    tables = _mel_tables.get(table_key) if table_key is not None else None
+    if tables is None:
+        rows = np.stack([np.asarray(t, dtype=np.int64) for t in (starts[0], [0] * U, starts[1], lengths)], axis=1)
+        tables = upload_tables([rows] + [p.frame_start for p in plans], device)
+        if table_key is not None:
+            if len(_mel_tables) >= 64:          # a training run has one geometry; a sweep over many must not pile tables up
+                _mel_tables.clear()
+            _mel_tables[table_key] = tables
+    geoms = tuple((p.n_fft, p.hop, center, p.total_frames, j) for p, (_, _, j) in zip(plans, res))
+    return sr, hr, tables[0], (tuple(tables[1:]), tuple(_hann(n, device) for n, _, _ in res), banks, geoms)
+
+
+def _mel_forward(sr, hr, row_t, tabs):
+    """mg_mel_loss_rows for every resolution -> row_out float64 [R, U, 4] = {sum, 0, 0, loss}."""
+    fs_ts, windows, banks, geoms = tabs
+    lib = _lib.load()
+    U = row_t.shape[0]
+    row_out = torch.empty(len(geoms), U, 4, dtype=torch.float64, device=sr.device)
+    for r, (fs_t, window, (W, bk, bj), (n_fft, hop, center, total_frames, n_mels)) in enumerate(zip(fs_ts, windows, banks, geoms)):
+        nbytes = lib.mg_mel_loss_rows_workspace(total_frames)
+        ws = _lib.workspace(nbytes, sr.device)
+        _lib.check(lib.mg_mel_loss_rows(_lib.ptr(hr), hr.numel(), _lib.ptr(sr), sr.numel(), _lib.ptr(row_t), U, _lib.ptr(fs_t),
+                                        total_frames, _lib.ptr(window), n_fft, hop, int(center), _lib.ptr(W), _lib.ptr(bk),
+                                        _lib.ptr(bj), n_mels, _lib.ptr(row_out[r]), _lib.ptr(ws), nbytes, _lib.stream()),
+                   "mg_mel_loss_rows")
+    return row_out
+
+
+def _mel_backward(sr, hr, row_t, tabs, grad_sr, grad_rows=None, go=None, scale=0.0):
+    """mg_mel_loss_rows_backward (grad_rows [U]) or its seeded form (go [1], scale) for every resolution, in resolution order: the
+    first writes every sample of the live rows of grad_sr, the later ones add to it."""
+    fs_ts, windows, banks, geoms = tabs
+    lib = _lib.load()
+    U, R = row_t.shape[0], len(geoms)
+    for r, (fs_t, window, (W, bk, bj), (n_fft, hop, center, total_frames, n_mels)) in enumerate(zip(fs_ts, windows, banks, geoms)):
+        nbytes = lib.mg_mel_loss_rows_backward_workspace(total_frames, n_fft)
+        ws = _lib.workspace(nbytes, sr.device)
+        head = (_lib.ptr(hr), hr.numel(), _lib.ptr(sr), sr.numel(), _lib.ptr(row_t), U, _lib.ptr(fs_t), total_frames, _lib.ptr(window),
+                n_fft, hop, int(center), _lib.ptr(W), _lib.ptr(bk), _lib.ptr(bj), n_mels)
+        tail = (int(r > 0), _lib.ptr(grad_sr), _lib.ptr(ws), nbytes, _lib.stream())
+        if go is None:
+            _lib.check(lib.mg_mel_loss_rows_backward(*head, _lib.ptr(grad_rows), *tail), "mg_mel_loss_rows_backward")
+        else:
+            _lib.check(lib.mg_mel_loss_rows_backward_seeded(*head, _lib.ptr(go), scale, R, *tail), "mg_mel_loss_rows_backward_seeded")
+    return grad_sr
+
+
+class _MelRows(torch.autograd.Function):
+    """Per-utterance mel loss [U] (float64) of a packed sr buffer against a packed, constant hr buffer: the losses of the
+    resolutions added in resolution order and divided by their number.  Backward: into a zero-filled buffer of sr's size."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, row_t, tabs):
+        row_out = _mel_forward(sr, hr, row_t, tabs)
+        ctx.save_for_backward(sr, hr, row_t)
+        ctx.tabs = tabs
+        total = row_out[0, :, 3].clone()
+        for r in range(1, row_out.shape[0]):
+            total = total + row_out[r, :, 3]
+        return total / row_out.shape[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        sr, hr, row_t = ctx.saved_tensors
+        grad_rows = (grad.double() / len(ctx.tabs[3])).float().contiguous()
+        return _mel_backward(sr, hr, row_t, ctx.tabs, torch.zeros_like(sr), grad_rows=grad_rows), None, None, None
+
+
+def mel_many(hrs, srs, sample_rate, resolutions=MEL_RESOLUTIONS, center=True, f_min=0.0, f_max=None):
+    """The multi-scale mel-spectrogram L1 loss of every utterance on its own, differentiable in sr -> float64 device tensor [U].
+    For one resolution (n_fft, hop, n_mels) -- periodic Hann window of n_fft samples, centred frames reflected at the utterance's
+    own ends, K = n_fft / 2 + 1 bins, F_u frames, m = sqrt(max(re^2 + im^2, 1e-7)) as for ``mrstft_many``, W = mel_fbank(sample_rate,
+    n_fft, n_mels, f_min, f_max) --
+        E_j = sum_k W[j][k] m_k,   loss_u = sum_{f,j} |ln max(E_hr, 1e-5) - ln max(E_sr, 1e-5)| / (F_u n_mels)
+    and the result is the mean over the resolutions.  Operand forms as for ``lsd_many``: lists of waveforms, or packed ``(buffer,
+    starts, lengths)`` / ``(buffer, starts[, lengths])`` read where they lie.  Two library launches per resolution forward and two
+    backward, whatever U is (csrc/mel_loss_rows.hip), plus the element-wise launches on [U] that join the resolutions;
+    deterministic; nothing is read back.  The filterbanks and their band tables are built once per (sample_rate, n_fft, n_mels,
+    f_min, f_max, device) and kept on the device.  The gradient is exactly 0 where autograd through torch.stft has NaN or Inf: sr ==
+    hr, silence, clamped bins, filters under the floor.  hr is a constant: a ground truth that requires grad raises
+    NotImplementedError.  ValueError (naming utterance and resolution) for an utterance that cannot be reflected at a resolution,
+    len <= n_fft / 2, and (naming resolution and filter) for a filterbank with an empty filter."""
+    return _MelRows.apply(*_mel_operands(hrs, srs, sample_rate, resolutions, center, f_min, f_max))
+
+
+def _mel_dense(sr_audio, hr_audio, sample_rate, resolutions):
+    hrs, srs, B, T = _dense_pack(sr_audio, hr_audio)
+    res = _mel_resolutions(resolutions)
+    return _mel_operands(hrs, srs, sample_rate, res, True, 0.0, None, (B, T, res, float(sample_rate), str(sr_audio.device)))
+
+
+def mel_loss(sr_audio, hr_audio, sample_rate, resolutions=MEL_RESOLUTIONS):
+    """``mel_many`` of a dense batch as a training loss -> 0-dim float64 tensor, the mean over the clips, differentiable in
+    sr_audio.  sr_audio / hr_audio: float32 device tensors [B, T], [B, 1, T] or [B, 1, 1, T], read in place (no packing copy).
+    The tables of a geometry are uploaded once and kept, so forward + backward capture into a graph on one stream after one
+    eager call (lsd_loss's note on live graphs from other streams applies)."""
+    return _MelRows.apply(*_mel_dense(sr_audio, hr_audio, sample_rate, resolutions)).mean()
+
+
+class _MelMeanLoss(torch.autograd.Function):
+    """scale * the mean over the clips of the mel loss as a node of the training step's loss family: a float32 [1] loss, the
+    constant factor inside, the upstream gradient read on the device.  Forward: mg_mel_loss_rows per resolution and
+    mg_stft_loss_mean (row_out has its layout).  Backward: mg_mel_loss_rows_backward_seeded per resolution into an uninitialised
+    buffer of sr's size -- the pack is dense and every row is live at every resolution, so the first resolution writes every sample."""
+
+    @staticmethod
+    def forward(ctx, sr, hr, row_t, tabs, scale):
+        row_out = _mel_forward(sr, hr, row_t, tabs)
+        loss = torch.empty(1, dtype=torch.float32, device=sr.device)
+        _lib.check(_lib.load().mg_stft_loss_mean(_lib.ptr(row_out), row_out.shape[1], row_out.shape[0], scale, _lib.ptr(loss),
+                                                 _lib.stream()), "mg_stft_loss_mean")
+        ctx.save_for_backward(sr, hr, row_t)
+        ctx.tabs, ctx.scale = tabs, scale
+        return loss.reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        sr, hr, row_t = ctx.saved_tensors
+        go = go.reshape(1).float().contiguous()
+        return _mel_backward(sr, hr, row_t, ctx.tabs, torch.empty_like(sr), go=go, scale=ctx.scale), None, None, None, None
+
+
+def mel_loss_term(sr_audio, hr_audio, sample_rate, scale, resolutions=MEL_RESOLUTIONS):
+    """``scale * mel_loss(sr_audio, hr_audio, sample_rate, resolutions)`` as a term of the training step -> 0-dim float32 tensor,
+    differentiable in sr_audio: mel_loss's operand forms, checks and cached tables, but one autograd node in the step's loss
+    convention (functional._LossFn).  Forward is mg_mel_loss_rows per resolution plus one reduction launch; backward is
+    mg_mel_loss_rows_backward_seeded per resolution, which forms every clip's upstream gradient in the kernel from the upstream
+    scalar -- in the arithmetic autograd performs for ``scale * mel_loss``, so a power-of-two scale gives that gradient bit for bit;
+    the GradScaler's loss scale in a --fp16 step stays on the device and is read when the kernel runs, so a captured step follows
+    it -- and writes every sample, so no buffer is zero-filled.  Capturable after one eager call."""
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError("scale must be finite")
+    sr, hr, row_t, tabs = _mel_dense(sr_audio, hr_audio, sample_rate, resolutions)
+    return _MelMeanLoss.apply(sr, hr, row_t, tabs, scale)
+
+
 def eval_model(model, eval_batches, opt, eval_path=None):
     """train.py:104-134: run ``model.inference`` over the evaluation batches (dicts with ``LR_audio`` / ``HR_audio`` like the
     reference's dataloader items, or ``(lr, hr)`` pairs), score every batch with ``compute_matrics`` and average -- the

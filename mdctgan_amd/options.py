@@ -77,6 +77,8 @@ _FLAGS = [
     ("lambda_lsd", dict(type=float, default=0.0)),
     # the multi-resolution STFT loss of to_audio(sr) as a generator loss (not in the reference: metrics.mrstft_loss_term); 0: off
     ("lambda_mrstft", dict(type=float, default=0.0)),
+    # the multi-scale mel-spectrogram L1 of to_audio(sr) as a generator loss (not in the reference: metrics.mel_loss_term); 0: off
+    ("lambda_mel", dict(type=float, default=0.0)),
     # transform
     ("lr_sampling_rate", dict(type=int, default=LR_SAMPLE_RATE)),
     ("hr_sampling_rate", dict(type=int, default=HR_SAMPLE_RATE)),

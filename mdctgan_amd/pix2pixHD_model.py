@@ -305,6 +305,7 @@ class Pix2PixHDModel(BaseModel):
         self.preprocess.return_stats = False
         self.lambda_lsd = self._check_lambda_lsd(opt) if self.isTrain else 0.0
         self.lambda_mrstft = self._check_lambda_mrstft(opt) if self.isTrain else 0.0
+        self.lambda_mel = self._check_lambda_mel(opt) if self.isTrain else 0.0
         self.freeze = opt.freeze_g_d or opt.freeze_g_u or opt.freeze_l_d or opt.freeze_l_u
         self.netG = networks.define_G(
             input_nc, opt.output_nc, opt.ngf, opt.netG, opt.n_downsample_global, opt.n_blocks_global,
@@ -332,7 +333,8 @@ class Pix2PixHDModel(BaseModel):
             self.limit_aux_loss = False
             self.criterionGAN = networks.GANLoss(use_lsgan=not opt.no_lsgan, device=self.device)
             self.loss_names = (["G_GAN"] + ([] if opt.no_ganFeat_loss else ["G_GAN_Feat"]) + (["G_lsd"] if self.lambda_lsd > 0 else [])
-                               + (["G_mrstft"] if self.lambda_mrstft > 0 else []) + ["D_real", "D_fake"])
+                               + (["G_mrstft"] if self.lambda_mrstft > 0 else []) + (["G_mel"] if self.lambda_mel > 0 else [])
+                               + ["D_real", "D_fake"])
             if opt.niter_fix_global > 0:
                 params = [v for k, v in self.netG.named_parameters()
                           if k.startswith("model" + str(opt.n_local_enhancers))]
@@ -392,7 +394,32 @@ class Pix2PixHDModel(BaseModel):
                              % (opt.segment_length, n, max(r[0] for r in STFT_RESOLUTIONS) // 2, e)) from None
         return lam
 
-    def loss_filter(self, g_gan, g_gan_feat, d_real, d_fake, g_lsd=None, g_mrstft=None):
+    def _check_lambda_mel(self, opt) -> float:
+        """--lambda_mel: what the term cannot serve is refused here, not at the first backward pass.  Like --lambda_mrstft the term has
+        its own transforms (metrics.MEL_RESOLUTIONS); its filterbanks are those of opt.hr_sampling_rate, the rate of the decoded clip."""
+        from .metrics import MEL_RESOLUTIONS, _mel_banks, plan_mel
+        lam = float(getattr(opt, "lambda_mel", 0.0))
+        if not lam >= 0.0:
+            raise ValueError("--lambda_mel must not be negative (got %r)" % lam)
+        if lam == 0.0:
+            return 0.0
+        if not self.preprocess._in_kernel:
+            raise NotImplementedError("--lambda_mel: to_audio has no backward for the dB and explicit-encoding codecs "
+                                      "(train with --arcsinh_transform or --raw_mdct)")
+        n = self.preprocess.audio_length(int(opt.segment_length))
+        try:
+            plan_mel([n], MEL_RESOLUTIONS, True)
+        except ValueError as e:
+            raise ValueError("--lambda_mel: a --segment_length of %d decodes to clips of %d samples, which the largest resolution "
+                             "cannot reflect-pad (more than %d are needed): %s"
+                             % (opt.segment_length, n, max(r[0] for r in MEL_RESOLUTIONS) // 2, e)) from None
+        try:
+            _mel_banks(MEL_RESOLUTIONS, opt.hr_sampling_rate, 0.0, None)
+        except ValueError as e:
+            raise ValueError("--lambda_mel: no mel filterbank at --hr_sampling_rate %s: %s" % (opt.hr_sampling_rate, e)) from None
+        return lam
+
+    def loss_filter(self, g_gan, g_gan_feat, d_real, d_fake, g_lsd=None, g_mrstft=None, g_mel=None):
         out = [g_gan]
         if not self.no_ganFeat_loss:
             out.append(g_gan_feat)
@@ -400,6 +427,8 @@ class Pix2PixHDModel(BaseModel):
             out.append(g_lsd)
         if g_mrstft is not None:
             out.append(g_mrstft)
+        if g_mel is not None:
+            out.append(g_mel)
         return out + [d_real, d_fake]
 
     # -- forward --------------------------------------------------------------------------------
@@ -426,17 +455,20 @@ class Pix2PixHDModel(BaseModel):
         return Fh.cat_channels(lr_spectro, x_spectro)        # pix2pixHD_model.py:425-427, 440: sr_input = sr_spectro
 
     def _forward(self, lr_audio, hr_audio, infer=False, share_d_pass=False):
-        """pix2pixHD_model.py:416-616: the live losses [G_GAN, G_GAN_Feat, (G_lsd,) (G_mrstft,) D_real, D_fake].  share_d_pass: the
+        """pix2pixHD_model.py:416-616: the live losses [G_GAN, G_GAN_Feat, (G_lsd,) (G_mrstft,) (G_mel,) D_real, D_fake].  share_d_pass: the
         caller backpropagates the two losses under Fh.backward_pass (optimize_parameters does); otherwise every loss
         keeps its own discriminator pass and plain loss.backward() calls work as in train.py.  --lambda_lsd > 0 adds G_lsd, the
         log-spectral distance of to_audio(sr_spectro, lr_norm_param) to hr_audio times lambda_lsd (metrics.lsd_loss_term): the
         place of the reference's commented-out audio-domain terms (pix2pixHD_model.py:453-498).  --lambda_mrstft > 0 adds G_mrstft
-        after it, the multi-resolution STFT loss of the same decoded waveform times lambda_mrstft (metrics.mrstft_loss_term)."""
+        after it, the multi-resolution STFT loss of the same decoded waveform times lambda_mrstft (metrics.mrstft_loss_term), and
+        --lambda_mel > 0 G_mel after that, its multi-scale mel-spectrogram L1 to hr_audio at opt.hr_sampling_rate times lambda_mel
+        (metrics.mel_loss_term).  Whatever combination of the three is on, to_audio runs once."""
         lsd = self.isTrain and self.lambda_lsd > 0
         mrstft = self.isTrain and self.lambda_mrstft > 0
-        if (lsd or mrstft) and int(hr_audio.shape[-1]) != self.preprocess.audio_length(lr_audio.shape[-1]):
+        mel = self.isTrain and self.lambda_mel > 0
+        if (lsd or mrstft or mel) and int(hr_audio.shape[-1]) != self.preprocess.audio_length(lr_audio.shape[-1]):
             raise ValueError("%s: hr_audio has %d samples per clip, to_audio returns %d for this lr_audio"
-                             % ("--lambda_lsd" if lsd else "--lambda_mrstft", hr_audio.shape[-1],
+                             % ("--lambda_lsd" if lsd else "--lambda_mrstft" if mrstft else "--lambda_mel", hr_audio.shape[-1],
                                 self.preprocess.audio_length(lr_audio.shape[-1])))
         sr_spectro, _, hr_spectro, _, hr_norm_param, lr_spectro, _, lr_norm_param = self.forward(lr_audio, hr_audio)
         pooled = self.isTrain and getattr(self.opt, "pool_size", 0) > 0     # the fake pass of the D loss sees the history
@@ -487,19 +519,21 @@ class Pix2PixHDModel(BaseModel):
                     for j in range(len(pred_fake[i]) - 1):
                         loss_G_GAN_Feat = loss_G_GAN_Feat + Fh.l1_loss(
                             pred_fake[i][j], pred_real[i][j].detach(), D_weights * feat_weights * self.lambda_feat)
-        loss_G_lsd = loss_G_mrstft = None
-        if lsd or mrstft:
-            from .metrics import lsd_loss_term, mrstft_loss_term
+        loss_G_lsd = loss_G_mrstft = loss_G_mel = None
+        if lsd or mrstft or mel:
+            from .metrics import lsd_loss_term, mel_loss_term, mrstft_loss_term
             # (the generator's output is float32 under --fp16 as well: autocast changes the convolutions' arithmetic, not the tensors)
             spec = sr_spectro if sr_spectro.dtype == torch.float32 and sr_spectro.is_contiguous() else sr_spectro.float().contiguous()
-            sr_audio = self.preprocess.to_audio(spec, lr_norm_param)       # once: both terms read the one decoded waveform
+            sr_audio = self.preprocess.to_audio(spec, lr_norm_param)       # once: every term reads the one decoded waveform
             if lsd:
                 loss_G_lsd = lsd_loss_term(sr_audio, hr_audio.detach(), self.opt, self.lambda_lsd)
             if mrstft:
                 loss_G_mrstft = mrstft_loss_term(sr_audio, hr_audio.detach(), self.lambda_mrstft)
+            if mel:
+                loss_G_mel = mel_loss_term(sr_audio, hr_audio.detach(), self.opt.hr_sampling_rate, self.lambda_mel)
         # visuals are materialised lazily (the reference copies three tensors to the host every step)
         self._visual_src = (lr_spectro, sr_spectro.detach(), hr_spectro, lr_norm_param, hr_norm_param)
-        return [self.loss_filter(loss_G_GAN, loss_G_GAN_Feat, loss_D_real, loss_D_fake, loss_G_lsd, loss_G_mrstft),
+        return [self.loss_filter(loss_G_GAN, loss_G_GAN_Feat, loss_D_real, loss_D_fake, loss_G_lsd, loss_G_mrstft, loss_G_mel),
                 torch.empty if not infer else sr_spectro]
 
     def optimize_parameters(self, lr_audio, hr_audio):
@@ -519,6 +553,8 @@ class Pix2PixHDModel(BaseModel):
             loss_G = loss_G + loss_dict["G_lsd"]
         if "G_mrstft" in loss_dict:   # (likewise; with both terms their gradients join at the decoded waveform first)
             loss_G = loss_G + loss_dict["G_mrstft"]
+        if "G_mel" in loss_dict:
+            loss_G = loss_G + loss_dict["G_mel"]
         red = getattr(self, "reducers", None)      # data-parallel gradient reducers (mdctgan_amd.ddp.attach)
         sc = self.scaler                           # train.py:183-199: one GradScaler, updated once per iteration
         seed_G, seed_D = self._backward_seeds(sc, loss_D.device)
