@@ -6,6 +6,12 @@
 // smaller tile (their sign and clamp decisions want a spectrum that is accurate per bin) and share them as the sd_* templates of
 // stft_frames.h, so that
 // nothing here -- and no bit of the LSD -- changes.  A change to the statements below belongs there as well.
+// What the LSD backward shares with those two losses all the same stands in frames_common.h: the conj Zt of the inverse tail (the
+// root value is the caller's) and the host side -- operand checks, grid, n_fft dispatch, the backward's epilogue.  Deliberately NOT
+// shared: this transform (float2, LSD_TILE, the N-entry root table) and with it the rest of lsd_rows_grad_frames_kernel's tail,
+// its windowed store included -- stated through a shared function the store compiles to other instructions at N = 512 and 2048
+// (same arithmetic, other registers and order), and the LSD metric's kernels are not to change at all; the LSD kernel's reduction,
+// in which every lane ends with the sum; and every loss's own expression for the seeded upstream gradient.
 #pragma once
 #include <limits.h>
 

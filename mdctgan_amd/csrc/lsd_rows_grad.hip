@@ -24,9 +24,13 @@
 // Neither kernel's arithmetic for a row depends on where the row sits: a row has the same gradient bits alone and in any pack.
 // mg_lsd_rows_backward_seeded is the same two launches for the loss node of a training step (metrics.lsd_loss_term): phase one
 // forms every row's upstream gradient itself from the node's upstream scalar on the device (SEEDED below).
+// Shared with stft_loss_rows.hip and mel_loss_rows.hip through frames_common.h: the conj Zt of the tail and the host side (operand
+// checks, grid, n_fft and flag dispatch, the backward's epilogue with the gather).  Deliberately this file's own (lsd_fft.h's head
+// says why): the float2 transform on LSD_TILE points with its N-entry root table, the rest of the tail around it, the reduction in
+// which every lane ends with the sum, and the seeded gradient divided by the row's frame count and rounded.
 #include <math.h>
 
-#include "lsd_gather.h"
+#include "frames_common.h"
 
 namespace {
 
@@ -119,10 +123,7 @@ __global__ __launch_bounds__(LSD_NT) void lsd_rows_grad_frames_kernel(const floa
 #pragma unroll
         for (int it = 0; it < HALF / LSD_NT; ++it) {
             const int idx = tid + it * LSD_NT, f2 = idx / M, k = idx % M;
-            const float2 h1 = buf[f2 * N + k], h2 = buf[f2 * N + M - k], w = root[k];
-            const float2 a = make_float2(h1.x + h2.x, h1.y - h2.y);                         // H_k + conj H_{M-k}
-            const float2 b = lsd_cmul(make_float2(h1.x - h2.x, h1.y + h2.y), make_float2(w.x, -w.y));
-            zt[it] = make_float2(a.x - b.y, -(a.y + b.x));                                  // conj (a + i b)
+            zt[it] = frames_conj_zt(buf[f2 * N + k], buf[f2 * N + M - k], root[k]);
         }
         __syncthreads();
 #pragma unroll
@@ -163,28 +164,19 @@ int lsd_rows_backward(const float* hr, long long hr_total, const float* sr, long
                       int n_rows, const long long* frame_start, long long total_frames, const float* hr_shift,
                       const float* window, int n_fft, int hop, int center, const float* up, double up_scale, bool seeded,
                       float* grad_sr, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!hr || !sr || !rows || !frame_start || !window || !up || !grad_sr || !workspace) return MG_ERR_ARG;
-    if (n_rows <= 0 || total_frames <= 0 || hr_total <= 0 || sr_total <= 0 || hop <= 0 || !lsd_size_ok(n_fft)) return MG_ERR_ARG;
-    const size_t need = mg_lsd_rows_backward_workspace(total_frames, n_fft);
-    if (need == 0 || workspace_bytes < need || !al16(workspace)) return MG_ERR_ARG;
-    if (total_frames > (kFar - (long long)n_rows * n_fft) / hop) return MG_ERR_ARG;          // the gather's slot count
-    float* frames = static_cast<float*>(workspace);
-    const long long ft = LSD_TILE / n_fft, n_tiles = (total_frames + ft - 1) / ft;
-    const unsigned blocks = (unsigned)(n_tiles < 2 * 256 * 4 ? n_tiles : 2 * 256 * 4);    // a few waves of two workgroups per CU (VGPR-bound)
+    if (!frames_args_ok(hr, hr_total, sr, sr_total, rows, n_rows, frame_start, total_frames, window, n_fft, hop) || !up || !grad_sr)
+        return MG_ERR_ARG;
+    const FramesGrid grid = frames_grid(total_frames, n_fft, LSD_TILE, 2);     // two workgroups per CU (VGPR-bound)
     hipStream_t st = (hipStream_t)stream;
-#define MG_LSDG_LAUNCH(NN, S, G)                                                                                                    \
-    hipLaunchKernelGGL((lsd_rows_grad_frames_kernel<NN, S, G>), dim3(blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rows, \
-                       n_rows, frame_start, total_frames, hr_shift, window, up, up_scale, hop, center != 0, n_tiles, frames)
-#define MG_LSDG_SHIFT(NN, G) do { if (hr_shift) MG_LSDG_LAUNCH(NN, true, G); else MG_LSDG_LAUNCH(NN, false, G); } while (0)
-#define MG_LSDG_SIZE(NN) do { if (seeded) MG_LSDG_SHIFT(NN, true); else MG_LSDG_SHIFT(NN, false); } while (0)
-    if (n_fft == 512) MG_LSDG_SIZE(512);
-    else if (n_fft == 1024) MG_LSDG_SIZE(1024);
-    else MG_LSDG_SIZE(2048);
-#undef MG_LSDG_SIZE
-#undef MG_LSDG_SHIFT
-#undef MG_LSDG_LAUNCH
-    MG_CHECK_LAUNCH();
-    return lsd_launch_gather(frames, rows, n_rows, frame_start, total_frames, n_fft, hop, center, sr_total, false, grad_sr, st);
+    return frames_backward(rows, n_rows, frame_start, total_frames, n_fft, hop, center, sr_total,
+                           mg_lsd_rows_backward_workspace(total_frames, n_fft), workspace, workspace_bytes, false, grad_sr, st,
+                           [&](float* frames) {
+        frames_with_n_fft(n_fft, [&](auto nn) { frames_with_flag(hr_shift != nullptr, [&](auto s) { frames_with_flag(seeded, [&](auto g) {
+            hipLaunchKernelGGL((lsd_rows_grad_frames_kernel<decltype(nn)::value, decltype(s)::value, decltype(g)::value>),
+                               dim3(grid.blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rows, n_rows, frame_start,
+                               total_frames, hr_shift, window, up, up_scale, hop, center != 0, grid.n_tiles, frames);
+        }); }); });
+    });
 }
 
 }  // namespace

@@ -38,6 +38,10 @@
 //   lsd_rows_grad_gather_kernel   phase two, lsd_gather.h.
 // Static LDS only, no atomics, no host read-back, launch counts independent of the number of rows; no arithmetic for a row depends
 // on where the row sits, so a row has the same value and gradient bits alone and in any pack.
+// Shared with stft_loss_rows.hip through stft_frames.h: everything up to the float32 spectrum, the sum of a frame's lanes
+// (sd_frame_sum) and the backward's tail from H_k on (sd_inverse_tail); the host side (operand checks, grid, n_fft dispatch, the
+// backward's epilogue with the gather) is frames_common.h's, shared with lsd_rows_grad.hip too.  Deliberately this file's own:
+// the seeded gradient ROUNDED to float32 (the STFT loss keeps the double; each is asserted bit for bit) and mel_loss_finish_kernel.
 #include "stft_frames.h"
 
 namespace {
@@ -82,7 +86,7 @@ __global__ __launch_bounds__(LSD_NT) void mel_loss_frames_kernel(const float* __
     static_assert(2 * NBINS <= 2 * N, "a frame's two m arrays fit its dead frame data");
     __shared__ __attribute__((aligned(16))) double2 buf[SD_TILE];          // [FT][hr, sr][M]; then, as double: [FT][2 N] holding m_hr, m_sr
     __shared__ __attribute__((aligned(16))) double2 root[N / 2];
-    __shared__ double red[LSD_NT / 64];
+    __shared__ double red[LSD_NT / 64][1];
     __shared__ LsdFrame info[FT];
     double* mbuf = reinterpret_cast<double*>(buf);
     const int tid = threadIdx.x;
@@ -123,24 +127,16 @@ __global__ __launch_bounds__(LSD_NT) void mel_loss_frames_kernel(const float* __
             }
         }
         __syncthreads();
-        double acc = 0.0;
+        double acc[1] = {0.0};
         for (int f = j; f < n_mels; f += TPF) {
             double eh, es;
             mel_energies<NBINS>(fbank, band_k, f, Mh, Ms, eh, es);
-            acc += fabs(log(fmax(eh, kMelFloor)) - log(fmax(es, kMelFloor)));
+            acc[0] += fabs(log(fmax(eh, kMelFloor)) - log(fmax(es, kMelFloor)));
         }
-        acc = wave_sum_d(acc);
-        if (TPF > 64) {
-            if ((tid & 63) == 0) red[tid >> 6] = acc;
-            __syncthreads();
-            if (j == 0) {
-                acc = red[fr * (TPF / 64)];
-                for (int w = 1; w < TPF / 64; ++w) acc += red[fr * (TPF / 64) + w];
-            }
-        }
+        sd_frame_sum<1, TPF>(acc, red, tid, fr, j);
         if (j == 0) {
             const long long g = tile * FT + fr;
-            if (g < total_frames) partial[g] = info[fr].live != 0 ? acc : 0.0;
+            if (g < total_frames) partial[g] = info[fr].live != 0 ? acc[0] : 0.0;
         }
         __syncthreads();                                    // buf, info and red are free for the next tile
     }
@@ -175,9 +171,7 @@ __global__ __launch_bounds__(LSD_NT) void mel_loss_grad_frames_kernel(const floa
                                                                       int hop, int center, long long n_tiles,
                                                                       float* __restrict__ frames_out) {
     constexpr int M = N / 2, FT = SD_TILE / N, TPF = LSD_NT / FT, NBINS = N / 2 + 1, BPL = (NBINS + TPF - 1) / TPF;
-    constexpr int HALF = SD_TILE / 2;                                       // the Zt of the tile's frames, densely: [FT][M]
     static_assert(TPF >= 64 && M % LSD_NT == 0, "a frame's lanes fill whole waves, a load pass stays inside one signal of a frame");
-    static_assert(HALF % LSD_NT == 0 && (HALF / 2) % LSD_NT == 0 && M % 2 == 0, "whole points and whole point pairs per thread");
     static_assert(2 * NBINS + MEL_MAX_FILTERS <= 2 * N, "a frame's m arrays and dE fit its dead frame data");
     __shared__ __attribute__((aligned(16))) double2 buf[SD_TILE];          // [FT][hr, sr][M] double; then, as double: [FT][2 N] holding
     __shared__ __attribute__((aligned(16))) double2 root[N / 2];           //   m_hr, m_sr, dE; then, as float2: [FT][N] holding H_k; then [FT][M]
@@ -265,39 +259,7 @@ __global__ __launch_bounds__(LSD_NT) void mel_loss_grad_frames_kernel(const floa
             }
         }
         __syncthreads();                                    // every lane has read its dE: the doubles are dead
-        // from here on: stft_loss_grad_frames_kernel.  H_k, k = 0 .. M, of frame fr at fbuf[fr N + k]
-#pragma unroll
-        for (int i = 0; i < BPL; ++i) {
-            const int k = j + i * TPF;
-            if (k < NBINS) fbuf[fr * N + k] = h[i];
-        }
-        __syncthreads();
-        // conj Zt of every frame, held in registers until all H are read, then packed densely
-        float2 zt[HALF / LSD_NT];
-#pragma unroll
-        for (int it = 0; it < HALF / LSD_NT; ++it) {
-            const int idx = tid + it * LSD_NT, f2 = idx / M, k = idx % M;
-            const float2 h1 = fbuf[f2 * N + k], h2 = fbuf[f2 * N + M - k], w = sd_root<N, float2>(root, k);
-            const float2 a = make_float2(h1.x + h2.x, h1.y - h2.y);                         // H_k + conj H_{M-k}
-            const float2 b = lsd_cmul(make_float2(h1.x - h2.x, h1.y + h2.y), make_float2(w.x, -w.y));
-            zt[it] = make_float2(a.x - b.y, -(a.y + b.x));                                  // conj (a + i b)
-        }
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < HALF / LSD_NT; ++it) fbuf[tid + it * LSD_NT] = zt[it];
-        __syncthreads();
-        sd_fft<M, HALF>(fbuf, root, tid);
-        // y[2m] = Re, y[2m+1] = -Im of the transform; two points = four samples per store
-#pragma unroll
-        for (int it = 0; it < HALF / 2 / LSD_NT; ++it) {
-            const int idx = tid + it * LSD_NT, f2 = idx / (M / 2), n = 4 * (idx % (M / 2));
-            const long long g = tile * FT + f2;
-            if (g < total_frames) {
-                const float4 v = *reinterpret_cast<const float4*>(fbuf + f2 * M + n / 2);
-                *reinterpret_cast<float4*>(frames_out + g * N + n) =
-                    make_float4(v.x * window[n], -v.y * window[n + 1], v.z * window[n + 2], -v.w * window[n + 3]);
-            }
-        }
+        sd_inverse_tail<N>(h, fbuf, root, window, frames_out, tile, total_frames, tid);
         __syncthreads();                                    // buf, info and coef are free for the next tile
     }
 }
@@ -305,9 +267,8 @@ __global__ __launch_bounds__(LSD_NT) void mel_loss_grad_frames_kernel(const floa
 bool mel_args_ok(const void* hr, long long hr_total, const void* sr, long long sr_total, const void* rows, int n_rows,
                  const void* frame_start, long long total_frames, const void* window, const void* fbank, const void* band_k,
                  const void* band_j, int n_mels, int n_fft, int hop) {
-    if (!hr || !sr || !rows || !frame_start || !window || !fbank || !band_k || !band_j) return false;
-    if (n_rows <= 0 || total_frames <= 0 || hr_total <= 0 || sr_total <= 0 || hop <= 0 || !lsd_size_ok(n_fft)) return false;
-    if (n_mels < 1 || n_mels > MEL_MAX_FILTERS) return false;
+    if (!frames_args_ok(hr, hr_total, sr, sr_total, rows, n_rows, frame_start, total_frames, window, n_fft, hop)) return false;
+    if (!fbank || !band_k || !band_j || n_mels < 1 || n_mels > MEL_MAX_FILTERS) return false;
     return ((uintptr_t)fbank & 3) == 0 && ((uintptr_t)band_k & 3) == 0 && ((uintptr_t)band_j & 3) == 0;
 }
 
@@ -330,21 +291,16 @@ int mg_mel_loss_rows(const float* hr, long long hr_total, const float* sr, long 
                      const float* fbank, const int* band_k, const int* band_j, int n_mels, double* row_out, void* workspace,
                      size_t workspace_bytes, void* stream) {
     if (!mel_args_ok(hr, hr_total, sr, sr_total, rows, n_rows, frame_start, total_frames, window, fbank, band_k, band_j, n_mels, n_fft,
-                     hop) || !row_out || !workspace)
+                     hop) || !row_out || !frames_workspace_ok(mg_mel_loss_rows_workspace(total_frames), workspace, workspace_bytes))
         return MG_ERR_ARG;
-    const size_t need = mg_mel_loss_rows_workspace(total_frames);
-    if (need == 0 || workspace_bytes < need || !al16(workspace)) return MG_ERR_ARG;
     double* partial = static_cast<double*>(workspace);
-    const long long ft = SD_TILE / n_fft, n_tiles = (total_frames + ft - 1) / ft;
-    const unsigned blocks = (unsigned)(n_tiles < 3 * 256 * 4 ? n_tiles : 3 * 256 * 4);    // as mg_stft_loss_rows
+    const FramesGrid grid = frames_grid(total_frames, n_fft, SD_TILE, 3);                 // as mg_stft_loss_rows
     hipStream_t st = (hipStream_t)stream;
-#define MG_MEL_LAUNCH(NN)                                                                                                          \
-    hipLaunchKernelGGL((mel_loss_frames_kernel<NN>), dim3(blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rows, n_rows, \
-                       frame_start, total_frames, window, fbank, band_k, n_mels, hop, center != 0, n_tiles, partial)
-    if (n_fft == 512) MG_MEL_LAUNCH(512);
-    else if (n_fft == 1024) MG_MEL_LAUNCH(1024);
-    else MG_MEL_LAUNCH(2048);
-#undef MG_MEL_LAUNCH
+    frames_with_n_fft(n_fft, [&](auto nn) {
+        hipLaunchKernelGGL((mel_loss_frames_kernel<decltype(nn)::value>), dim3(grid.blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr,
+                           sr_total, rows, n_rows, frame_start, total_frames, window, fbank, band_k, n_mels, hop, center != 0,
+                           grid.n_tiles, partial);
+    });
     MG_CHECK_LAUNCH();
     const unsigned fblocks = (unsigned)((n_rows + 255) / 256 < 1024 ? (n_rows + 255) / 256 : 1024);
     hipLaunchKernelGGL(mel_loss_finish_kernel, dim3(fblocks), dim3(256), 0, st, partial, rows, n_rows, frame_start, total_frames,
@@ -364,27 +320,19 @@ int mel_loss_rows_backward(const float* hr, long long hr_total, const float* sr,
                            double up_scale, int n_res, bool seeded, int accumulate, float* grad_sr, void* workspace,
                            size_t workspace_bytes, void* stream) {
     if (!mel_args_ok(hr, hr_total, sr, sr_total, rows, n_rows, frame_start, total_frames, window, fbank, band_k, band_j, n_mels, n_fft,
-                     hop) || !up || !grad_sr || !workspace || n_res <= 0)
+                     hop) || !up || !grad_sr || n_res <= 0)
         return MG_ERR_ARG;
-    const size_t need = mg_mel_loss_rows_backward_workspace(total_frames, n_fft);
-    if (need == 0 || workspace_bytes < need || !al16(workspace)) return MG_ERR_ARG;
-    if (total_frames > (kFar - (long long)n_rows * n_fft) / hop) return MG_ERR_ARG;          // the gather's slot count
-    float* frames = static_cast<float*>(workspace);
-    const long long ft = SD_TILE / n_fft, n_tiles = (total_frames + ft - 1) / ft;
-    const unsigned blocks = (unsigned)(n_tiles < 3 * 256 * 4 ? n_tiles : 3 * 256 * 4);
+    const FramesGrid grid = frames_grid(total_frames, n_fft, SD_TILE, 3);
     hipStream_t st = (hipStream_t)stream;
-#define MG_MELG_LAUNCH(NN, G)                                                                                                         \
-    hipLaunchKernelGGL((mel_loss_grad_frames_kernel<NN, G>), dim3(blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rows,     \
-                       n_rows, frame_start, total_frames, window, fbank, band_k, band_j, n_mels, up, up_scale, n_res, hop,           \
-                       center != 0, n_tiles, frames)
-#define MG_MELG_SIZE(NN) do { if (seeded) MG_MELG_LAUNCH(NN, true); else MG_MELG_LAUNCH(NN, false); } while (0)
-    if (n_fft == 512) MG_MELG_SIZE(512);
-    else if (n_fft == 1024) MG_MELG_SIZE(1024);
-    else MG_MELG_SIZE(2048);
-#undef MG_MELG_SIZE
-#undef MG_MELG_LAUNCH
-    MG_CHECK_LAUNCH();
-    return lsd_launch_gather(frames, rows, n_rows, frame_start, total_frames, n_fft, hop, center, sr_total, accumulate != 0, grad_sr, st);
+    return frames_backward(rows, n_rows, frame_start, total_frames, n_fft, hop, center, sr_total,
+                           mg_mel_loss_rows_backward_workspace(total_frames, n_fft), workspace, workspace_bytes, accumulate != 0,
+                           grad_sr, st, [&](float* frames) {
+        frames_with_n_fft(n_fft, [&](auto nn) { frames_with_flag(seeded, [&](auto g) {
+            hipLaunchKernelGGL((mel_loss_grad_frames_kernel<decltype(nn)::value, decltype(g)::value>), dim3(grid.blocks),
+                               dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rows, n_rows, frame_start, total_frames, window,
+                               fbank, band_k, band_j, n_mels, up, up_scale, n_res, hop, center != 0, grid.n_tiles, frames);
+        }); });
+    });
 }
 
 }  // namespace

@@ -1,12 +1,16 @@
 // What the frame kernels of the multi-resolution STFT loss (stft_loss_rows.hip) and of the mel-spectrogram loss (mel_loss_rows.hip)
 // share: the clamp of the magnitudes, the tile of SD_TILE complex double points per workgroup, the transform of lsd_fft.h restated
 // for a vector type (double2 forward, float2 for the inverse), the staging of the windowed, reflected frames in double, the split
-// into "the float32 spectrum of the definition" and the test of a row's frame range.  Each statement stands here once so that the
-// two losses cannot drift apart; stft_loss_rows.hip's head says why the forward transform runs in double.
+// into "the float32 spectrum of the definition", the sum of a frame's lanes (sd_frame_sum), the whole tail of the backward frames
+// kernels from the Hermitian spectrum in registers to the windowed frames in the workspace (sd_inverse_tail) and the test of a
+// row's frame range.  Each statement stands here once so that the two losses cannot drift apart; stft_loss_rows.hip's head says why
+// the forward transform runs in double.  Beneath this header, frames_common.h holds what the LSD backward shares as well.
+// Deliberately NOT shared between the two losses: the seeded upstream gradient (the STFT loss uses the double quotient unrounded,
+// the mel loss rounds it to float32 first; both are asserted bit for bit) and the two finish kernels (different formulas).
 #pragma once
 #include <math.h>
 
-#include "lsd_gather.h"
+#include "frames_common.h"
 
 namespace {
 
@@ -158,6 +162,71 @@ __device__ __forceinline__ void sd_load_tile(double2* __restrict__ buf, const Ls
             e[q] = (double)v * (double)window[2 * m + q];
         }
         buf[i] = make_double2(e[0], e[1]);
+    }
+}
+
+// acc[q], q < Q, summed over the TPF lanes of frame fr (lane j of the frame): a wave's tree, then for a frame of several waves
+// the hand-off through red and the ascending sum on lane j == 0, which alone ends with the sums.  One barrier where TPF > 64.
+template <int Q, int TPF>
+__device__ __forceinline__ void sd_frame_sum(double (&acc)[Q], double (*red)[Q], int tid, int fr, int j) {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) acc[q] = wave_sum_d(acc[q]);
+    if (TPF > 64) {
+        if ((tid & 63) == 0) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) red[tid >> 6][q] = acc[q];
+        }
+        __syncthreads();
+        if (j == 0) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                acc[q] = red[fr * (TPF / 64)][q];
+                for (int w = 1; w < TPF / 64; ++w) acc[q] += red[fr * (TPF / 64) + w][q];
+            }
+        }
+    }
+}
+
+// The tail of a backward frames kernel, from "the Hermitian spectrum H_k (G_k / 2 for 0 < k < N/2, Re G_k for k = 0, N/2, rounded
+// to float32) of bins k = j + i TPF of frame fr = tid / TPF is in h[i]" to "y[n] window[n] of the tile's frames is in frames_out
+// [total_frames][N]".  The caller's barrier comes first: every lane has read what lies in fbuf, the tile's SD_TILE double2 seen as
+// float2.  H_k goes to fbuf[fr N + k] (the frames' regions fill half of the buffer); the inverse real transform is the adjoint of
+// the forward's pack-and-split (lsd_rows_grad.hip's head has the algebra): conj Zt of every frame is held in registers until all H
+// are read, packed densely as [FT][M], the forward stages run on it in float32, and the result is stored in 16-byte stores.
+template <int N, int BPL>
+__device__ __forceinline__ void sd_inverse_tail(const float2 (&h)[BPL], float2* fbuf, const double2* root, const float* window,
+                                                float* frames_out, long long tile, long long total_frames, int tid) {
+    constexpr int M = N / 2, FT = SD_TILE / N, TPF = LSD_NT / FT, NBINS = N / 2 + 1, HALF = SD_TILE / 2;
+    static_assert(BPL == (NBINS + TPF - 1) / TPF, "h holds the lane's bins");
+    static_assert(HALF % LSD_NT == 0 && (HALF / 2) % LSD_NT == 0 && M % 2 == 0, "whole points and whole point pairs per thread");
+    const int fr = tid / TPF, j = tid % TPF;
+#pragma unroll
+    for (int i = 0; i < BPL; ++i) {
+        const int k = j + i * TPF;
+        if (k < NBINS) fbuf[fr * N + k] = h[i];
+    }
+    __syncthreads();
+    float2 zt[HALF / LSD_NT];
+#pragma unroll
+    for (int it = 0; it < HALF / LSD_NT; ++it) {
+        const int idx = tid + it * LSD_NT, f2 = idx / M, k = idx % M;
+        zt[it] = frames_conj_zt(fbuf[f2 * N + k], fbuf[f2 * N + M - k], sd_root<N, float2>(root, k));
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < HALF / LSD_NT; ++it) fbuf[tid + it * LSD_NT] = zt[it];
+    __syncthreads();
+    sd_fft<M, HALF>(fbuf, root, tid);
+    // y[2m] = Re, y[2m+1] = -Im of the transform; two points = four samples per store
+#pragma unroll
+    for (int it = 0; it < HALF / 2 / LSD_NT; ++it) {
+        const int idx = tid + it * LSD_NT, f2 = idx / (M / 2), n = 4 * (idx % (M / 2));
+        const long long g = tile * FT + f2;
+        if (g < total_frames) {
+            const float4 v = *reinterpret_cast<const float4*>(fbuf + f2 * M + n / 2);
+            *reinterpret_cast<float4*>(frames_out + g * N + n) =
+                make_float4(v.x * window[n], -v.y * window[n + 1], v.z * window[n + 2], -v.w * window[n + 3]);
+        }
     }
 }
 

@@ -40,6 +40,11 @@
 // Static LDS only, no atomics, no host read-back, launch counts independent of the number of rows; no arithmetic for a row depends
 // on where the row sits, so a row has the same value and gradient bits alone and in any pack.  Tables that do not agree with
 // themselves lose samples; nothing is read or written outside a buffer, and only samples of live rows are written.
+// Shared with mel_loss_rows.hip through stft_frames.h: everything up to the float32 spectrum, the sum of a frame's lanes
+// (sd_frame_sum) and the backward's tail from H_k on (sd_inverse_tail); with lsd_rows_grad.hip as well, through frames_common.h:
+// the conj Zt of that tail and the host side (operand checks, grid, n_fft dispatch, the backward's epilogue with the gather).
+// Deliberately this file's own: the seeded gradient ((go * up_scale) / n_rows) / n_res in double, UNROUNDED (the mel loss rounds it
+// to float32, the LSD divides by the row's frame count and rounds: each is asserted bit for bit), and stft_loss_finish_kernel.
 #include "stft_frames.h"
 
 namespace {
@@ -82,22 +87,7 @@ __global__ __launch_bounds__(LSD_NT) void stft_loss_frames_kernel(const float* _
             acc[1] += pa;
             acc[2] += fabs(0.5 * (log(pa) - log(pb)));
         }
-#pragma unroll
-        for (int q = 0; q < 3; ++q) acc[q] = wave_sum_d(acc[q]);
-        if (TPF > 64) {
-            if ((tid & 63) == 0) {
-#pragma unroll
-                for (int q = 0; q < 3; ++q) red[tid >> 6][q] = acc[q];
-            }
-            __syncthreads();
-            if (j == 0) {
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    acc[q] = red[fr * (TPF / 64)][q];
-                    for (int w = 1; w < TPF / 64; ++w) acc[q] += red[fr * (TPF / 64) + w][q];
-                }
-            }
-        }
+        sd_frame_sum<3, TPF>(acc, red, tid, fr, j);
         if (j == 0) {
             const long long g = tile * FT + fr;
             if (g < total_frames) {
@@ -144,9 +134,7 @@ __global__ __launch_bounds__(LSD_NT) void stft_loss_grad_frames_kernel(const flo
                                                                        int hop, int center, long long n_tiles,
                                                                        float* __restrict__ frames_out) {
     constexpr int M = N / 2, FT = SD_TILE / N, TPF = LSD_NT / FT, NBINS = N / 2 + 1, BPL = (NBINS + TPF - 1) / TPF;
-    constexpr int HALF = SD_TILE / 2;                                       // the Zt of the tile's frames, densely: [FT][M]
     static_assert(TPF >= 64 && M % LSD_NT == 0, "a frame's lanes fill whole waves, a load pass stays inside one signal of a frame");
-    static_assert(HALF % LSD_NT == 0 && (HALF / 2) % LSD_NT == 0 && M % 2 == 0, "whole points and whole point pairs per thread");
     __shared__ __attribute__((aligned(16))) double2 buf[SD_TILE];          // [FT][hr, sr][M] double; then, as float2: [FT][N] holding
     __shared__ __attribute__((aligned(16))) double2 root[N / 2];           //   H_k, k = 0 .. M, of every frame; then [FT][M]
     __shared__ LsdFrame info[FT];
@@ -197,39 +185,7 @@ __global__ __launch_bounds__(LSD_NT) void stft_loss_grad_frames_kernel(const flo
             }
         }
         __syncthreads();                                    // every lane has read its Z[k] and Z[M-k]: the doubles are dead
-        // pass two: H_k, k = 0 .. M, of frame fr at fbuf[fr N + k] (float2: the frames' regions fill half of buf)
-#pragma unroll
-        for (int i = 0; i < BPL; ++i) {
-            const int k = j + i * TPF;
-            if (k < NBINS) fbuf[fr * N + k] = h[i];
-        }
-        __syncthreads();
-        // conj Zt of every frame, held in registers until all H are read, then packed densely
-        float2 zt[HALF / LSD_NT];
-#pragma unroll
-        for (int it = 0; it < HALF / LSD_NT; ++it) {
-            const int idx = tid + it * LSD_NT, f2 = idx / M, k = idx % M;
-            const float2 h1 = fbuf[f2 * N + k], h2 = fbuf[f2 * N + M - k], w = sd_root<N, float2>(root, k);
-            const float2 a = make_float2(h1.x + h2.x, h1.y - h2.y);                         // H_k + conj H_{M-k}
-            const float2 b = lsd_cmul(make_float2(h1.x - h2.x, h1.y + h2.y), make_float2(w.x, -w.y));
-            zt[it] = make_float2(a.x - b.y, -(a.y + b.x));                                  // conj (a + i b)
-        }
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < HALF / LSD_NT; ++it) fbuf[tid + it * LSD_NT] = zt[it];
-        __syncthreads();
-        sd_fft<M, HALF>(fbuf, root, tid);
-        // y[2m] = Re, y[2m+1] = -Im of the transform; two points = four samples per store
-#pragma unroll
-        for (int it = 0; it < HALF / 2 / LSD_NT; ++it) {
-            const int idx = tid + it * LSD_NT, f2 = idx / (M / 2), n = 4 * (idx % (M / 2));
-            const long long g = tile * FT + f2;
-            if (g < total_frames) {
-                const float4 v = *reinterpret_cast<const float4*>(fbuf + f2 * M + n / 2);
-                *reinterpret_cast<float4*>(frames_out + g * N + n) =
-                    make_float4(v.x * window[n], -v.y * window[n + 1], v.z * window[n + 2], -v.w * window[n + 3]);
-            }
-        }
+        sd_inverse_tail<N>(h, fbuf, root, window, frames_out, tile, total_frames, tid);
         __syncthreads();                                    // buf, info and coef are free for the next tile
     }
 }
@@ -273,21 +229,16 @@ size_t mg_stft_loss_rows_backward_workspace(long long total_frames, int n_fft) {
 int mg_stft_loss_rows(const float* hr, long long hr_total, const float* sr, long long sr_total, const mg_metric_row* rows, int n_rows,
                       const long long* frame_start, long long total_frames, const float* window, int n_fft, int hop, int center,
                       double* row_out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!hr || !sr || !rows || !frame_start || !window || !row_out || !workspace) return MG_ERR_ARG;
-    if (n_rows <= 0 || total_frames <= 0 || hr_total <= 0 || sr_total <= 0 || hop <= 0 || !lsd_size_ok(n_fft)) return MG_ERR_ARG;
-    const size_t need = mg_stft_loss_rows_workspace(total_frames);
-    if (need == 0 || workspace_bytes < need || !al16(workspace)) return MG_ERR_ARG;
+    if (!frames_args_ok(hr, hr_total, sr, sr_total, rows, n_rows, frame_start, total_frames, window, n_fft, hop) || !row_out ||
+        !frames_workspace_ok(mg_stft_loss_rows_workspace(total_frames), workspace, workspace_bytes))
+        return MG_ERR_ARG;
     double* partial = static_cast<double*>(workspace);
-    const long long ft = SD_TILE / n_fft, n_tiles = (total_frames + ft - 1) / ft;
-    const unsigned blocks = (unsigned)(n_tiles < 3 * 256 * 4 ? n_tiles : 3 * 256 * 4);    // a few waves of three workgroups per CU
+    const FramesGrid grid = frames_grid(total_frames, n_fft, SD_TILE, 3);
     hipStream_t st = (hipStream_t)stream;
-#define MG_STFT_LAUNCH(NN)                                                                                                          \
-    hipLaunchKernelGGL((stft_loss_frames_kernel<NN>), dim3(blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rows, n_rows, \
-                       frame_start, total_frames, window, hop, center != 0, n_tiles, partial)
-    if (n_fft == 512) MG_STFT_LAUNCH(512);
-    else if (n_fft == 1024) MG_STFT_LAUNCH(1024);
-    else MG_STFT_LAUNCH(2048);
-#undef MG_STFT_LAUNCH
+    frames_with_n_fft(n_fft, [&](auto nn) {
+        hipLaunchKernelGGL((stft_loss_frames_kernel<decltype(nn)::value>), dim3(grid.blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr,
+                           sr_total, rows, n_rows, frame_start, total_frames, window, hop, center != 0, grid.n_tiles, partial);
+    });
     MG_CHECK_LAUNCH();
     const unsigned fblocks = (unsigned)((n_rows + 255) / 256 < 1024 ? (n_rows + 255) / 256 : 1024);
     hipLaunchKernelGGL(stft_loss_finish_kernel, dim3(fblocks), dim3(256), 0, st, partial, rows, n_rows, frame_start, total_frames,
@@ -305,27 +256,20 @@ int stft_loss_rows_backward(const float* hr, long long hr_total, const float* sr
                             int n_rows, const long long* frame_start, long long total_frames, const float* window, int n_fft, int hop,
                             int center, const double* row_sums, const float* up, double up_scale, int n_res, bool seeded,
                             int accumulate, float* grad_sr, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!hr || !sr || !rows || !frame_start || !window || !row_sums || !up || !grad_sr || !workspace) return MG_ERR_ARG;
-    if (n_rows <= 0 || total_frames <= 0 || hr_total <= 0 || sr_total <= 0 || hop <= 0 || n_res <= 0 || !lsd_size_ok(n_fft))
+    if (!frames_args_ok(hr, hr_total, sr, sr_total, rows, n_rows, frame_start, total_frames, window, n_fft, hop) || !row_sums || !up ||
+        !grad_sr || n_res <= 0)
         return MG_ERR_ARG;
-    const size_t need = mg_stft_loss_rows_backward_workspace(total_frames, n_fft);
-    if (need == 0 || workspace_bytes < need || !al16(workspace)) return MG_ERR_ARG;
-    if (total_frames > (kFar - (long long)n_rows * n_fft) / hop) return MG_ERR_ARG;          // the gather's slot count
-    float* frames = static_cast<float*>(workspace);
-    const long long ft = SD_TILE / n_fft, n_tiles = (total_frames + ft - 1) / ft;
-    const unsigned blocks = (unsigned)(n_tiles < 3 * 256 * 4 ? n_tiles : 3 * 256 * 4);
+    const FramesGrid grid = frames_grid(total_frames, n_fft, SD_TILE, 3);
     hipStream_t st = (hipStream_t)stream;
-#define MG_STFTG_LAUNCH(NN, G)                                                                                                        \
-    hipLaunchKernelGGL((stft_loss_grad_frames_kernel<NN, G>), dim3(blocks), dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rows,    \
-                       n_rows, frame_start, total_frames, window, row_sums, up, up_scale, n_res, hop, center != 0, n_tiles, frames)
-#define MG_STFTG_SIZE(NN) do { if (seeded) MG_STFTG_LAUNCH(NN, true); else MG_STFTG_LAUNCH(NN, false); } while (0)
-    if (n_fft == 512) MG_STFTG_SIZE(512);
-    else if (n_fft == 1024) MG_STFTG_SIZE(1024);
-    else MG_STFTG_SIZE(2048);
-#undef MG_STFTG_SIZE
-#undef MG_STFTG_LAUNCH
-    MG_CHECK_LAUNCH();
-    return lsd_launch_gather(frames, rows, n_rows, frame_start, total_frames, n_fft, hop, center, sr_total, accumulate != 0, grad_sr, st);
+    return frames_backward(rows, n_rows, frame_start, total_frames, n_fft, hop, center, sr_total,
+                           mg_stft_loss_rows_backward_workspace(total_frames, n_fft), workspace, workspace_bytes, accumulate != 0,
+                           grad_sr, st, [&](float* frames) {
+        frames_with_n_fft(n_fft, [&](auto nn) { frames_with_flag(seeded, [&](auto g) {
+            hipLaunchKernelGGL((stft_loss_grad_frames_kernel<decltype(nn)::value, decltype(g)::value>), dim3(grid.blocks),
+                               dim3(LSD_NT), 0, st, hr, hr_total, sr, sr_total, rows, n_rows, frame_start, total_frames, window,
+                               row_sums, up, up_scale, n_res, hop, center != 0, grid.n_tiles, frames);
+        }); });
+    });
 }
 
 }  // namespace

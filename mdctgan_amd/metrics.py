@@ -302,28 +302,47 @@ def _pack_with_grad(waves, layout, device):
     return torch.cat(parts)
 
 
-_lsd_tables = {}            # lsd_loss: the row tables of a dense geometry (B, T, n_fft, hop, center, device), uploaded once
+_loss_tables = {}           # the device tables of the losses' dense geometries, (loss, geometry) -> tensors, uploaded once
+
+
+def _row_tables(key, starts, lengths, more, device):
+    """The tables of a loss in one copy -> device tensors: the metric rows {hr start, 0, sr start, length} (compute_matrics_many's
+    without the lr column), then what more() lists.  A caller that names its geometry (key is not None) finds the same tensors
+    again -- a captured graph goes on reading them.  The cache is ONE for all losses: the insertion of a 65th geometry by any
+    loss drops every loss's tables (never those being inserted), so a graph captured over one of the 64 dropped geometries must
+    be captured again; a training run has a few geometries and never gets there."""
+    tables = _loss_tables.get(key) if key is not None else None
+    if tables is None:
+        rows = np.stack([np.asarray(t, dtype=np.int64) for t in (starts[0], [0] * len(lengths), starts[1], lengths)], axis=1)
+        tables = upload_tables([rows] + more(), device)
+        if key is not None:
+            if len(_loss_tables) >= 64:         # a training run has a few geometries; a sweep over many must not pile tables up
+                _loss_tables.clear()            # (before the insertion: never the geometry in use)
+            _loss_tables[key] = tables
+    return tables
+
+
+def _hr_is_constant(hr_op, what):
+    """hr_op: _packed_operand's result for the ground truth."""
+    if any(t.requires_grad for t in ([hr_op[0]] if hr_op[0] is not None else hr_op[1])):
+        raise NotImplementedError("the %s has no gradient with respect to hr: detach the ground truth" % what)
+
+
+def _finite_scale(scale) -> float:
+    scale = float(scale)
+    if not math.isfinite(scale):
+        raise ValueError("scale must be finite")
+    return scale
 
 
 def _lsd_operands(hrs, srs, opt, hr_shift, table_key=None):
     """What every LSD loss node is applied to: -> (sr, hr, row_t, fs_t, frame_t, hr_shift, window, geom)."""
-    hr_op = _packed_operand(hrs, "hrs")
-    if any(t.requires_grad for t in ([hr_op[0]] if hr_op[0] is not None else hr_op[1])):
-        raise NotImplementedError("the LSD has no gradient with respect to hr: detach the ground truth")
+    _hr_is_constant(_packed_operand(hrs, "hrs"), "LSD")
     n_fft, hop, win, plan, device, (hr, sr), starts = _metric_operands(((hrs, "hrs"), (srs, "srs")), opt, hr_shift,
                                                                        differentiable=True)
-    lengths, center = plan.lengths, plan.center
-    U = len(lengths)
-
-    # compute_matrics_many's tables (no lr column), in one copy; a caller that names its geometry finds them again
-    tables = _lsd_tables.get(table_key) if table_key is not None else None
-    if tables is None:
-        rows = np.stack([np.asarray(t, dtype=np.int64) for t in (starts[0], [0] * U, starts[1], lengths)], axis=1)
-        tables = upload_tables([rows, plan.frame_start, window_table(plan.frame_start[:-1], plan.frames)], device)
-        if table_key is not None:
-            _lsd_tables[table_key] = tables
-    row_t, fs_t, frame_t = tables
-    geom = (n_fft, hop, center, plan.total_frames, max(plan.frames))
+    row_t, fs_t, frame_t = _row_tables(table_key, starts, plan.lengths,
+                                       lambda: [plan.frame_start, window_table(plan.frame_start[:-1], plan.frames)], device)
+    geom = (n_fft, hop, plan.center, plan.total_frames, max(plan.frames))
     return sr, hr, row_t, fs_t, frame_t, hr_shift, _window(win, device), geom
 
 
@@ -370,7 +389,7 @@ def _dense_pack(sr_audio, hr_audio):
 def _dense_batch(sr_audio, hr_audio, opt):
     """lsd_loss's and lsd_loss_term's operand checks -> the arguments of _lsd_operands: both batches as packs read in place."""
     hrs, srs, B, T = _dense_pack(sr_audio, hr_audio)
-    key = (B, T, int(opt.n_fft), int(opt.hop_length), bool(opt.center), str(sr_audio.device))
+    key = ("lsd", B, T, int(opt.n_fft), int(opt.hop_length), bool(opt.center), str(sr_audio.device))
     return hrs, srs, opt, None, key
 
 
@@ -420,20 +439,24 @@ def lsd_loss_term(sr_audio, hr_audio, opt, scale):
     arithmetic autograd performs for ``scale * lsd_loss``, so a power-of-two scale gives that gradient bit for bit -- and writes
     every sample, so no buffer is zero-filled.  The upstream gradient (the GradScaler's loss scale in a --fp16 step) stays on the
     device and is read when the kernel runs: a captured step follows it.  Capturable after one eager call, like lsd_loss."""
-    scale = float(scale)
-    if not math.isfinite(scale):
-        raise ValueError("scale must be finite")
+    scale = _finite_scale(scale)
     sr, hr, row_t, fs_t, _, _, window, geom = _lsd_operands(*_dense_batch(sr_audio, hr_audio, opt))
     return _LsdMeanLoss.apply(sr, hr, row_t, fs_t, window, geom, scale)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The multi-resolution STFT loss (spectral convergence + log-magnitude L1): csrc/stft_loss_rows.hip
+# The losses of several resolutions, two launches each way per resolution, row_out [R, U, 4]: the multi-resolution STFT loss
+# (spectral convergence + log-magnitude L1, csrc/stft_loss_rows.hip) and the multi-scale mel-spectrogram L1 loss
+# (csrc/mel_loss_rows.hip).  One operand builder, one forward and one backward loop, one pair of autograd nodes and one dense-batch
+# wrapper, parameterised by a _RowsLoss; what differs between the two stands in their resolution parsers and in mel's filterbanks.
 # ---------------------------------------------------------------------------------------------------------------------
 STFT_RESOLUTIONS = ((512, 128), (1024, 256), (2048, 512))       # (n_fft, hop) of the default loss
 STFT_CLAMP = 1e-7                                               # m = sqrt(max(re^2 + im^2, STFT_CLAMP))
+MEL_RESOLUTIONS = ((512, 128, 40), (1024, 256, 80), (2048, 512, 160))       # (n_fft, hop, n_mels) of the default loss
+MEL_FLOOR = 1e-5                                                            # l = ln(max(E, MEL_FLOOR))
+MEL_MAX_FILTERS = 256                                                       # the kernels' limit on n_mels
 
-_mrstft_tables = {}         # mrstft_loss: the tables of a dense geometry (B, T, resolutions, center, device), uploaded once
+_mel_fbanks = {}            # (sample_rate, n_fft, n_mels, f_min, f_max, device) -> (W, band_k, band_j) on the device
 
 
 def _hann(n_fft: int, device):
@@ -444,188 +467,55 @@ def _hann(n_fft: int, device):
     return _windows[key]
 
 
-def _resolutions(resolutions):
+def _parse_resolutions(resolutions, fields, kernels):
+    """-> a tuple of int tuples, one value per field: ("n_fft", "hop") or ("n_fft", "hop", "n_mels"); `kernels` names the loss."""
+    shape = "(%s) %s" % (", ".join(fields), "pair" if len(fields) == 2 else "triple")
     try:
-        res = tuple((int(n), int(h)) for n, h in resolutions)
+        res = tuple(tuple(int(v) for v in r) for r in resolutions)
+        if any(len(r) != len(fields) for r in res):
+            raise ValueError
     except (TypeError, ValueError):
-        raise ValueError("resolutions: a sequence of (n_fft, hop) pairs") from None
+        raise ValueError("resolutions: a sequence of %ss" % shape) from None
     if not res:
-        raise ValueError("resolutions: at least one (n_fft, hop) pair")
-    for n, h in res:
-        if n not in LSD_ROWS_N_FFT:
-            raise NotImplementedError("the STFT loss kernels serve n_fft in %s (got %d)" % (LSD_ROWS_N_FFT, n))
-        if h < 1:
-            raise ValueError("resolution (%d, %d): the hop must be at least 1" % (n, h))
+        raise ValueError("resolutions: at least one %s" % shape)
+    for r in res:
+        if r[0] not in LSD_ROWS_N_FFT:
+            raise NotImplementedError("the %s loss kernels serve n_fft in %s (got %d)" % (kernels, LSD_ROWS_N_FFT, r[0]))
+        if r[1] < 1:
+            raise ValueError("resolution %s: the hop must be at least 1" % (r,))
+        if len(r) == 3 and not 1 <= r[2] <= MEL_MAX_FILTERS:
+            raise ValueError("resolution %s: the mel loss kernels serve 1 to %d filters" % (r, MEL_MAX_FILTERS))
     return res
+
+
+def _resolutions(resolutions):
+    return _parse_resolutions(resolutions, ("n_fft", "hop"), "STFT")
+
+
+def _mel_resolutions(resolutions):
+    return _parse_resolutions(resolutions, ("n_fft", "hop", "n_mels"), "mel")
+
+
+def _plan_resolutions(lengths, res, center):
+    plans = []
+    for r in res:
+        try:
+            plans.append(plan_metrics(lengths, r[0], r[1], center))
+        except ValueError as e:
+            raise ValueError("resolution %s: %s" % (r, e)) from None
+    return plans
 
 
 def plan_mrstft(lengths, resolutions=STFT_RESOLUTIONS, center: bool = True):
     """plan_metrics for every resolution (host only) -> [MetricsPlan]; ValueError naming the utterance AND the resolution where an
     utterance has no frame or (centred) cannot be reflected: len <= n_fft / 2."""
-    plans = []
-    for n, h in _resolutions(resolutions):
-        try:
-            plans.append(plan_metrics(lengths, n, h, center))
-        except ValueError as e:
-            raise ValueError("resolution (%d, %d): %s" % (n, h, e)) from None
-    return plans
+    return _plan_resolutions(lengths, _resolutions(resolutions), center)
 
 
-def _mrstft_operands(hrs, srs, resolutions, center, table_key=None):
-    """What every MR-STFT node is applied to -> (sr, hr, row_t, tabs); tabs = (frame_start tables, windows, geometries (n_fft,
-    hop, center, total_frames)), one entry per resolution."""
-    res, center = _resolutions(resolutions), bool(center)
-    ops_, lengths = _checked_operands(((hrs, "hrs"), (srs, "srs")))
-    if any(t.requires_grad for t in ([ops_[0][0]] if ops_[0][0] is not None else ops_[0][1])):
-        raise NotImplementedError("the MR-STFT loss has no gradient with respect to hr: detach the ground truth")
-    plans = plan_mrstft(lengths, res, center)
-    device, (hr, sr), starts = _pack_operands(ops_, True)
-    U = len(lengths)
-    tables = _mrstft_tables.get(table_key) if table_key is not None else None
-    if tables is None:
-        rows = np.stack([np.asarray(t, dtype=np.int64) for t in (starts[0], [0] * U, starts[1], lengths)], axis=1)
-        tables = upload_tables([rows] + [p.frame_start for p in plans], device)
-        if table_key is not None:
-            if len(_mrstft_tables) >= 64:       # a training run has one geometry; a sweep over many must not pile tables up
-                _mrstft_tables.clear()
-            _mrstft_tables[table_key] = tables
-    geoms = tuple((p.n_fft, p.hop, center, p.total_frames) for p in plans)
-    return sr, hr, tables[0], (tuple(tables[1:]), tuple(_hann(n, device) for n, _ in res), geoms)
-
-
-def _mrstft_forward(sr, hr, row_t, tabs):
-    """mg_stft_loss_rows for every resolution -> row_out float64 [R, U, 4] = {A, B, C, loss}."""
-    fs_ts, windows, geoms = tabs
-    lib = _lib.load()
-    U = row_t.shape[0]
-    row_out = torch.empty(len(geoms), U, 4, dtype=torch.float64, device=sr.device)
-    for r, (fs_t, window, (n_fft, hop, center, total_frames)) in enumerate(zip(fs_ts, windows, geoms)):
-        nbytes = lib.mg_stft_loss_rows_workspace(total_frames)
-        ws = _lib.workspace(nbytes, sr.device)
-        _lib.check(lib.mg_stft_loss_rows(_lib.ptr(hr), hr.numel(), _lib.ptr(sr), sr.numel(), _lib.ptr(row_t), U, _lib.ptr(fs_t),
-                                         total_frames, _lib.ptr(window), n_fft, hop, int(center), _lib.ptr(row_out[r]), _lib.ptr(ws),
-                                         nbytes, _lib.stream()), "mg_stft_loss_rows")
-    return row_out
-
-
-def _mrstft_backward(sr, hr, row_t, tabs, row_out, grad_sr, grad_rows=None, go=None, scale=0.0):
-    """mg_stft_loss_rows_backward (grad_rows [U]) or its seeded form (go [1], scale) for every resolution, in resolution order: the
-    first writes every sample of the live rows of grad_sr, the later ones add to it."""
-    fs_ts, windows, geoms = tabs
-    lib = _lib.load()
-    U, R = row_t.shape[0], len(geoms)
-    for r, (fs_t, window, (n_fft, hop, center, total_frames)) in enumerate(zip(fs_ts, windows, geoms)):
-        nbytes = lib.mg_stft_loss_rows_backward_workspace(total_frames, n_fft)
-        ws = _lib.workspace(nbytes, sr.device)
-        head = (_lib.ptr(hr), hr.numel(), _lib.ptr(sr), sr.numel(), _lib.ptr(row_t), U, _lib.ptr(fs_t), total_frames, _lib.ptr(window),
-                n_fft, hop, int(center), _lib.ptr(row_out[r]))
-        tail = (int(r > 0), _lib.ptr(grad_sr), _lib.ptr(ws), nbytes, _lib.stream())
-        if go is None:
-            _lib.check(lib.mg_stft_loss_rows_backward(*head, _lib.ptr(grad_rows), *tail), "mg_stft_loss_rows_backward")
-        else:
-            _lib.check(lib.mg_stft_loss_rows_backward_seeded(*head, _lib.ptr(go), scale, R, *tail),
-                       "mg_stft_loss_rows_backward_seeded")
-    return grad_sr
-
-
-class _MrStftRows(torch.autograd.Function):
-    """Per-utterance MR-STFT loss [U] (float64) of a packed sr buffer against a packed, constant hr buffer: the losses of the
-    resolutions added in resolution order and divided by their number.  Backward: into a zero-filled buffer of sr's size."""
-
-    @staticmethod
-    def forward(ctx, sr, hr, row_t, tabs):
-        row_out = _mrstft_forward(sr, hr, row_t, tabs)
-        ctx.save_for_backward(sr, hr, row_t, row_out)
-        ctx.tabs = tabs
-        total = row_out[0, :, 3].clone()
-        for r in range(1, row_out.shape[0]):
-            total = total + row_out[r, :, 3]
-        return total / row_out.shape[0]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad):
-        sr, hr, row_t, row_out = ctx.saved_tensors
-        grad_rows = (grad.double() / row_out.shape[0]).float().contiguous()
-        return _mrstft_backward(sr, hr, row_t, ctx.tabs, row_out, torch.zeros_like(sr), grad_rows=grad_rows), None, None, None
-
-
-def mrstft_many(hrs, srs, resolutions=STFT_RESOLUTIONS, center=True):
-    """The multi-resolution STFT loss of every utterance on its own, differentiable in sr -> float64 device tensor [U].  For one
-    resolution (n_fft, hop) -- periodic Hann window of n_fft samples, centred frames reflected at the utterance's own ends, K =
-    n_fft / 2 + 1 bins, F_u frames, m = sqrt(max(re^2 + im^2, 1e-7)) --
-        loss_u = sqrt(sum (m_hr - m_sr)^2 / sum m_hr^2) + sum |ln m_hr - ln m_sr| / (F_u K)
-    with the sums over all frames and bins of utterance u, and the result is the mean over the resolutions.  Operand forms as for
-    ``lsd_many``: lists of waveforms, or packed ``(buffer, starts, lengths)`` / ``(buffer, starts[, lengths])`` read where they
-    lie.  Two library launches per resolution forward and two backward, whatever U is (csrc/stft_loss_rows.hip), plus the
-    element-wise launches on [U] that join the resolutions (a copy, R - 1 adds, a divide; backward: a divide, a cast and the zero
-    fill); deterministic; nothing is read back.  The gradient is exactly 0 where autograd through torch.stft has NaN or Inf: sr == hr, silence, clamped bins.  hr
-    is a constant: a ground truth that requires grad raises NotImplementedError.  ValueError (naming utterance and resolution)
-    for an utterance that cannot be reflected at a resolution, len <= n_fft / 2."""
-    return _MrStftRows.apply(*_mrstft_operands(hrs, srs, resolutions, center))
-
-
-def _mrstft_dense(sr_audio, hr_audio, resolutions):
-    hrs, srs, B, T = _dense_pack(sr_audio, hr_audio)
-    res = _resolutions(resolutions)
-    return _mrstft_operands(hrs, srs, res, True, (B, T, res, True, str(sr_audio.device)))
-
-
-def mrstft_loss(sr_audio, hr_audio, resolutions=STFT_RESOLUTIONS):
-    """``mrstft_many`` of a dense batch as a training loss -> 0-dim float64 tensor, the mean over the clips, differentiable in
-    sr_audio.  sr_audio / hr_audio: float32 device tensors [B, T], [B, 1, T] or [B, 1, 1, T], read in place (no packing copy).
-    The tables of a geometry are uploaded once and kept, so forward + backward capture into a graph on one stream after one
-    eager call (lsd_loss's note on live graphs from other streams applies)."""
-    return _MrStftRows.apply(*_mrstft_dense(sr_audio, hr_audio, resolutions)).mean()
-
-
-class _MrStftMeanLoss(torch.autograd.Function):
-    """scale * the mean over the clips of the MR-STFT loss as a node of the training step's loss family: a float32 [1] loss, the
-    constant factor inside, the upstream gradient read on the device.  Forward: mg_stft_loss_rows per resolution and
-    mg_stft_loss_mean.  Backward: mg_stft_loss_rows_backward_seeded per resolution into an uninitialised buffer of sr's size -- the
-    pack is dense and every row is live at every resolution, so the first resolution writes every sample."""
-
-    @staticmethod
-    def forward(ctx, sr, hr, row_t, tabs, scale):
-        row_out = _mrstft_forward(sr, hr, row_t, tabs)
-        loss = torch.empty(1, dtype=torch.float32, device=sr.device)
-        _lib.check(_lib.load().mg_stft_loss_mean(_lib.ptr(row_out), row_out.shape[1], row_out.shape[0], scale, _lib.ptr(loss),
-                                                 _lib.stream()), "mg_stft_loss_mean")
-        ctx.save_for_backward(sr, hr, row_t, row_out)
-        ctx.tabs, ctx.scale = tabs, scale
-        return loss.reshape(())
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, go):
-        sr, hr, row_t, row_out = ctx.saved_tensors
-        go = go.reshape(1).float().contiguous()
-        return _mrstft_backward(sr, hr, row_t, ctx.tabs, row_out, torch.empty_like(sr), go=go, scale=ctx.scale), None, None, None, None
-
-
-def mrstft_loss_term(sr_audio, hr_audio, scale, resolutions=STFT_RESOLUTIONS):
-    """``scale * mrstft_loss(sr_audio, hr_audio, resolutions)`` as a term of the training step -> 0-dim float32 tensor,
-    differentiable in sr_audio: mrstft_loss's operand forms, checks and cached tables, but one autograd node in the step's loss
-    convention (functional._LossFn).  Forward is mg_stft_loss_rows per resolution plus one reduction launch; backward is
-    mg_stft_loss_rows_backward_seeded per resolution, which forms every clip's upstream gradient in the kernel, in double, from the
-    upstream scalar -- the GradScaler's loss scale in a --fp16 step stays on the device and is read when the kernel runs, so a
-    captured step follows it -- and writes every sample, so no buffer is zero-filled.  Capturable after one eager call."""
-    scale = float(scale)
-    if not math.isfinite(scale):
-        raise ValueError("scale must be finite")
-    sr, hr, row_t, tabs = _mrstft_dense(sr_audio, hr_audio, resolutions)
-    return _MrStftMeanLoss.apply(sr, hr, row_t, tabs, scale)
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# The multi-scale mel-spectrogram L1 loss: csrc/mel_loss_rows.hip
-# ---------------------------------------------------------------------------------------------------------------------
-MEL_RESOLUTIONS = ((512, 128, 40), (1024, 256, 80), (2048, 512, 160))       # (n_fft, hop, n_mels) of the default loss
-MEL_FLOOR = 1e-5                                                            # l = ln(max(E, MEL_FLOOR))
-MEL_MAX_FILTERS = 256                                                       # the kernels' limit on n_mels
-
-_mel_tables = {}            # mel_loss: the tables of a dense geometry (B, T, resolutions, center, device), uploaded once
-_mel_fbanks = {}            # (sample_rate, n_fft, n_mels, f_min, f_max, device) -> (W, band_k, band_j) on the device
+def plan_mel(lengths, resolutions=MEL_RESOLUTIONS, center: bool = True):
+    """plan_metrics for every resolution (n_fft, hop, n_mels) (host only) -> [MetricsPlan]; ValueError naming the utterance AND the
+    resolution where an utterance has no frame or (centred) cannot be reflected: len <= n_fft / 2."""
+    return _plan_resolutions(lengths, _mel_resolutions(resolutions), center)
 
 
 def mel_fbank(sample_rate, n_fft: int, n_mels: int, f_min: float = 0.0, f_max=None):
@@ -678,35 +568,6 @@ def mel_band_tables(fbank):
     return tables[0], tables[1]
 
 
-def _mel_resolutions(resolutions):
-    try:
-        res = tuple((int(n), int(h), int(j)) for n, h, j in resolutions)
-    except (TypeError, ValueError):
-        raise ValueError("resolutions: a sequence of (n_fft, hop, n_mels) triples") from None
-    if not res:
-        raise ValueError("resolutions: at least one (n_fft, hop, n_mels) triple")
-    for n, h, j in res:
-        if n not in LSD_ROWS_N_FFT:
-            raise NotImplementedError("the mel loss kernels serve n_fft in %s (got %d)" % (LSD_ROWS_N_FFT, n))
-        if h < 1:
-            raise ValueError("resolution (%d, %d, %d): the hop must be at least 1" % (n, h, j))
-        if not 1 <= j <= MEL_MAX_FILTERS:
-            raise ValueError("resolution (%d, %d, %d): the mel loss kernels serve 1 to %d filters" % (n, h, j, MEL_MAX_FILTERS))
-    return res
-
-
-def plan_mel(lengths, resolutions=MEL_RESOLUTIONS, center: bool = True):
-    """plan_metrics for every resolution (n_fft, hop, n_mels) (host only) -> [MetricsPlan]; ValueError naming the utterance AND the
-    resolution where an utterance has no frame or (centred) cannot be reflected: len <= n_fft / 2."""
-    plans = []
-    for n, h, j in _mel_resolutions(resolutions):
-        try:
-            plans.append(plan_metrics(lengths, n, h, center))
-        except ValueError as e:
-            raise ValueError("resolution (%d, %d, %d): %s" % (n, h, j, e)) from None
-    return plans
-
-
 def _mel_bank(sample_rate, n_fft, n_mels, f_min, f_max, device=None):
     """mel_fbank and its band tables, checked; device None: the host check alone, else the three tensors on the device (built once
     per (sample_rate, n_fft, n_mels, f_min, f_max, device) and kept).  ValueError naming the filter for an empty one."""
@@ -732,74 +593,92 @@ def _mel_banks(res, sample_rate, f_min, f_max, device=None):
     return tuple(banks)
 
 
-def _mel_operands(hrs, srs, sample_rate, resolutions, center, f_min, f_max, table_key=None):
-    """What every mel-loss node is applied to -> (sr, hr, row_t, tabs); tabs = (frame_start tables, windows, filterbanks (W, band_k,
-    band_j), geometries (n_fft, hop, center, total_frames, n_mels)), one entry per resolution."""
-    res, center = _mel_resolutions(resolutions), bool(center)
+@dataclass(frozen=True)
+class _RowsLoss:
+    """One loss of the family.  what: its name in messages; entry: its forward C entry point -- entry + "_workspace", "_backward",
+    "_backward_workspace" and "_backward_seeded" are the others; parse: its resolution parser; extras(res, device, *params): per
+    resolution, what its entry points take between `center` and the outputs (device None: the host checks alone, for their
+    refusals); sums: whether the backward reads the forward's row_out."""
+    what: str
+    entry: str
+    parse: object
+    extras: object
+    sums: bool
+
+
+_MRSTFT = _RowsLoss("MR-STFT loss", "mg_stft_loss_rows", _resolutions, lambda res, device: ((),) * len(res), True)
+def _mel_extras(res, device, sample_rate, f_min, f_max):
+    """(W, band_k, band_j, n_mels) per resolution.  _rows_loss_operands calls this twice: with device None before anything is packed
+    -- _mel_banks then builds and checks the banks on the host, which is where an empty filter is refused -- and with the device."""
+    return tuple(bank + (r[2],) for bank, r in zip(_mel_banks(res, sample_rate, f_min, f_max, device), res))
+
+
+_MEL = _RowsLoss("mel loss", "mg_mel_loss_rows", _mel_resolutions, _mel_extras, False)
+
+
+def _rows_loss_operands(loss, hrs, srs, resolutions, center, params=(), table_key=None):
+    """What every node of the family is applied to -> (loss, sr, hr, row_t, tabs); tabs = (frame_start tables, windows, extras,
+    geometries (n_fft, hop, center, total_frames)), one entry per resolution.  params: loss.extras' (mel: sample_rate, f_min,
+    f_max).  Every refusal comes before anything is packed or uploaded."""
+    res, center = loss.parse(resolutions), bool(center)
     ops_, lengths = _checked_operands(((hrs, "hrs"), (srs, "srs")))
-    if any(t.requires_grad for t in ([ops_[0][0]] if ops_[0][0] is not None else ops_[0][1])):
-        raise NotImplementedError("the mel loss has no gradient with respect to hr: detach the ground truth")
-    plans = plan_mel(lengths, res, center)
-    _mel_banks(res, sample_rate, f_min, f_max)          # (refusals before anything is packed or uploaded)
+    _hr_is_constant(ops_[0], loss.what)
+    plans = _plan_resolutions(lengths, res, center)
+    loss.extras(res, None, *params)
     device, (hr, sr), starts = _pack_operands(ops_, True)
-    banks = _mel_banks(res, sample_rate, f_min, f_max, device)
-    U = len(lengths)
-    tables = _mel_tables.get(table_key) if table_key is not None else None
-    if tables is None:
-        rows = np.stack([np.asarray(t, dtype=np.int64) for t in (starts[0], [0] * U, starts[1], lengths)], axis=1)
-        tables = upload_tables([rows] + [p.frame_start for p in plans], device)
-        if table_key is not None:
-            if len(_mel_tables) >= 64:          # a training run has one geometry; a sweep over many must not pile tables up
-                _mel_tables.clear()
-            _mel_tables[table_key] = tables
-    geoms = tuple((p.n_fft, p.hop, center, p.total_frames, j) for p, (_, _, j) in zip(plans, res))
-    return sr, hr, tables[0], (tuple(tables[1:]), tuple(_hann(n, device) for n, _, _ in res), banks, geoms)
+    extras = loss.extras(res, device, *params)
+    tables = _row_tables(table_key, starts, lengths, lambda: [p.frame_start for p in plans], device)
+    geoms = tuple((p.n_fft, p.hop, center, p.total_frames) for p in plans)
+    return loss, sr, hr, tables[0], (tuple(tables[1:]), tuple(_hann(r[0], device) for r in res), extras, geoms)
 
 
-def _mel_forward(sr, hr, row_t, tabs):
-    """mg_mel_loss_rows for every resolution -> row_out float64 [R, U, 4] = {sum, 0, 0, loss}."""
-    fs_ts, windows, banks, geoms = tabs
+def _ptrs(args):
+    return tuple(_lib.ptr(a) if torch.is_tensor(a) else a for a in args)
+
+
+def _rows_loss_forward(loss, sr, hr, row_t, tabs):
+    """loss.entry for every resolution -> row_out float64 [R, U, 4]: {A, B, C, loss} (MR-STFT), {sum, 0, 0, loss} (mel)."""
     lib = _lib.load()
     U = row_t.shape[0]
-    row_out = torch.empty(len(geoms), U, 4, dtype=torch.float64, device=sr.device)
-    for r, (fs_t, window, (W, bk, bj), (n_fft, hop, center, total_frames, n_mels)) in enumerate(zip(fs_ts, windows, banks, geoms)):
-        nbytes = lib.mg_mel_loss_rows_workspace(total_frames)
+    row_out = torch.empty(len(tabs[3]), U, 4, dtype=torch.float64, device=sr.device)
+    for r, (fs_t, window, extra, (n_fft, hop, center, total_frames)) in enumerate(zip(*tabs)):
+        nbytes = getattr(lib, loss.entry + "_workspace")(total_frames)
         ws = _lib.workspace(nbytes, sr.device)
-        _lib.check(lib.mg_mel_loss_rows(_lib.ptr(hr), hr.numel(), _lib.ptr(sr), sr.numel(), _lib.ptr(row_t), U, _lib.ptr(fs_t),
-                                        total_frames, _lib.ptr(window), n_fft, hop, int(center), _lib.ptr(W), _lib.ptr(bk),
-                                        _lib.ptr(bj), n_mels, _lib.ptr(row_out[r]), _lib.ptr(ws), nbytes, _lib.stream()),
-                   "mg_mel_loss_rows")
+        _lib.check(getattr(lib, loss.entry)(_lib.ptr(hr), hr.numel(), _lib.ptr(sr), sr.numel(), _lib.ptr(row_t), U, _lib.ptr(fs_t),
+                                            total_frames, _lib.ptr(window), n_fft, hop, int(center), *_ptrs(extra),
+                                            _lib.ptr(row_out[r]), _lib.ptr(ws), nbytes, _lib.stream()), loss.entry)
     return row_out
 
 
-def _mel_backward(sr, hr, row_t, tabs, grad_sr, grad_rows=None, go=None, scale=0.0):
-    """mg_mel_loss_rows_backward (grad_rows [U]) or its seeded form (go [1], scale) for every resolution, in resolution order: the
+def _rows_loss_backward(loss, sr, hr, row_t, tabs, row_out, grad_sr, grad_rows=None, go=None, scale=0.0):
+    """loss.entry + "_backward" (grad_rows [U]) or its seeded form (go [1], scale) for every resolution, in resolution order: the
     first writes every sample of the live rows of grad_sr, the later ones add to it."""
-    fs_ts, windows, banks, geoms = tabs
     lib = _lib.load()
-    U, R = row_t.shape[0], len(geoms)
-    for r, (fs_t, window, (W, bk, bj), (n_fft, hop, center, total_frames, n_mels)) in enumerate(zip(fs_ts, windows, banks, geoms)):
-        nbytes = lib.mg_mel_loss_rows_backward_workspace(total_frames, n_fft)
+    U, R = row_t.shape[0], len(tabs[3])
+    for r, (fs_t, window, extra, (n_fft, hop, center, total_frames)) in enumerate(zip(*tabs)):
+        nbytes = getattr(lib, loss.entry + "_backward_workspace")(total_frames, n_fft)
         ws = _lib.workspace(nbytes, sr.device)
         head = (_lib.ptr(hr), hr.numel(), _lib.ptr(sr), sr.numel(), _lib.ptr(row_t), U, _lib.ptr(fs_t), total_frames, _lib.ptr(window),
-                n_fft, hop, int(center), _lib.ptr(W), _lib.ptr(bk), _lib.ptr(bj), n_mels)
+                n_fft, hop, int(center)) + _ptrs(extra) + ((_lib.ptr(row_out[r]),) if loss.sums else ())
         tail = (int(r > 0), _lib.ptr(grad_sr), _lib.ptr(ws), nbytes, _lib.stream())
         if go is None:
-            _lib.check(lib.mg_mel_loss_rows_backward(*head, _lib.ptr(grad_rows), *tail), "mg_mel_loss_rows_backward")
+            what = loss.entry + "_backward"
+            _lib.check(getattr(lib, what)(*head, _lib.ptr(grad_rows), *tail), what)
         else:
-            _lib.check(lib.mg_mel_loss_rows_backward_seeded(*head, _lib.ptr(go), scale, R, *tail), "mg_mel_loss_rows_backward_seeded")
+            what = loss.entry + "_backward_seeded"
+            _lib.check(getattr(lib, what)(*head, _lib.ptr(go), scale, R, *tail), what)
     return grad_sr
 
 
-class _MelRows(torch.autograd.Function):
-    """Per-utterance mel loss [U] (float64) of a packed sr buffer against a packed, constant hr buffer: the losses of the
-    resolutions added in resolution order and divided by their number.  Backward: into a zero-filled buffer of sr's size."""
+class _RowsLossRows(torch.autograd.Function):
+    """Per-utterance loss [U] (float64) of a packed sr buffer against a packed, constant hr buffer: the losses of the resolutions
+    added in resolution order and divided by their number.  Backward: into a zero-filled buffer of sr's size."""
 
     @staticmethod
-    def forward(ctx, sr, hr, row_t, tabs):
-        row_out = _mel_forward(sr, hr, row_t, tabs)
-        ctx.save_for_backward(sr, hr, row_t)
-        ctx.tabs = tabs
+    def forward(ctx, loss, sr, hr, row_t, tabs):
+        row_out = _rows_loss_forward(loss, sr, hr, row_t, tabs)
+        ctx.save_for_backward(sr, hr, row_t, row_out)
+        ctx.loss, ctx.tabs = loss, tabs
         total = row_out[0, :, 3].clone()
         for r in range(1, row_out.shape[0]):
             total = total + row_out[r, :, 3]
@@ -808,9 +687,77 @@ class _MelRows(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad):
-        sr, hr, row_t = ctx.saved_tensors
-        grad_rows = (grad.double() / len(ctx.tabs[3])).float().contiguous()
-        return _mel_backward(sr, hr, row_t, ctx.tabs, torch.zeros_like(sr), grad_rows=grad_rows), None, None, None
+        sr, hr, row_t, row_out = ctx.saved_tensors
+        grad_rows = (grad.double() / row_out.shape[0]).float().contiguous()
+        return None, _rows_loss_backward(ctx.loss, sr, hr, row_t, ctx.tabs, row_out, torch.zeros_like(sr),
+                                         grad_rows=grad_rows), None, None, None
+
+
+class _RowsLossMean(torch.autograd.Function):
+    """scale * the mean over the clips of a loss of the family as a node of the training step's loss family: a float32 [1] loss, the
+    constant factor inside, the upstream gradient read on the device.  Forward: loss.entry per resolution and mg_stft_loss_mean
+    (row_out has one layout).  Backward: the seeded entry point per resolution into an uninitialised buffer of sr's size -- the
+    pack is dense and every row is live at every resolution, so the first resolution writes every sample."""
+
+    @staticmethod
+    def forward(ctx, loss, sr, hr, row_t, tabs, scale):
+        row_out = _rows_loss_forward(loss, sr, hr, row_t, tabs)
+        out = torch.empty(1, dtype=torch.float32, device=sr.device)
+        _lib.check(_lib.load().mg_stft_loss_mean(_lib.ptr(row_out), row_out.shape[1], row_out.shape[0], scale, _lib.ptr(out),
+                                                 _lib.stream()), "mg_stft_loss_mean")
+        ctx.save_for_backward(sr, hr, row_t, row_out)
+        ctx.loss, ctx.tabs, ctx.scale = loss, tabs, scale
+        return out.reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        sr, hr, row_t, row_out = ctx.saved_tensors
+        go = go.reshape(1).float().contiguous()
+        return None, _rows_loss_backward(ctx.loss, sr, hr, row_t, ctx.tabs, row_out, torch.empty_like(sr), go=go,
+                                         scale=ctx.scale), None, None, None, None
+
+
+def _rows_loss_dense(loss, sr_audio, hr_audio, resolutions, params=()):
+    """The dense-batch losses' operands: both batches as packs read in place, the tables kept under the geometry."""
+    hrs, srs, B, T = _dense_pack(sr_audio, hr_audio)
+    res = loss.parse(resolutions)
+    key = (loss.entry, B, T, res) + tuple(None if p is None else float(p) for p in params) + (str(sr_audio.device),)
+    return _rows_loss_operands(loss, hrs, srs, res, True, params, key)
+
+
+def mrstft_many(hrs, srs, resolutions=STFT_RESOLUTIONS, center=True):
+    """The multi-resolution STFT loss of every utterance on its own, differentiable in sr -> float64 device tensor [U].  For one
+    resolution (n_fft, hop) -- periodic Hann window of n_fft samples, centred frames reflected at the utterance's own ends, K =
+    n_fft / 2 + 1 bins, F_u frames, m = sqrt(max(re^2 + im^2, 1e-7)) --
+        loss_u = sqrt(sum (m_hr - m_sr)^2 / sum m_hr^2) + sum |ln m_hr - ln m_sr| / (F_u K)
+    with the sums over all frames and bins of utterance u, and the result is the mean over the resolutions.  Operand forms as for
+    ``lsd_many``: lists of waveforms, or packed ``(buffer, starts, lengths)`` / ``(buffer, starts[, lengths])`` read where they
+    lie.  Two library launches per resolution forward and two backward, whatever U is (csrc/stft_loss_rows.hip), plus the
+    element-wise launches on [U] that join the resolutions (a copy, R - 1 adds, a divide; backward: a divide, a cast and the zero
+    fill); deterministic; nothing is read back.  The gradient is exactly 0 where autograd through torch.stft has NaN or Inf: sr == hr, silence, clamped bins.  hr
+    is a constant: a ground truth that requires grad raises NotImplementedError.  ValueError (naming utterance and resolution)
+    for an utterance that cannot be reflected at a resolution, len <= n_fft / 2."""
+    return _RowsLossRows.apply(*_rows_loss_operands(_MRSTFT, hrs, srs, resolutions, center))
+
+
+def mrstft_loss(sr_audio, hr_audio, resolutions=STFT_RESOLUTIONS):
+    """``mrstft_many`` of a dense batch as a training loss -> 0-dim float64 tensor, the mean over the clips, differentiable in
+    sr_audio.  sr_audio / hr_audio: float32 device tensors [B, T], [B, 1, T] or [B, 1, 1, T], read in place (no packing copy).
+    The tables of a geometry are uploaded once and kept, so forward + backward capture into a graph on one stream after one
+    eager call (lsd_loss's note on live graphs from other streams applies)."""
+    return _RowsLossRows.apply(*_rows_loss_dense(_MRSTFT, sr_audio, hr_audio, resolutions)).mean()
+
+
+def mrstft_loss_term(sr_audio, hr_audio, scale, resolutions=STFT_RESOLUTIONS):
+    """``scale * mrstft_loss(sr_audio, hr_audio, resolutions)`` as a term of the training step -> 0-dim float32 tensor,
+    differentiable in sr_audio: mrstft_loss's operand forms, checks and cached tables, but one autograd node in the step's loss
+    convention (functional._LossFn).  Forward is mg_stft_loss_rows per resolution plus one reduction launch; backward is
+    mg_stft_loss_rows_backward_seeded per resolution, which forms every clip's upstream gradient in the kernel, in double, from the
+    upstream scalar -- the GradScaler's loss scale in a --fp16 step stays on the device and is read when the kernel runs, so a
+    captured step follows it -- and writes every sample, so no buffer is zero-filled.  Capturable after one eager call."""
+    scale = _finite_scale(scale)
+    return _RowsLossMean.apply(*_rows_loss_dense(_MRSTFT, sr_audio, hr_audio, resolutions), scale)
 
 
 def mel_many(hrs, srs, sample_rate, resolutions=MEL_RESOLUTIONS, center=True, f_min=0.0, f_max=None):
@@ -827,13 +774,7 @@ def mel_many(hrs, srs, sample_rate, resolutions=MEL_RESOLUTIONS, center=True, f_
     hr, silence, clamped bins, filters under the floor.  hr is a constant: a ground truth that requires grad raises
     NotImplementedError.  ValueError (naming utterance and resolution) for an utterance that cannot be reflected at a resolution,
     len <= n_fft / 2, and (naming resolution and filter) for a filterbank with an empty filter."""
-    return _MelRows.apply(*_mel_operands(hrs, srs, sample_rate, resolutions, center, f_min, f_max))
-
-
-def _mel_dense(sr_audio, hr_audio, sample_rate, resolutions):
-    hrs, srs, B, T = _dense_pack(sr_audio, hr_audio)
-    res = _mel_resolutions(resolutions)
-    return _mel_operands(hrs, srs, sample_rate, res, True, 0.0, None, (B, T, res, float(sample_rate), str(sr_audio.device)))
+    return _RowsLossRows.apply(*_rows_loss_operands(_MEL, hrs, srs, resolutions, center, (sample_rate, f_min, f_max)))
 
 
 def mel_loss(sr_audio, hr_audio, sample_rate, resolutions=MEL_RESOLUTIONS):
@@ -841,31 +782,7 @@ def mel_loss(sr_audio, hr_audio, sample_rate, resolutions=MEL_RESOLUTIONS):
     sr_audio.  sr_audio / hr_audio: float32 device tensors [B, T], [B, 1, T] or [B, 1, 1, T], read in place (no packing copy).
     The tables of a geometry are uploaded once and kept, so forward + backward capture into a graph on one stream after one
     eager call (lsd_loss's note on live graphs from other streams applies)."""
-    return _MelRows.apply(*_mel_dense(sr_audio, hr_audio, sample_rate, resolutions)).mean()
-
-
-class _MelMeanLoss(torch.autograd.Function):
-    """scale * the mean over the clips of the mel loss as a node of the training step's loss family: a float32 [1] loss, the
-    constant factor inside, the upstream gradient read on the device.  Forward: mg_mel_loss_rows per resolution and
-    mg_stft_loss_mean (row_out has its layout).  Backward: mg_mel_loss_rows_backward_seeded per resolution into an uninitialised
-    buffer of sr's size -- the pack is dense and every row is live at every resolution, so the first resolution writes every sample."""
-
-    @staticmethod
-    def forward(ctx, sr, hr, row_t, tabs, scale):
-        row_out = _mel_forward(sr, hr, row_t, tabs)
-        loss = torch.empty(1, dtype=torch.float32, device=sr.device)
-        _lib.check(_lib.load().mg_stft_loss_mean(_lib.ptr(row_out), row_out.shape[1], row_out.shape[0], scale, _lib.ptr(loss),
-                                                 _lib.stream()), "mg_stft_loss_mean")
-        ctx.save_for_backward(sr, hr, row_t)
-        ctx.tabs, ctx.scale = tabs, scale
-        return loss.reshape(())
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, go):
-        sr, hr, row_t = ctx.saved_tensors
-        go = go.reshape(1).float().contiguous()
-        return _mel_backward(sr, hr, row_t, ctx.tabs, torch.empty_like(sr), go=go, scale=ctx.scale), None, None, None, None
+    return _RowsLossRows.apply(*_rows_loss_dense(_MEL, sr_audio, hr_audio, resolutions, (sample_rate, 0.0, None))).mean()
 
 
 def mel_loss_term(sr_audio, hr_audio, sample_rate, scale, resolutions=MEL_RESOLUTIONS):
@@ -876,11 +793,8 @@ def mel_loss_term(sr_audio, hr_audio, sample_rate, scale, resolutions=MEL_RESOLU
     scalar -- in the arithmetic autograd performs for ``scale * mel_loss``, so a power-of-two scale gives that gradient bit for bit;
     the GradScaler's loss scale in a --fp16 step stays on the device and is read when the kernel runs, so a captured step follows
     it -- and writes every sample, so no buffer is zero-filled.  Capturable after one eager call."""
-    scale = float(scale)
-    if not math.isfinite(scale):
-        raise ValueError("scale must be finite")
-    sr, hr, row_t, tabs = _mel_dense(sr_audio, hr_audio, sample_rate, resolutions)
-    return _MelMeanLoss.apply(sr, hr, row_t, tabs, scale)
+    scale = _finite_scale(scale)
+    return _RowsLossMean.apply(*_rows_loss_dense(_MEL, sr_audio, hr_audio, resolutions, (sample_rate, 0.0, None)), scale)
 
 
 def eval_model(model, eval_batches, opt, eval_path=None):

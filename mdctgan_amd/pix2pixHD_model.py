@@ -286,6 +286,38 @@ class BaseModel(torch.nn.Module):
             network.load_state_dict(usable, strict=False)
 
 
+# The audio-domain terms of the generator's loss in their order among the losses: (loss name, option, how the step calls the term:
+# the metrics module, the options, decoded waveform, ground truth, weight).  loss_names, the terms of _forward, their sum into
+# loss_G and the flag that an error names all follow this table.
+_AUDIO_TERMS = (
+    ("G_lsd", "lambda_lsd", lambda M, opt, sr, hr, lam: M.lsd_loss_term(sr, hr, opt, lam)),
+    ("G_mrstft", "lambda_mrstft", lambda M, opt, sr, hr, lam: M.mrstft_loss_term(sr, hr, lam)),
+    ("G_mel", "lambda_mel", lambda M, opt, sr, hr, lam: M.mel_loss_term(sr, hr, opt.hr_sampling_rate, lam)),
+)
+
+
+def _audio_lambda(opt, option, preprocess, plan=None, resolutions=None) -> float:
+    """The refusals the three --lambda_* options share -> the weight (0.0: the term is off).  plan / resolutions: a term with
+    transforms of its own refuses a --segment_length whose decoded clips its largest resolution cannot reflect-pad."""
+    lam = float(getattr(opt, option, 0.0))
+    if not lam >= 0.0:
+        raise ValueError("--%s must not be negative (got %r)" % (option, lam))
+    if lam == 0.0:
+        return 0.0
+    if not preprocess._in_kernel:
+        raise NotImplementedError("--%s: to_audio has no backward for the dB and explicit-encoding codecs "
+                                  "(train with --arcsinh_transform or --raw_mdct)" % option)
+    if plan is not None:
+        n = preprocess.audio_length(int(opt.segment_length))
+        try:
+            plan([n], resolutions, True)
+        except ValueError as e:
+            raise ValueError("--%s: a --segment_length of %d decodes to clips of %d samples, which the largest resolution "
+                             "cannot reflect-pad (more than %d are needed): %s"
+                             % (option, opt.segment_length, n, max(r[0] for r in resolutions) // 2, e)) from None
+    return lam
+
+
 class Pix2PixHDModel(BaseModel):
     def name(self):
         return "Pix2PixHDModel"
@@ -332,9 +364,8 @@ class Pix2PixHDModel(BaseModel):
             self.old_lr = opt.lr
             self.limit_aux_loss = False
             self.criterionGAN = networks.GANLoss(use_lsgan=not opt.no_lsgan, device=self.device)
-            self.loss_names = (["G_GAN"] + ([] if opt.no_ganFeat_loss else ["G_GAN_Feat"]) + (["G_lsd"] if self.lambda_lsd > 0 else [])
-                               + (["G_mrstft"] if self.lambda_mrstft > 0 else []) + (["G_mel"] if self.lambda_mel > 0 else [])
-                               + ["D_real", "D_fake"])
+            self.loss_names = (["G_GAN"] + ([] if opt.no_ganFeat_loss else ["G_GAN_Feat"])
+                               + [name for name, option, _ in _AUDIO_TERMS if getattr(self, option) > 0] + ["D_real", "D_fake"])
             if opt.niter_fix_global > 0:
                 params = [v for k, v in self.netG.named_parameters()
                           if k.startswith("model" + str(opt.n_local_enhancers))]
@@ -358,14 +389,9 @@ class Pix2PixHDModel(BaseModel):
     def _check_lambda_lsd(self, opt) -> float:
         """--lambda_lsd: what the term cannot serve is refused here, not at the first backward pass."""
         from .metrics import LSD_ROWS_N_FFT
-        lam = float(getattr(opt, "lambda_lsd", 0.0))
-        if not lam >= 0.0:
-            raise ValueError("--lambda_lsd must not be negative (got %r)" % lam)
+        lam = _audio_lambda(opt, "lambda_lsd", self.preprocess)
         if lam == 0.0:
             return 0.0
-        if not self.preprocess._in_kernel:
-            raise NotImplementedError("--lambda_lsd: to_audio has no backward for the dB and explicit-encoding codecs "
-                                      "(train with --arcsinh_transform or --raw_mdct)")
         if opt.win_length != opt.n_fft:
             raise NotImplementedError("--lambda_lsd needs win_length == n_fft (got %d and %d)" % (opt.win_length, opt.n_fft))
         if 2 * opt.n_fft not in LSD_ROWS_N_FFT:
@@ -377,42 +403,15 @@ class Pix2PixHDModel(BaseModel):
         """--lambda_mrstft: what the term cannot serve is refused here, not at the first backward pass.  Unlike --lambda_lsd the term
         has its own transforms (metrics.STFT_RESOLUTIONS): it does not depend on the codec's n_fft."""
         from .metrics import STFT_RESOLUTIONS, plan_mrstft
-        lam = float(getattr(opt, "lambda_mrstft", 0.0))
-        if not lam >= 0.0:
-            raise ValueError("--lambda_mrstft must not be negative (got %r)" % lam)
-        if lam == 0.0:
-            return 0.0
-        if not self.preprocess._in_kernel:
-            raise NotImplementedError("--lambda_mrstft: to_audio has no backward for the dB and explicit-encoding codecs "
-                                      "(train with --arcsinh_transform or --raw_mdct)")
-        n = self.preprocess.audio_length(int(opt.segment_length))
-        try:
-            plan_mrstft([n], STFT_RESOLUTIONS, True)
-        except ValueError as e:
-            raise ValueError("--lambda_mrstft: a --segment_length of %d decodes to clips of %d samples, which the largest resolution "
-                             "cannot reflect-pad (more than %d are needed): %s"
-                             % (opt.segment_length, n, max(r[0] for r in STFT_RESOLUTIONS) // 2, e)) from None
-        return lam
+        return _audio_lambda(opt, "lambda_mrstft", self.preprocess, plan_mrstft, STFT_RESOLUTIONS)
 
     def _check_lambda_mel(self, opt) -> float:
         """--lambda_mel: what the term cannot serve is refused here, not at the first backward pass.  Like --lambda_mrstft the term has
         its own transforms (metrics.MEL_RESOLUTIONS); its filterbanks are those of opt.hr_sampling_rate, the rate of the decoded clip."""
         from .metrics import MEL_RESOLUTIONS, _mel_banks, plan_mel
-        lam = float(getattr(opt, "lambda_mel", 0.0))
-        if not lam >= 0.0:
-            raise ValueError("--lambda_mel must not be negative (got %r)" % lam)
+        lam = _audio_lambda(opt, "lambda_mel", self.preprocess, plan_mel, MEL_RESOLUTIONS)
         if lam == 0.0:
             return 0.0
-        if not self.preprocess._in_kernel:
-            raise NotImplementedError("--lambda_mel: to_audio has no backward for the dB and explicit-encoding codecs "
-                                      "(train with --arcsinh_transform or --raw_mdct)")
-        n = self.preprocess.audio_length(int(opt.segment_length))
-        try:
-            plan_mel([n], MEL_RESOLUTIONS, True)
-        except ValueError as e:
-            raise ValueError("--lambda_mel: a --segment_length of %d decodes to clips of %d samples, which the largest resolution "
-                             "cannot reflect-pad (more than %d are needed): %s"
-                             % (opt.segment_length, n, max(r[0] for r in MEL_RESOLUTIONS) // 2, e)) from None
         try:
             _mel_banks(MEL_RESOLUTIONS, opt.hr_sampling_rate, 0.0, None)
         except ValueError as e:
@@ -420,16 +419,8 @@ class Pix2PixHDModel(BaseModel):
         return lam
 
     def loss_filter(self, g_gan, g_gan_feat, d_real, d_fake, g_lsd=None, g_mrstft=None, g_mel=None):
-        out = [g_gan]
-        if not self.no_ganFeat_loss:
-            out.append(g_gan_feat)
-        if g_lsd is not None:
-            out.append(g_lsd)
-        if g_mrstft is not None:
-            out.append(g_mrstft)
-        if g_mel is not None:
-            out.append(g_mel)
-        return out + [d_real, d_fake]
+        out = [g_gan] if self.no_ganFeat_loss else [g_gan, g_gan_feat]
+        return out + [t for t in (g_lsd, g_mrstft, g_mel) if t is not None] + [d_real, d_fake]
 
     # -- forward --------------------------------------------------------------------------------
     def _two_channel(self, spectro):
@@ -463,13 +454,10 @@ class Pix2PixHDModel(BaseModel):
         after it, the multi-resolution STFT loss of the same decoded waveform times lambda_mrstft (metrics.mrstft_loss_term), and
         --lambda_mel > 0 G_mel after that, its multi-scale mel-spectrogram L1 to hr_audio at opt.hr_sampling_rate times lambda_mel
         (metrics.mel_loss_term).  Whatever combination of the three is on, to_audio runs once."""
-        lsd = self.isTrain and self.lambda_lsd > 0
-        mrstft = self.isTrain and self.lambda_mrstft > 0
-        mel = self.isTrain and self.lambda_mel > 0
-        if (lsd or mrstft or mel) and int(hr_audio.shape[-1]) != self.preprocess.audio_length(lr_audio.shape[-1]):
-            raise ValueError("%s: hr_audio has %d samples per clip, to_audio returns %d for this lr_audio"
-                             % ("--lambda_lsd" if lsd else "--lambda_mrstft" if mrstft else "--lambda_mel", hr_audio.shape[-1],
-                                self.preprocess.audio_length(lr_audio.shape[-1])))
+        terms = [t for t in _AUDIO_TERMS if self.isTrain and getattr(self, t[1]) > 0]
+        if terms and int(hr_audio.shape[-1]) != self.preprocess.audio_length(lr_audio.shape[-1]):
+            raise ValueError("--%s: hr_audio has %d samples per clip, to_audio returns %d for this lr_audio"
+                             % (terms[0][1], hr_audio.shape[-1], self.preprocess.audio_length(lr_audio.shape[-1])))
         sr_spectro, _, hr_spectro, _, hr_norm_param, lr_spectro, _, lr_norm_param = self.forward(lr_audio, hr_audio)
         pooled = self.isTrain and getattr(self.opt, "pool_size", 0) > 0     # the fake pass of the D loss sees the history
         stacked = (self.stack_d_loss_passes and self.abs_spectro and self.arcsinh_transform and not pooled
@@ -519,21 +507,17 @@ class Pix2PixHDModel(BaseModel):
                     for j in range(len(pred_fake[i]) - 1):
                         loss_G_GAN_Feat = loss_G_GAN_Feat + Fh.l1_loss(
                             pred_fake[i][j], pred_real[i][j].detach(), D_weights * feat_weights * self.lambda_feat)
-        loss_G_lsd = loss_G_mrstft = loss_G_mel = None
-        if lsd or mrstft or mel:
-            from .metrics import lsd_loss_term, mel_loss_term, mrstft_loss_term
+        audio = {}                                                          # loss_filter's g_lsd, g_mrstft, g_mel
+        if terms:
             # (the generator's output is float32 under --fp16 as well: autocast changes the convolutions' arithmetic, not the tensors)
             spec = sr_spectro if sr_spectro.dtype == torch.float32 and sr_spectro.is_contiguous() else sr_spectro.float().contiguous()
             sr_audio = self.preprocess.to_audio(spec, lr_norm_param)       # once: every term reads the one decoded waveform
-            if lsd:
-                loss_G_lsd = lsd_loss_term(sr_audio, hr_audio.detach(), self.opt, self.lambda_lsd)
-            if mrstft:
-                loss_G_mrstft = mrstft_loss_term(sr_audio, hr_audio.detach(), self.lambda_mrstft)
-            if mel:
-                loss_G_mel = mel_loss_term(sr_audio, hr_audio.detach(), self.opt.hr_sampling_rate, self.lambda_mel)
+            from . import metrics
+            for name, option, term in terms:
+                audio[name.lower()] = term(metrics, self.opt, sr_audio, hr_audio.detach(), getattr(self, option))
         # visuals are materialised lazily (the reference copies three tensors to the host every step)
         self._visual_src = (lr_spectro, sr_spectro.detach(), hr_spectro, lr_norm_param, hr_norm_param)
-        return [self.loss_filter(loss_G_GAN, loss_G_GAN_Feat, loss_D_real, loss_D_fake, loss_G_lsd, loss_G_mrstft, loss_G_mel),
+        return [self.loss_filter(loss_G_GAN, loss_G_GAN_Feat, loss_D_real, loss_D_fake, **audio),
                 torch.empty if not infer else sr_spectro]
 
     def optimize_parameters(self, lr_audio, hr_audio):
@@ -549,12 +533,9 @@ class Pix2PixHDModel(BaseModel):
         # 2 ones_like fills per iteration)
         loss_D = loss_dict["D_fake"] + loss_dict["D_real"]
         loss_G = loss_dict["G_GAN"] + loss_dict["G_GAN_Feat"] if "G_GAN_Feat" in loss_dict else loss_dict["G_GAN"]
-        if "G_lsd" in loss_dict:      # its gradient joins the discriminator's at sr_spectro by autograd's accumulation: one float32 add
-            loss_G = loss_G + loss_dict["G_lsd"]
-        if "G_mrstft" in loss_dict:   # (likewise; with both terms their gradients join at the decoded waveform first)
-            loss_G = loss_G + loss_dict["G_mrstft"]
-        if "G_mel" in loss_dict:
-            loss_G = loss_G + loss_dict["G_mel"]
+        for name, _, _ in _AUDIO_TERMS:     # a term's gradient joins the discriminator's at sr_spectro by autograd's accumulation: one
+            if name in loss_dict:           # float32 add; with several terms their gradients join at the decoded waveform first
+                loss_G = loss_G + loss_dict[name]
         red = getattr(self, "reducers", None)      # data-parallel gradient reducers (mdctgan_amd.ddp.attach)
         sc = self.scaler                           # train.py:183-199: one GradScaler, updated once per iteration
         seed_G, seed_D = self._backward_seeds(sc, loss_D.device)
