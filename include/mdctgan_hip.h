@@ -268,6 +268,39 @@ int mg_train_pair_rows(const float* corpus, long long corpus_total, const mg_tra
                        const mg_resample_bank* to_hr, const mg_resample_bank* to_lr, const mg_resample_bank* lr_to_hr, float* lr,
                        float* hr, long long out_rows, float* lr_full, long long lr_full_total, long long max_full_len,
                        void* stream);
+/*   mg_train_hr_rows / mg_train_lr_rows   the two legs of mg_train_pair_rows as entry points of their own: the same kernels on the
+ *                       same grids, hence the same bits, lr_full included.  For a batch whose low-rate leg reads another buffer
+ *                       than its high-rate leg (the low-pass augmentation below filters the windows into a scratch buffer first):
+ *                       neither leg is computed twice.  Arguments and refusals as in mg_train_pair_rows. */
+int mg_train_hr_rows(const float* corpus, long long corpus_total, const mg_train_row* rows, int n_rows, int seg_len,
+                     const mg_resample_bank* to_hr, float* hr, long long out_rows, void* stream);
+int mg_train_lr_rows(const float* corpus, long long corpus_total, const mg_train_row* rows, int n_rows, int seg_len,
+                     const mg_resample_bank* to_lr, const mg_resample_bank* lr_to_hr, float* lr, long long out_rows, float* lr_full,
+                     long long lr_full_total, long long max_full_len, void* stream);
+
+/* Low-pass rows (csrc/sos_rows.hip): an IIR filter given as a cascade of second-order sections over the rows of a packed buffer,
+ * one pass or forward-backward (zero phase) -- a different anti-aliasing filter per training example before the rate change
+ * (lowpass.py designs Butterworth and Chebyshev-I filters; not in the reference).
+ *   mg_sos_row    the row reads x[in_pos, in_pos + len) and writes out[out_pos, out_pos + len); len == 0 marks a dead row.
+ *   sos           double [n_rows][MG_SOS_MAX_SECTIONS][6] on the device: b0 b1 b2 a0 a1 a2 per section, a0 == 1 (it is not
+ *                 read); an unused section is the identity 1 0 0 1 0 0.  The caller checks stability (|a2| < 1, |a1| < 1 + a2).
+ *   mg_sos_rows   y = cascade(x) from a zero state in double; zero_phase != 0: then the cascade again, from a zero state, over the
+ *                 reversed result, the value in between kept in double -- sosfilt(sos, sosfilt(sos, x)[::-1])[::-1] in float64,
+ *                 rounded to float32 once.  The signal is zero outside the row's window (cut to x); every store is guarded.
+ *                 Parallel inside a row: chunks of MG_SOS_CHUNK samples, counted from the row's first sample (from its last in the
+ *                 reverse pass), each run from a zero state; the true start states are carried along the row in ascending chunk
+ *                 order with the chunk transition matrix (taken on the device from zero-input runs); the chunks are run again
+ *                 from them.  No atomics, every sum has one fixed order: a row has the same bits alone as inside any pack, in any
+ *                 order, run to run.  3 launches (6 with zero_phase) whatever n_rows is; static LDS, no host synchronisation.
+ *                 max_len: the longest row (at most 2^30); longer rows are dropped.  workspace: mg_sos_rows_workspace(n_rows,
+ *                 max_len) bytes, 8-byte aligned (0: invalid arguments).  MG_ERR_ARG before any launch: a null pointer, n_rows,
+ *                 x_total, out_total or max_len <= 0, a short workspace, out overlapping x. */
+#define MG_SOS_MAX_SECTIONS 6
+#define MG_SOS_CHUNK 256
+typedef struct { long long in_pos, len, out_pos; } mg_sos_row;
+size_t mg_sos_rows_workspace(int n_rows, long long max_len);
+int mg_sos_rows(const float* x, long long x_total, const mg_sos_row* rows, const double* sos, int n_rows, long long max_len,
+                int zero_phase, float* out, long long out_total, void* workspace, size_t workspace_bytes, void* stream);
 
 /* F2  util/util.py:132-177 compute_matrics on the device (train.py:104-134 eval_model, generate_audio.py:60).
  *   mg_metrics_rows   out[b] = {sum hr^2, sum (sr - hr)^2, sum (lr - hr)^2} (double) for clips [B, T]  -> MSE / SNR

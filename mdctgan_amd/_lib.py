@@ -119,6 +119,10 @@ SIGNATURES = {
     "mg_rows_moments": (_i, [_p, _ll, _p, _i, _ll, _p, _p, _sz, _p]),
     "mg_add_noise_rows": (_i, [_p, _p, _ll, _p, _i, _ll, _p, _p, C.c_double, _ll, _p]),
     "mg_train_pair_rows": (_i, [_p, _ll, _p, _i, _i, _RB, _RB, _RB, _p, _p, _ll, _p, _ll, _ll, _p]),
+    "mg_train_hr_rows": (_i, [_p, _ll, _p, _i, _i, _RB, _p, _ll, _p]),
+    "mg_train_lr_rows": (_i, [_p, _ll, _p, _i, _i, _RB, _RB, _p, _ll, _p, _ll, _ll, _p]),
+    "mg_sos_rows_workspace": (_sz, [_i, _ll]),
+    "mg_sos_rows": (_i, [_p, _ll, _p, _p, _i, _ll, _i, _p, _ll, _p, _sz, _p]),
     "mg_metrics_rows":(_i, [_p, _p, _p, _i, _i, _p, _p]),
     "mg_stft_num_frames": (_i, [_i, _i, _i, _i]),
     "mg_stft_frames": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p]),

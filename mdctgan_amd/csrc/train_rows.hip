@@ -175,25 +175,15 @@ inline int tile_for(const Bank& up) {
     return (int)(t < kTile ? t : kTile);
 }
 
-}  // namespace
+// The two legs' checks and launches, shared by the three entry points below
+inline bool pair_args_ok(const float* corpus, long long corpus_total, const mg_train_row* rows, int n_rows, int seg_len,
+                         long long out_rows) {
+    return corpus && rows && n_rows > 0 && seg_len > 0 && seg_len <= kMaxLen && corpus_total > 0 && out_rows > 0 &&
+           out_rows <= LLONG_MAX / seg_len;
+}
 
-extern "C" {
-
-// See include/mdctgan_hip.h.
-int mg_train_pair_rows(const float* corpus, long long corpus_total, const mg_train_row* rows, int n_rows, int seg_len,
-                       const mg_resample_bank* to_hr, const mg_resample_bank* to_lr, const mg_resample_bank* lr_to_hr, float* lr,
-                       float* hr, long long out_rows, float* lr_full, long long lr_full_total, long long max_full_len,
-                       void* stream) {
-    if (!corpus || !rows || !hr || n_rows <= 0 || seg_len <= 0 || seg_len > kMaxLen || corpus_total <= 0 || out_rows <= 0)
-        return MG_ERR_ARG;
-    if (!bank_ok(to_hr) || !bank_ok(to_lr) || !bank_ok(lr_to_hr)) return MG_ERR_ARG;
-    if (lr_full ? (lr_full_total <= 0 || max_full_len <= 0) : !lr) return MG_ERR_ARG;
-    if (out_rows > LLONG_MAX / seg_len) return MG_ERR_ARG;
-    const Bank bh = bank_of(to_hr), bd = bank_of(to_lr), bu = bank_of(lr_to_hr);
-    const int tile_len = tile_for(bu);
-    if (tile_len <= 0) return MG_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-
+int launch_hr(const float* corpus, long long corpus_total, const mg_train_row* rows, int n_rows, int seg_len, const Bank& bh,
+              float* hr, long long out_rows, hipStream_t st) {
     const dim3 gh = rows_grid(n_rows, seg_len, kThreads);
     if (bank_fits(bh))
         hipLaunchKernelGGL(train_hr_rows_kernel<true>, gh, dim3(kThreads), 0, st, corpus, corpus_total, rows, n_rows, seg_len, bh, hr,
@@ -202,7 +192,14 @@ int mg_train_pair_rows(const float* corpus, long long corpus_total, const mg_tra
         hipLaunchKernelGGL(train_hr_rows_kernel<false>, gh, dim3(kThreads), 0, st, corpus, corpus_total, rows, n_rows, seg_len, bh, hr,
                            out_rows);
     MG_CHECK_LAUNCH();
+    return MG_OK;
+}
 
+int launch_lr(const float* corpus, long long corpus_total, const mg_train_row* rows, int n_rows, int seg_len, const Bank& bd,
+              const Bank& bu, float* lr, long long out_rows, float* lr_full, long long lr_full_total, long long max_full_len,
+              hipStream_t st) {
+    const int tile_len = tile_for(bu);
+    if (tile_len <= 0) return MG_ERR_UNSUPPORTED;
     const dim3 gl = rows_grid(n_rows, lr_full ? max_full_len : (long long)seg_len, tile_len);
 #define MG_TL_LAUNCH(D, U, F)                                                                                                     \
     hipLaunchKernelGGL((train_lr_rows_kernel<D, U, F>), gl, dim3(kThreads), 0, st, corpus, corpus_total, rows, n_rows, seg_len, bd, \
@@ -217,6 +214,41 @@ int mg_train_pair_rows(const float* corpus, long long corpus_total, const mg_tra
 #undef MG_TL_LAUNCH
     MG_CHECK_LAUNCH();
     return MG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// See include/mdctgan_hip.h.
+int mg_train_pair_rows(const float* corpus, long long corpus_total, const mg_train_row* rows, int n_rows, int seg_len,
+                       const mg_resample_bank* to_hr, const mg_resample_bank* to_lr, const mg_resample_bank* lr_to_hr, float* lr,
+                       float* hr, long long out_rows, float* lr_full, long long lr_full_total, long long max_full_len,
+                       void* stream) {
+    if (!hr || !pair_args_ok(corpus, corpus_total, rows, n_rows, seg_len, out_rows)) return MG_ERR_ARG;
+    if (!bank_ok(to_hr) || !bank_ok(to_lr) || !bank_ok(lr_to_hr)) return MG_ERR_ARG;
+    if (lr_full ? (lr_full_total <= 0 || max_full_len <= 0) : !lr) return MG_ERR_ARG;
+    if (tile_for(bank_of(lr_to_hr)) <= 0) return MG_ERR_UNSUPPORTED;
+    const int rc = launch_hr(corpus, corpus_total, rows, n_rows, seg_len, bank_of(to_hr), hr, out_rows, (hipStream_t)stream);
+    if (rc != MG_OK) return rc;
+    return launch_lr(corpus, corpus_total, rows, n_rows, seg_len, bank_of(to_lr), bank_of(lr_to_hr), lr, out_rows, lr_full,
+                     lr_full_total, max_full_len, (hipStream_t)stream);
+}
+
+int mg_train_hr_rows(const float* corpus, long long corpus_total, const mg_train_row* rows, int n_rows, int seg_len,
+                     const mg_resample_bank* to_hr, float* hr, long long out_rows, void* stream) {
+    if (!hr || !pair_args_ok(corpus, corpus_total, rows, n_rows, seg_len, out_rows) || !bank_ok(to_hr)) return MG_ERR_ARG;
+    return launch_hr(corpus, corpus_total, rows, n_rows, seg_len, bank_of(to_hr), hr, out_rows, (hipStream_t)stream);
+}
+
+int mg_train_lr_rows(const float* corpus, long long corpus_total, const mg_train_row* rows, int n_rows, int seg_len,
+                     const mg_resample_bank* to_lr, const mg_resample_bank* lr_to_hr, float* lr, long long out_rows, float* lr_full,
+                     long long lr_full_total, long long max_full_len, void* stream) {
+    if (!pair_args_ok(corpus, corpus_total, rows, n_rows, seg_len, out_rows)) return MG_ERR_ARG;
+    if (!bank_ok(to_lr) || !bank_ok(lr_to_hr)) return MG_ERR_ARG;
+    if (lr_full ? (lr_full_total <= 0 || max_full_len <= 0) : !lr) return MG_ERR_ARG;
+    return launch_lr(corpus, corpus_total, rows, n_rows, seg_len, bank_of(to_lr), bank_of(lr_to_hr), lr, out_rows, lr_full,
+                     lr_full_total, max_full_len, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -97,13 +97,20 @@ def seg_pad_audio(waveform: torch.Tensor, segment_length: int) -> torch.Tensor:
 
 
 def make_training_pair(waveform: torch.Tensor, orig_sample_rate: int, hr_sampling_rate: int, lr_sampling_rate: int,
-                       segment_length: int, add_noise: bool = False, snr: float = 55.0, noise=None, generator=None):
+                       segment_length: int, add_noise: bool = False, snr: float = 55.0, noise=None, generator=None,
+                       lowpass_sos=None):
     """AudioDataset.__getitem__ (data/audio_dataset.py:66-82): HR = resample to hr_rate; LR = resample to lr_rate and back up to
     hr_rate, plus the noise of :72-78 under add_noise (on the full resampled waveform, before the crop; see add_noise); both
     cropped / padded to segment_length.  [B, L] -> (lr, hr).  The random file offset of readaudio (:43-48) and whole batches cut
-    from a corpus in HBM in shared launches: train_data.draw_windows / training_batch_many."""
+    from a corpus in HBM in shared launches: train_data.draw_windows / training_batch_many.
+    lowpass_sos (not in the reference; [n <= 6, 6] second-order sections at orig_sample_rate, lowpass.lowpass_sos): the LR leg
+    reads lowpass.lowpass_waveform(waveform, lowpass_sos), the zero-phase IIR low-pass of the waveform; HR is unchanged."""
     hr = resample(waveform, orig_sample_rate, hr_sampling_rate)
-    lr = resample(resample(waveform, orig_sample_rate, lr_sampling_rate), lr_sampling_rate, hr_sampling_rate)
+    src = waveform
+    if lowpass_sos is not None:
+        from .lowpass import lowpass_waveform
+        src = lowpass_waveform(waveform, lowpass_sos)
+    lr = resample(resample(src, orig_sample_rate, lr_sampling_rate), lr_sampling_rate, hr_sampling_rate)
     if add_noise:
         lr = add_noise_rows_of(lr, snr, segment_length, noise, generator, in_place=lr.data_ptr() != waveform.data_ptr())
     return seg_pad_audio(lr, segment_length), seg_pad_audio(hr, segment_length)
@@ -262,7 +269,9 @@ def plan_front_end(lengths, rates, hr_rate: int, lr_rate: int, is_lr_input: bool
 
 def data_options(opt) -> dict:
     """lr_sampling_rate, hr_sampling_rate and segment_length are required; is_lr_input / add_noise default to off, snr to 55,
-    gen_overlap to 0, batch_size to 64, out_segment_length to segment_length.  `opt`: an options namespace or a dict."""
+    gen_overlap to 0, batch_size to 64, out_segment_length to segment_length; lowpass_aug (a comma list of filter kinds, or a
+    sequence of them; empty: off) with lowpass_order / lowpass_ripple / lowpass_cutoff becomes `lowpass`, a lowpass.LowpassSpec or
+    None.  `opt`: an options namespace or a dict."""
     get = (lambda k, d=None: opt.get(k, d)) if isinstance(opt, dict) else (lambda k, d=None: getattr(opt, k, d))
     o = dict(lr_sampling_rate=get("lr_sampling_rate"), hr_sampling_rate=get("hr_sampling_rate"),
              segment_length=get("segment_length"), is_lr_input=bool(get("is_lr_input", False)),
@@ -271,6 +280,11 @@ def data_options(opt) -> dict:
     for k in ("lr_sampling_rate", "hr_sampling_rate", "segment_length"):
         if o[k] is None:
             raise ValueError("front_end_many needs %s" % k)
+    o["lowpass"] = None
+    if get("lowpass_aug", ""):
+        from .lowpass import spec_from_options
+        o["lowpass"] = spec_from_options(get("lowpass_aug"), get("lowpass_order", (2, 10)), get("lowpass_ripple", (0.01, 1.0)),
+                                         get("lowpass_cutoff", (0.9, 1.0)))
     return o
 
 

@@ -9,6 +9,8 @@ restated on the host (``crop_window``, ``draw_windows``): the same draws from th
 ``--add_noise`` the low-rate leg is written at full length first, because the reference takes the noise power over the waveform
 before the crop; ``mg_rows_moments`` (twice), ``mg_add_noise_rows`` and ``mg_segments_gather`` finish the batch.
 ``make_graphed_training_batch`` captures the launches once over a fixed-size table; a replay only copies a new table in.
+``lowpass=`` (or ``--lowpass_aug``; not in the reference) puts a different zero-phase IIR low-pass per row in front of the low-rate leg:
+``mg_sos_rows`` filters the B windows into a packed scratch buffer, ``mg_train_lr_rows`` reads that and ``mg_train_hr_rows`` the corpus.
 Decoding files stays outside: the caller hands over loaded waveforms.
 """
 from __future__ import annotations
@@ -20,12 +22,13 @@ import numpy as np
 import torch
 
 from . import _lib
+from .lowpass import MG_SOS_MAX_SECTIONS, LowpassSpec, check_sos, draw_lowpass, identity_sos, sos_rows, sos_table_bits
 from .packed import (PackedLayout, add_noise_packed, aligned_layout, check_table, noise_buffer, pack_waves, upload_tables,
                      window_table)
 from .resample import data_options, filter_bank, make_training_pair, resample, resample_length
 
 __all__ = ["TrainingCorpus", "TrainingBatchPlan", "pack_corpus", "crop_window", "draw_windows", "windows_at", "pair_lengths",
-           "plan_training_batch", "train_pair_rows", "training_batch_many", "make_graphed_training_batch",
+           "plan_training_batch", "train_pair_rows", "train_hr_rows", "train_lr_rows", "training_batch_many", "make_graphed_training_batch",
            "make_training_pair", "resample"]         # (the last two: resample.py's per-waveform path, the yardstick of every row)
 
 ROW_COLS = 5            # mg_train_row: in_pos, in_len, out_row, full_pos, full_len
@@ -201,25 +204,30 @@ def _bank(orig_freq: int, new_freq: int, device):
     return _lib.ResampleBank(kern.data_ptr() if (orig, new) != (1, 1) else None, orig, new, width)
 
 
+def _check_pair_args(what, corpus_buffer, table, L, dense, lr_full):
+    """The tensor checks the three leg wrappers share; dense: (tensor, name) of the [rows, L] outputs the call writes."""
+    n = check_table(table, ROW_COLS, what).shape[0]
+    if corpus_buffer.dtype != torch.float32 or not corpus_buffer.is_contiguous():
+        raise ValueError("%s: the corpus is a contiguous float32 buffer" % what)
+    for t, name in dense:
+        if t is None or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != L or not t.is_contiguous():
+            raise ValueError("%s: %s is a contiguous float32 [rows, %d] tensor" % (what, name, L))
+    if len({t.shape[0] for t, _ in dense}) > 1:
+        raise ValueError("%s: lr and hr have the same number of rows" % what)
+    if lr_full is not None and (lr_full.dtype != torch.float32 or not lr_full.is_contiguous()):
+        raise ValueError("%s: lr_full is a contiguous float32 buffer" % what)
+    return n
+
+
 def train_pair_rows(corpus_buffer: torch.Tensor, table: torch.Tensor, segment_length: int, file_rate: int, hr_rate: int,
                     lr_rate: int, hr: torch.Tensor, lr=None, lr_full=None, max_full_len: int = 0):
     """mg_train_pair_rows: every row of `table` (int64 [n, 5] on the device: in_pos, in_len, out_row, full_pos, full_len) reads its
     window of the packed corpus and writes row out_row of hr and lr ([rows, segment_length] float32) -- or, with lr_full (a packed
     float32 buffer), its whole low-rate signal to lr_full[full_pos : full_pos + full_len] in place of lr."""
     lib = _lib.load()
-    n = check_table(table, ROW_COLS, "train_pair_rows").shape[0]
     L = int(segment_length)
-    if corpus_buffer.dtype != torch.float32 or not corpus_buffer.is_contiguous():
-        raise ValueError("train_pair_rows: the corpus is a contiguous float32 buffer")
-    for t, name in ((hr, "hr"), (lr, "lr")):
-        if t is None and name == "lr" and lr_full is not None:
-            continue
-        if t is None or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != L or not t.is_contiguous():
-            raise ValueError("train_pair_rows: %s is a contiguous float32 [rows, %d] tensor" % (name, L))
-    if lr is not None and lr.shape[0] != hr.shape[0]:
-        raise ValueError("train_pair_rows: lr and hr have the same number of rows")
-    if lr_full is not None and (lr_full.dtype != torch.float32 or not lr_full.is_contiguous()):
-        raise ValueError("train_pair_rows: lr_full is a contiguous float32 buffer")
+    n = _check_pair_args("train_pair_rows", corpus_buffer, table, L,
+                          [(hr, "hr")] + ([(lr, "lr")] if lr is not None or lr_full is None else []), lr_full)
     dev = corpus_buffer.device
     to_hr, to_lr, up = _bank(file_rate, hr_rate, dev), _bank(file_rate, lr_rate, dev), _bank(lr_rate, hr_rate, dev)
     _lib.check(lib.mg_train_pair_rows(_lib.ptr(corpus_buffer), corpus_buffer.numel(), _lib.ptr(table), n, L, to_hr, to_lr, up,
@@ -227,6 +235,34 @@ def train_pair_rows(corpus_buffer: torch.Tensor, table: torch.Tensor, segment_le
                                       0 if lr_full is None else lr_full.numel(), int(max_full_len), _lib.stream()),
                "mg_train_pair_rows")
     return lr, hr
+
+
+def train_hr_rows(corpus_buffer: torch.Tensor, table: torch.Tensor, segment_length: int, file_rate: int, hr_rate: int,
+                  hr: torch.Tensor):
+    """mg_train_hr_rows: the high-rate leg of train_pair_rows alone (the same kernel, the same bits)."""
+    lib = _lib.load()
+    L = int(segment_length)
+    n = _check_pair_args("train_hr_rows", corpus_buffer, table, L, [(hr, "hr")], None)
+    _lib.check(lib.mg_train_hr_rows(_lib.ptr(corpus_buffer), corpus_buffer.numel(), _lib.ptr(table), n, L,
+                                    _bank(file_rate, hr_rate, corpus_buffer.device), _lib.ptr(hr), hr.shape[0], _lib.stream()),
+               "mg_train_hr_rows")
+    return hr
+
+
+def train_lr_rows(buffer: torch.Tensor, table: torch.Tensor, segment_length: int, file_rate: int, hr_rate: int, lr_rate: int,
+                  lr=None, lr_full=None, max_full_len: int = 0, out_rows=None):
+    """mg_train_lr_rows: the low-rate leg of train_pair_rows alone (the same kernel, the same bits, lr_full included), over any
+    packed buffer -- the low-passed windows of training_batch_many(lowpass=), say.  out_rows: the rows of the batch when lr is
+    None (with lr_full; default: the table's)."""
+    lib = _lib.load()
+    L = int(segment_length)
+    n = _check_pair_args("train_lr_rows", buffer, table, L, [(lr, "lr")] if lr is not None or lr_full is None else [], lr_full)
+    dev = buffer.device
+    _lib.check(lib.mg_train_lr_rows(_lib.ptr(buffer), buffer.numel(), _lib.ptr(table), n, L, _bank(file_rate, lr_rate, dev),
+                                    _bank(lr_rate, hr_rate, dev), _lib.ptr(lr), lr.shape[0] if lr is not None else int(out_rows or n),
+                                    _lib.ptr(lr_full), 0 if lr_full is None else lr_full.numel(), int(max_full_len),
+                                    _lib.stream()), "mg_train_lr_rows")
+    return lr if lr is not None else lr_full
 
 
 def _windows(corpus, idx, o, offsets, lengths, generator):
@@ -251,8 +287,37 @@ def _out_pair(out, B, L, device):
     return lr, hr
 
 
+def _lowpass_table(lowpass, corpus, idx, lr_rate, generator):
+    """The coefficient table float64 [B, 6, 6] of a batch: drawn from a LowpassSpec (after the window draws, from the same stream), or
+    the caller's, refused on the host when a section is unstable or not finite."""
+    if isinstance(lowpass, LowpassSpec):
+        return draw_lowpass([corpus.rates[i] for i in idx], lr_rate, lowpass, generator)
+    coef = check_sos(lowpass)
+    if coef.shape[0] != len(idx):
+        raise ValueError("lowpass: one [%d, 6] set of sections per batch row (%d rows, %d sets)"
+                         % (MG_SOS_MAX_SECTIONS, len(idx), coef.shape[0]))
+    return coef
+
+
+def _lowpass_rows(plan: TrainingBatchPlan, starts):
+    """Where the low-passed windows sit: batch row b is filtered from its corpus window into scratch[starts[b] : starts[b] + len].
+    -> (the mg_sos_row table int64 [plan.rows, 3] in batch-row order, rows past the batch dead; every group's mg_train_row table
+    with in_pos moved to the scratch buffer -- what the low-rate leg reads)."""
+    starts = np.asarray(starts, dtype=np.int64)
+    sos_tab = np.zeros((plan.rows, 3), dtype=np.int64)
+    moved = []
+    for g in plan.groups:
+        rows = g.rows.copy()
+        live = rows[:, 1] > 0
+        b = rows[live, 2]
+        sos_tab[b] = np.stack([rows[live, 0], rows[live, 1], starts[b]], axis=1)
+        rows[live, 0] = starts[b]
+        moved.append(rows)
+    return sos_tab, moved
+
+
 def training_batch_many(corpus: TrainingCorpus, indices, opt_or_kwargs, offsets=None, generator=None, noise=None, out=None,
-                        lengths=None, noise_generator=None):
+                        lengths=None, noise_generator=None, lowpass=None):
     """AudioDataset.readaudio + __getitem__ (data/audio_dataset.py:34-82) for the files `indices` of a packed corpus ->
     (lr, hr), each float32 [B, segment_length] on the corpus' device; row b is resample.make_training_pair on its window alone,
     bit for bit.  opt_or_kwargs: an options namespace or a dict with lr_sampling_rate, hr_sampling_rate, segment_length and
@@ -263,8 +328,14 @@ def training_batch_many(corpus: TrainingCorpus, indices, opt_or_kwargs, offsets=
     add_noise: `noise` is a list of one waveform per batch row of the row's full low-rate length (plan.lr_len; for tests: the
     reference draws from the CPU stream, which a device cannot reproduce), otherwise torch.randn(..., generator=noise_generator)
     on the device.
+    lowpass (default: the options' --lowpass_aug; not in the reference): a lowpass.LowpassSpec -- one filter per row is drawn
+    from the same CPU stream, after the windows -- or an explicit coefficient table float64 [B, 6, 6] (lowpass.pad_sos of
+    lowpass.lowpass_sos at the row's file rate).  Row b of lr is then make_training_pair(window_b, lowpass_sos=table[b]), bit for
+    bit; hr keeps its bits.  The noise of add_noise comes after the filter.
     Launches: one table copy and mg_train_pair_rows per distinct file rate; under add_noise also two mg_rows_moments,
-    mg_add_noise_rows and mg_segments_gather -- whatever the batch size.  Nothing is read back."""
+    mg_add_noise_rows and mg_segments_gather -- whatever the batch size.  With lowpass: the coefficients travel in the same copy,
+    mg_sos_rows (6 launches) filters all windows into a scratch buffer of aligned_layout, and every rate's mg_train_pair_rows
+    becomes mg_train_hr_rows over the corpus and mg_train_lr_rows over the scratch buffer.  Nothing is read back."""
     from .mdct import segments_gather
     o = data_options(opt_or_kwargs)
     L, hr_rate, lr_rate = int(o["segment_length"]), int(o["hr_sampling_rate"]), int(o["lr_sampling_rate"])
@@ -279,27 +350,48 @@ def training_batch_many(corpus: TrainingCorpus, indices, opt_or_kwargs, offsets=
             raise ValueError("add_noise: noise holds one waveform per batch row, of the lengths %s" % plan.lr_len)
     elif noise is not None:
         raise ValueError("noise= is for add_noise")
+    lowpass = o["lowpass"] if lowpass is None else lowpass
+    coef = None if lowpass is None else _lowpass_table(lowpass, corpus, idx, lr_rate, generator)
     lr, hr = _out_pair(out, B, L, dev)
 
     # every table in one copy: each group's rows, then under add_noise the windows of lr_full in batch order
     full = PackedLayout(plan.full_start, plan.lr_len, plan.full_total)
-    *group_rows, win = upload_tables([g.rows for g in plan.groups]
-                                     + [window_table(full.starts, full.lengths) if o["add_noise"] else []], dev)
+    win_part = [window_table(full.starts, full.lengths) if o["add_noise"] else []]
     lr_full = torch.empty(full.total, dtype=torch.float32, device=dev) if o["add_noise"] else None
-    for g, rows in zip(plan.groups, group_rows):
-        train_pair_rows(corpus.buffer, rows, L, g.file_rate, hr_rate, lr_rate, hr, None if o["add_noise"] else lr, lr_full,
-                        g.max_full_len)
+    if coef is None:
+        *group_rows, win = upload_tables([g.rows for g in plan.groups] + win_part, dev)
+        for g, rows in zip(plan.groups, group_rows):
+            train_pair_rows(corpus.buffer, rows, L, g.file_rate, hr_rate, lr_rate, hr, None if o["add_noise"] else lr, lr_full,
+                            g.max_full_len)
+    else:
+        # ... and with lowpass the scratch windows, the groups' rows over the scratch buffer and the coefficients
+        scratch = aligned_layout([int(n) for n in (lengths.tolist() if torch.is_tensor(lengths) else lengths)])
+        sos_tab, moved = _lowpass_rows(plan, scratch.starts)
+        n_g = len(plan.groups)
+        *tables, sos_dev, coef_dev, win = upload_tables([g.rows for g in plan.groups] + moved + [sos_tab, sos_table_bits(coef)]
+                                                        + win_part, dev)
+        filtered = torch.empty(scratch.total, dtype=torch.float32, device=dev)
+        sos_rows(corpus.buffer, sos_dev, coef_dev.view(torch.float64), out=filtered, max_len=max(scratch.lengths))
+        for g, rows, rows_lp in zip(plan.groups, tables[:n_g], tables[n_g:]):
+            train_hr_rows(corpus.buffer, rows, L, g.file_rate, hr_rate, hr)
+            train_lr_rows(filtered, rows_lp, L, g.file_rate, hr_rate, lr_rate, None if o["add_noise"] else lr, lr_full,
+                          g.max_full_len, out_rows=B)
     if o["add_noise"]:
         add_noise_packed(lr_full, win, max(plan.lr_len), o["snr"], L, noise_buffer(noise, full, dev, noise_generator))
         segments_gather(lr_full, win, L, out=lr)
     return lr, hr
 
 
-def make_graphed_training_batch(corpus: TrainingCorpus, batch: int, opt_or_kwargs):
+def make_graphed_training_batch(corpus: TrainingCorpus, batch: int, opt_or_kwargs, lowpass=None):
     """Capture the launches of training_batch_many once, over a table of `batch` rows, and return run(indices, offsets=None,
     generator=None, lengths=None) -> (lr, hr): it plans the windows on the host, copies the new table in and replays.  The
     returned tensors are the captured outputs, [batch, segment_length], rewritten by every replay; fewer than `batch` indices
     leave the remaining rows dead (they keep what they held).  The graph is a plain chain of two kernels.
+    lowpass (a lowpass.LowpassSpec; default: the options' --lowpass_aug): the six launches of mg_sos_rows join the chain in front of
+    mg_train_hr_rows and mg_train_lr_rows -- still a plain chain -- over a scratch buffer of `batch` aligned rows of segment_length
+    samples (a window of more frames is refused); run(...) draws the filters after the windows, or takes run(..., lowpass=table),
+    and copies windows and coefficients in one copy.  run.last_lowpass: the table of the last replay; run.filtered: the scratch
+    buffer, row b's low-passed window at aligned_layout([segment_length] * batch).starts[b]; run.workspace: mg_sos_rows' workspace.
     Defined for a corpus with ONE file rate (the launches of a capture are fixed; the row grouping of mixed rates is not);
     add_noise draws from a random stream inside the capture, which is out of scope."""
     o = data_options(opt_or_kwargs)
@@ -310,14 +402,35 @@ def make_graphed_training_batch(corpus: TrainingCorpus, batch: int, opt_or_kwarg
     batch = int(batch)
     if batch <= 0:
         raise ValueError("batch must be positive")
+    spec = o["lowpass"] if lowpass is None else lowpass
+    if spec is not None and not isinstance(spec, LowpassSpec):
+        raise ValueError("make_graphed_training_batch: lowpass is a LowpassSpec (an explicit table goes to run(..., lowpass=))")
     L, hr_rate, lr_rate = int(o["segment_length"]), int(o["hr_sampling_rate"]), int(o["lr_sampling_rate"])
     dev, rate = corpus.buffer.device, corpus.rates[0]
-    table = torch.zeros(batch, ROW_COLS, dtype=torch.int64, device=dev)              # all rows dead
     lr = torch.zeros(batch, L, dtype=torch.float32, device=dev)
     hr = torch.zeros(batch, L, dtype=torch.float32, device=dev)
+    if spec is None:
+        table = torch.zeros(batch, ROW_COLS, dtype=torch.int64, device=dev)          # all rows dead
 
-    def launch():
-        train_pair_rows(corpus.buffer, table, L, rate, hr_rate, lr_rate, hr, lr)
+        def launch():
+            train_pair_rows(corpus.buffer, table, L, rate, hr_rate, lr_rate, hr, lr)
+    else:
+        # one storage for every table of a replay: the rows over the corpus, the rows over the scratch buffer, the filter's rows
+        # and the coefficients (identity sections until the first replay)
+        shapes = [(batch, ROW_COLS), (batch, ROW_COLS), (batch, 3), (batch, MG_SOS_MAX_SECTIONS, 6)]
+        sizes = [int(np.prod(sh)) for sh in shapes]
+        storage = torch.zeros(sum(sizes), dtype=torch.int64, device=dev)
+        table, table_lp, sos_tab, coef_bits = (storage[e - n:e].view(sh) for sh, n, e in zip(shapes, sizes, np.cumsum(sizes)))
+        coef = coef_bits.view(torch.float64)
+        coef.copy_(torch.from_numpy(np.broadcast_to(identity_sos(), shapes[3]).copy()))
+        scratch = aligned_layout([L] * batch)
+        filtered = torch.zeros(scratch.total, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.load().mg_sos_rows_workspace(batch, L), dtype=torch.uint8, device=dev)
+
+        def launch():
+            sos_rows(corpus.buffer, sos_tab, coef, out=filtered, max_len=L, workspace=ws)
+            train_hr_rows(corpus.buffer, table, L, rate, hr_rate, hr)
+            train_lr_rows(filtered, table_lp, L, rate, hr_rate, lr_rate, lr)
     side = torch.cuda.Stream(device=dev)
     side.wait_stream(torch.cuda.current_stream(dev))
     with torch.cuda.stream(side):
@@ -328,14 +441,29 @@ def make_graphed_training_batch(corpus: TrainingCorpus, batch: int, opt_or_kwarg
     with torch.cuda.graph(graph):
         launch()
 
-    def run(indices, offsets=None, generator=None, lengths=None):
+    def run(indices, offsets=None, generator=None, lengths=None, lowpass=None):
         idx = _indices(corpus, indices)
         if len(idx) > batch:
             raise ValueError("the capture holds %d rows, got %d indices" % (batch, len(idx)))
         offs, lens = _windows(corpus, idx, o, offsets, lengths, generator)
         plan = plan_training_batch(corpus, idx, offs, lens, L, hr_rate, lr_rate, pad_to=batch)
-        table.copy_(torch.from_numpy(plan.table()))
+        if spec is None:
+            if lowpass is not None:
+                raise ValueError("this capture was made without lowpass")
+            table.copy_(torch.from_numpy(plan.table()))
+        else:
+            if max(int(n) for n in (lens.tolist() if torch.is_tensor(lens) else lens)) > L:
+                raise ValueError("a window of more than segment_length (%d) frames does not fit the captured scratch buffer" % L)
+            picked = _lowpass_table(spec if lowpass is None else lowpass, corpus, idx, lr_rate, generator)
+            rows_f, (rows_lp,) = _lowpass_rows(plan, scratch.starts)
+            full = np.broadcast_to(identity_sos(), shapes[3]).copy()
+            full[:len(idx)] = picked
+            storage.copy_(torch.from_numpy(np.concatenate([plan.table().reshape(-1), rows_lp.reshape(-1), rows_f.reshape(-1),
+                                                           sos_table_bits(full).reshape(-1)])))
+            run.last_lowpass = picked
         graph.replay()
         return lr, hr
-    run.graph, run.table, run.batch = graph, table, batch
+    run.graph, run.table, run.batch, run.last_lowpass = graph, table, batch, None
+    # the capture holds raw pointers: every buffer its kernels touch lives as long as `run`
+    run.filtered, run.workspace = (filtered, ws) if spec is not None else (None, None)
     return run
