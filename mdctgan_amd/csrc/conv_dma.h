@@ -896,13 +896,18 @@ inline bool conv_dma_wgrad_rowreg(const mg_conv_geom* g) {
     }
     return true;
 }
+// whether the weight gradient runs its RR = true instances (built for the two-buffer ring only; MG_NO_WGRAD_RR: read per call):
+// what conv_dma_wgrad_launch dispatches on and mg_conv_plan_name prints
+inline bool conv_dma_wgrad_rr(const mg_conv_geom* g) {
+    return conv_dma_wgrad_rowreg(g) && !getenv("MG_NO_WGRAD_RR") && (!conv_dma_half(g) || cd_half_nbuf() == 2);
+}
 void conv_dma_wgrad_launch(const mg_conv_geom* g, const CdPlan& p, const void* x, const void* dy, float* dw, int accumulate,
                            float* part, hipStream_t st) {
     CdArgs a = cd_args(g);
     a.x = x; a.w = dy; a.y = dw; a.part = p.splits > 1 ? part : nullptr; a.accumulate = accumulate;
     a.tiles_m = (g->Co + p.bm - 1) / p.bm; a.tiles_n = g->KH * g->KW * g->Ci / p.bn; a.splits = p.splits; a.cps = p.cps;
     const dim3 grid((unsigned)((long long)a.tiles_m * a.tiles_n * a.splits));
-    if (conv_dma_wgrad_rowreg(g) && !getenv("MG_NO_WGRAD_RR") && (!conv_dma_half(g) || cd_half_nbuf() == 2)) {
+    if (conv_dma_wgrad_rr(g)) {
         if (conv_dma_half(g)) {
             if (p.bm == 128 && p.bn == 128) cd_launch(conv_wgrad_dma_kernel<128, 128, true, 2, true>, DgCfgG<128, 128, 2, 2, 1, 1, 2>::LDS_BYTES, grid, a, st);
             else if (p.bm == 64 && p.bn == 128) cd_launch(conv_wgrad_dma_kernel<64, 128, true, 2, true>, DgCfgG<64, 128, 2, 2, 1, 1, 2>::LDS_BYTES, grid, a, st);

@@ -20,6 +20,7 @@
 // buffering, one barrier per k-chunk; with 64-cycle MFMAs the loader hides completely.
 #include "common.h"
 #include "mdctgan_hip.h"
+#include "internal.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <cstring>
@@ -1039,14 +1040,22 @@ __global__ void colsum_partial_kernel(const float* __restrict__ a, long long M, 
     }
 }
 
+// The split-K combine launches.  blocks: the caller's grid rule over the n / 4 float4s of the result (conv_grid, dense_grid,
+// wino_grid); the kernels walk grid strides, so any count >= 1 gives the same bits.
+inline unsigned conv_grid(size_t n4) {
+    const size_t b = (n4 + 255) / 256;
+    return (unsigned)(b > 4096 ? 4096 : b);
+}
+inline void splitk_epilogue(unsigned blocks, const float* part, int splits, size_t n, int N, const float* bias, int act, float* out,
+                            int round_f16, hipStream_t st) {
+    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(blocks), dim3(256), 0, st, part, splits, n, N, bias, act, out, round_f16);
+}
+inline void splitk_reduce(unsigned blocks, const float* part, int splits, size_t n, float* out, int accumulate, hipStream_t st) {
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, part, splits, n, out, accumulate);
+}
+
 }  // namespace
 
-extern "C" __attribute__((visibility("hidden"))) int mg_conv_rowdot_kq(const mg_conv_geom* g);       // conv_rowdot.hip (library-internal)
-extern "C" __attribute__((visibility("hidden"))) int mg_instnorm_slab_ok(int HW, int C);              // instnorm.hip (library-internal)
-extern "C" __attribute__((visibility("hidden"))) int mg_instnorm_fwd_slabs(const float* part, int S, const float* bias, int round_f16,
-                                                                          float* x_out, int B, int HW, int C, float eps, int act,
-                                                                          const float* residual, float* y, float* mean, float* rstd,
-                                                                          void* stream, void* y16);
 #include "wino.h"
 #include "wino4.h"
 #include "wino42.h"
@@ -1232,8 +1241,7 @@ void dense_wino_gemm(const DensePlan& p, int pass, int P, long long T, int Co, i
     probe_end(st);
     if (p.splits > 1) {
         const size_t n = (size_t)P * dd.M * dd.N;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(dense_grid(n / 4)), dim3(256), 0, st, (const float*)part, p.splits, n, C,
-                           0);
+        splitk_reduce(dense_grid(n / 4), part, p.splits, n, C, 0, st);
     }
 }
 inline size_t slab_count(int old_splits, int dense) {      // split-K slabs a workspace must hold (either path may run)
@@ -1252,6 +1260,14 @@ struct FwdDefer { const float* part; int splits; const float* bias; int round_f1
 // float32 -> float16 staging copy of n elements (n % 8 == 0 for every eligible layer: Ci, Co % 64 == 0)
 inline void cd_cast16(const float* src, void* dst, size_t n, hipStream_t st) {
     hipLaunchKernelGGL(h16_cast_kernel, dim3(h16_grid(n / 8)), dim3(256), 0, st, src, (_Float16*)dst, n / 8);
+}
+// The float16 copy of an operand of a DMA pass: the caller's (kept) when handed over -- cast into it unless its producer filled
+// it already -- else a cast into the workspace; either way the workspace pointer moves past the operand's slot
+inline const void* cd_stage16(const float* src, const void* kept, bool filled, size_t n, size_t slot_bytes, char*& wsp, hipStream_t st) {
+    void* dst = kept ? const_cast<void*>(kept) : (void*)wsp;
+    if (!(kept && filled)) cd_cast16(src, dst, n, st);
+    wsp += slot_bytes;
+    return dst;
 }
 // ReflectionPad2d(1) + 3x3 stride-1 data gradient on the DMA kernel: the zero-padded "full" data gradient over the padded
 // (H+2) x (W+2) domain (cd_reflect_geom: pad 0, same OH x OW), folded back onto H x W by wino_fold_reflect_kernel
@@ -1281,18 +1297,9 @@ int cd_dgrad_run(const mg_conv_geom* g, const float* dy, const float* w, const f
     const void* dyin = dy;
     const void* win = w;
     if (half) {
-        void* dy16 = md ? (void*)md : (void*)wsp;      // shared with the weight gradient
-        if (!(md && dy16_filled))                      // MG_TILES_MD_FILLED: the producer of dy wrote the copy (mg_instnorm_bwd_h)
-            cd_cast16(dy, dy16, (size_t)g->B * g->OH * g->OW * g->Co, st);
-        dyin = dy16;
-        wsp += conv_dma_h_dy_bytes(g);
-        if (u) {
-            win = u;
-        } else {
-            cd_cast16(w, wsp, (size_t)g->Co * g->KH * g->KW * g->Ci, st);
-            win = wsp;
-        }
-        wsp += conv_dma_h_w_bytes(g);
+        // dy: md is shared with the weight gradient; MG_TILES_MD_FILLED: the producer of dy wrote the copy (mg_instnorm_bwd_h)
+        dyin = cd_stage16(dy, md, dy16_filled != 0, (size_t)g->B * g->OH * g->OW * g->Co, conv_dma_h_dy_bytes(g), wsp, st);
+        win = cd_stage16(w, u, true, (size_t)g->Co * g->KH * g->KW * g->Ci, conv_dma_h_w_bytes(g), wsp, st);
         MG_CHECK_LAUNCH();
     }
     probe_begin(st);
@@ -1301,9 +1308,7 @@ int cd_dgrad_run(const mg_conv_geom* g, const float* dy, const float* w, const f
     MG_CHECK_LAUNCH();
     if (cp.splits > 1) {
         const size_t n = (size_t)g->B * g->H * g->W * g->Ci;
-        const unsigned blocks = (unsigned)((n / 4 + 255) / 256 > 4096 ? 4096 : (n / 4 + 255) / 256);
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(blocks), dim3(256), 0, st, (const float*)wsp, cp.splits, n, g->Ci,
-                           bias, act, dx, round_f16);
+        splitk_epilogue(conv_grid(n / 4), (const float*)wsp, cp.splits, n, g->Ci, bias, act, dx, round_f16, st);
         MG_CHECK_LAUNCH();
     }
     return MG_OK;
@@ -1446,8 +1451,15 @@ TilePlan gemm_plan(long long M, int N, int chunks, int classes, bool can_split, 
     }
     return out;
 }
-inline bool use_k32(const TilePlan& tp, int Ci) {
-    return tp.k32 && fwd32_enabled() && Ci % BK2 == 0 && (tp.splits == 1 || tp.cps % 2 == 0);
+// the 32-deep forward kernel takes whole 32-channel chunks and, when K is split, an even number of 16-deep chunks per split
+inline bool k32_fits(int Ci, int splits, int cps) { return fwd32_enabled() && Ci % BK2 == 0 && (splits == 1 || cps % 2 == 0); }
+// float32: where the plan asks for it; float16: whenever the shape allows it (its stage / fragment traffic is what the f16 loop
+// is made of)
+inline bool use_k32(const TilePlan& tp, int Ci) { return tp.k32 && k32_fits(Ci, tp.splits, tp.cps); }
+template <typename Plan>
+inline void one_split(Plan& p, int cps) {      // no K split (workspace or an alignment is missing): one split walks every chunk
+    p.splits = 1;
+    p.cps = cps;
 }
 TilePlan fwd_plan(const mg_conv_geom* g) {
     const long long M = (long long)g->B * g->OH * g->OW;
@@ -1492,6 +1504,69 @@ WgradPlan wgrad_plan(const mg_conv_geom* g) {
     splits = (chunks + cps - 1) / cps;
     return {big, tiles, splits, cps};
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// The pick: the one instance of the generic implicit GEMM a pass launches -- conv_fwd_kernel<bm, bn, veca, tag> /
+// conv_fwd32_kernel<bm, bn, tag> (k32), conv_dgrad_kernel / conv_wgrad_kernel<bm, bn, veca, vecb, tag> -- and its K split.
+// A launcher fills it from the geometry and what its buffers allow and dispatches on it; mg_conv_plan_name fills it with
+// everything allowed and prints it.  Neither holds a condition of its own.
+// ---------------------------------------------------------------------------------------------------------
+struct GemmPick { int bm, bn; bool veca, vecb; int tag; bool k32; int splits, cps; };
+// What the entry point's buffers allow.  veca / vecb: the A / B operand (forward: both) is 16-byte aligned, so float4 loads may
+// read it; split: a workspace of the queried size is there and it, the output and the bias are 16-byte aligned (the combine
+// kernels read and write float4s)
+struct BufFacts { bool veca, vecb, split; };
+constexpr BufFacts kAnyBuf{true, true, true};
+inline int conv_tag(const mg_conv_geom* g) { return g->precision == MG_PRECISION_F16 ? 2 : 0; }
+GemmPick fwd_pick(const mg_conv_geom* g, BufFacts f) {
+    TilePlan tp = fwd_plan(g);
+    if (tp.splits > 1 && !f.split) one_split(tp, 1 << 30);
+    const bool vec = g->Ci % BK == 0 && f.veca && f.vecb;
+    const bool k32 = vec && (conv_tag(g) ? k32_fits(g->Ci, tp.splits, tp.cps) : use_k32(tp, g->Ci));
+    return {tp.bm, tp.bn, vec, vec, conv_tag(g), k32, tp.splits, tp.cps};
+}
+GemmPick dgrad_pick(const mg_conv_geom* g, BufFacts f) {
+    TilePlan tp = dgrad_plan(g);
+    if (tp.splits > 1 && !f.split) one_split(tp, 1 << 30);
+    return {tp.bm, tp.bn, g->Co % BK == 0 && f.veca, g->Ci % 4 == 0 && f.vecb, conv_tag(g), false, tp.splits, tp.cps};
+}
+GemmPick wgrad_pick(const mg_conv_geom* g, BufFacts f) {
+    WgradPlan p = wgrad_plan(g);
+    if (p.splits > 1 && !f.split) one_split(p, 1 << 30);
+    const int t = p.big ? 128 : 64;
+    return {t, t, g->Co % 4 == 0 && f.veca, g->Ci % 4 == 0 && f.vecb, conv_tag(g), false, p.splits, p.cps};
+}
+void gemm_pick_name(int pass, const GemmPick& p, char* out, int out_len) {
+    const char* va = p.veca ? "true" : "false";
+    const char* vb = p.vecb ? "true" : "false";
+    if (pass == 0 && p.k32) snprintf(out, out_len, "conv_fwd32_kernel<%d, %d, %d>", p.bm, p.bn, p.tag);
+    else if (pass == 0) snprintf(out, out_len, "conv_fwd_kernel<%d, %d, %s, %d>", p.bm, p.bn, va, p.tag);
+    else snprintf(out, out_len, pass == 1 ? "conv_dgrad_kernel<%d, %d, %s, %s, %d>" : "conv_wgrad_kernel<%d, %d, %s, %s, %d>", p.bm,
+                  p.bn, va, vb, p.tag);
+}
+
+// Dispatch of a pick's run-time values onto template arguments: each calls f with std::integral_constant / std::bool_constant
+// values, so nesting them instantiates exactly the product of their alternatives.
+template <typename F>
+void dispatch_tile(int bm, int bn, F&& f) {      // 128x128, 64x64, 128x64
+    if (bm == 128 && bn == 128) f(std::integral_constant<int, 128>{}, std::integral_constant<int, 128>{});
+    else if (bm == 64) f(std::integral_constant<int, 64>{}, std::integral_constant<int, 64>{});
+    else f(std::integral_constant<int, 128>{}, std::integral_constant<int, 64>{});
+}
+template <typename F>
+void dispatch_bool(bool v, F&& f) {
+    if (v) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <typename F>
+void dispatch_tag(int tag, F&& f) {      // the convolutions' own tags: 0 float32, 2 float16
+    if (tag == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 0>{});
+}
+// The weight gradient's reduce runs one block more than conv_grid unless capped.  splitk_reduce_kernel walks grid strides, so
+// the extra block finds nothing to do -- except for a dw of fewer than 4 elements (n / 4 == 0), where it IS block 0, the one
+// that sums the scalar tail, and the grid would otherwise be empty.
+inline unsigned wgrad_reduce_grid(size_t n4) { return (n4 + 255) / 256 > 4096 ? 4096u : (unsigned)((n4 + 255) / 256 + 1); }
 
 // ---------------------------------------------------------------------------------------------------------
 // Kernel families.  conv_route() (after the family predicates, below) names the one a pass of a layer takes; the launchers,
@@ -1569,8 +1644,7 @@ WinoGemm wino_gemm_plan(const WinoGeo& w, int pass, const mg_conv_geom* g) {
     WinoGemm s{dense_plan(pass, w.f.P, w.T, g->Co, w.Kc, w.hp), {}, w.hp ? 3 : w.f.P == 16 ? 1 : 5};
     if (pass == 0) {
         s.tp = gemm_plan(w.T, g->Co, w.Kc / BK, w.f.P, true, 0);
-        // f16: the 32-deep kernel whenever the shape allows it
-        s.tp.k32 = w.hp ? fwd32_enabled() && w.Kc % BK2 == 0 && (s.tp.splits == 1 || s.tp.cps % 2 == 0) : use_k32(s.tp, w.Kc);
+        s.tp.k32 = w.hp ? k32_fits(w.Kc, s.tp.splits, s.tp.cps) : use_k32(s.tp, w.Kc);
     } else if (pass == 1) {
         s.tp = gemm_plan(w.T, w.Kc, g->Co / BK, w.f.P, true, 1);
     } else {        // dU [Co][Kc] on 64x64 or 128x128 tiles, the tiles' reduction split over blockIdx.z
@@ -1611,14 +1685,6 @@ size_t wino_ws_bytes(ConvRoute r, int pass, const mg_conv_geom* g) {
     return wino_ws(w, wino_gemm_plan(w, pass, g), pass, g).bytes;
 }
 
-template <typename Launch>
-int wino_launch_tiles(const TilePlan& tp, Launch&& launch) {
-    if (tp.bm == 128 && tp.bn == 128) launch(std::integral_constant<int, 128>{}, std::integral_constant<int, 128>{});
-    else if (tp.bm == 64) launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 64>{});
-    else launch(std::integral_constant<int, 128>{}, std::integral_constant<int, 64>{});
-    return 0;
-}
-
 // pass 0: Mx = V U^T (a = V, b = U); 1: dV = Md U (a = Md, b = U); 2: dU = Md^T V (a = Md, b = V).  part: split-K slabs.
 void wino_gemm(const WinoGeo& w, const WinoGemm& s, int pass, const mg_conv_geom* g, const float* a, const float* b, float* c,
                float* part, hipStream_t st) {
@@ -1643,7 +1709,7 @@ void wino_gemm(const WinoGeo& w, const WinoGemm& s, int pass, const mg_conv_geom
                 hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, true, true, TAG>), grid, dim3(256), 0, st, gg, b, a, target, tp.cps, 0, bt);
             return;
         }
-        wino_launch_tiles(tp, [&](auto bm, auto bn) {
+        dispatch_tile(tp.bm, tp.bn, [&](auto bm, auto bn) {
             constexpr int BM_ = decltype(bm)::value, BN_ = decltype(bn)::value;
             const dim3 grid((unsigned)(((T + BM_ - 1) / BM_) * (((pass == 0 ? Co : Kc) + BN_ - 1) / BN_)), tp.splits, P);
             if (pass == 1)          // dV_z = dM_z U_z: same position, no flip
@@ -1665,12 +1731,11 @@ void wino_gemm(const WinoGeo& w, const WinoGemm& s, int pass, const mg_conv_geom
     if (!pp) return;
     if (pass == 2) {
         const size_t n = (size_t)P * Co * Kc;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(wino_grid(n / 4)), dim3(256), 0, st, (const float*)pp, tp.splits, n, c, 0);
+        splitk_reduce(wino_grid(n / 4), pp, tp.splits, n, c, 0, st);
     } else {
         const int N = pass == 0 ? Co : Kc;
         const size_t n = (size_t)P * T * N;
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(wino_grid(n / 4)), dim3(256), 0, st, (const float*)pp, tp.splits, n, N,
-                           (const float*)nullptr, MG_ACT_NONE, c);
+        splitk_epilogue(wino_grid(n / 4), pp, tp.splits, n, N, nullptr, MG_ACT_NONE, c, 0, st);
     }
 }
 
@@ -1811,7 +1876,6 @@ int wino_wgrad(const WinoGeo& w, const mg_conv_geom* g, const float* x, const fl
     }
     return MG_OK;
 }
-
 // ---------------------------------------------------------------------------------------------------------
 // Ci <= 4 layers (conv_smallc.h): VALU kernels for the data gradient and the weight gradient
 // ---------------------------------------------------------------------------------------------------------
@@ -1950,14 +2014,6 @@ inline bool conv_dma_h_any(const mg_conv_geom* g) {
 
 extern "C" {
 
-// (library-internal: conv_rowdot.hip; hidden from the .so's exports)
-__attribute__((visibility("hidden"))) int mg_conv_rowdot_kq(const mg_conv_geom* g);
-__attribute__((visibility("hidden"))) int mg_conv_rowdot_fwd(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int act,
-                       void* stream);
-__attribute__((visibility("hidden"))) size_t mg_conv_rowdot_wgrad_workspace(const mg_conv_geom* g);
-__attribute__((visibility("hidden"))) int mg_conv_rowdot_wgrad(const mg_conv_geom* g, const float* x, const float* dy, float* dw, float* dbias,
-                         int accumulate, void* workspace, size_t workspace_bytes, void* stream);
-
 int mg_abi_version(void) { return 4; }
 int mg_conv_geom_size(void) { return (int)sizeof(mg_conv_geom); }
 
@@ -2044,10 +2100,7 @@ int mg_conv_plan_name(int pass, const mg_conv_geom* g, char* out, int out_len) {
         const WinoGeo w = wino_geo(r, g);
         const WinoGemm s = wino_gemm_plan(w, pass, g);
         if (s.dp.ok) dense_name(pass, w.f.P, s.dp, dense_dims(pass, w.T, g->Co, w.Kc).N, out, out_len);
-        else if (pass == 0 && s.tp.k32) snprintf(out, out_len, "conv_fwd32_kernel<%d, %d, %d>", s.tp.bm, s.tp.bn, s.tag);
-        else snprintf(out, out_len, pass == 0 ? "conv_fwd_kernel<%d, %d, true, %d>" : pass == 1 ? "conv_dgrad_kernel<%d, %d, true, true, %d>"
-                                                                                         : "conv_wgrad_kernel<%d, %d, true, true, %d>",
-                      s.tp.bm, s.tp.bn, s.tag);
+        else gemm_pick_name(pass, GemmPick{s.tp.bm, s.tp.bn, true, true, s.tag, s.tp.k32, s.tp.splits, s.tp.cps}, out, out_len);
         break;
     }
     case R_SMALLC:
@@ -2067,32 +2120,12 @@ int mg_conv_plan_name(int pass, const mg_conv_geom* g, char* out, int out_len) {
             snprintf(out, out_len, "conv_dgrad_dma_kernel<%d, %d, %s, %d>", cp.bm, cp.bn, half, nbuf);
         } else {
             const CdPlan cp = conv_dma_wgrad_plan(g);
-            const bool rr = conv_dma_wgrad_rowreg(g) && !getenv("MG_NO_WGRAD_RR") && (!prec_h(g) || cd_half_nbuf() == 2);
-            snprintf(out, out_len, "conv_wgrad_dma_kernel<%d, %d, %s, %d, %s>", cp.bm, cp.bn, half, nbuf, rr ? "true" : "false");
+            snprintf(out, out_len, "conv_wgrad_dma_kernel<%d, %d, %s, %d, %s>", cp.bm, cp.bn, half, nbuf, conv_dma_wgrad_rr(g) ? "true" : "false");
         }
         break;
     }
     default:
-        if (pass == 0) {
-            const TilePlan tp = fwd_plan(g);
-            const bool vec16 = g->Ci % BK == 0;
-            const bool k32h = vec16 && fwd32_enabled() && g->Ci % BK2 == 0 && (tp.splits == 1 || tp.cps % 2 == 0);
-            if (prec_h(g) && k32h)
-                snprintf(out, out_len, "conv_fwd32_kernel<%d, %d, 2>", tp.bm, tp.bn);
-            else if (!prec_h(g) && use_k32(tp, g->Ci))
-                snprintf(out, out_len, "conv_fwd32_kernel<%d, %d, 0>", tp.bm, tp.bn);
-            else
-                snprintf(out, out_len, "conv_fwd_kernel<%d, %d, %s, %d>", tp.bm, tp.bn, (g->Ci % BK == 0) ? "true" : "false",
-                         prec_h(g) ? 2 : 0);
-        } else if (pass == 1) {
-            const TilePlan tp = dgrad_plan(g);
-            snprintf(out, out_len, "conv_dgrad_kernel<%d, %d, %s, %s, %d>", tp.bm, tp.bn, (g->Co % BK == 0) ? "true" : "false",
-                     (g->Ci % 4 == 0) ? "true" : "false", prec_h(g) ? 2 : 0);
-        } else {
-            const WgradPlan p = wgrad_plan(g);
-            snprintf(out, out_len, "conv_wgrad_kernel<%d, %d, %s, %s, %d>", p.big ? 128 : 64, p.big ? 128 : 64,
-                     (g->Co % 4 == 0) ? "true" : "false", (g->Ci % 4 == 0) ? "true" : "false", prec_h(g) ? 2 : 0);
-        }
+        gemm_pick_name(pass, pass == 0 ? fwd_pick(g, kAnyBuf) : pass == 1 ? dgrad_pick(g, kAnyBuf) : wgrad_pick(g, kAnyBuf), out, out_len);
     }
     return MG_OK;
 }
@@ -2339,26 +2372,15 @@ static int conv_fwd(const mg_conv_geom* g, const float* x, const float* w, const
     if (conv_route(0, g, true) == R_DMA && aligned16(x) && aligned16(w) && aligned16(y) && (!bias || aligned16(bias)) &&
         (!cd_half || (workspace && aligned16(workspace) && workspace_bytes >= mg_conv_fwd_workspace(g)))) {
         CdPlan cp = conv_dma_fwd_plan(g);
-        if (cp.splits > 1 && (!workspace || workspace_bytes < mg_conv_fwd_workspace(g) || !aligned16(workspace))) {
-            cp.splits = 1;
-            cp.cps = 1 << 28;
-        }
+        if (cp.splits > 1 && (!workspace || workspace_bytes < mg_conv_fwd_workspace(g) || !aligned16(workspace)))
+            one_split(cp, 1 << 28);
         const void* xin = x;
         const void* win = w;
         char* wsp = (char*)workspace;
         if (cd_half) {          // float16 copies: the activation by a cast pass, the weights from the cache when there is one
-            void* x16 = (wt && wt->v) ? (void*)wt->v : (void*)wsp;         // kept by the caller for the weight gradient
-            if (!(wt && wt->v && (wt->flags & MG_TILES_V_FILLED)))         // ... unless x's producer already wrote it (mg_instnorm_fwd_h)
-                cd_cast16(x, x16, (size_t)g->B * g->H * g->W * g->Ci, st);
-            xin = x16;
-            wsp += conv_dma_h_x_bytes(g);
-            if (u) {
-                win = u;
-            } else {
-                cd_cast16(w, wsp, (size_t)g->Co * g->KH * g->KW * g->Ci, st);
-                win = wsp;
-            }
-            wsp += conv_dma_h_w_bytes(g);
+            // x: v is kept by the caller for the weight gradient; v_filled: x's producer already wrote it (mg_instnorm_fwd_h)
+            xin = cd_stage16(x, v, v_filled, (size_t)g->B * g->H * g->W * g->Ci, conv_dma_h_x_bytes(g), wsp, st);
+            win = cd_stage16(w, u, true, (size_t)g->Co * g->KH * g->KW * g->Ci, conv_dma_h_w_bytes(g), wsp, st);
             MG_CHECK_LAUNCH();
         }
         probe_begin(st);
@@ -2371,47 +2393,35 @@ static int conv_fwd(const mg_conv_geom* g, const float* x, const float* w, const
                 *defer = FwdDefer{(const float*)wsp, cp.splits, bias, cd_half ? 1 : 0, true};
                 return MG_OK;
             }
-            const unsigned blocks = (unsigned)((n / 4 + 255) / 256 > 4096 ? 4096 : (n / 4 + 255) / 256);
-            hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(blocks), dim3(256), 0, st, (const float*)wsp, cp.splits, n, N,
-                               bias, act, y, cd_half ? 1 : 0);
+            splitk_epilogue(conv_grid(n / 4), (const float*)wsp, cp.splits, n, N, bias, act, y, cd_half ? 1 : 0, st);
             MG_CHECK_LAUNCH();
         }
         return MG_OK;
     }
-    const bool vec = (g->Ci % BK == 0) && aligned16(x) && aligned16(w);
-    TilePlan tp = fwd_plan(g);
-    if (tp.splits > 1 && (!workspace || !aligned16(workspace) || workspace_bytes < mg_conv_fwd_workspace(g) || !aligned16(y) ||
-                          (bias && !aligned16(bias)))) {
-        tp.splits = 1;
-        tp.cps = 1 << 30;
-    }
-    float* part = tp.splits > 1 ? (float*)workspace : nullptr;
-    const bool hp = prec_h(g);
-    // f16: the 32-deep kernel whenever the shape allows it (its stage / fragment traffic is what the f16 loop is made of)
-    const bool k32 = vec && (hp ? (fwd32_enabled() && g->Ci % BK2 == 0 && (tp.splits == 1 || tp.cps % 2 == 0))
-                                : use_k32(tp, g->Ci));
-#define MG_LAUNCH_FWD(BM_, BN_)                                                                                    \
-    do {                                                                                                           \
-        dim3 grid((unsigned)(((M + BM_ - 1) / BM_) * ((N + BN_ - 1) / BN_)), tp.splits);                           \
-        if (k32 && hp) launch_fwd32<BM_, BN_, 2>(grid, st, gg, x, w, bias, y, act, tp.splits == 1 ? (1 << 29) : tp.cps / 2, part, Batch{0, 0, 0, 0}); \
-        else if (k32) launch_fwd32<BM_, BN_, 0>(grid, st, gg, x, w, bias, y, act, tp.splits == 1 ? (1 << 29) : tp.cps / 2, part, Batch{0, 0, 0, 0}); \
-        else if (hp && vec) hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, true, 2>), grid, dim3(256), 0, st, gg, x, w, bias, y, act, tp.cps, part, Batch{0, 0, 0, 0});  \
-        else if (hp) hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, false, 2>), grid, dim3(256), 0, st, gg, x, w, bias, y, act, tp.cps, part, Batch{0, 0, 0, 0});    \
-        else if (vec) hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, true>), grid, dim3(256), 0, st, gg, x, w, bias, y, act, tp.cps, part, Batch{0, 0, 0, 0});  \
-        else hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, false>), grid, dim3(256), 0, st, gg, x, w, bias, y, act, tp.cps, part, Batch{0, 0, 0, 0});    \
-    } while (0)
+    const GemmPick p = fwd_pick(g, BufFacts{aligned16(x), aligned16(w),
+                                            workspace && aligned16(workspace) && aligned16(y) && (!bias || aligned16(bias)) &&
+                                                workspace_bytes >= mg_conv_fwd_workspace(g)});
+    float* part = p.splits > 1 ? (float*)workspace : nullptr;
     probe_begin(st);
-    if (tp.bm == 128 && tp.bn == 128) MG_LAUNCH_FWD(128, 128);
-    else if (tp.bm == 64) MG_LAUNCH_FWD(64, 64);
-    else MG_LAUNCH_FWD(128, 64);
+    dispatch_tile(p.bm, p.bn, [&](auto bm, auto bn) {
+        constexpr int BM_ = decltype(bm)::value, BN_ = decltype(bn)::value;
+        const dim3 grid((unsigned)(((M + BM_ - 1) / BM_) * ((N + BN_ - 1) / BN_)), p.splits);
+        dispatch_tag(p.tag, [&](auto tag) {
+            constexpr int TAG = decltype(tag)::value;
+            if (p.k32)
+                launch_fwd32<BM_, BN_, TAG>(grid, st, gg, x, w, bias, y, act, p.splits == 1 ? (1 << 29) : p.cps / 2, part, Batch{0, 0, 0, 0});
+            else
+                dispatch_bool(p.veca, [&](auto vec) {
+                    hipLaunchKernelGGL((conv_fwd_kernel<BM_, BN_, decltype(vec)::value, TAG>), grid, dim3(256), 0, st, gg, x, w, bias, y,
+                                       act, p.cps, part, Batch{0, 0, 0, 0});
+                });
+        });
+    });
     probe_end(st);
-#undef MG_LAUNCH_FWD
     MG_CHECK_LAUNCH();
     if (part) {
         const size_t n = (size_t)M * N;
-        const unsigned blocks = (unsigned)((n / 4 + 255) / 256 > 4096 ? 4096 : (n / 4 + 255) / 256);
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(blocks), dim3(256), 0, st, (const float*)part, tp.splits, n, N,
-                           bias, act, y, (int)hp);
+        splitk_epilogue(conv_grid(n / 4), part, p.splits, n, N, bias, act, y, p.tag == 2, st);
         MG_CHECK_LAUNCH();
     }
     return MG_OK;
@@ -2489,42 +2499,28 @@ static int conv_dgrad(const mg_conv_geom* g, const float* dy, const float* w, co
     // every input pixel is produced by exactly one class launch; classes cover all of [0,H)x[0,W)
     const long long Mc = (long long)g->B * ((g->H + s - 1) / s) * ((g->W + s - 1) / s);   // largest class
     const int N = g->Ci;
-    const bool veca = (g->Co % BK == 0) && aligned16(dy);
-    const bool vecb = (g->Ci % 4 == 0) && aligned16(w);
-    TilePlan tp = dgrad_plan(g);
-    if (tp.splits > 1 && (!workspace || !aligned16(workspace) || workspace_bytes < mg_conv_dgrad_workspace(g) || !aligned16(dx) ||
-                          (bias && !aligned16(bias)))) {
-        tp.splits = 1;
-        tp.cps = 1 << 30;
-    }
-    float* part = tp.splits > 1 ? (float*)workspace : nullptr;
-    const bool hp = prec_h(g);
-#define MG_LAUNCH_DGRAD_T(BM_, BN_, TAG_)                                                                          \
-    do {                                                                                                           \
-        dim3 grid((unsigned)(((Mc + BM_ - 1) / BM_) * ((N + BN_ - 1) / BN_)), tp.splits, s * s);                   \
-        if (veca && vecb)                                                                                          \
-            hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, true, true, TAG_>), grid, dim3(256), 0, st, gg, dy, w, bias, dx, act, tp.cps, part, Batch{0, 0, 0, 0});  \
-        else if (veca)                                                                                             \
-            hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, true, false, TAG_>), grid, dim3(256), 0, st, gg, dy, w, bias, dx, act, tp.cps, part, Batch{0, 0, 0, 0}); \
-        else if (vecb)                                                                                             \
-            hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, false, true, TAG_>), grid, dim3(256), 0, st, gg, dy, w, bias, dx, act, tp.cps, part, Batch{0, 0, 0, 0}); \
-        else                                                                                                       \
-            hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, false, false, TAG_>), grid, dim3(256), 0, st, gg, dy, w, bias, dx, act, tp.cps, part, Batch{0, 0, 0, 0});\
-    } while (0)
-#define MG_LAUNCH_DGRAD(BM_, BN_) do { if (hp) MG_LAUNCH_DGRAD_T(BM_, BN_, 2); else MG_LAUNCH_DGRAD_T(BM_, BN_, 0); } while (0)
+    const GemmPick p = dgrad_pick(g, BufFacts{aligned16(dy), aligned16(w),
+                                              workspace && aligned16(workspace) && aligned16(dx) && (!bias || aligned16(bias)) &&
+                                                  workspace_bytes >= mg_conv_dgrad_workspace(g)});
+    float* part = p.splits > 1 ? (float*)workspace : nullptr;
     probe_begin(st);
-    if (tp.bm == 128 && tp.bn == 128) MG_LAUNCH_DGRAD(128, 128);
-    else if (tp.bm == 64) MG_LAUNCH_DGRAD(64, 64);
-    else MG_LAUNCH_DGRAD(128, 64);
+    dispatch_tile(p.bm, p.bn, [&](auto bm, auto bn) {
+        constexpr int BM_ = decltype(bm)::value, BN_ = decltype(bn)::value;
+        const dim3 grid((unsigned)(((Mc + BM_ - 1) / BM_) * ((N + BN_ - 1) / BN_)), p.splits, s * s);
+        dispatch_tag(p.tag, [&](auto tag) {
+            dispatch_bool(p.veca, [&](auto veca) {
+                dispatch_bool(p.vecb, [&](auto vecb) {
+                    hipLaunchKernelGGL((conv_dgrad_kernel<BM_, BN_, decltype(veca)::value, decltype(vecb)::value, decltype(tag)::value>),
+                                       grid, dim3(256), 0, st, gg, dy, w, bias, dx, act, p.cps, part, Batch{0, 0, 0, 0});
+                });
+            });
+        });
+    });
     probe_end(st);
-#undef MG_LAUNCH_DGRAD_T
-#undef MG_LAUNCH_DGRAD
     MG_CHECK_LAUNCH();
     if (part) {
         const size_t n = (size_t)g->B * g->H * g->W * N;
-        const unsigned blocks = (unsigned)((n / 4 + 255) / 256 > 4096 ? 4096 : (n / 4 + 255) / 256);
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(blocks), dim3(256), 0, st, (const float*)part, tp.splits, n, N,
-                           bias, act, dx, (int)hp);
+        splitk_epilogue(conv_grid(n / 4), part, p.splits, n, N, bias, act, dx, p.tag == 2, st);
         MG_CHECK_LAUNCH();
     }
     return MG_OK;
@@ -2666,20 +2662,8 @@ int mg_conv_wgrad_chk(const mg_conv_geom* g, const float* x, const float* dy, fl
         const void* dyin = dy;
         char* wsp = (char*)workspace;
         if (conv_dma_half(g)) {          // float16 copies: the caller's (made by the forward / data-gradient call) or cast here
-            if (wt && wt->v) {
-                xin = wt->v;
-            } else {
-                cd_cast16(x, wsp, (size_t)g->B * g->H * g->W * g->Ci, st);
-                xin = wsp;
-            }
-            wsp += conv_dma_h_x_bytes(g);
-            if (wt && wt->md) {
-                dyin = wt->md;
-            } else {
-                cd_cast16(dy, wsp, (size_t)g->B * g->OH * g->OW * g->Co, st);
-                dyin = wsp;
-            }
-            wsp += conv_dma_h_dy_bytes(g);
+            xin = cd_stage16(x, wt ? wt->v : nullptr, true, (size_t)g->B * g->H * g->W * g->Ci, conv_dma_h_x_bytes(g), wsp, st);
+            dyin = cd_stage16(dy, wt ? wt->md : nullptr, true, (size_t)g->B * g->OH * g->OW * g->Co, conv_dma_h_dy_bytes(g), wsp, st);
             MG_CHECK_LAUNCH();
         }
         probe_begin(st);
@@ -2687,50 +2671,37 @@ int mg_conv_wgrad_chk(const mg_conv_geom* g, const float* x, const float* dy, fl
         probe_end(st);
         MG_CHECK_LAUNCH();
         if (cp.splits > 1) {
-            const unsigned blocks = (unsigned)((n_out / 4 + 255) / 256 > 4096 ? 4096 : (n_out / 4 + 255) / 256 + 1);
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)wsp, cp.splits, n_out, dw,
-                               accumulate);
+            splitk_reduce(wgrad_reduce_grid(n_out / 4), (const float*)wsp, cp.splits, n_out, dw, accumulate, st);
             MG_CHECK_LAUNCH();
         }
         if (dbias)
             return mg_colsum(dy, (long long)g->B * g->OH * g->OW, g->Co, dbias, accumulate, workspace, workspace_bytes, stream);
         return MG_OK;
     }
-    WgradPlan p = wgrad_plan(g);
-    if (p.splits > 1 && (!aligned16(dw) || !aligned16(workspace))) {      // splitk_reduce_kernel reads the slabs and stores (accumulates into) dw as float4s
-        p.splits = 1;
-        p.cps = 1 << 30;
-    }
-    const bool veca = (g->Co % 4 == 0) && aligned16(dy);
-    const bool vecb = (g->Ci % 4 == 0) && aligned16(x);
+    // (split: splitk_reduce_kernel reads the slabs and stores / accumulates into dw as float4s)
+    const GemmPick p = wgrad_pick(g, BufFacts{aligned16(dy), aligned16(x), aligned16(dw) && aligned16(workspace)});
     const size_t n_out = (size_t)g->Co * g->KH * g->KW * g->Ci;
     float* target = p.splits > 1 ? (float*)workspace : dw;
     const int acc_direct = (p.splits > 1) ? 0 : accumulate;
-    const bool hp = prec_h(g);
-#define MG_LAUNCH_WGRAD_T(BM_, BN_, TAG_)                                                                           \
-    do {                                                                                                            \
-        dim3 grid((unsigned)p.tiles, 1, p.splits);                                                                  \
-        if (veca && vecb)                                                                                           \
-            hipLaunchKernelGGL((conv_wgrad_kernel<BM_, BN_, true, true, TAG_>), grid, dim3(256), 0, st, gg, x, dy, target, p.cps, acc_direct, Batch{0, 0, 0, 0});  \
-        else if (veca)                                                                                              \
-            hipLaunchKernelGGL((conv_wgrad_kernel<BM_, BN_, true, false, TAG_>), grid, dim3(256), 0, st, gg, x, dy, target, p.cps, acc_direct, Batch{0, 0, 0, 0}); \
-        else if (vecb)                                                                                              \
-            hipLaunchKernelGGL((conv_wgrad_kernel<BM_, BN_, false, true, TAG_>), grid, dim3(256), 0, st, gg, x, dy, target, p.cps, acc_direct, Batch{0, 0, 0, 0}); \
-        else                                                                                                        \
-            hipLaunchKernelGGL((conv_wgrad_kernel<BM_, BN_, false, false, TAG_>), grid, dim3(256), 0, st, gg, x, dy, target, p.cps, acc_direct, Batch{0, 0, 0, 0});\
-    } while (0)
-#define MG_LAUNCH_WGRAD(BM_, BN_) do { if (hp) MG_LAUNCH_WGRAD_T(BM_, BN_, 2); else MG_LAUNCH_WGRAD_T(BM_, BN_, 0); } while (0)
     probe_begin(st);
-    if (p.big) MG_LAUNCH_WGRAD(128, 128);
-    else MG_LAUNCH_WGRAD(64, 64);
+    dispatch_tile(p.bm, p.bn, [&](auto bm, auto bn) {
+        constexpr int BM_ = decltype(bm)::value, BN_ = decltype(bn)::value;
+        if constexpr (BM_ == BN_) {      // (the weight gradient has square tiles only)
+            const dim3 grid((unsigned)(((g->Co + BM_ - 1) / BM_) * ((g->KH * g->KW * g->Ci + BN_ - 1) / BN_)), 1, p.splits);
+            dispatch_tag(p.tag, [&](auto tag) {
+                dispatch_bool(p.veca, [&](auto veca) {
+                    dispatch_bool(p.vecb, [&](auto vecb) {
+                        hipLaunchKernelGGL((conv_wgrad_kernel<BM_, BN_, decltype(veca)::value, decltype(vecb)::value, decltype(tag)::value>),
+                                           grid, dim3(256), 0, st, gg, x, dy, target, p.cps, acc_direct, Batch{0, 0, 0, 0});
+                    });
+                });
+            });
+        }
+    });
     probe_end(st);
-#undef MG_LAUNCH_WGRAD_T
-#undef MG_LAUNCH_WGRAD
     MG_CHECK_LAUNCH();
     if (p.splits > 1) {
-        const unsigned blocks = (unsigned)((n_out / 4 + 255) / 256 > 4096 ? 4096 : (n_out / 4 + 255) / 256 + 1);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, (const float*)workspace, p.splits,
-                           n_out, dw, accumulate);
+        splitk_reduce(wgrad_reduce_grid(n_out / 4), (const float*)workspace, p.splits, n_out, dw, accumulate, st);
         MG_CHECK_LAUNCH();
     }
     if (dbias) {

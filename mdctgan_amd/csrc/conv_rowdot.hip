@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "mdctgan_hip.h"
+#include "internal.h"
 
 namespace {
 
@@ -288,12 +289,11 @@ inline int rowdot_waves(long long M) {
 
 }  // namespace
 
-// internal to the library (called from conv_igemm.hip, another translation unit): not part of the C ABI, hidden from the .so's exports
-#define MG_INTERNAL __attribute__((visibility("hidden")))
+// internal to the library (called from conv_igemm.hip, another translation unit): declared MG_INTERNAL in internal.h
 extern "C" {
 
 // 0: not applicable, otherwise the per-lane slice count of the kernel instance that would run
-MG_INTERNAL int mg_conv_rowdot_kq(const mg_conv_geom* g) {
+int mg_conv_rowdot_kq(const mg_conv_geom* g) {
     if (!g || g->Co != 1 || g->Ci % 4 != 0 || g->KH > 255 || g->KW > 255 || g->Ci >= 32768) return 0;
     const int K = g->KH * g->KW * g->Ci;
     if (K <= 16 * 256) return 16;
@@ -301,8 +301,7 @@ MG_INTERNAL int mg_conv_rowdot_kq(const mg_conv_geom* g) {
     return 0;
 }
 
-MG_INTERNAL int mg_conv_rowdot_fwd(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int act,
-                       void* stream) {
+int mg_conv_rowdot_fwd(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int act, void* stream) {
     const int kq = mg_conv_rowdot_kq(g);
     if (!kq || !x || !w || !y) return MG_ERR_ARG;
     const Geom gg{g->B, g->H, g->W, g->Ci, g->OH, g->OW, g->Co, g->KH, g->KW, g->stride, g->pad, g->reflect};
@@ -327,7 +326,7 @@ MG_INTERNAL int mg_conv_rowdot_fwd(const mg_conv_geom* g, const float* x, const 
     return MG_OK;
 }
 
-MG_INTERNAL size_t mg_conv_rowdot_wgrad_workspace(const mg_conv_geom* g) {
+size_t mg_conv_rowdot_wgrad_workspace(const mg_conv_geom* g) {
     if (!mg_conv_rowdot_kq(g)) return 0;
     const int KP = g->KH * g->KW * g->Ci + 4;
     const dim3 tg = co1_grid(g);
@@ -335,7 +334,7 @@ MG_INTERNAL size_t mg_conv_rowdot_wgrad_workspace(const mg_conv_geom* g) {
     return ((size_t)nw * KP + KP) * sizeof(float) + mg_colsum_workspace(nw, KP) + 512;
 }
 
-MG_INTERNAL int mg_conv_rowdot_wgrad(const mg_conv_geom* g, const float* x, const float* dy, float* dw, float* dbias,
+int mg_conv_rowdot_wgrad(const mg_conv_geom* g, const float* x, const float* dy, float* dw, float* dbias,
                          int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
     const int kq = mg_conv_rowdot_kq(g);
     if (!kq || !x || !dy || !dw || !workspace || workspace_bytes < mg_conv_rowdot_wgrad_workspace(g)) return MG_ERR_ARG;

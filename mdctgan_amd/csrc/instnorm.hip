@@ -5,6 +5,7 @@
 // residual add :462 that follow it.
 #include <cstdlib>
 #include "act.h"
+#include "internal.h"
 
 namespace {
 
@@ -542,11 +543,10 @@ int mg_instnorm_fwd_h(const float* x, int B, int HW, int C, float eps, int act, 
     return MG_OK;
 }
 
-// library-internal (conv_igemm.hip: mg_conv_fwd_instnorm_*): InstanceNorm straight from a convolution's split-K slabs
-__attribute__((visibility("hidden"))) int mg_instnorm_slab_ok(int HW, int C) { return slab_np(HW, C) ? 1 : 0; }
-__attribute__((visibility("hidden"))) int mg_instnorm_fwd_slabs(const float* part, int S, const float* bias, int round_f16, float* x_out,
-                                                               int B, int HW, int C, float eps, int act, const float* residual,
-                                                               float* y, float* mean, float* rstd, void* stream, void* y16v) {
+// library-internal (internal.h; conv_igemm.hip: mg_conv_fwd_instnorm_*): InstanceNorm straight from a convolution's split-K slabs
+int mg_instnorm_slab_ok(int HW, int C) { return slab_np(HW, C) ? 1 : 0; }
+int mg_instnorm_fwd_slabs(const float* part, int S, const float* bias, int round_f16, float* x_out, int B, int HW, int C, float eps,
+                          int act, const float* residual, float* y, float* mean, float* rstd, void* stream, void* y16v) {
     const int np = slab_np(HW, C);
     _Float16* y16 = (_Float16*)y16v;
     if (!np || !part || S < 1 || !y || !mean || !rstd) return MG_ERR_ARG;

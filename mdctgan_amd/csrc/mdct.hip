@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "mdctgan_hip.h"
+#include "internal.h"
 
 namespace {
 
@@ -589,8 +590,8 @@ int mg_imdct4_stitched_rows(const float* spec, int B, int F, int n_fft, const fl
 }
 
 const char* mg_mdct_last_kernel(int which) { return g_last_kernel[which == 1 ? 1 : 0]; }
-// library-internal: the entry points of mdct_pow2.hip report their kernels through the same two slots
-__attribute__((visibility("hidden"))) void mg_mdct_note_kernel(int which, const char* name) { g_last_kernel[which == 1 ? 1 : 0] = name; }
+// library-internal (internal.h): the entry points of mdct_pow2.hip report their kernels through the same two slots
+void mg_mdct_note_kernel(int which, const char* name) { g_last_kernel[which == 1 ? 1 : 0] = name; }
 
 // See include/mdctgan_hip.h.  The factored kernels' guards (stage-matrix image, T % 4, 16-byte alignment, 32-bit buffer offsets,
 // MG_MDCT_CT / MG_MDCT_FT) decide as in the forward; where they fail MG_ERR_UNSUPPORTED sends the caller to the generic

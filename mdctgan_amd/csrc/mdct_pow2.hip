@@ -31,6 +31,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "mdctgan_hip.h"
+#include "internal.h"
 
 namespace {
 
@@ -418,8 +419,6 @@ int imdct4_pow2_dispatch(const float* spec, int B, int F, int n_fft, const float
                          int out_len, int out_f64, float scale, StitchArgs sa, void* stream, bool row_table = false);
 
 }  // namespace
-
-extern "C" __attribute__((visibility("hidden"))) void mg_mdct_note_kernel(int which, const char* name);     // mdct.hip (library-internal)
 
 extern "C" {
 

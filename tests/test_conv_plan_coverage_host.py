@@ -1,8 +1,10 @@
-"""Every convolution kernel instance the dispatch macros of csrc/conv_igemm.hip, csrc/conv_dma.h and dense_launch can launch is
-reached by a per-element float64 parity case: the case tables of test_conv_gpu.py, test_amp_gpu.py and test_conv_plans_gpu.py
-are walked with their planner hooks applied and mg_conv_plan_name collected for the three passes -- on the host, no GPU.
-The list below is written out by hand from MG_LAUNCH_FWD / MG_LAUNCH_DGRAD / MG_LAUNCH_WGRAD, wino_launch_tiles,
-CD_TILE_DISPATCH / conv_dma_wgrad_launch and dense_launch: whoever adds a tile or a tag adds it here and then needs a case."""
+"""Every convolution kernel instance the dispatchers of csrc/conv_igemm.hip, csrc/conv_dma.h and dense_launch
+can launch is reached by a per-element float64 parity case: the case tables of test_conv_gpu.py, test_amp_gpu.py and
+test_conv_plans_gpu.py are walked with their planner hooks applied and mg_conv_plan_name collected for the three passes -- on
+the host, no GPU.  The list below is written out by hand from the alternatives of dispatch_tile / dispatch_tag / dispatch_bool
+as the three generic launchers and wino_gemm nest them, CD_TILE_DISPATCH / conv_dma_wgrad_launch and dense_launch: whoever adds
+a tile or a tag adds it here and then needs a case.  (mg_conv_plan_name prints the pick the launcher dispatches on, so a name
+seen here is an instance launched.)"""
 import itertools
 import os
 
@@ -11,8 +13,8 @@ import test_conv_gpu
 import test_conv_plans_gpu as P
 
 F32, F16 = 0, 1
-IGEMM_TILES = ((128, 128), (128, 64), (64, 64))                  # MG_LAUNCH_FWD / MG_LAUNCH_DGRAD / wino_launch_tiles
-WGRAD_TILES = ((128, 128), (64, 64))                             # MG_LAUNCH_WGRAD, wino_wgrad
+IGEMM_TILES = ((128, 128), (128, 64), (64, 64))                  # dispatch_tile: conv_fwd, conv_dgrad, wino_gemm
+WGRAD_TILES = ((128, 128), (64, 64))                             # ... its square tiles: mg_conv_wgrad_chk, wino_gemm's pass 2
 DMA_TILES = ((64, 64), (64, 128), (128, 64), (128, 128))         # CD_TILE_DISPATCH, dense_launch
 # tags: 0 float32 convolution, 2 float16 convolution, 1 / 5 the float32 Winograd-domain GEMMs of 16 / 25 positions, 3 the float16 ones
 
