@@ -82,13 +82,15 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
     return base + idx;
 }
 
-// Host side: blocks of 256 threads for a grid-stride pass over n elements, `per_thread` elements a thread, at most 4096 blocks
-inline unsigned grid_for(size_t n, int per_thread = 1) {
-    size_t b = (n + 256 * (size_t)per_thread - 1) / (256 * (size_t)per_thread);
-    if (b > 4096) b = 4096;
+// Host side, the one grid rule of the grid-stride kernels: ceil(n / per_block) blocks, at most `cap`, at least one
+inline unsigned grid_blocks(size_t n, size_t cap, size_t per_block = 256) {
+    size_t b = (n + per_block - 1) / per_block;
+    if (b > cap) b = cap;
     if (b < 1) b = 1;
     return (unsigned)b;
 }
+// blocks of 256 threads for a grid-stride pass over n elements, `per_thread` elements a thread, at most 4096 blocks
+inline unsigned grid_for(size_t n, int per_thread = 1) { return grid_blocks(n, 4096, 256 * (size_t)per_thread); }
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 #define MG_CHECK_LAUNCH()                              \

@@ -13,7 +13,7 @@
 //     dX[p][ci]   = sum_tap Gt[tap][p] * W[tap][ci]          (GEMM pixels x Ci x 64)
 // Every x element is read once per pass, the FLOPs (64/taps more than necessary) run on the MFMA pipe, and the tap-major
 // Zt / Gt make both the GEMM epilogue and the gather / scatter kernels fully coalesced.
-// Included inside the anonymous namespace of conv_igemm.hip, after dense_gemm.h.
+// Included inside the anonymous namespace of conv_plan.h, after dense_gemm.h.
 #pragma once
 
 constexpr int CO1_TAPS = 64;       // tap rows of the padded weight matrix / Zt / Gt
@@ -191,10 +191,7 @@ __global__ void co1_sum_final_kernel(const float* __restrict__ part, int n, floa
     if (threadIdx.x == 0) out[0] = accumulate ? out[0] + red[0] : red[0];
 }
 
-inline unsigned co1_grid(long long n) {
-    long long b = (n + 255) / 256;
-    return (unsigned)(b > 16384 ? 16384 : (b < 1 ? 1 : b));
-}
+inline unsigned co1_grid(long long n) { return grid_blocks((size_t)n, 16384); }      // (n >= 0 at every site)
 
 // Zt[64][ldz] = Wp[64][Ci] x X[Mp][Ci]^T   (columns [Mp, ldz) are never written and never gathered)
 inline void co1_gemm_z(const mg_conv_geom* g, const float* wp, const float* x, float* zt, hipStream_t st) {

@@ -16,7 +16,7 @@
 constexpr unsigned CD_OOB = 0x80000000u;      // >= any num_records: the DMA lane reads zeros
 
 // HALF instances (autocast, MG_PRECISION_F16): the same kernels over float16 copies of the activations and weights (cast
-// pre-passes, conv_igemm.hip) on v_mfma_f32_32x32x16_f16.  A chunk row is still 128 bytes -- 64 channels -- so the gather,
+// pre-passes, conv_plan.h: cd_stage16) on v_mfma_f32_32x32x16_f16.  A chunk row is still 128 bytes -- 64 channels -- so the gather,
 // the LDS images of the k-contiguous operands and the pipeline are unchanged; ds_read_b128 yields the 8-half MFMA operand.
 // Row-contiguous operands (the weight gradient's two sides, the data gradient's weights) are k-major LDS images [64][R]
 // halves read with ds_read_b64_tr_b16 (16 lanes fetch a [4 k][16 columns] block, every lane receives the 4 k of its

@@ -11,7 +11,7 @@
 // per element, which is what bounds these layers.  The arithmetic is that of the TAG-2 implicit-GEMM kernels (operands
 // rounded to float16, exact products, float32 accumulation, forward / data-gradient outputs rounded through float16).
 // Eligibility: stride 1, Ci % 64 == 0, Co % 64 == 0, output pixels <= MG_H16_MAX_RATIO x Co (default 2, measured: configs[1] --fp16 90.5 / 92.4 / 92.5 steps/s at 1 / 2 / 4
-// ).  Included inside conv_igemm.hip's second anonymous namespace.
+// ).  Included inside the anonymous namespace of conv_plan.h, after dense_gemm_h.h (to_geom, the probe, FwdDefer, splitk_*).
 #pragma once
 
 __device__ __forceinline__ uint4 h16_pack8(const float4 a, const float4 b) {
@@ -201,10 +201,7 @@ size_t h16_wgrad_ws(const mg_conv_geom* g) {
     const long long M = (long long)g->B * g->OH * g->OW;
     return h16_wgrad_cs_offset(g) + (mg_colsum_workspace(M, g->Co) + 255) / 256 * 256 + 256;
 }
-inline unsigned h16_grid(size_t n) {
-    size_t b = (n + 255) / 256;
-    return (unsigned)(b > 16384 ? 16384 : (b < 1 ? 1 : b));
-}
+inline unsigned h16_grid(size_t n) { return grid_blocks(n, 16384); }
 int h16_prepare(const mg_conv_geom* g, const float* w, void* w16, hipStream_t st) {
     const size_t n8 = (size_t)g->Co * g->KH * g->KW * g->Ci / 8;
     hipLaunchKernelGGL(h16_cast_kernel, dim3(h16_grid(n8)), dim3(256), 0, st, w, (_Float16*)w16, n8);
@@ -277,8 +274,7 @@ int h16_fwd(const mg_conv_geom* g, const float* x, const float* w, const float* 
         if (defer && act == MG_ACT_NONE && p.splits > 1) {
             *defer = FwdDefer{part, p.splits, bias, 1, true};        // the caller's InstanceNorm kernel finishes the sum
         } else {
-            hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(h16_grid(n / 4)), dim3(256), 0, st, (const float*)part, p.splits, n, g->Co,
-                               bias, act, y, 1);
+            splitk_epilogue(h16_grid(n / 4), part, p.splits, n, g->Co, bias, act, y, 1, st);
         }
     }
     MG_CHECK_LAUNCH();
@@ -311,8 +307,7 @@ int h16_dgrad(const mg_conv_geom* g, const float* dy, const float* w, float* dx,
         const size_t n = (size_t)M * g->Ci;
         const float* ad = addend ? *addend : nullptr;
         if (addend) *addend = nullptr;
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(h16_grid(n / 4)), dim3(256), 0, st, (const float*)part, p.splits, n, g->Ci,
-                           (const float*)nullptr, MG_ACT_NONE, dx, 1, ad);
+        splitk_epilogue(h16_grid(n / 4), part, p.splits, n, g->Ci, nullptr, MG_ACT_NONE, dx, 1, st, ad);
     }
     MG_CHECK_LAUNCH();
     return MG_OK;
@@ -361,8 +356,7 @@ int h16_wgrad(const mg_conv_geom* g, const float* x, const float* dy, float* dw,
     probe_end(st);
     if (p.splits > 1) {
         const size_t n = (size_t)g->Co * N;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(h16_grid(n / 4)), dim3(256), 0, st, (const float*)part, p.splits, n, dw,
-                           accumulate);
+        splitk_reduce(h16_grid(n / 4), part, p.splits, n, dw, accumulate, st);
     }
     MG_CHECK_LAUNCH();
     return MG_OK;

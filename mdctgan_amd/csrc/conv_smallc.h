@@ -4,7 +4,7 @@
 // into a 64 x 48 result (weight gradient): the MFMA tiles run nearly empty and the loaders gather single floats
 // (3-4 TFLOP/s measured).  Both are a few hundred FMAs per pixel on data that streams once, so they run on the VALU
 // with the weights / patch values as wave-uniform scalar operands and the activations as coalesced vector loads.
-// Included in conv_igemm.hip's anonymous namespace (Geom, reflect_idx, ld4, splitk_reduce_kernel).
+// Needs: conv_kernels.h (Geom, reflect_idx, ld4).  Its host side is conv_smallc_host.h.
 #pragma once
 
 namespace {
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(KH * 64) void conv_smallc_wgrad_kernel(Geom g, cons
 
 // ---- forward of the same layers on the MFMA pipe ----------------------------------------------------------------------------
 // y[b][oy][ox][co] = act(bias[co] + sum_k patch(b, oy, ox)[k] * w[co][k]),  k = (ky, kx, ci) in OHWI order, K = KH*KW*CI even.
-// As a GEMM this is [pixels] x [K <= 98] x [Co]: the implicit-GEMM loaders of conv_igemm.hip gather single floats for it
+// As a GEMM this is [pixels] x [K <= 98] x [Co]: the implicit-GEMM loaders of conv_kernels.h gather single floats for it
 // (2-3 channels per pixel: 29 TFLOP/s on the 2 -> 64 stem).  Here one workgroup owns an output row: the KH input rows it touches
 // are staged once into LDS with the padding materialised (as in the weight gradient above), so the A fragment of
 // v_mfma_f32_32x32x2_f32 -- lane (pixel r, k parity h) needs patch(r)[2j + h] -- is ONE ds_read_b32 at

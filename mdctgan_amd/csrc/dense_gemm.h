@@ -1,7 +1,7 @@
 // Batched dense GEMM on the exact-f32 MFMA pipe for the Winograd-domain products (forward, data gradient, weight
 // gradient of the F(2x2,3x3) / F(2x2,4x4) / F(4x4,2x2) families): C_z[M][N] = A_z[M][K] * B_z[K][N], z = 0..P-1.
 //
-// What differs from the convolution kernels' dense paths (conv_igemm.hip) -- all measured on MI355X with
+// What differs from the convolution kernels' dense paths (conv_kernels.h) -- all measured on MI355X with
 // scripts/ubench/gemm_bench.hip:
 //  * the workgroup tile and the per-wave tile are template parameters: a wave owns MB x NB accumulator blocks of 32x32
 //    (two or four independent MFMA chains per wave, every LDS fragment feeds NB / MB MFMAs), 4 or 8 waves per workgroup;

@@ -1,5 +1,5 @@
 // 32-deep chunk of the exact-f32 MFMA GEMM over row-major LDS images (row pitch 36 floats, k contiguous): shared by the
-// forward convolution kernel (conv_igemm.hip) and the MDCT GEMM kernel (mdct.hip).  Included inside each translation
+// forward convolution kernel (conv_kernels.h) and the MDCT GEMM kernel (mdct.hip).  Included inside each translation
 // unit's anonymous namespace.
 #pragma once
 

@@ -8,7 +8,7 @@
 //             reflection / zero padding is the transpose of the forward gather)
 //   wgrad     dg = G^T [ sum_tiles (B^T d B) .* (A dy A^T) ] G
 // The element-wise products summed over channels / tiles are 16 independent GEMMs, run as ONE batched launch of
-// the implicit-GEMM kernels with a 1x1 geometry (conv_igemm.hip); everything here is the HBM-bound transforms.
+// the implicit-GEMM kernels with a 1x1 geometry (conv_kernels.h); everything here is the HBM-bound transforms.
 // Layouts: V / M: [16][T][C] (T = B * TH * TW tiles), U: [16][Co][Ci].
 #pragma once
 #include "adam.h"
@@ -724,9 +724,6 @@ __global__ void wino_adam_kernel(const float* __restrict__ dU, int Co, int Ci, f
     }
 }
 
-inline unsigned wino_grid(size_t n) {
-    size_t b = (n + 255) / 256;
-    return (unsigned)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
-}
+inline unsigned wino_grid(size_t n) { return grid_blocks(n, 8192); }
 
 }  // namespace

@@ -1,8 +1,8 @@
-"""Every convolution kernel instance the dispatchers of csrc/conv_igemm.hip, csrc/conv_dma.h and dense_launch
+"""Every convolution kernel instance the dispatchers of csrc/conv_igemm.hip, csrc/wino_host.h, csrc/conv_dma.h and dense_launch
 can launch is reached by a per-element float64 parity case: the case tables of test_conv_gpu.py, test_amp_gpu.py and
 test_conv_plans_gpu.py are walked with their planner hooks applied and mg_conv_plan_name collected for the three passes -- on
-the host, no GPU.  The list below is written out by hand from the alternatives of dispatch_tile / dispatch_tag / dispatch_bool
-as the three generic launchers and wino_gemm nest them, CD_TILE_DISPATCH / conv_dma_wgrad_launch and dense_launch: whoever adds
+the host, no GPU.  The list below is written out by hand from the alternatives of dispatch_tile / dispatch_tag /
+dispatch_wino_tag / dispatch_bool (csrc/conv_plan.h) as the three generic launchers and wino_gemm nest them, CD_TILE_DISPATCH / conv_dma_wgrad_launch and dense_launch: whoever adds
 a tile or a tag adds it here and then needs a case.  (mg_conv_plan_name prints the pick the launcher dispatches on, so a name
 seen here is an instance launched.)"""
 import itertools
