@@ -535,10 +535,18 @@ typedef struct {
                     * torch.autocast(float16) for convolutions (train.py:161-164 with --fp16): operands rounded to
                     * float16 as they are staged, products on the f16 MFMA pipe, float32 accumulation, outputs of the
                     * forward / data-gradient passes rounded through float16 (overflow -> inf, as a float16 tensor
-                    * would), weight gradients kept in float32.  Tensors stay float32 in memory. */
+                    * would), weight gradients kept in float32.  Tensors stay float32 in memory.
+                    * MG_PRECISION_F32_WINO43 (opt-in, forward passes of inference only): exact float32 products as
+                    * MG_PRECISION_F32, in Winograd F(4x4,3x3) arithmetic where the layer is eligible -- 3x3 stride-1 pad-1,
+                    * H and W multiples of 4, Ci and Co multiples of 16 and >= 256 (MG_WINO43_MIN_C in the environment, read
+                    * per call, overrides the 256).  36 positions, K = Ci, T = B*(H/4)*(W/4) tiles; points (0, 1, -1, 1/2, -2,
+                    * inf), error ~3.5e-6 of the output scale at Ci = 1024 (F(2x2,3x3): 4e-7).  An ineligible geometry runs
+                    * exactly as under MG_PRECISION_F32 (same kernels, same bits).  An eligible one has no gradients: the
+                    * data- and weight-gradient entry points return MG_ERR_UNSUPPORTED and their workspace queries 0. */
 } mg_conv_geom;
 #define MG_PRECISION_F32 0
 #define MG_PRECISION_F16 1
+#define MG_PRECISION_F32_WINO43 2
 
 /* y = act(conv(x, w) + bias)            (bias nullable).  workspace (nullable): mg_conv_fwd_workspace() bytes of
  * scratch that lets deep-K / small-M*N layers split K across workgroups (without it they run unsplit). */
@@ -612,7 +620,11 @@ int mg_conv_fwd_instnorm_h(const mg_conv_geom* g, const float* x, const float* w
  * tiles need.  v_next: mg_conv_wino_tiles_bytes(g_next, 0) bytes (16 * T * Co floats); the next layer's call takes it as tiles->v
  * with MG_TILES_V_FILLED and skips its own input transform -- bit-identical results (the same float32 arithmetic on the same
  * values).  Only where mg_conv_wino_vnext_ok(g) != 0 (float32 F(2x2,3x3) layers on maps of <= 64 tiles per sample); MG_ERR_ARG
- * elsewhere.  Replaces nothing in the reference: it removes one launch and one read of y per trunk layer. */
+ * elsewhere.  Replaces nothing in the reference: it removes one launch and one read of y per trunk layer.
+ * MG_PRECISION_F32_WINO43 layers that run as F(4x4,3x3) have the same pair: on maps of <= 40 tiles (640 pixels) per sample with
+ * Co % 32 == 0 the inverse transform and the InstanceNorm are one kernel, mg_conv_wino_vnext_ok(g) != 0, and v_next is the
+ * 36 * T * Co float image of a following F(4x4,3x3) layer.  The caller hands an image only to a layer of the family it was written
+ * for (the same mg_conv_wino_weights_bytes / (Co * Ci) positions). */
 int mg_conv_wino_vnext_ok(const mg_conv_geom* g);
 int mg_conv_fwd_instnorm_next(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y_raw, float eps,
                               int act, const float* residual, float* y, float* mean, float* rstd, void* workspace,

@@ -26,7 +26,7 @@ class ConvGeom(C.Structure):
                 ("B", "H", "W", "Ci", "OH", "OW", "Co", "KH", "KW", "stride", "pad", "reflect", "precision")]
 
 
-PRECISION_F32, PRECISION_F16 = 0, 1
+PRECISION_F32, PRECISION_F16, PRECISION_F32_WINO43 = 0, 1, 2
 
 
 _p, _i, _f, _ll, _sz = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t

@@ -20,7 +20,7 @@ constexpr int CO1_TAPS = 64;       // tap rows of the padded weight matrix / Zt 
 
 inline bool co1_gemm_ok(const mg_conv_geom* g) {
     const long long Mp = (long long)g->B * g->H * g->W;
-    return (g->precision == MG_PRECISION_F32 || g->precision == MG_PRECISION_F16) && g->Co == 1 && g->KH * g->KW <= CO1_TAPS && g->Ci % 64 == 0 && Mp % 4 == 0 &&
+    return (g->precision == MG_PRECISION_F32 || g->precision == MG_PRECISION_F16 || g->precision == MG_PRECISION_F32_WINO43) && g->Co == 1 && g->KH * g->KW <= CO1_TAPS && g->Ci % 64 == 0 && Mp % 4 == 0 &&
            Mp * CO1_TAPS < (1LL << 29) && Mp * g->Ci < (1LL << 29);
 }
 inline long long co1_ldz(const mg_conv_geom* g) { return ((long long)g->B * g->H * g->W + 31) / 32 * 32; }

@@ -666,7 +666,7 @@ __global__ __launch_bounds__(256) void conv_dgrad_dma_kernel(CdArgs g) {
 
 inline bool conv_dma_half(const mg_conv_geom* g) { return g->precision == MG_PRECISION_F16; }
 inline bool conv_dma_prec_ok(const mg_conv_geom* g) {
-    return g->precision == MG_PRECISION_F32 || g->precision == MG_PRECISION_F16;
+    return g->precision == MG_PRECISION_F32 || g->precision == MG_PRECISION_F16 || g->precision == MG_PRECISION_F32_WINO43;
 }
 inline int conv_dma_ck(const mg_conv_geom* g) { return conv_dma_half(g) ? 64 : 32; }
 inline double conv_dma_es(const mg_conv_geom* g) { return conv_dma_half(g) ? 2.0 : 4.0; }

@@ -17,6 +17,7 @@
 #include "wino.h"
 #include "wino4.h"
 #include "wino42.h"
+#include "wino43.h"
 #include "conv_smallc.h"
 // host side: probe, plans and picks (with the LDS-DMA families inside its namespace), then the two orchestrations
 #include "conv_plan.h"
@@ -27,9 +28,12 @@ namespace {
 
 // The kernel family of a pass (0 fwd, 1 dgrad, 2 wgrad) of a layer; generic: only the tail every family falls back to.  The
 // special families' predicates are pairwise disjoint apart from co1 / rowdot (both Co == 1: co1 first), so their order here
-// is no priority.
+// is no priority.  F(4x4,3x3) is asked first: its precision value is its own, and a geometry of that value which it does not
+// take meets every other predicate as MG_PRECISION_F32 does.  It names all three passes (the route is a function of the geometry
+// alone); the gradient entry points refuse it.
 ConvRoute conv_route(int pass, const mg_conv_geom* g, bool generic) {
     if (!generic) {
+        if (wino43_ok(g)) return R_WINO43;
         if (co1_gemm_ok(g)) return R_CO1;
         if (pass != 1 && mg_conv_rowdot_kq(g)) return R_ROWDOT;
         if (h16_ok(g)) return R_H16;
@@ -67,7 +71,7 @@ double mg_conv_plan_flops(int pass, const mg_conv_geom* g) {
     if (!geom_ok(g)) return 0.0;
     switch (const ConvRoute r = conv_route(pass, g)) {
     case R_CO1: return 2.0 * CO1_TAPS * (double)g->B * g->H * g->W * g->Ci;      // the 64-tap GEMM (conv_co1.h)
-    case R_WINO: case R_WINO4: case R_WINO42: {
+    case R_WINO: case R_WINO4: case R_WINO42: case R_WINO43: {
         const WinoGeo w = wino_geo(r, g);
         return 2.0 * w.f.P * (double)w.T * (double)g->Co * w.Kc;
     }
@@ -83,7 +87,8 @@ int mg_conv_plan_splits(int pass, const mg_conv_geom* g) {
         const mg_conv_geom gp = cd_reflect_geom(g);
         return conv_dma_dgrad_plan(&gp).splits;
     }
-    if (r == R_WINO || r == R_WINO4 || r == R_WINO42) {      // the Winograd-domain GEMM stage, on either kernel family
+    if (r == R_WINO43 && pass != 0) return 0;      // forward only
+    if (r == R_WINO || r == R_WINO4 || r == R_WINO42 || r == R_WINO43) {      // the Winograd-domain GEMM stage, on either kernel family
         const WinoGemm s = wino_gemm_plan(wino_geo(r, g), pass, g);
         return s.dp.ok ? s.dp.splits : s.tp.splits;
     }
@@ -112,6 +117,7 @@ int mg_conv_plan_order(int pass, const mg_conv_geom* g, int* gm, int* cls_order)
 int mg_conv_plan_name(int pass, const mg_conv_geom* g, char* out, int out_len) {
     if (!geom_ok(g) || !out || out_len < 64 || pass < 0 || pass > 2) return MG_ERR_ARG;
     const char* half = prec_h(g) ? "true" : "false";
+    if (pass != 0 && conv_route(pass, g) == R_WINO43) return MG_ERR_UNSUPPORTED;      // F(4x4,3x3) has no gradient passes
     switch (const ConvRoute r = conv_route(pass, g)) {
     case R_CO1:          // single-output-channel layers as tap GEMMs (conv_co1.h)
         snprintf(out, out_len, pass == 0 ? "dgemm32g_kernel<64, 128, 2, 2, 0, 0, 2, 0, 0>"
@@ -135,7 +141,7 @@ int mg_conv_plan_name(int pass, const mg_conv_geom* g, char* out, int out_len) {
         snprintf(out, out_len, pass == 1 ? "hgemm_kernel<128, 128, 4, 2, true, %d>" : "hgemm_kernel<128, 128, 4, 2, false, %d>", deep ? 3 : 2);
         break;
     }
-    case R_WINO: case R_WINO4: case R_WINO42: {
+    case R_WINO: case R_WINO4: case R_WINO42: case R_WINO43: {
         const WinoGeo w = wino_geo(r, g);
         const WinoGemm s = wino_gemm_plan(w, pass, g);
         if (s.dp.ok) dense_name(pass, w.f.P, s.dp, dense_dims(pass, w.T, g->Co, w.Kc).N, out, out_len);
@@ -175,7 +181,7 @@ size_t mg_conv_fwd_workspace(const mg_conv_geom* g) {
     switch (r) {
     case R_CO1: return co1_fwd_ws(g);
     case R_H16: return h16_fwd_ws(g);
-    case R_WINO: case R_WINO4: case R_WINO42: return wino_ws_bytes(r, 0, g);
+    case R_WINO: case R_WINO4: case R_WINO42: case R_WINO43: return wino_ws_bytes(r, 0, g);
     default: break;
     }
     const TilePlan tp = fwd_plan(g);
@@ -191,6 +197,7 @@ size_t mg_conv_dgrad_workspace(const mg_conv_geom* g) {
     case R_CO1: return co1_dgrad_ws(g);
     case R_H16: return h16_dgrad_ws(g);
     case R_WINO: case R_WINO4: case R_WINO42: return wino_ws_bytes(r, 1, g);
+    case R_WINO43: return 0;          // no data gradient in F(4x4,3x3) arithmetic: mg_conv_dgrad_w refuses the geometry
     default: break;
     }
     const TilePlan tp = dgrad_plan(g);
@@ -211,7 +218,7 @@ size_t mg_conv_wino_weights_bytes(const mg_conv_geom* g) {
     switch (const ConvRoute r = conv_route(0, g)) {
     case R_CO1: return (size_t)CO1_TAPS * g->Ci * sizeof(float);      // tap GEMM: the weights zero-padded to 64 tap rows
     case R_H16: return h16_weights_bytes(g);                          // the float16 weight copy of the autocast GEMM path (conv_h16.h)
-    case R_WINO: case R_WINO4: case R_WINO42: {
+    case R_WINO: case R_WINO4: case R_WINO42: case R_WINO43: {
         const WinoGeo w = wino_geo(r, g);
         return (size_t)w.f.P * g->Co * w.Kc * sizeof(float);
     }
@@ -222,7 +229,7 @@ int mg_conv_wino_prepare(const mg_conv_geom* g, const float* w, float* u, void* 
     if (!mg_conv_wino_weights_bytes(g) || !w || !u || !aligned16(w) || !aligned16(u)) return MG_ERR_ARG;
     switch (const ConvRoute r = conv_route(0, g)) {
     case R_CO1: co1_pad_w(g, w, u, (hipStream_t)stream); break;
-    case R_WINO: case R_WINO4: case R_WINO42: wino_xform_u(wino_geo(r, g), g, w, u, (hipStream_t)stream); break;
+    case R_WINO: case R_WINO4: case R_WINO42: case R_WINO43: wino_xform_u(wino_geo(r, g), g, w, u, (hipStream_t)stream); break;
     default: return h16_prepare(g, w, u, (hipStream_t)stream);
     }
     MG_CHECK_LAUNCH();
@@ -234,6 +241,9 @@ size_t mg_conv_wino_tiles_bytes(const mg_conv_geom* g, int which) {
     switch (const ConvRoute r = conv_route(0, g)) {
     case R_H16: return 0;
     case R_CO1: return which == 1 ? co1_zt_bytes(g) : (which == 0 ? co1_xr_bytes(g) : 0);   // Gt (data gradient -> weight gradient); autocast: the rounded x
+    case R_WINO43:      // V only: no gradient pass reads an image of the output gradient
+        if (which != 0) return 0;
+        [[fallthrough]];
     case R_WINO: case R_WINO4: case R_WINO42: {
         const WinoGeo w = wino_geo(r, g);
         return which == 0 ? (size_t)w.f.P * w.T * w.Kc * sizeof(float) : which == 1 ? (size_t)w.f.P * w.T * g->Co * sizeof(float) : 0;
@@ -273,6 +283,10 @@ int mg_conv_wgrad(const mg_conv_geom* g, const float* x, const float* dy, float*
 static bool wino_norm_ok(const mg_conv_geom* g) {
     return geom_ok(g) && conv_route(0, g) == R_WINO && !prec_h(g) && wino_out_norm_ok(g->OH / 2, g->OW / 2, g->Co);
 }
+// ... and the F(4x4,3x3) one (wino43.h: wino43_out_norm_kernel): maps of <= 40 tiles per sample, which also admit the hand-over
+static bool wino43_norm_ok(const mg_conv_geom* g) {
+    return geom_ok(g) && conv_route(0, g) == R_WINO43 && wino43_out_norm_ok(g->OH / 4, g->OW / 4, g->Co);
+}
 int mg_conv_wino_md_from_norm_ok(const mg_conv_geom* g) { return wino_norm_ok(g) ? 1 : 0; }
 int mg_instnorm_bwd_wino_md(const mg_conv_geom* g, const float* gy, const float* y_raw, const float* mean, const float* rstd,
                             int act, float* md, void* stream) {
@@ -303,6 +317,7 @@ int mg_conv_fwd_instnorm_w(const mg_conv_geom* g, const float* x, const float* w
 // The fused F(2x2,3x3) output transform + InstanceNorm kernel can also write the NEXT 3x3 stride-1 pad-1 layer's input image
 // (wino.h: wino_out_norm_kernel<NT, true>): maps of <= 64 tiles per sample.
 static bool wino_vnext_ok(const mg_conv_geom* g) {
+    if (wino43_norm_ok(g)) return true;
     return wino_norm_ok(g) && wino_out_norm_next_ok(g->OH / 2, g->OW / 2, g->Co) && g->Co % 16 == 0;
 }
 int mg_conv_wino_vnext_ok(const mg_conv_geom* g) { return g && wino_vnext_ok(g) ? 1 : 0; }
@@ -339,10 +354,11 @@ static int conv_fwd_instnorm_impl(const mg_conv_geom* g, const float* x, const f
     if (!workspace || workspace_bytes < mg_conv_fwd_instnorm_workspace(g)) return MG_ERR_ARG;
     // y_raw == NULL (inference: no backward pass will read the raw convolution output): the fused kernel skips that store -- a
     // fifth of its HBM bytes at batch 64 -- and the two-call path normalises in place
-    if (wino_norm_ok(g) && aligned16(x) && aligned16(w) && (!y_raw || aligned16(y_raw)) && aligned16(y) && aligned16(mean) &&
+    const bool n43 = wino43_norm_ok(g);
+    if ((n43 || wino_norm_ok(g)) && aligned16(x) && aligned16(w) && (!y_raw || aligned16(y_raw)) && aligned16(y) && aligned16(mean) &&
         aligned16(rstd) && aligned16(workspace) && (!bias || aligned16(bias)) && (!residual || aligned16(residual))) {
         const WinoNorm nrm{eps, act, residual, y, mean, rstd, v_next, next_reflect};
-        return wino_fwd(wino_geo(R_WINO, g), g, x, w, bias, y_raw, MG_ACT_NONE, (float*)workspace, (hipStream_t)stream,
+        return wino_fwd(wino_geo(n43 ? R_WINO43 : R_WINO, g), g, x, w, bias, y_raw, MG_ACT_NONE, (float*)workspace, (hipStream_t)stream,
                         wt ? wt->u : nullptr, wt ? wt->v : nullptr, wt && wt->v && (wt->flags & MG_TILES_V_FILLED), &nrm);
     }
     if (v_next) return MG_ERR_ARG;           // (unreachable after wino_vnext_ok: the fused path above is the only writer of v_next)
@@ -390,9 +406,10 @@ static int conv_fwd(const mg_conv_geom* g, const float* x, const float* w, const
             return rc;
         }
         break;
-    case R_WINO: case R_WINO4: case R_WINO42:
+    case R_WINO: case R_WINO4: case R_WINO42: case R_WINO43:
         if (al && workspace_bytes >= wino_ws_bytes(r, 0, g))
-            return wino_fwd(wino_geo(r, g), g, x, w, bias, y, act, (float*)workspace, st, u, v, r == R_WINO && !prec_h(g) && v_filled);
+            return wino_fwd(wino_geo(r, g), g, x, w, bias, y, act, (float*)workspace, st, u, v,
+                            (r == R_WINO43 || (r == R_WINO && !prec_h(g))) && v_filled);
         break;
     case R_SMALLC:
         if ((reinterpret_cast<uintptr_t>(w) & 7) == 0) {      // conv_smallc_fwd_kernel reads its weights as float2s
@@ -489,6 +506,7 @@ static int conv_dgrad(const mg_conv_geom* g, const float* dy, const float* w, co
     float* md = wt ? wt->md : nullptr;
     hipStream_t st = (hipStream_t)stream;
     if (g->reflect && g->stride != 1) return MG_ERR_UNSUPPORTED;
+    if (conv_route(1, g) == R_WINO43) return MG_ERR_UNSUPPORTED;          // forward only: a training pass never carries this precision
     const bool plain = !bias && act == MG_ACT_NONE;       // all but the F(2x2,3x3) and generic data gradients need it
     const bool al = workspace && aligned16(dy) && aligned16(w) && aligned16(dx) && aligned16(workspace);
     switch (const ConvRoute r = conv_route(1, g)) {
@@ -597,6 +615,7 @@ size_t mg_conv_wgrad_workspace(const mg_conv_geom* g) {
     case R_ROWDOT: return mg_conv_rowdot_wgrad_workspace(g);
     case R_H16: return h16_wgrad_ws(g);
     case R_WINO: case R_WINO4: case R_WINO42: return wino_ws_bytes(r, 2, g);
+    case R_WINO43: return 0;          // no weight gradient in F(4x4,3x3) arithmetic: mg_conv_wgrad_chk refuses the geometry
     case R_SMALLC: return smallc_wgrad_ws(g);
     default: break;
     }
@@ -644,6 +663,7 @@ int mg_conv_wgrad_h16(const mg_conv_geom* g, const float* x, const float* dy, vo
 int mg_conv_wgrad_chk(const mg_conv_geom* g, const float* x, const float* dy, float* dw, float* dbias, int accumulate,
                       void* workspace, size_t workspace_bytes, void* stream, const mg_wino_tiles* wt, float* found_inf) {
     if (!geom_ok(g) || !dw) return MG_ERR_ARG;
+    if (conv_route(2, g) == R_WINO43) return MG_ERR_UNSUPPORTED;          // forward only
     if (found_inf && !mg_conv_wgrad_checks_finite(g)) return MG_ERR_UNSUPPORTED;   // nobody would look at dw: refuse instead of skipping silently
     if (found_inf && !(x && dy && aligned16(x) && aligned16(dy) && aligned16(dw) && aligned16(workspace))) return MG_ERR_ARG;
     if (!wino_tiles_ok(g, wt)) return MG_ERR_ARG;

@@ -37,7 +37,7 @@ Geom to_geom(const mg_conv_geom* g) {
 inline bool prec_h(const mg_conv_geom* g) { return g->precision == MG_PRECISION_F16; }
 
 bool geom_ok(const mg_conv_geom* g) {
-    if (g && g->precision != MG_PRECISION_F32 && g->precision != MG_PRECISION_F16) return false;
+    if (g && g->precision != MG_PRECISION_F32 && g->precision != MG_PRECISION_F16 && g->precision != MG_PRECISION_F32_WINO43) return false;
     if (!g || g->B <= 0 || g->H <= 0 || g->W <= 0 || g->Ci <= 0 || g->Co <= 0 || g->KH <= 0 || g->KW <= 0) return false;
     if (g->stride < 1 || g->stride > 2 || g->pad < 0) return false;
     if (g->OH != (g->H + 2 * g->pad - g->KH) / g->stride + 1) return false;
@@ -152,6 +152,13 @@ void dense_launch(const DensePlan& p, const DgArgs& a, hipStream_t st) {
         else if (p.bm == 64 && p.bn == 128) dgemm32g_launch<64, 128, 2, 2, AL, BL, 2, 16>(a, st);
         else if (p.bm == 128 && p.bn == 64) dgemm32g_launch<128, 64, 2, 2, AL, BL, 2, 16>(a, st);
         else dgemm32g_launch<64, 64, 2, 2, AL, BL, 2, 16>(a, st);
+    } else if (p.dma && a.P == 36) {      // F(4x4,3x3) has a forward pass only
+        if constexpr (AL == DG_KC && BL == DG_KC) {
+            if (p.bm == 128 && p.bn == 128) dgemm32g_launch<128, 128, 2, 2, AL, BL, 2, 36>(a, st);
+            else if (p.bm == 64 && p.bn == 128) dgemm32g_launch<64, 128, 2, 2, AL, BL, 2, 36>(a, st);
+            else if (p.bm == 128 && p.bn == 64) dgemm32g_launch<128, 64, 2, 2, AL, BL, 2, 36>(a, st);
+            else dgemm32g_launch<64, 64, 2, 2, AL, BL, 2, 36>(a, st);
+        }
     } else if (p.dma) {
         if (p.bm == 128 && p.bn == 128) dgemm32g_launch<128, 128, 2, 2, AL, BL, 2, 25>(a, st);
         else if (p.bm == 64 && p.bn == 128) dgemm32g_launch<64, 128, 2, 2, AL, BL, 2, 25>(a, st);
@@ -522,7 +529,7 @@ inline unsigned wgrad_reduce_grid(size_t n4) { return (n4 + 255) / 256 > 4096 ? 
 // conv_route(pass, g, true): DMA (over the reflect-padded domain for a data gradient), else the implicit GEMM -- and a co1
 // pass tries rowdot first.
 // ---------------------------------------------------------------------------------------------------------
-enum ConvRoute { R_IGEMM, R_DMA, R_DMA_REFLECT, R_CO1, R_ROWDOT, R_H16, R_WINO, R_WINO4, R_WINO42, R_SMALLC };
+enum ConvRoute { R_IGEMM, R_DMA, R_DMA_REFLECT, R_CO1, R_ROWDOT, R_H16, R_WINO, R_WINO4, R_WINO42, R_WINO43, R_SMALLC };
 ConvRoute conv_route(int pass, const mg_conv_geom* g, bool generic = false);
 
 }  // namespace

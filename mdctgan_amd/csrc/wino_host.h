@@ -1,16 +1,28 @@
 // Winograd orchestration on the host: the family predicates, WinoGeo, the GEMM-stage plan, the workspace layout, wino_gemm, the
 // transforms and the three pipelines wino_fwd / wino_dgrad / wino_wgrad.
-// Needs: conv_plan.h (plans, dispatchers, ConvRoute, h16_ok), wino.h, wino4.h, wino42.h.
+// Needs: conv_plan.h (plans, dispatchers, ConvRoute, h16_ok), wino.h, wino4.h, wino42.h, wino43.h.
 #pragma once
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------
 // Winograd orchestration: F(2x2,3x3) (wino.h), F(2x2,4x4) for the stride-1 4x4 PatchGAN layers (wino4.h) and F(4x4,2x2)
-// over the space-to-depth view for the stride-2 ones (wino42.h).  Every pass is one pipeline: transforms into the Winograd
+// over the space-to-depth view for the stride-2 ones (wino42.h), and the opt-in forward-only F(4x4,3x3) of an inference pass
+// (wino43.h).  Every pass is one pipeline: transforms into the Winograd
 // domain, the P position GEMMs as one batched launch, the transform back.
 // ---------------------------------------------------------------------------------------------------------
 bool h16_ok(const mg_conv_geom* g);
+// MG_PRECISION_F32_WINO43 geometries (forward passes under no_grad, opted in): the weight-heavy GEMM-bound layers, where the
+// 36-position GEMMs issue 1.78x fewer FLOPs than F(2x2,3x3)'s 16.  min_c is read per call so the parity tests reach small shapes.
+// Disjoint from every other family's predicate by being asked first (conv_route); an ineligible geometry of this precision
+// routes as MG_PRECISION_F32 does.
+bool wino43_ok(const mg_conv_geom* g) {
+    if (g->precision != MG_PRECISION_F32_WINO43) return false;
+    const char* mc = getenv("MG_WINO43_MIN_C");
+    const int min_c = mc ? atoi(mc) : 256;
+    return g->KH == 3 && g->KW == 3 && g->stride == 1 && g->pad == 1 && g->H % 4 == 0 && g->W % 4 == 0 && g->Ci % 16 == 0 &&
+           g->Co % 16 == 0 && g->Ci >= min_c && g->Co >= min_c;
+}
 bool wino_ok(const mg_conv_geom* g) {
     static const bool off = getenv("MG_NO_WINOGRAD") != nullptr;
     if (h16_ok(g)) return false;             // weight-dominated autocast layers take the float16 GEMM path (conv_h16.h)
@@ -46,10 +58,11 @@ bool wino42_ok(const mg_conv_geom* g) {
 // Per family: positions P, channels per thread of the transform kernels (their grid divisor), and the weight-gradient plan's
 // tile count above which it takes 128x128 tiles, and whether a full grid still splits a deep reduction in three
 struct WinoFamily { int P, vec; long long big_T; bool split3; };
-constexpr WinoFamily kWinoFamily[3] = {
+constexpr WinoFamily kWinoFamily[4] = {
     {16, 4, 1024, false},      // F(2x2,3x3); short reductions (the 8x16 blocks of configs[1]): 64x64 tiles measured 125 vs 148 us
     {25, 2, 4096, true},       // F(2x2,4x4); measured at 2448 tiles: 64x64 232 us, 128x128 252 us
     {25, 2, 4096, true},       // F(4x4,2x2)
+    {36, 2, 4096, true},       // F(4x4,3x3): forward only, the weight-gradient fields are never read
 };
 // A layer in the Winograd domain: T = B * TH * TW tiles, Kc = the GEMMs' input depth (4 Ci for F(4x4,2x2))
 struct WinoGeo { ConvRoute r; WinoFamily f; long long T; int TH, TW, Kc; bool hp; };
@@ -57,6 +70,7 @@ WinoGeo wino_geo(ConvRoute r, const mg_conv_geom* g) {
     WinoGeo w{r, kWinoFamily[r - R_WINO], 0, 0, 0, r == R_WINO42 ? 4 * g->Ci : g->Ci, prec_h(g)};
     if (r == R_WINO) { w.TH = g->H / 2; w.TW = g->W / 2; }
     else if (r == R_WINO4) { w.TH = (g->H + 1) / 2; w.TW = (g->W + 1) / 2; }
+    else if (r == R_WINO43) { w.TH = g->H / 4; w.TW = g->W / 4; }
     else { w.TH = (g->OH + 3) / 4; w.TW = (g->OW + 3) / 4; }
     w.T = (long long)g->B * w.TH * w.TW;
     return w;
@@ -64,7 +78,7 @@ WinoGeo wino_geo(ConvRoute r, const mg_conv_geom* g) {
 inline size_t al256(size_t n) { return (n + 63) / 64 * 64; }   // in floats
 
 // The GEMM stage of a pass (dense_dims): dense_gemm.h where dense_plan takes the shape, else the convolution kernels (TAG 1;
-// 3 = float16; 5 = the 25-position families) on tile plan tp (forward: k32 = the 32-deep kernel).  The one plan that the
+// 3 = float16; 5 = the 25- and 36-position families) on tile plan tp (forward: k32 = the 32-deep kernel).  The one plan that the
 // launch, the workspace (split-K slabs of either path) and mg_conv_plan_name use.
 struct WinoGemm { DensePlan dp; TilePlan tp; int tag; };
 WinoGemm wino_gemm_plan(const WinoGeo& w, int pass, const mg_conv_geom* g) {
@@ -167,6 +181,7 @@ void wino_xform_u(const WinoGeo& w, const mg_conv_geom* g, const float* wt, floa
     const dim3 grid(wino_grid((size_t)g->Co * w.Kc / w.f.vec));
     if (w.r == R_WINO) hipLaunchKernelGGL(wino_weight_xform_kernel, grid, dim3(256), 0, st, wt, g->Co, g->Ci, U);
     else if (w.r == R_WINO4) hipLaunchKernelGGL(wino4_weight_xform_kernel, grid, dim3(256), 0, st, wt, g->Co, g->Ci, U);
+    else if (w.r == R_WINO43) hipLaunchKernelGGL(wino43_weight_xform_kernel, grid, dim3(256), 0, st, wt, g->Co, g->Ci, U);
     else hipLaunchKernelGGL(wino42_weight_xform_kernel, grid, dim3(256), 0, st, wt, g->Co, g->Ci, U);
 }
 void wino_xform_v(const WinoGeo& w, const mg_conv_geom* g, const float* x, float* V, hipStream_t st) {
@@ -175,6 +190,8 @@ void wino_xform_v(const WinoGeo& w, const mg_conv_geom* g, const float* x, float
         hipLaunchKernelGGL(wino_input_xform_kernel, grid, dim3(256), 0, st, x, g->B, g->H, g->W, g->Ci, w.TH, w.TW, 1, g->reflect, V);
     else if (w.r == R_WINO4)
         hipLaunchKernelGGL(wino4_input_xform_kernel, grid, dim3(256), 0, st, x, g->B, g->H, g->W, g->Ci, w.TH, w.TW, V);
+    else if (w.r == R_WINO43)
+        hipLaunchKernelGGL(wino43_input_xform_kernel, grid, dim3(256), 0, st, x, g->B, g->H, g->W, g->Ci, w.TH, w.TW, g->reflect, V);
     else
         hipLaunchKernelGGL(wino42_input_xform_kernel, grid, dim3(256), 0, st, x, g->B, g->H, g->W, g->Ci, w.TH, w.TW, V);
 }
@@ -186,8 +203,8 @@ void wino_xform_md(const WinoGeo& w, const mg_conv_geom* g, const float* dy, flo
 }
 
 // u_pre: the caller's U (mg_conv_wino_prepare); v_keep: the caller keeps V for the weight gradient; v_filled: x's producer
-// wrote V already (mg_conv_fwd_instnorm_next of the layer in front).  nrm (F(2x2,3x3), float32): output transform +
-// InstanceNorm in one kernel (y = the raw convolution output, nrm->y the normalised one).
+// wrote V already (mg_conv_fwd_instnorm_next of the layer in front).  nrm (F(2x2,3x3) and F(4x4,3x3), float32): output transform
+// + InstanceNorm in one kernel (y = the raw convolution output, nrm->y the normalised one).
 int wino_fwd(const WinoGeo& w, const mg_conv_geom* g, const float* x, const float* wt, const float* bias, float* y, int act,
              float* ws, hipStream_t st, const float* u_pre, float* v_keep, bool v_filled, const WinoNorm* nrm = nullptr) {
     const WinoGemm s = wino_gemm_plan(w, 0, g);
@@ -198,6 +215,23 @@ int wino_fwd(const WinoGeo& w, const mg_conv_geom* g, const float* x, const floa
     if (!u_pre) wino_xform_u(w, g, wt, U, st);
     if (!(v_filled && v_keep)) wino_xform_v(w, g, x, V, st);
     wino_gemm(w, s, 0, g, V, U, Mx, ws + o.part, st);
+    if (nrm && w.r == R_WINO43) {       // (callers ask wino43_out_norm_ok first: <= 40 tiles, NT <= 3)
+        const dim3 grid(g->Co / 32, g->B);
+        const int nt = (w.TH * w.TW + 15) / 16;
+        auto go = [&](auto kern, size_t lds) {
+            if (lds) hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wino43_plane_bytes(1, W43_NORM_TILES));
+            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, (const float*)Mx, g->B, w.TH, w.TW, g->Co, bias, *nrm, y);
+        };
+        const size_t plane = wino43_plane_bytes(w.TH, w.TW);
+        if (nt > 3) return MG_ERR_ARG;
+        if (nrm->v_next) {
+            if (nt == 1) go(wino43_out_norm_kernel<1, true>, plane); else if (nt == 2) go(wino43_out_norm_kernel<2, true>, plane); else go(wino43_out_norm_kernel<3, true>, plane);
+        } else {
+            if (nt == 1) go(wino43_out_norm_kernel<1>, 0); else if (nt == 2) go(wino43_out_norm_kernel<2>, 0); else go(wino43_out_norm_kernel<3>, 0);
+        }
+        MG_CHECK_LAUNCH();
+        return MG_OK;
+    }
     if (nrm) {
         const dim3 grid(g->Co / 32, g->B);
         const int nt = (w.TH * w.TW + 31) / 32;
@@ -218,6 +252,8 @@ int wino_fwd(const WinoGeo& w, const mg_conv_geom* g, const float* x, const floa
                            (int)w.hp);
     else if (w.r == R_WINO4)
         hipLaunchKernelGGL(wino4_output_xform_kernel, grid, dim3(256), 0, st, (const float*)Mx, g->B, w.TH, w.TW, g->Co, bias, act, y);
+    else if (w.r == R_WINO43)
+        hipLaunchKernelGGL(wino43_output_xform_kernel, grid, dim3(256), 0, st, (const float*)Mx, g->B, w.TH, w.TW, g->Co, bias, act, y);
     else
         hipLaunchKernelGGL(wino42_output_xform_kernel, grid, dim3(256), 0, st, (const float*)Mx, g->B, g->OH, g->OW, w.TH, w.TW, g->Co,
                            bias, act, y);

@@ -424,7 +424,9 @@ class _ConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, cfg):
         x = to_cl(x)
-        stride, pad, reflect, act, transposed, weight_grad = cfg
+        stride, pad, reflect, act, transposed, weight_grad = cfg[:6]
+        # the precision is read by conv2d() / conv_transpose2d(): amp.wino43 looks at the grad mode, which is always off in here
+        prec = cfg[6] if len(cfg) > 6 else amp.current_precision()
         B, _, H, W = x.shape
         w = weight.detach()
         assert w.is_contiguous(memory_format=CL), "conv weights must be channels_last (OHWI) tensors"
@@ -433,7 +435,7 @@ class _ConvFn(torch.autograd.Function):
         if not transposed:
             Co, Ci = w.shape[0], w.shape[1]
             assert Ci == x.shape[1]
-            g = ops.conv_geom(B, H, W, Ci, Co, KH, KW, stride, pad, reflect, amp.current_precision())
+            g = ops.conv_geom(B, H, W, Ci, Co, KH, KW, stride, pad, reflect, prec)
             _tag_g16(g, weight, bias, weight_grad)
             # Winograd layers: transform the weights once, reuse the image for the data gradient of this step
             if ctx.needs_input_grad[0]:
@@ -458,8 +460,7 @@ class _ConvFn(torch.autograd.Function):
             # high-res [B, sH, sW, Cout_T] -> low-res [B, H, W, Cin_T]
             cin_t, cout_t = w.shape[0], w.shape[1]
             assert cin_t == x.shape[1]
-            g = ops.conv_geom(B, stride * H, stride * W, cout_t, cin_t, KH, KW, stride, pad, False,
-                              amp.current_precision())
+            g = ops.conv_geom(B, stride * H, stride * W, cout_t, cin_t, KH, KW, stride, pad, False, prec)
             assert (g.OH, g.OW) == (H, W), "unsupported ConvTranspose2d geometry"
             # the weight image (Winograd U / float16 copy) serves this call and the backward's data gradient
             u = _weight_image(g, weight) if (ctx.needs_input_grad[0] and x.is_cuda) else None
@@ -469,7 +470,7 @@ class _ConvFn(torch.autograd.Function):
             y = ops.conv_dgrad(g, nhwc_view(x), w, b, act, u=u, md_out=x16, md_filled=x16 is not None)
             ctx.u, ctx.v = u, (x16 if (weight_grad and weight.requires_grad) else None)
         y = nchw_view(y)
-        ctx.g, ctx.cfg = g, cfg
+        ctx.g, ctx.cfg = g, cfg[:6]
         ctx.weight, ctx.bias = weight, bias
         ctx.save_for_backward(x, y if act != ACT_NONE else None)
         return _hang_extra(ctx, y) if act in (ACT_RELU, ACT_LRELU02) else y
@@ -619,11 +620,11 @@ def _conv_backward(ctx, gy, x, y, add=None):
 
 
 def conv2d(x, weight, bias, stride=1, padding=0, reflect=False, act=ACT_NONE, weight_grad=True):
-    return _ConvFn.apply(x, weight, bias, (stride, padding, bool(reflect), act, False, weight_grad))
+    return _ConvFn.apply(x, weight, bias, (stride, padding, bool(reflect), act, False, weight_grad, amp.current_precision()))
 
 
 def conv_transpose2d(x, weight, bias, stride=2, padding=1, act=ACT_NONE, weight_grad=True):
-    return _ConvFn.apply(x, weight, bias, (stride, padding, False, act, True, weight_grad))
+    return _ConvFn.apply(x, weight, bias, (stride, padding, False, act, True, weight_grad, amp.current_precision()))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -644,7 +645,8 @@ class _ConvInstNormFn(torch.autograd.Function):
         B, _, H, W = x.shape
         w = weight.detach()
         assert w.is_contiguous(memory_format=CL), "conv weights must be channels_last (OHWI) tensors"
-        g = ops.conv_geom(B, H, W, w.shape[1], w.shape[0], w.shape[2], w.shape[3], 1, pad, reflect, amp.current_precision())
+        prec = cfg[8] if len(cfg) > 8 else amp.current_precision()       # (read by conv_instnorm(), as the grad mode is)
+        g = ops.conv_geom(B, H, W, w.shape[1], w.shape[0], w.shape[2], w.shape[3], 1, pad, reflect, prec)
         _tag_g16(g, weight, bias, weight_grad)
         if ctx.needs_input_grad[0]:
             u = _weight_image(g, weight, weight_grad)
@@ -654,8 +656,10 @@ class _ConvInstNormFn(torch.autograd.Function):
             u = None
         v, v_filled = None, False
         x16 = _h16_of(x) if ops.precast_ok(0, g) else None
-        xv = (_wino_v_of(x, (B, H, W, w.shape[1], bool(reflect), g.precision))
-              if (pad == 1 and w.shape[2] == 3 and w.shape[3] == 3 and ops.wino_vnext_ok(g)) else None)
+        # (the key names the family by its positions: under amp.wino43 a layer in front may have written F(4x4,3x3) tiles for a
+        # layer that itself runs F(2x2,3x3), or the other way round -- neither reads the other family's image)
+        npos = ops.wino_vnext_positions(g) if (pad == 1 and w.shape[2] == 3 and w.shape[3] == 3) else 0
+        xv = _wino_v_of(x, (B, H, W, w.shape[1], bool(reflect), g.precision, npos)) if npos else None
         if x16 is not None:
             v, v_filled = x16, True
             H16_STATS["used_fwd"] += 1
@@ -667,8 +671,9 @@ class _ConvInstNormFn(torch.autograd.Function):
         # ... and this layer writes the NEXT trunk layer's image when told that one follows (cfg[7]: its padding mode)
         next_reflect = cfg[7] if len(cfg) > 7 else None
         v_next = None
-        if next_reflect is not None and ops.wino_vnext_ok(g) and os.environ.get("MG_NO_WINO_NEXT", "0") != "1":
-            v_next = torch.empty(16 * B * (g.OH // 2) * (g.OW // 2) * g.Co, dtype=torch.float32, device=x.device)
+        if next_reflect is not None and npos and os.environ.get("MG_NO_WINO_NEXT", "0") != "1":
+            tile = 2 if npos == 16 else 4       # F(2x2,3x3) / F(4x4,3x3) output tiles
+            v_next = torch.empty(npos * B * (g.OH // tile) * (g.OW // tile) * g.Co, dtype=torch.float32, device=x.device)
         y16 = (torch.empty(B * g.OH * g.OW * g.Co, dtype=torch.float16, device=x.device)
                if _want_h16(B, g.OH * g.OW, g.Co) else None)
         # under torch.no_grad() nobody reads the raw convolution output again (grad mode is read by conv_instnorm(): inside a
@@ -684,7 +689,7 @@ class _ConvInstNormFn(torch.autograd.Function):
             ctx.save_for_backward(x, nchw_view(y_raw), mean, rstd)
         out = _attach_h16(nchw_view(y), y16)
         if v_next is not None:
-            _attach_wino_v(out, v_next, (B, g.OH, g.OW, g.Co, bool(next_reflect), g.precision))
+            _attach_wino_v(out, v_next, (B, g.OH, g.OW, g.Co, bool(next_reflect), g.precision, npos))
         return out
 
     @staticmethod
@@ -748,7 +753,7 @@ def conv_instnorm(x, weight, bias, padding=0, reflect=False, act=ACT_NONE, resid
     """act(InstanceNorm2d(affine=False)(conv2d(x, weight, bias, stride 1))) + residual.  skip: ("give" | "take", SkipGrad).
     next_reflect (None | bool): the output feeds another 3x3 stride-1 pad-1 convolution with that padding mode -- where the fused
     kernel runs it also writes that layer's Winograd input image (see _attach_wino_v)."""
-    cfg = (padding, bool(reflect), weight_grad, act, eps, skip, torch.is_grad_enabled(), next_reflect)
+    cfg = (padding, bool(reflect), weight_grad, act, eps, skip, torch.is_grad_enabled(), next_reflect, amp.current_precision())
     return _ConvInstNormFn.apply(x, weight, bias, residual, cfg)
 
 

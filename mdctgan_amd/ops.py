@@ -128,10 +128,26 @@ def conv_fwd(g: ConvGeom, x, w, bias=None, act=ACT_NONE, u=None, v_out=None, v_f
 
 def wino_vnext_ok(g: ConvGeom) -> bool:
     """True when conv_fwd_instnorm can also write the next 3x3 layer's Winograd input image (float32 F(2x2,3x3), small maps)."""
-    key = ("vn", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision)
+    key = ("vn", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision, _wino43_env(g))
     hit = _CASTS.get(key)
     if hit is None:
         hit = _CASTS[key] = bool(_lib.load().mg_conv_wino_vnext_ok(g))
+    return hit
+
+
+def _wino43_env(g: ConvGeom):
+    """What the F(4x4,3x3) predicate reads from the environment per call (a cache key beside the geometry)."""
+    import os
+    return os.environ.get("MG_WINO43_MIN_C") if g.precision == _lib.PRECISION_F32_WINO43 else None
+
+
+def wino_vnext_positions(g: ConvGeom) -> int:
+    """Positions P of the Winograd family of a layer with wino_vnext_ok(g) -- 16: F(2x2,3x3), 36: F(4x4,3x3); 0: no hand-over.
+    An input image handed from layer to layer (conv_fwd_instnorm's v_next) is only good for the family it was written for."""
+    key = ("vp", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision, _wino43_env(g))
+    hit = _CASTS.get(key)
+    if hit is None:
+        hit = _CASTS[key] = wino_weights_bytes(g) // (4 * g.Co * g.Ci) if wino_vnext_ok(g) else 0
     return hit
 
 

@@ -698,7 +698,9 @@ class Pix2PixHDModel(BaseModel):
         """pix2pixHD_model.py:618-638.  stitch / rows: see Audio2MDCT.to_audio (sr_audio is then the stitched waveform / the packed
         buffer of stitched waveforms)."""
         self._finish_pending()
-        with torch.no_grad():
+        # --wino43 / MG_WINO43=1 (read per call, as MG_F32_SPLIT is): the eligible 3x3 layers of this pass run as F(4x4,3x3)
+        wino43 = bool(getattr(self.opt, "wino43", False)) or os.environ.get("MG_WINO43", "0") == "1"
+        with torch.no_grad(), amp.wino43(wino43):
             lr_spectro, lr_pha, lr_norm_param = self.preprocess.forward(lr_audio)
             sr_spectro = self.netG.forward(self._two_channel(lr_spectro))
             if self.fit_residual:
