@@ -542,11 +542,24 @@ typedef struct {
                     * per call, overrides the 256).  36 positions, K = Ci, T = B*(H/4)*(W/4) tiles; points (0, 1, -1, 1/2, -2,
                     * inf), error ~3.5e-6 of the output scale at Ci = 1024 (F(2x2,3x3): 4e-7).  An ineligible geometry runs
                     * exactly as under MG_PRECISION_F32 (same kernels, same bits).  An eligible one has no gradients: the
-                    * data- and weight-gradient entry points return MG_ERR_UNSUPPORTED and their workspace queries 0. */
+                    * data- and weight-gradient entry points return MG_ERR_UNSUPPORTED and their workspace queries 0.
+                    * MG_PRECISION_F16_INFER (opt-in, forward passes of inference only): the arithmetic of MG_PRECISION_F16
+                    * -- operands rounded to float16, exact products on the f16 MFMA, float32 accumulation, convolution
+                    * outputs rounded through float16, tensors float32 in memory -- with the Winograd F(2x2,3x3) images of an
+                    * eligible layer kept as float16 in HBM (csrc/wino_h16.h): 3x3 stride-1 pad-1, H and W even, Ci and Co
+                    * multiples of 64 and >= 256, >= 256 tiles (MG_INFER_F16_MIN_C / MG_INFER_F16_MIN_TILES in the
+                    * environment, read per call, override the two 256), and not one of the weight-streaming layers of small
+                    * batches (<= 2 Co pixels), which keep their float16 GEMM path unless MG_INFER_F16_MIN_TILES is set.  An ineligible geometry runs exactly as
+                    * under MG_PRECISION_F16 (same kernels, same bits).  An eligible one has no gradients: the data- and
+                    * weight-gradient entry points return MG_ERR_UNSUPPORTED and their workspace queries 0; its u / v images
+                    * (mg_wino_tiles) are float16: 16*Co*Ci and 16*T*Ci halves, sized by the same two queries. */
 } mg_conv_geom;
 #define MG_PRECISION_F32 0
 #define MG_PRECISION_F16 1
 #define MG_PRECISION_F32_WINO43 2
+#define MG_PRECISION_F16_INFER 3
+/* the two values whose arithmetic is half precision */
+#define MG_PRECISION_IS_HALF(p) ((p) == MG_PRECISION_F16 || (p) == MG_PRECISION_F16_INFER)
 
 /* y = act(conv(x, w) + bias)            (bias nullable).  workspace (nullable): mg_conv_fwd_workspace() bytes of
  * scratch that lets deep-K / small-M*N layers split K across workgroups (without it they run unsplit). */
@@ -629,6 +642,15 @@ int mg_conv_wino_vnext_ok(const mg_conv_geom* g);
 int mg_conv_fwd_instnorm_next(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y_raw, float eps,
                               int act, const float* residual, float* y, float* mean, float* rstd, void* workspace,
                               size_t workspace_bytes, void* stream, const mg_wino_tiles* tiles, float* v_next, int next_reflect);
+/* The MG_PRECISION_F16_INFER sibling of the two calls above, for a layer that runs on float16 Winograd images
+ * (mg_conv_wino_vnext_ok(g) != 0 under that precision: maps of <= 64 tiles per sample; MG_ERR_ARG elsewhere).  v_next16 (nullable):
+ * float16(B^T y B), 16 * T * Co halves = mg_conv_wino_tiles_bytes(g_next, 0) bytes, which the next layer takes as tiles->v with
+ * MG_TILES_V_FILLED.  y16 (nullable): float16(y), as mg_conv_fwd_instnorm_h writes it, for a consumer that stages its operand from
+ * a plain float16 copy.  The convolution output is rounded through float16 before the statistics; y is float32. */
+int mg_conv_fwd_instnorm_next_h(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y_raw, float eps,
+                                int act, const float* residual, float* y, float* mean, float* rstd, void* workspace,
+                                size_t workspace_bytes, void* stream, const mg_wino_tiles* tiles, void* v_next16, int next_reflect,
+                                void* y16);
 int mg_conv_dgrad_w(const mg_conv_geom* g, const float* dy, const float* w, const float* bias, float* dx, int act,
                     void* workspace, size_t workspace_bytes, void* stream, const mg_wino_tiles* tiles);
 /* dw [Co, KH, KW, Ci] = sum over pixels; dbias [Co] (nullable) = column sums of dy.

@@ -26,7 +26,12 @@ class ConvGeom(C.Structure):
                 ("B", "H", "W", "Ci", "OH", "OW", "Co", "KH", "KW", "stride", "pad", "reflect", "precision")]
 
 
-PRECISION_F32, PRECISION_F16, PRECISION_F32_WINO43 = 0, 1, 2
+PRECISION_F32, PRECISION_F16, PRECISION_F32_WINO43, PRECISION_F16_INFER = 0, 1, 2, 3
+
+
+def is_half(precision) -> bool:
+    """MG_PRECISION_IS_HALF: the two precisions whose arithmetic is autocast's (training, and the opt-in inference mode)."""
+    return precision in (PRECISION_F16, PRECISION_F16_INFER)
 
 
 _p, _i, _f, _ll, _sz = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t
@@ -96,6 +101,7 @@ SIGNATURES = {
     "mg_conv_fwd_instnorm_w": (_i, [_G, _p, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _sz, _p, _W]),
     "mg_conv_fwd_instnorm_h": (_i, [_G, _p, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _sz, _p, _W, _p]),
     "mg_conv_fwd_instnorm_next": (_i, [_G, _p, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _sz, _p, _W, _p, _i]),
+    "mg_conv_fwd_instnorm_next_h": (_i, [_G, _p, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _sz, _p, _W, _p, _i, _p]),
     "mg_conv_wino_vnext_ok": (_i, [_G]),
     "mg_conv_dgrad_w": (_i, [_G, _p, _p, _p, _p, _i, _p, _sz, _p, _W]),
     "mg_conv_wgrad_w": (_i, [_G, _p, _p, _p, _p, _i, _p, _sz, _p, _W]),

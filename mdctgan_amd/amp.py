@@ -18,15 +18,18 @@ import torch
 
 from . import _lib, ops
 
-_state = {"precision": _lib.PRECISION_F32, "wino43": False}
+_state = {"precision": _lib.PRECISION_F32, "wino43": False, "infer_f16": False}
 
 
 def current_precision() -> int:
     """The precision a convolution geometry made now carries.  Inside ``wino43()`` a float32 forward pass under
     ``torch.no_grad()`` carries PRECISION_F32_WINO43; with gradients enabled, or inside ``autocast(True)``, the context changes
     nothing.  (An autograd Function's ``forward`` runs with grad mode off even in training: the functional wrappers ask here
-    before they enter one.)"""
+    before they enter one.)  Inside ``infer_f16()`` every forward pass under ``torch.no_grad()`` carries PRECISION_F16_INFER,
+    whatever ``autocast`` and ``wino43`` say (that mode covers float32 only); with gradients enabled it changes nothing either."""
     p = _state["precision"]
+    if _state["infer_f16"] and not torch.is_grad_enabled():
+        return _lib.PRECISION_F16_INFER
     if _state["wino43"] and p == _lib.PRECISION_F32 and not torch.is_grad_enabled():
         return _lib.PRECISION_F32_WINO43
     return p
@@ -44,6 +47,20 @@ def wino43(enabled: bool = True):
         yield
     finally:
         _state["wino43"] = prev
+
+
+@contextlib.contextmanager
+def infer_f16(enabled: bool = True):
+    """Opt-in half-precision inference: forward passes under ``torch.no_grad()`` run with autocast's arithmetic
+    (include/mdctgan_hip.h: MG_PRECISION_F16_INFER), and the eligible 3x3 stride-1 pad-1 layers keep their Winograd images as
+    float16 in HBM (csrc/wino_h16.h).  Off by default; Pix2PixHDModel.inference enters it for --infer_fp16 / MG_INFER_F16=1.
+    ``--fp16`` / ``autocast`` keep meaning "train with AMP"."""
+    prev = _state["infer_f16"]
+    _state["infer_f16"] = bool(enabled)
+    try:
+        yield
+    finally:
+        _state["infer_f16"] = prev
 
 
 @contextlib.contextmanager

@@ -20,7 +20,7 @@ constexpr int CO1_TAPS = 64;       // tap rows of the padded weight matrix / Zt 
 
 inline bool co1_gemm_ok(const mg_conv_geom* g) {
     const long long Mp = (long long)g->B * g->H * g->W;
-    return (g->precision == MG_PRECISION_F32 || g->precision == MG_PRECISION_F16 || g->precision == MG_PRECISION_F32_WINO43) && g->Co == 1 && g->KH * g->KW <= CO1_TAPS && g->Ci % 64 == 0 && Mp % 4 == 0 &&
+    return (g->precision == MG_PRECISION_F32 || MG_PRECISION_IS_HALF(g->precision) || g->precision == MG_PRECISION_F32_WINO43) && g->Co == 1 && g->KH * g->KW <= CO1_TAPS && g->Ci % 64 == 0 && Mp % 4 == 0 &&
            Mp * CO1_TAPS < (1LL << 29) && Mp * g->Ci < (1LL << 29);
 }
 inline long long co1_ldz(const mg_conv_geom* g) { return ((long long)g->B * g->H * g->W + 31) / 32 * 32; }
@@ -33,7 +33,7 @@ inline int co1_wgrad_splits(const mg_conv_geom* g) {
     if (s > chunks / 4) s = chunks / 4;
     return s < 1 ? 1 : s;
 }
-inline bool co1_half(const mg_conv_geom* g) { return g->precision == MG_PRECISION_F16; }
+inline bool co1_half(const mg_conv_geom* g) { return MG_PRECISION_IS_HALF(g->precision); }
 // autocast: x rounded to float16 values (float32 storage), made by the forward call and kept for the weight gradient
 inline size_t co1_xr_bytes(const mg_conv_geom* g) { return co1_half(g) ? co1_al((size_t)g->B * g->H * g->W * g->Ci * 4) : 0; }
 inline size_t co1_fwd_ws(const mg_conv_geom* g) { return co1_wp_bytes(g) + co1_zt_bytes(g) + co1_xr_bytes(g) + 256; }

@@ -664,9 +664,9 @@ __global__ __launch_bounds__(256) void conv_dgrad_dma_kernel(CdArgs g) {
 #endif
 }
 
-inline bool conv_dma_half(const mg_conv_geom* g) { return g->precision == MG_PRECISION_F16; }
+inline bool conv_dma_half(const mg_conv_geom* g) { return MG_PRECISION_IS_HALF(g->precision); }
 inline bool conv_dma_prec_ok(const mg_conv_geom* g) {
-    return g->precision == MG_PRECISION_F32 || g->precision == MG_PRECISION_F16 || g->precision == MG_PRECISION_F32_WINO43;
+    return g->precision == MG_PRECISION_F32 || MG_PRECISION_IS_HALF(g->precision) || g->precision == MG_PRECISION_F32_WINO43;
 }
 inline int conv_dma_ck(const mg_conv_geom* g) { return conv_dma_half(g) ? 64 : 32; }
 inline double conv_dma_es(const mg_conv_geom* g) { return conv_dma_half(g) ? 2.0 : 4.0; }

@@ -152,7 +152,7 @@ inline double h16_max_ratio() {
     return r;
 }
 bool h16_ok(const mg_conv_geom* g) {
-    if (g->precision != MG_PRECISION_F16 || g->stride != 1) return false;
+    if (!MG_PRECISION_IS_HALF(g->precision) || g->stride != 1) return false;
     if (g->Ci % 64 != 0 || g->Co % 64 != 0) return false;
     const long long M = (long long)g->B * g->OH * g->OW, Min = (long long)g->B * g->H * g->W;
     const long long Mx = M > Min ? M : Min;

@@ -21,6 +21,7 @@
 #include "conv_smallc.h"
 // host side: probe, plans and picks (with the LDS-DMA families inside its namespace), then the two orchestrations
 #include "conv_plan.h"
+#include "wino_h16.h"
 #include "wino_host.h"
 #include "conv_smallc_host.h"
 
@@ -34,6 +35,7 @@ namespace {
 ConvRoute conv_route(int pass, const mg_conv_geom* g, bool generic) {
     if (!generic) {
         if (wino43_ok(g)) return R_WINO43;
+        if (winoh_ok(g)) return R_WINOH;           // (likewise: its precision value is its own; the rest as MG_PRECISION_F16)
         if (co1_gemm_ok(g)) return R_CO1;
         if (pass != 1 && mg_conv_rowdot_kq(g)) return R_ROWDOT;
         if (h16_ok(g)) return R_H16;
@@ -71,7 +73,7 @@ double mg_conv_plan_flops(int pass, const mg_conv_geom* g) {
     if (!geom_ok(g)) return 0.0;
     switch (const ConvRoute r = conv_route(pass, g)) {
     case R_CO1: return 2.0 * CO1_TAPS * (double)g->B * g->H * g->W * g->Ci;      // the 64-tap GEMM (conv_co1.h)
-    case R_WINO: case R_WINO4: case R_WINO42: case R_WINO43: {
+    case R_WINO: case R_WINO4: case R_WINO42: case R_WINO43: case R_WINOH: {
         const WinoGeo w = wino_geo(r, g);
         return 2.0 * w.f.P * (double)w.T * (double)g->Co * w.Kc;
     }
@@ -88,6 +90,7 @@ int mg_conv_plan_splits(int pass, const mg_conv_geom* g) {
         return conv_dma_dgrad_plan(&gp).splits;
     }
     if (r == R_WINO43 && pass != 0) return 0;      // forward only
+    if (r == R_WINOH) return pass == 0 ? 1 : 0;    // forward only, never split
     if (r == R_WINO || r == R_WINO4 || r == R_WINO42 || r == R_WINO43) {      // the Winograd-domain GEMM stage, on either kernel family
         const WinoGemm s = wino_gemm_plan(wino_geo(r, g), pass, g);
         return s.dp.ok ? s.dp.splits : s.tp.splits;
@@ -118,6 +121,7 @@ int mg_conv_plan_name(int pass, const mg_conv_geom* g, char* out, int out_len) {
     if (!geom_ok(g) || !out || out_len < 64 || pass < 0 || pass > 2) return MG_ERR_ARG;
     const char* half = prec_h(g) ? "true" : "false";
     if (pass != 0 && conv_route(pass, g) == R_WINO43) return MG_ERR_UNSUPPORTED;      // F(4x4,3x3) has no gradient passes
+    if (pass != 0 && conv_route(pass, g) == R_WINOH) return MG_ERR_UNSUPPORTED;       // nor have the float16 images
     switch (const ConvRoute r = conv_route(pass, g)) {
     case R_CO1:          // single-output-channel layers as tap GEMMs (conv_co1.h)
         snprintf(out, out_len, pass == 0 ? "dgemm32g_kernel<64, 128, 2, 2, 0, 0, 2, 0, 0>"
@@ -148,6 +152,7 @@ int mg_conv_plan_name(int pass, const mg_conv_geom* g, char* out, int out_len) {
         else gemm_pick_name(pass, GemmPick{s.tp.bm, s.tp.bn, true, true, s.tag, s.tp.k32, s.tp.splits, s.tp.cps}, out, out_len);
         break;
     }
+    case R_WINOH: snprintf(out, out_len, "%s", winoh_gemm_name(wino_geo(r, g).T, g->Co)); break;
     case R_SMALLC:
         if (pass == 0) snprintf(out, out_len, "conv_smallc_fwd_kernel<%d, %d, %d, %d>", g->KH, g->KW, g->Ci, g->stride);
         else if (pass == 1) snprintf(out, out_len, "conv_smallc_dgrad_kernel<%d, %s>", g->Ci, half);
@@ -182,6 +187,7 @@ size_t mg_conv_fwd_workspace(const mg_conv_geom* g) {
     case R_CO1: return co1_fwd_ws(g);
     case R_H16: return h16_fwd_ws(g);
     case R_WINO: case R_WINO4: case R_WINO42: case R_WINO43: return wino_ws_bytes(r, 0, g);
+    case R_WINOH: return winoh_ws(wino_geo(r, g), g).bytes;
     default: break;
     }
     const TilePlan tp = fwd_plan(g);
@@ -197,7 +203,7 @@ size_t mg_conv_dgrad_workspace(const mg_conv_geom* g) {
     case R_CO1: return co1_dgrad_ws(g);
     case R_H16: return h16_dgrad_ws(g);
     case R_WINO: case R_WINO4: case R_WINO42: return wino_ws_bytes(r, 1, g);
-    case R_WINO43: return 0;          // no data gradient in F(4x4,3x3) arithmetic: mg_conv_dgrad_w refuses the geometry
+    case R_WINO43: case R_WINOH: return 0;          // no data gradient on these routes: mg_conv_dgrad_w refuses the geometry
     default: break;
     }
     const TilePlan tp = dgrad_plan(g);
@@ -222,6 +228,7 @@ size_t mg_conv_wino_weights_bytes(const mg_conv_geom* g) {
         const WinoGeo w = wino_geo(r, g);
         return (size_t)w.f.P * g->Co * w.Kc * sizeof(float);
     }
+    case R_WINOH: return (size_t)16 * g->Co * g->Ci * 2;             // U16
     default: return conv_dma_h_any(g) ? h16_weights_bytes(g) : 0;     // ... and of the float16 implicit GEMMs (conv_dma.h)
     }
 }
@@ -230,6 +237,7 @@ int mg_conv_wino_prepare(const mg_conv_geom* g, const float* w, float* u, void* 
     switch (const ConvRoute r = conv_route(0, g)) {
     case R_CO1: co1_pad_w(g, w, u, (hipStream_t)stream); break;
     case R_WINO: case R_WINO4: case R_WINO42: case R_WINO43: wino_xform_u(wino_geo(r, g), g, w, u, (hipStream_t)stream); break;
+    case R_WINOH: winoh_xform_u(g, w, (_Float16*)u, (hipStream_t)stream); break;
     default: return h16_prepare(g, w, u, (hipStream_t)stream);
     }
     MG_CHECK_LAUNCH();
@@ -241,6 +249,7 @@ size_t mg_conv_wino_tiles_bytes(const mg_conv_geom* g, int which) {
     switch (const ConvRoute r = conv_route(0, g)) {
     case R_H16: return 0;
     case R_CO1: return which == 1 ? co1_zt_bytes(g) : (which == 0 ? co1_xr_bytes(g) : 0);   // Gt (data gradient -> weight gradient); autocast: the rounded x
+    case R_WINOH: return which == 0 ? (size_t)16 * wino_geo(r, g).T * g->Ci * 2 : 0;      // V16 only
     case R_WINO43:      // V only: no gradient pass reads an image of the output gradient
         if (which != 0) return 0;
         [[fallthrough]];
@@ -287,6 +296,10 @@ static bool wino_norm_ok(const mg_conv_geom* g) {
 static bool wino43_norm_ok(const mg_conv_geom* g) {
     return geom_ok(g) && conv_route(0, g) == R_WINO43 && wino43_out_norm_ok(g->OH / 4, g->OW / 4, g->Co);
 }
+// ... and the one on float16 images (wino_h16.h: winoh_out_norm_kernel): the F(2x2,3x3) ranges, <= 160 tiles and <= 64 for the hand-over
+static bool winoh_norm_ok(const mg_conv_geom* g) {
+    return geom_ok(g) && conv_route(0, g) == R_WINOH && wino_out_norm_ok(g->OH / 2, g->OW / 2, g->Co);
+}
 int mg_conv_wino_md_from_norm_ok(const mg_conv_geom* g) { return wino_norm_ok(g) ? 1 : 0; }
 int mg_instnorm_bwd_wino_md(const mg_conv_geom* g, const float* gy, const float* y_raw, const float* mean, const float* rstd,
                             int act, float* md, void* stream) {
@@ -318,13 +331,14 @@ int mg_conv_fwd_instnorm_w(const mg_conv_geom* g, const float* x, const float* w
 // (wino.h: wino_out_norm_kernel<NT, true>): maps of <= 64 tiles per sample.
 static bool wino_vnext_ok(const mg_conv_geom* g) {
     if (wino43_norm_ok(g)) return true;
+    if (winoh_norm_ok(g)) return wino_out_norm_next_ok(g->OH / 2, g->OW / 2, g->Co);
     return wino_norm_ok(g) && wino_out_norm_next_ok(g->OH / 2, g->OW / 2, g->Co) && g->Co % 16 == 0;
 }
 int mg_conv_wino_vnext_ok(const mg_conv_geom* g) { return g && wino_vnext_ok(g) ? 1 : 0; }
 
 static int conv_fwd_instnorm_impl(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y_raw, float eps,
                                   int act, const float* residual, float* y, float* mean, float* rstd, void* workspace,
-                                  size_t workspace_bytes, void* stream, const mg_wino_tiles* wt, void* y16, float* v_next,
+                                  size_t workspace_bytes, void* stream, const mg_wino_tiles* wt, void* y16, void* v_next,
                                   int next_reflect);
 static int conv_fwd(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int act, void* workspace,
                     size_t workspace_bytes, void* stream, const mg_wino_tiles* wt, FwdDefer* defer);
@@ -333,8 +347,19 @@ int mg_conv_fwd_instnorm_next(const mg_conv_geom* g, const float* x, const float
                               int act, const float* residual, float* y, float* mean, float* rstd, void* workspace,
                               size_t workspace_bytes, void* stream, const mg_wino_tiles* wt, float* v_next, int next_reflect) {
     if (!g || !v_next || !aligned16(v_next) || !wino_vnext_ok(g)) return MG_ERR_ARG;
+    if (conv_route(0, g) == R_WINOH) return MG_ERR_ARG;       // that layer's image is halves: mg_conv_fwd_instnorm_next_h
     return conv_fwd_instnorm_impl(g, x, w, bias, y_raw, eps, act, residual, y, mean, rstd, workspace, workspace_bytes, stream, wt, nullptr,
                                   v_next, next_reflect);
+}
+
+int mg_conv_fwd_instnorm_next_h(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y_raw, float eps,
+                                int act, const float* residual, float* y, float* mean, float* rstd, void* workspace,
+                                size_t workspace_bytes, void* stream, const mg_wino_tiles* wt, void* v_next16, int next_reflect,
+                                void* y16) {
+    if (!g || !geom_ok(g) || conv_route(0, g) != R_WINOH || !wino_vnext_ok(g)) return MG_ERR_ARG;
+    if ((v_next16 && !aligned16(v_next16)) || (y16 && !aligned16(y16))) return MG_ERR_ARG;
+    return conv_fwd_instnorm_impl(g, x, w, bias, y_raw, eps, act, residual, y, mean, rstd, workspace, workspace_bytes, stream, wt, y16,
+                                  v_next16, next_reflect);
 }
 
 int mg_conv_fwd_instnorm_h(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y_raw, float eps,
@@ -346,7 +371,7 @@ int mg_conv_fwd_instnorm_h(const mg_conv_geom* g, const float* x, const float* w
 
 static int conv_fwd_instnorm_impl(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y_raw, float eps,
                                   int act, const float* residual, float* y, float* mean, float* rstd, void* workspace,
-                                  size_t workspace_bytes, void* stream, const mg_wino_tiles* wt, void* y16, float* v_next,
+                                  size_t workspace_bytes, void* stream, const mg_wino_tiles* wt, void* y16, void* v_next,
                                   int next_reflect) {
     if (y16 && !prec_h(g)) return MG_ERR_UNSUPPORTED;          // the float32 layers' fused inverse transform + norm has no float16 output
     if (!geom_ok(g) || !x || !w || !y || !mean || !rstd) return MG_ERR_ARG;
@@ -354,10 +379,18 @@ static int conv_fwd_instnorm_impl(const mg_conv_geom* g, const float* x, const f
     if (!workspace || workspace_bytes < mg_conv_fwd_instnorm_workspace(g)) return MG_ERR_ARG;
     // y_raw == NULL (inference: no backward pass will read the raw convolution output): the fused kernel skips that store -- a
     // fifth of its HBM bytes at batch 64 -- and the two-call path normalises in place
+    if (winoh_norm_ok(g) && aligned16(x) && aligned16(w) && (!y_raw || aligned16(y_raw)) && aligned16(y) && aligned16(mean) &&
+        aligned16(rstd) && aligned16(workspace) && (!bias || aligned16(bias)) && (!residual || aligned16(residual)) &&
+        (!y16 || (reinterpret_cast<uintptr_t>(y16) & 7) == 0)) {
+        const WinohNorm nrm{eps, act, residual, y, mean, rstd, (_Float16*)y16, (_Float16*)v_next, next_reflect};
+        return winoh_fwd(wino_geo(R_WINOH, g), g, x, w, bias, y_raw, MG_ACT_NONE, (char*)workspace, (hipStream_t)stream,
+                         wt ? (const void*)wt->u : nullptr, wt ? (void*)wt->v : nullptr, wt && wt->v && (wt->flags & MG_TILES_V_FILLED),
+                         &nrm);
+    }
     const bool n43 = wino43_norm_ok(g);
     if ((n43 || wino_norm_ok(g)) && aligned16(x) && aligned16(w) && (!y_raw || aligned16(y_raw)) && aligned16(y) && aligned16(mean) &&
         aligned16(rstd) && aligned16(workspace) && (!bias || aligned16(bias)) && (!residual || aligned16(residual))) {
-        const WinoNorm nrm{eps, act, residual, y, mean, rstd, v_next, next_reflect};
+        const WinoNorm nrm{eps, act, residual, y, mean, rstd, (float*)v_next, next_reflect};
         return wino_fwd(wino_geo(n43 ? R_WINO43 : R_WINO, g), g, x, w, bias, y_raw, MG_ACT_NONE, (float*)workspace, (hipStream_t)stream,
                         wt ? wt->u : nullptr, wt ? wt->v : nullptr, wt && wt->v && (wt->flags & MG_TILES_V_FILLED), &nrm);
     }
@@ -410,6 +443,10 @@ static int conv_fwd(const mg_conv_geom* g, const float* x, const float* w, const
         if (al && workspace_bytes >= wino_ws_bytes(r, 0, g))
             return wino_fwd(wino_geo(r, g), g, x, w, bias, y, act, (float*)workspace, st, u, v,
                             (r == R_WINO43 || (r == R_WINO && !prec_h(g))) && v_filled);
+        break;
+    case R_WINOH:
+        if (al && workspace_bytes >= winoh_ws(wino_geo(r, g), g).bytes)
+            return winoh_fwd(wino_geo(r, g), g, x, w, bias, y, act, (char*)workspace, st, u, v, v_filled);
         break;
     case R_SMALLC:
         if ((reinterpret_cast<uintptr_t>(w) & 7) == 0) {      // conv_smallc_fwd_kernel reads its weights as float2s
@@ -506,7 +543,7 @@ static int conv_dgrad(const mg_conv_geom* g, const float* dy, const float* w, co
     float* md = wt ? wt->md : nullptr;
     hipStream_t st = (hipStream_t)stream;
     if (g->reflect && g->stride != 1) return MG_ERR_UNSUPPORTED;
-    if (conv_route(1, g) == R_WINO43) return MG_ERR_UNSUPPORTED;          // forward only: a training pass never carries this precision
+    if (conv_route(1, g) == R_WINO43 || conv_route(1, g) == R_WINOH) return MG_ERR_UNSUPPORTED;      // forward only: a training pass never carries these precisions
     const bool plain = !bias && act == MG_ACT_NONE;       // all but the F(2x2,3x3) and generic data gradients need it
     const bool al = workspace && aligned16(dy) && aligned16(w) && aligned16(dx) && aligned16(workspace);
     switch (const ConvRoute r = conv_route(1, g)) {
@@ -615,7 +652,7 @@ size_t mg_conv_wgrad_workspace(const mg_conv_geom* g) {
     case R_ROWDOT: return mg_conv_rowdot_wgrad_workspace(g);
     case R_H16: return h16_wgrad_ws(g);
     case R_WINO: case R_WINO4: case R_WINO42: return wino_ws_bytes(r, 2, g);
-    case R_WINO43: return 0;          // no weight gradient in F(4x4,3x3) arithmetic: mg_conv_wgrad_chk refuses the geometry
+    case R_WINO43: case R_WINOH: return 0;          // no weight gradient on these routes: mg_conv_wgrad_chk refuses the geometry
     case R_SMALLC: return smallc_wgrad_ws(g);
     default: break;
     }
@@ -663,7 +700,7 @@ int mg_conv_wgrad_h16(const mg_conv_geom* g, const float* x, const float* dy, vo
 int mg_conv_wgrad_chk(const mg_conv_geom* g, const float* x, const float* dy, float* dw, float* dbias, int accumulate,
                       void* workspace, size_t workspace_bytes, void* stream, const mg_wino_tiles* wt, float* found_inf) {
     if (!geom_ok(g) || !dw) return MG_ERR_ARG;
-    if (conv_route(2, g) == R_WINO43) return MG_ERR_UNSUPPORTED;          // forward only
+    if (conv_route(2, g) == R_WINO43 || conv_route(2, g) == R_WINOH) return MG_ERR_UNSUPPORTED;      // forward only
     if (found_inf && !mg_conv_wgrad_checks_finite(g)) return MG_ERR_UNSUPPORTED;   // nobody would look at dw: refuse instead of skipping silently
     if (found_inf && !(x && dy && aligned16(x) && aligned16(dy) && aligned16(dw) && aligned16(workspace))) return MG_ERR_ARG;
     if (!wino_tiles_ok(g, wt)) return MG_ERR_ARG;

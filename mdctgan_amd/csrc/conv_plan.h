@@ -34,10 +34,11 @@ Geom to_geom(const mg_conv_geom* g) {
     return Geom{g->B, g->H, g->W, g->Ci, g->OH, g->OW, g->Co, g->KH, g->KW, g->stride, g->pad, g->reflect};
 }
 
-inline bool prec_h(const mg_conv_geom* g) { return g->precision == MG_PRECISION_F16; }
+// half-precision arithmetic: autocast training, and the opt-in inference mode that shares its arithmetic
+inline bool prec_h(const mg_conv_geom* g) { return MG_PRECISION_IS_HALF(g->precision); }
 
 bool geom_ok(const mg_conv_geom* g) {
-    if (g && g->precision != MG_PRECISION_F32 && g->precision != MG_PRECISION_F16 && g->precision != MG_PRECISION_F32_WINO43) return false;
+    if (g && g->precision != MG_PRECISION_F32 && !MG_PRECISION_IS_HALF(g->precision) && g->precision != MG_PRECISION_F32_WINO43) return false;
     if (!g || g->B <= 0 || g->H <= 0 || g->W <= 0 || g->Ci <= 0 || g->Co <= 0 || g->KH <= 0 || g->KW <= 0) return false;
     if (g->stride < 1 || g->stride > 2 || g->pad < 0) return false;
     if (g->OH != (g->H + 2 * g->pad - g->KH) / g->stride + 1) return false;
@@ -465,7 +466,7 @@ struct GemmPick { int bm, bn; bool veca, vecb; int tag; bool k32; int splits, cp
 // kernels read and write float4s)
 struct BufFacts { bool veca, vecb, split; };
 constexpr BufFacts kAnyBuf{true, true, true};
-inline int conv_tag(const mg_conv_geom* g) { return g->precision == MG_PRECISION_F16 ? 2 : 0; }
+inline int conv_tag(const mg_conv_geom* g) { return MG_PRECISION_IS_HALF(g->precision) ? 2 : 0; }
 GemmPick fwd_pick(const mg_conv_geom* g, BufFacts f) {
     TilePlan tp = fwd_plan(g);
     if (tp.splits > 1 && !f.split) one_split(tp, 1 << 30);
@@ -529,7 +530,7 @@ inline unsigned wgrad_reduce_grid(size_t n4) { return (n4 + 255) / 256 > 4096 ? 
 // conv_route(pass, g, true): DMA (over the reflect-padded domain for a data gradient), else the implicit GEMM -- and a co1
 // pass tries rowdot first.
 // ---------------------------------------------------------------------------------------------------------
-enum ConvRoute { R_IGEMM, R_DMA, R_DMA_REFLECT, R_CO1, R_ROWDOT, R_H16, R_WINO, R_WINO4, R_WINO42, R_WINO43, R_SMALLC };
+enum ConvRoute { R_IGEMM, R_DMA, R_DMA_REFLECT, R_CO1, R_ROWDOT, R_H16, R_WINO, R_WINO4, R_WINO42, R_WINO43, R_WINOH, R_SMALLC };
 ConvRoute conv_route(int pass, const mg_conv_geom* g, bool generic = false);
 
 }  // namespace

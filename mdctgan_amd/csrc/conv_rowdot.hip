@@ -308,20 +308,20 @@ int mg_conv_rowdot_fwd(const mg_conv_geom* g, const float* x, const float* w, co
     if (const int kind = co1_tile_kind(g)) {
         if (kind == 1)
             hipLaunchKernelGGL((co1_tile_fwd_kernel<7, 7>), co1_grid(g), dim3(256), 0, (hipStream_t)stream, gg, x, w, bias, y,
-                               act, (int)(g->precision == MG_PRECISION_F16));
+                               act, (int)MG_PRECISION_IS_HALF(g->precision));
         else
             hipLaunchKernelGGL((co1_tile_fwd_kernel<4, 4>), co1_grid(g), dim3(256), 0, (hipStream_t)stream, gg, x, w, bias, y,
-                               act, (int)(g->precision == MG_PRECISION_F16));
+                               act, (int)MG_PRECISION_IS_HALF(g->precision));
         MG_CHECK_LAUNCH();
         return MG_OK;
     }
     const int nw = rowdot_waves((long long)g->B * g->OH * g->OW);
     if (kq == 16)
         hipLaunchKernelGGL(conv_rowdot_fwd_kernel<16>, dim3(nw / 4), dim3(256), 0, (hipStream_t)stream, gg, x, w, bias, y, act,
-                           (int)(g->precision == MG_PRECISION_F16));
+                           (int)MG_PRECISION_IS_HALF(g->precision));
     else
         hipLaunchKernelGGL(conv_rowdot_fwd_kernel<32>, dim3(nw / 4), dim3(256), 0, (hipStream_t)stream, gg, x, w, bias, y, act,
-                           (int)(g->precision == MG_PRECISION_F16));
+                           (int)MG_PRECISION_IS_HALF(g->precision));
     MG_CHECK_LAUNCH();
     return MG_OK;
 }
@@ -349,13 +349,13 @@ int mg_conv_rowdot_wgrad(const mg_conv_geom* g, const float* x, const float* dy,
     char* cs_ws = (char*)(sums + KP);
     cs_ws += (16 - (reinterpret_cast<uintptr_t>(cs_ws) & 15)) & 15;
     if (kind == 1)
-        hipLaunchKernelGGL((co1_tile_wgrad_kernel<7, 7>), tg, dim3(256), 0, st, gg, x, dy, part, KP, (int)(g->precision == MG_PRECISION_F16));
+        hipLaunchKernelGGL((co1_tile_wgrad_kernel<7, 7>), tg, dim3(256), 0, st, gg, x, dy, part, KP, (int)MG_PRECISION_IS_HALF(g->precision));
     else if (kind == 2)
-        hipLaunchKernelGGL((co1_tile_wgrad_kernel<4, 4>), tg, dim3(256), 0, st, gg, x, dy, part, KP, (int)(g->precision == MG_PRECISION_F16));
+        hipLaunchKernelGGL((co1_tile_wgrad_kernel<4, 4>), tg, dim3(256), 0, st, gg, x, dy, part, KP, (int)MG_PRECISION_IS_HALF(g->precision));
     else if (kq == 16)
-        hipLaunchKernelGGL(conv_rowdot_wgrad_kernel<16>, dim3(nw / 4), dim3(256), 0, st, gg, x, dy, part, KP, (int)(g->precision == MG_PRECISION_F16));
+        hipLaunchKernelGGL(conv_rowdot_wgrad_kernel<16>, dim3(nw / 4), dim3(256), 0, st, gg, x, dy, part, KP, (int)MG_PRECISION_IS_HALF(g->precision));
     else
-        hipLaunchKernelGGL(conv_rowdot_wgrad_kernel<32>, dim3(nw / 4), dim3(256), 0, st, gg, x, dy, part, KP, (int)(g->precision == MG_PRECISION_F16));
+        hipLaunchKernelGGL(conv_rowdot_wgrad_kernel<32>, dim3(nw / 4), dim3(256), 0, st, gg, x, dy, part, KP, (int)MG_PRECISION_IS_HALF(g->precision));
     MG_CHECK_LAUNCH();
     const int rc = mg_colsum(part, nw, KP, sums, 0, cs_ws, mg_colsum_workspace(nw, KP), stream);
     if (rc != MG_OK) return rc;

@@ -1,6 +1,6 @@
 // Winograd orchestration on the host: the family predicates, WinoGeo, the GEMM-stage plan, the workspace layout, wino_gemm, the
 // transforms and the three pipelines wino_fwd / wino_dgrad / wino_wgrad.
-// Needs: conv_plan.h (plans, dispatchers, ConvRoute, h16_ok), wino.h, wino4.h, wino42.h, wino43.h.
+// Needs: conv_plan.h (plans, dispatchers, ConvRoute, h16_ok), wino.h, wino4.h, wino42.h, wino43.h, wino_h16.h.
 #pragma once
 
 namespace {
@@ -22,6 +22,25 @@ bool wino43_ok(const mg_conv_geom* g) {
     const int min_c = mc ? atoi(mc) : 256;
     return g->KH == 3 && g->KW == 3 && g->stride == 1 && g->pad == 1 && g->H % 4 == 0 && g->W % 4 == 0 && g->Ci % 16 == 0 &&
            g->Co % 16 == 0 && g->Ci >= min_c && g->Co >= min_c;
+}
+// MG_PRECISION_F16_INFER geometries (forward passes under no_grad, opted in) that run F(2x2,3x3) on two-byte images (wino_h16.h):
+// the float16 Winograd branch's own channel and tile thresholds (below; read per call here so the parity tests reach small
+// shapes), whole 64-deep chunks and 64-column tiles, and every operand of one position below 2 GiB (32-bit DMA byte offsets).
+// Asked first by conv_route, as wino43_ok is; an ineligible geometry of this precision routes as MG_PRECISION_F16 does.
+bool winoh_ok(const mg_conv_geom* g) {
+    if (g->precision != MG_PRECISION_F16_INFER) return false;
+    if (g->KH != 3 || g->KW != 3 || g->stride != 1 || g->pad != 1 || g->H % 2 || g->W % 2 || g->H < 2 || g->W < 2) return false;
+    if (g->Ci % 64 != 0 || g->Co % 64 != 0) return false;
+    const char* mc = getenv("MG_INFER_F16_MIN_C");
+    const char* mt = getenv("MG_INFER_F16_MIN_TILES");
+    // the weight-streaming layers of small batches keep the hgemm_sa path (conv_h16.h) -- unless the caller names a tile threshold
+    // of its own, which then is the whole rule about the tile count
+    if (!mt && h16_ok(g)) return false;
+    const int min_c = mc ? atoi(mc) : 256;
+    const long long min_tiles = mt ? atoll(mt) : 256, T = (long long)g->B * (g->H / 2) * (g->W / 2);
+    if (g->Ci < min_c || g->Co < min_c || T < min_tiles) return false;
+    const long long lim = 1LL << 31;
+    return T * g->Ci * 2 < lim && (long long)g->Co * g->Ci * 2 < lim && T * g->Co * 4 < lim;
 }
 bool wino_ok(const mg_conv_geom* g) {
     static const bool off = getenv("MG_NO_WINOGRAD") != nullptr;
@@ -58,17 +77,18 @@ bool wino42_ok(const mg_conv_geom* g) {
 // Per family: positions P, channels per thread of the transform kernels (their grid divisor), and the weight-gradient plan's
 // tile count above which it takes 128x128 tiles, and whether a full grid still splits a deep reduction in three
 struct WinoFamily { int P, vec; long long big_T; bool split3; };
-constexpr WinoFamily kWinoFamily[4] = {
+constexpr WinoFamily kWinoFamily[5] = {
     {16, 4, 1024, false},      // F(2x2,3x3); short reductions (the 8x16 blocks of configs[1]): 64x64 tiles measured 125 vs 148 us
     {25, 2, 4096, true},       // F(2x2,4x4); measured at 2448 tiles: 64x64 232 us, 128x128 252 us
     {25, 2, 4096, true},       // F(4x4,2x2)
     {36, 2, 4096, true},       // F(4x4,3x3): forward only, the weight-gradient fields are never read
+    {16, 4, 1024, false},      // F(2x2,3x3) on float16 images: forward only
 };
 // A layer in the Winograd domain: T = B * TH * TW tiles, Kc = the GEMMs' input depth (4 Ci for F(4x4,2x2))
 struct WinoGeo { ConvRoute r; WinoFamily f; long long T; int TH, TW, Kc; bool hp; };
 WinoGeo wino_geo(ConvRoute r, const mg_conv_geom* g) {
     WinoGeo w{r, kWinoFamily[r - R_WINO], 0, 0, 0, r == R_WINO42 ? 4 * g->Ci : g->Ci, prec_h(g)};
-    if (r == R_WINO) { w.TH = g->H / 2; w.TW = g->W / 2; }
+    if (r == R_WINO || r == R_WINOH) { w.TH = g->H / 2; w.TW = g->W / 2; }
     else if (r == R_WINO4) { w.TH = (g->H + 1) / 2; w.TW = (g->W + 1) / 2; }
     else if (r == R_WINO43) { w.TH = g->H / 4; w.TW = g->W / 4; }
     else { w.TH = (g->OH + 3) / 4; w.TW = (g->OW + 3) / 4; }
@@ -257,6 +277,54 @@ int wino_fwd(const WinoGeo& w, const mg_conv_geom* g, const float* x, const floa
     else
         hipLaunchKernelGGL(wino42_output_xform_kernel, grid, dim3(256), 0, st, (const float*)Mx, g->B, g->OH, g->OW, w.TH, w.TW, g->Co,
                            bias, act, y);
+    MG_CHECK_LAUNCH();
+    return MG_OK;
+}
+
+// The forward pass on float16 images (wino_h16.h).  Workspace: U16 | V16 | M (float32), each 256-byte aligned.  u_pre / v_keep /
+// v_filled as in wino_fwd, the images being halves; nrm (maps of <= 160 tiles per sample; its v_next: <= 64): the fused tail.
+struct WinohWs { size_t u, v, mx, bytes; };
+inline WinohWs winoh_ws(const WinoGeo& w, const mg_conv_geom* g) {
+    auto al = [](size_t n) { return (n + 255) / 256 * 256; };
+    WinohWs o{};
+    o.u = 0;
+    o.v = o.u + al((size_t)16 * g->Co * g->Ci * 2);
+    o.mx = o.v + al((size_t)16 * w.T * g->Ci * 2);
+    o.bytes = o.mx + al((size_t)16 * w.T * g->Co * 4) + 256;
+    return o;
+}
+void winoh_xform_u(const mg_conv_geom* g, const float* wt, _Float16* U, hipStream_t st) {
+    hipLaunchKernelGGL(winoh_weight_xform_kernel, dim3(wino_grid((size_t)g->Co * g->Ci / 4)), dim3(256), 0, st, wt, g->Co, g->Ci, U);
+}
+int winoh_fwd(const WinoGeo& w, const mg_conv_geom* g, const float* x, const float* wt, const float* bias, float* y, int act,
+              char* ws, hipStream_t st, const void* u_pre, void* v_keep, bool v_filled, const WinohNorm* nrm = nullptr) {
+    const WinohWs o = winoh_ws(w, g);
+    _Float16* U = u_pre ? (_Float16*)const_cast<void*>(u_pre) : (_Float16*)(ws + o.u);
+    _Float16* V = v_keep ? (_Float16*)v_keep : (_Float16*)(ws + o.v);
+    float* Mx = (float*)(ws + o.mx);
+    if (!u_pre) winoh_xform_u(g, wt, U, st);
+    if (!(v_filled && v_keep))
+        hipLaunchKernelGGL(winoh_input_xform_kernel, dim3(wino_grid((size_t)w.T * g->Ci / 4)), dim3(256), 0, st, x, g->B, g->H, g->W,
+                           g->Ci, w.TH, w.TW, g->reflect, V);
+    probe_begin(st);
+    winoh_gemm_launch(V, U, Mx, w.T, g->Co, g->Ci, st);
+    probe_end(st);
+    if (nrm) {
+        const dim3 grid(g->Co / 32, g->B);
+        const int nt = (w.TH * w.TW + 31) / 32;
+#define MG_OUT_NORM(NT_) hipLaunchKernelGGL(winoh_out_norm_kernel<NT_>, grid, dim3(256), 0, st, (const float*)Mx, g->B, w.TH, w.TW, g->Co, bias, *nrm, y)
+#define MG_OUT_NORM_NEXT(NT_) hipLaunchKernelGGL((winoh_out_norm_kernel<NT_, true>), grid, dim3(256), 0, st, (const float*)Mx, g->B, w.TH, w.TW, g->Co, bias, *nrm, y)
+        if (nrm->v_next && nt == 1) MG_OUT_NORM_NEXT(1);
+        else if (nrm->v_next && nt == 2) MG_OUT_NORM_NEXT(2);
+        else if (nrm->v_next || nt > 5) return MG_ERR_ARG;       // (callers ask winoh_norm_ok / mg_conv_wino_vnext_ok first)
+        else if (nt == 1) MG_OUT_NORM(1); else if (nt == 2) MG_OUT_NORM(2); else if (nt == 3) MG_OUT_NORM(3); else if (nt == 4) MG_OUT_NORM(4); else MG_OUT_NORM(5);
+#undef MG_OUT_NORM_NEXT
+#undef MG_OUT_NORM
+        MG_CHECK_LAUNCH();
+        return MG_OK;
+    }
+    hipLaunchKernelGGL(wino_output_xform_kernel, dim3(wino_grid((size_t)w.T * g->Co / 4)), dim3(256), 0, st, (const float*)Mx, g->B,
+                       w.TH, w.TW, g->Co, bias, act, y, 1);
     MG_CHECK_LAUNCH();
     return MG_OK;
 }

@@ -66,7 +66,7 @@ def _want_h16(B, HW, C, half=None):
     activation-dominated sizes (a tensor whose consumer streams weights, pixels <= 2 C, is im2col'ed from float32 by
     conv_h16.h instead)."""
     if half is None:
-        half = amp.current_precision() == _lib.PRECISION_F16
+        half = _lib.is_half(amp.current_precision())
     # (round 6: also every SMALL tensor, <= 2 Mi elements -- 2 more bytes per element in a kernel that sits at the launch floor cost
     # nothing, and the stride-2 / transposed rungs next to the trunk then skip their cast launch)
     return (bool(half) and C % 64 == 0 and (B * HW > 2 * C or B * HW * C <= (1 << 21))
@@ -606,7 +606,7 @@ def _conv_backward(ctx, gy, x, y, add=None):
             ctx.v = None
         else:
             flag = _producer_flag(weight, g)
-            half = ops.tiles_are_casts(g) and g.precision == _lib.PRECISION_F16 and g.Co != 1
+            half = ops.tiles_are_casts(g) and _lib.is_half(g.precision) and g.Co != 1
             ops.conv_wgrad(g, nhwc_view(gy), nhwc_view(x), wbuf, None, wacc, found_inf=flag,
                            v=g16 if half else None, md=getattr(ctx, "v", None) if half else None)
             ctx.v = None
@@ -624,7 +624,10 @@ def conv2d(x, weight, bias, stride=1, padding=0, reflect=False, act=ACT_NONE, we
 
 
 def conv_transpose2d(x, weight, bias, stride=2, padding=1, act=ACT_NONE, weight_grad=True):
-    return _ConvFn.apply(x, weight, bias, (stride, padding, False, act, True, weight_grad, amp.current_precision()))
+    prec = amp.current_precision()
+    if prec == _lib.PRECISION_F16_INFER:       # this call IS a data-gradient pass, which that forward-only value does not name
+        prec = _lib.PRECISION_F16
+    return _ConvFn.apply(x, weight, bias, (stride, padding, False, act, True, weight_grad, prec))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -673,9 +676,12 @@ class _ConvInstNormFn(torch.autograd.Function):
         v_next = None
         if next_reflect is not None and npos and os.environ.get("MG_NO_WINO_NEXT", "0") != "1":
             tile = 2 if npos == 16 else 4       # F(2x2,3x3) / F(4x4,3x3) output tiles
-            v_next = torch.empty(npos * B * (g.OH // tile) * (g.OW // tile) * g.Co, dtype=torch.float32, device=x.device)
+            v_next = torch.empty(npos * B * (g.OH // tile) * (g.OW // tile) * g.Co, device=x.device,
+                                 dtype=torch.float16 if ops.wino_images_half(g) else torch.float32)
         y16 = (torch.empty(B * g.OH * g.OW * g.Co, dtype=torch.float16, device=x.device)
-               if _want_h16(B, g.OH * g.OW, g.Co) else None)
+               if _want_h16(B, g.OH * g.OW, g.Co, _lib.is_half(prec)) else None)
+        if v_next is not None and v_next.dtype == torch.float16:
+            y16 = None          # the consumer named by next_reflect reads the float16 image, not a float16 copy of y
         # under torch.no_grad() nobody reads the raw convolution output again (grad mode is read by conv_instnorm(): inside a
         # Function's forward it is always off, and needs_input_grad ignores it)
         need_raw = bool(cfg[6]) and any(ctx.needs_input_grad) if len(cfg) > 6 else any(ctx.needs_input_grad)
@@ -727,7 +733,7 @@ class _ConvInstNormFn(torch.autograd.Function):
                 _notify(bias)
             return dx, None, None, dres, None
         d16 = (torch.empty(gy.numel(), dtype=torch.float16, device=gy.device)
-               if (_want_h16(g.B, g.OH * g.OW, g.Co, g.precision == _lib.PRECISION_F16) and ops.precast_ok(1, g)) else None)
+               if (_want_h16(g.B, g.OH * g.OW, g.Co, _lib.is_half(g.precision)) and ops.precast_ok(1, g)) else None)
         d_raw = _attach_h16(nchw_view(ops.instnorm_bwd(nhwc_view(gy), nhwc_view(y_raw), mean, rstd, ctx.norm_act, dx16=d16)), d16)
         # the skip connection's gradient joins the data gradient inside its last kernel (no elementwise add launch)
         dx = _conv_backward(ctx, d_raw, x, None, add=nhwc_view(skip_g) if (skip_g is not None and ctx.needs_input_grad[0]) else None)
@@ -759,13 +765,14 @@ def conv_instnorm(x, weight, bias, padding=0, reflect=False, act=ACT_NONE, resid
 
 class _InstNormFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, residual, act, eps):
+    def forward(ctx, x, residual, act, eps, half):
+        # half: the precision as instance_norm_act() read it (amp.infer_f16 looks at the grad mode, which is always off in here)
         x = to_cl(x)
         res = to_cl(residual) if residual is not None else None
         B, C, H, W = x.shape
-        y16 = torch.empty(x.numel(), dtype=torch.float16, device=x.device) if _want_h16(B, H * W, C) else None
+        y16 = torch.empty(x.numel(), dtype=torch.float16, device=x.device) if _want_h16(B, H * W, C, half) else None
         y, mean, rstd = ops.instnorm_fwd(nhwc_view(x), act, nhwc_view(res) if res is not None else None, eps, y16=y16)
-        ctx.act, ctx.half = act, amp.current_precision() == _lib.PRECISION_F16
+        ctx.act, ctx.half = act, half
         ctx.save_for_backward(x, mean, rstd)
         return _hang_extra(ctx, _attach_h16(nchw_view(y), y16))
 
@@ -796,12 +803,12 @@ class _InstNormFn(torch.autograd.Function):
                 dx = _attach_h16(nchw_view(ops.instnorm_bwd(nhwc_view(gy), nhwc_view(x), mean, rstd, ctx.act, dx16=d16,
                                                             dy2=nhwc_view(extra) if extra is not None else None)), d16)
         dres = gy if ctx.needs_input_grad[1] else None
-        return dx, dres, None, None
+        return dx, dres, None, None, None
 
 
 def instance_norm_act(x, act=ACT_NONE, residual=None, eps=1e-5):
     """act(InstanceNorm2d(affine=False)(x)) + residual."""
-    return _InstNormFn.apply(x, residual, act, eps)
+    return _InstNormFn.apply(x, residual, act, eps, _lib.is_half(amp.current_precision()))
 
 
 class _BatchNormFn(torch.autograd.Function):

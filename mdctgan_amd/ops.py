@@ -10,7 +10,8 @@ from ._lib import ACT_LRELU02, ACT_NONE, ACT_RELU, ACT_TANH, ConvGeom  # noqa: F
 
 def conv_geom(B, H, W, Ci, Co, KH, KW, stride, pad, reflect, precision=0) -> ConvGeom:
     """precision: _lib.PRECISION_F32 (exact float32) or _lib.PRECISION_F16 (autocast arithmetic: f16 MFMA products,
-    float32 accumulation, forward / data-gradient outputs rounded through float16)."""
+    float32 accumulation, forward / data-gradient outputs rounded through float16); _lib.PRECISION_F32_WINO43 and
+    _lib.PRECISION_F16_INFER are the two opt-in forward-only values of an inference pass (amp.wino43 / amp.infer_f16)."""
     OH = (H + 2 * pad - KH) // stride + 1
     OW = (W + 2 * pad - KW) // stride + 1
     return ConvGeom(B, H, W, Ci, OH, OW, Co, KH, KW, stride, pad, int(bool(reflect)), int(precision))
@@ -73,11 +74,11 @@ def tiles_are_casts(g: ConvGeom) -> bool:
     """True for layers whose v / md "tiles" are usable on their own (Winograd images only work as a pair): the autocast
     layers on the float16 implicit GEMMs (csrc/conv_dma.h: plain float16 copies of x / dy) and the single-output-channel
     tap GEMMs (csrc/conv_co1.h: md = the scattered dy)."""
-    key = (g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision)
+    key = (g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision, _route_env(g))
     hit = _CASTS.get(key)
     if hit is None:
         name = plan_name(2, g)
-        half = g.precision == _lib.PRECISION_F16 and name.startswith("conv_wgrad_dma_kernel") and ", true" in name
+        half = _lib.is_half(g.precision) and name.startswith("conv_wgrad_dma_kernel") and ", true" in name
         # ... and the single-output-channel tap GEMMs (csrc/conv_co1.h): md is the scattered dy, there is no v
         co1 = g.Co == 1 and wino_weights_bytes(g) == 64 * g.Ci * 4
         hit = _CASTS[key] = half or co1
@@ -99,9 +100,9 @@ def _tiles(u=None, v=None, md=None, add=None, flags=0):
 def precast_ok(pass_id: int, g: ConvGeom) -> bool:
     """True when this pass of the layer reads its activation operand from a plain float16 copy and honours MG_TILES_V_FILLED
     (pass 0) / MG_TILES_MD_FILLED (pass 1): the HALF instances of the implicit GEMMs (csrc/conv_dma.h)."""
-    if g.precision != _lib.PRECISION_F16:
+    if not _lib.is_half(g.precision):
         return False
-    key = ("pc", pass_id, g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision)
+    key = ("pc", pass_id, g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision, _route_env(g))
     hit = _CASTS.get(key)
     if hit is None:
         name = plan_name(pass_id, g)
@@ -127,27 +128,39 @@ def conv_fwd(g: ConvGeom, x, w, bias=None, act=ACT_NONE, u=None, v_out=None, v_f
 
 
 def wino_vnext_ok(g: ConvGeom) -> bool:
-    """True when conv_fwd_instnorm can also write the next 3x3 layer's Winograd input image (float32 F(2x2,3x3), small maps)."""
-    key = ("vn", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision, _wino43_env(g))
+    """True when conv_fwd_instnorm can also write the next 3x3 layer's Winograd input image (float32 F(2x2,3x3) and F(4x4,3x3),
+    F(2x2,3x3) on float16 images; small maps)."""
+    key = ("vn", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision, _route_env(g))
     hit = _CASTS.get(key)
     if hit is None:
         hit = _CASTS[key] = bool(_lib.load().mg_conv_wino_vnext_ok(g))
     return hit
 
 
-def _wino43_env(g: ConvGeom):
-    """What the F(4x4,3x3) predicate reads from the environment per call (a cache key beside the geometry)."""
+def _route_env(g: ConvGeom):
+    """What the predicates of the two opt-in inference precisions read from the environment per call (a cache key beside the
+    geometry)."""
     import os
-    return os.environ.get("MG_WINO43_MIN_C") if g.precision == _lib.PRECISION_F32_WINO43 else None
+    if g.precision == _lib.PRECISION_F32_WINO43:
+        return os.environ.get("MG_WINO43_MIN_C")
+    if g.precision == _lib.PRECISION_F16_INFER:
+        return (os.environ.get("MG_INFER_F16_MIN_C"), os.environ.get("MG_INFER_F16_MIN_TILES"))
+    return None
+
+
+def wino_images_half(g: ConvGeom) -> bool:
+    """True when the layer's Winograd images (u, v, a hand-over v_next) are float16: the eligible layers of PRECISION_F16_INFER."""
+    return g.precision == _lib.PRECISION_F16_INFER and plan_name(0, g).startswith("winoh_gemm_kernel")
 
 
 def wino_vnext_positions(g: ConvGeom) -> int:
     """Positions P of the Winograd family of a layer with wino_vnext_ok(g) -- 16: F(2x2,3x3), 36: F(4x4,3x3); 0: no hand-over.
     An input image handed from layer to layer (conv_fwd_instnorm's v_next) is only good for the family it was written for."""
-    key = ("vp", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision, _wino43_env(g))
+    key = ("vp", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision, _route_env(g))
     hit = _CASTS.get(key)
     if hit is None:
-        hit = _CASTS[key] = wino_weights_bytes(g) // (4 * g.Co * g.Ci) if wino_vnext_ok(g) else 0
+        elem = 2 if (wino_vnext_ok(g) and wino_images_half(g)) else 4
+        hit = _CASTS[key] = wino_weights_bytes(g) // (elem * g.Co * g.Ci) if wino_vnext_ok(g) else 0
     return hit
 
 
@@ -167,6 +180,16 @@ def conv_fwd_instnorm(g: ConvGeom, x, w, bias=None, act=ACT_NONE, residual=None,
     if PROFILER is not None:
         PROFILER.begin(0, g)
     tiles = _tiles(u, v_out, None, None, TILES_V_FILLED if v_filled else 0)
+    if v_next is not None and v_next.dtype == torch.float16:
+        # a layer on float16 Winograd images (PRECISION_F16_INFER): the one entry point that writes both side outputs
+        _lib.check(lib.mg_conv_fwd_instnorm_next_h(g, _lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(y_raw), eps, act,
+                                                   _lib.ptr(residual), _lib.ptr(y), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(ws),
+                                                   ws.numel(), _lib.stream(), tiles, _lib.ptr(v_next), int(bool(next_reflect)),
+                                                   _lib.ptr(y16)),
+                   "mg_conv_fwd_instnorm_next_h")
+        if PROFILER is not None:
+            PROFILER.end()
+        return y, y_raw, mean, rstd
     if v_next is not None and y16 is not None:
         # the two entry points each write ONE of the side outputs (v_next: float32 layers, y16: autocast layers); a caller that
         # asks for both would get an uninitialised float16 copy attached to the output
@@ -553,9 +576,9 @@ def adam_step_segs(p, g, g16, m, v, p16, segs, nsegs, n_total, nbytes, state, be
 
 def weights_are_casts(g: ConvGeom) -> bool:
     """True when the layer's cached weight image (mg_conv_wino_prepare) is the plain float16 copy of its OHWI weights."""
-    if g.precision != _lib.PRECISION_F16:
+    if not _lib.is_half(g.precision):
         return False
-    key = ("w", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect)
+    key = ("w", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision, _route_env(g))
     hit = _CASTS.get(key)
     if hit is None:
         hit = _CASTS[key] = wino_weights_bytes(g) == g.Co * g.KH * g.KW * g.Ci * 2

@@ -81,6 +81,8 @@ _FLAGS = [
     ("lambda_mel", dict(type=float, default=0.0)),
     # inference: eligible 3x3 layers as Winograd F(4x4,3x3) (not in the reference: amp.wino43); off by default
     ("wino43", True),
+    # inference: half-precision arithmetic, float16 Winograd images on the trunk (not in the reference: amp.infer_f16); off by default
+    ("infer_fp16", True),
     # a different IIR low-pass per training example in front of the low-rate leg (not in the reference: lowpass.py); "": off
     ("lowpass_aug", dict(type=str, default="")), ("lowpass_order", dict(type=int, default=(2, 10), nargs=2)),
     ("lowpass_ripple", dict(type=float, default=(0.01, 1.0), nargs=2)),

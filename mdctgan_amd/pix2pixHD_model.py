@@ -700,7 +700,9 @@ class Pix2PixHDModel(BaseModel):
         self._finish_pending()
         # --wino43 / MG_WINO43=1 (read per call, as MG_F32_SPLIT is): the eligible 3x3 layers of this pass run as F(4x4,3x3)
         wino43 = bool(getattr(self.opt, "wino43", False)) or os.environ.get("MG_WINO43", "0") == "1"
-        with torch.no_grad(), amp.wino43(wino43):
+        # --infer_fp16 / MG_INFER_F16=1 (likewise): the pass runs in half-precision arithmetic (amp.infer_f16)
+        infer_f16 = bool(getattr(self.opt, "infer_fp16", False)) or os.environ.get("MG_INFER_F16", "0") == "1"
+        with torch.no_grad(), amp.wino43(wino43), amp.infer_f16(infer_f16):
             lr_spectro, lr_pha, lr_norm_param = self.preprocess.forward(lr_audio)
             sr_spectro = self.netG.forward(self._two_channel(lr_spectro))
             if self.fit_residual:
