@@ -302,6 +302,42 @@ size_t mg_sos_rows_workspace(int n_rows, long long max_len);
 int mg_sos_rows(const float* x, long long x_total, const mg_sos_row* rows, const double* sos, int n_rows, long long max_len,
                 int zero_phase, float* out, long long out_total, void* workspace, size_t workspace_bytes, void* stream);
 
+/* WAV payloads (csrc/pcm_rows.hip): torchaudio.load(normalize=True) (data/audio_dataset.py:37-51, :143) and torchaudio.save
+ * (generate_audio.py:89-96) for MANY files in shared launches.  The payload bytes of every file sit in one byte buffer (the host
+ * stages each at a 16-byte aligned offset), the waveforms in one packed float32 buffer; one mg_pcm_row per channel of a file.
+ *   mg_pcm_row          decode: the row reads channel `channel` of `frames` interleaved little-endian frames of `channels` samples
+ *                       that start at byte src_pos, and writes float32 samples to out[dst_pos, dst_pos + frames).  encode: src_pos
+ *                       is the sample position of this channel's row in x, dst_pos the byte offset of the file's payload.
+ *   mg_pcm_decode_rows  U8: (x - 128) / 128.  S16, S24: x / 2^(bits - 1), exact.  S32: float32(x) 2^-31 -- one round to nearest even,
+ *                       then an exact scale.  F32: the bits as they are, NaNs included.  F64: one round-to-nearest-even cast.  One
+ *                       workgroup per chunk of MG_MOMENTS_CHUNK frames of a row.  moments != NULL: double [n_rows][2] = {sum x,
+ *                       sum x^2} of every decoded row from the same pass, bit for bit mg_rows_moments over out[dst_pos, dst_pos +
+ *                       frames) with the same max length (one small launch more); workspace: mg_pcm_decode_rows_workspace(n_rows,
+ *                       max_frames) bytes, 8-byte aligned, read only with moments.  max_frames: the longest row (sizes the grid and
+ *                       the workspace; longer rows lose their tail).
+ *   mg_pcm_encode_rows  MG_PCM_F32: a bit copy.  MG_PCM_S16 / MG_PCM_S24: clamp(rint(x 2^(bits - 1)), -2^(bits - 1), 2^(bits - 1) - 1),
+ *                       round half to even, the product exact, NaN -> 0.  clipped [n_rows]: per row the samples that were clamped or
+ *                       NaN (0 for F32).  The rows of one file write disjoint bytes of the same frames.  One workgroup per row.  A
+ *                       row of any other format is a dead row here (the table lives on the device): the binding refuses it with
+ *                       MG_ERR_UNSUPPORTED's exception before the launch.  No dither.
+ * A row is cut to both of its buffers in whole frames: no load or store touches a byte outside [0, bytes_total) or a sample outside
+ * the float buffer.  A row with frames <= 0, a negative or too large position, channels outside [1, 65535], channel outside
+ * [0, channels) or an unknown format is dead (decode writes nothing and gives moments {0, 0}; encode gives clipped 0).  No atomics,
+ * every sum has one fixed order: a row has the same bits alone as inside any pack.  No host synchronisation; the launch count
+ * does not depend on n_rows.  MG_ERR_ARG before any launch: a null pointer, n_rows, a total or max_frames <= 0, a short workspace. */
+#define MG_PCM_U8 0
+#define MG_PCM_S16 1
+#define MG_PCM_S24 2
+#define MG_PCM_S32 3
+#define MG_PCM_F32 4
+#define MG_PCM_F64 5
+typedef struct { long long src_pos, frames, channels, channel, format, dst_pos; } mg_pcm_row;
+size_t mg_pcm_decode_rows_workspace(int n_rows, long long max_frames);
+int mg_pcm_decode_rows(const void* bytes, long long bytes_total, const mg_pcm_row* rows, int n_rows, long long max_frames,
+                       float* out, long long out_total, double* moments, void* workspace, size_t workspace_bytes, void* stream);
+int mg_pcm_encode_rows(const float* x, long long x_total, const mg_pcm_row* rows, int n_rows, long long max_frames, void* bytes,
+                       long long bytes_total, long long* clipped, void* stream);
+
 /* F2  util/util.py:132-177 compute_matrics on the device (train.py:104-134 eval_model, generate_audio.py:60).
  *   mg_metrics_rows   out[b] = {sum hr^2, sum (sr - hr)^2, sum (lr - hr)^2} (double) for clips [B, T]  -> MSE / SNR
  *   mg_stft_frames    reflect-padded (center != 0), windowed frames [B * F, n_fft], F = mg_stft_num_frames(): the A

@@ -129,6 +129,9 @@ SIGNATURES = {
     "mg_train_lr_rows": (_i, [_p, _ll, _p, _i, _i, _RB, _RB, _p, _ll, _p, _ll, _ll, _p]),
     "mg_sos_rows_workspace": (_sz, [_i, _ll]),
     "mg_sos_rows": (_i, [_p, _ll, _p, _p, _i, _ll, _i, _p, _ll, _p, _sz, _p]),
+    "mg_pcm_decode_rows_workspace": (_sz, [_i, _ll]),
+    "mg_pcm_decode_rows": (_i, [_p, _ll, _p, _i, _ll, _p, _ll, _p, _p, _sz, _p]),
+    "mg_pcm_encode_rows": (_i, [_p, _ll, _p, _i, _ll, _p, _ll, _p, _p]),
     "mg_metrics_rows":(_i, [_p, _p, _p, _i, _i, _p, _p]),
     "mg_stft_num_frames": (_i, [_i, _i, _i, _i]),
     "mg_stft_frames": (_i, [_p, _i, _i, _p, _i, _i, _i, _p, _p]),

@@ -13,7 +13,9 @@ device row tables (``mg_seg_row``: position, window) say where each batch row re
 the segments (``mg_segments_gather``), and the row-table decode (``mg_imdct4_stitched_rows``, ``mg_imdct4_pow2_stitched_rows``)
 stitches every utterance in its own window.  The launch topology does not depend on the mix of lengths, so one captured graph
 serves them all.  ``super_resolve_many`` starts one step earlier, from raw files at their own sampling rates: the packed
-front end of ``resample.front_end_many`` leaves the packed input buffer that these batches read.
+front end of ``resample.front_end_many`` leaves the packed input buffer that these batches read.  ``super_resolve_files``,
+``evaluate_files`` and the command line (``python -m mdctgan_amd.generate_audio``) start and end at WAV files: ``wavio`` decodes
+all of them in one launch in front of that, and encodes all outputs in one launch behind it.
 """
 from __future__ import annotations
 
@@ -287,17 +289,19 @@ def generate_many(model, waves, batch_size: int = 64, gen_overlap: int = 0, pad_
     return _run_packed(model, pack_waves(waves, plan.in_layout, dev), plan, pad_batches)
 
 
-def super_resolve_many(model, raws, rates, batch_size: int = 64, gen_overlap=None, noise=None, generator=None):
+def super_resolve_many(model, raws, rates, batch_size: int = 64, gen_overlap=None, noise=None, generator=None,
+                       raw_moments=None):
     """From raw files to super-resolved waveforms for a whole test set: resample.front_end_many (AudioTestDataset.read_audio +
     post_processing, data/audio_dataset.py:141-186, for all utterances in shared launches) followed by generate_many's batches
     over the packed buffer it leaves -- no per-utterance launch, no repacking.  raws: waveforms [T_u] or [1, T_u] (host or device)
     at sampling rates `rates`.  lr_sampling_rate, hr_sampling_rate, is_lr_input, add_noise, snr, segment_length and (unless given)
     gen_overlap come from model.opt.  noise / generator: see front_end_many.  -> list of stitched waveforms [1, total_u], views
-    of one packed buffer, bit for bit generate_many(model, front_end_many(...)'s views)."""
+    of one packed buffer, bit for bit generate_many(model, front_end_many(...)'s views).  raws may be packed already (a
+    wavio.WavPack or a triple) and raw_moments given: see front_end_many."""
     from .resample import front_end_many
     dev = next(model.netG.parameters()).device
     packed, _, plan = front_end_many(raws, rates, _front_end_kwargs(model, batch_size, gen_overlap), noise=noise,
-                                     generator=generator, device=dev)
+                                     generator=generator, device=dev, raw_moments=raw_moments)
     return _run_packed(model, packed, plan.utterances)
 
 
@@ -311,7 +315,8 @@ def _front_end_kwargs(model, batch_size, gen_overlap) -> dict:
                 out_segment_length=_decoded_segment_length(model.preprocess, L))
 
 
-def evaluate_many(model, raws, rates, batch_size: int = 64, gen_overlap=None, noise=None, generator=None, metric_path=None):
+def evaluate_many(model, raws, rates, batch_size: int = 64, gen_overlap=None, noise=None, generator=None, metric_path=None,
+                  raw_moments=None):
     """generate_audio.py:22-88 for a whole test set of files at hr_sampling_rate: super_resolve_many, then every utterance scored
     against its own ground truth by metrics.compute_matrics_many -- front end, generator batches and metrics over the same packed
     buffers, the host never waiting.  The ground truth is read_audio's waveform, the packed raw buffer plus the per-utterance DC
@@ -320,7 +325,7 @@ def evaluate_many(model, raws, rates, batch_size: int = 64, gen_overlap=None, no
     raw_audio with the model's output sample by sample, which means something only then.
     -> (waveforms, scores): super_resolve_many's list, and a float64 device tensor [U, 7] = (mse, snr_sr, snr_lr, 0, 0, 0, lsd) per
     utterance.  metric_path: one `MSE,SNR_SR,LSD` line per utterance is appended (:86-88) -- the only read-back, after everything
-    is queued."""
+    is queued.  raws may be packed already and raw_moments given: see front_end_many."""
     from .metrics import compute_matrics_many
     from .resample import front_end_many
     opt = model.opt
@@ -331,7 +336,7 @@ def evaluate_many(model, raws, rates, batch_size: int = 64, gen_overlap=None, no
                              % (u, r, int(opt.hr_sampling_rate)))
     dev = next(model.netG.parameters()).device
     packed, _, plan = front_end_many(raws, rates, _front_end_kwargs(model, batch_size, gen_overlap), noise=noise,
-                                     generator=generator, device=dev, keep_raw=True)
+                                     generator=generator, device=dev, keep_raw=True, raw_moments=raw_moments)
     utt = plan.utterances
     waves, out = _run_packed(model, packed, utt, with_buffer=True)
     srs = (out, utt.out_start, utt.out_length) if out is not None else waves
@@ -416,3 +421,142 @@ def make_graphed_generate_many(model, max_segments: int, max_samples: int, batch
         return run.last
     run.graph, run.pinned, run.last = graph, pinned, None
     return run
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Files in, files out
+# ---------------------------------------------------------------------------------------------------------------------
+@dataclass
+class FilesResult:
+    """super_resolve_files' result.  `waves[r]`: the super-resolved waveform [1, T'_r] of row r of `pack` (wavio.WavPack: channel
+    pack.channel[r] of pack.paths[pack.file[r]]), cropped to the row's final front-end length.  `out_paths[f]`: the file written
+    for input f (None without out_dir).  `clipped[r]`: the samples of row r that the encoder clamped or found NaN (None without
+    out_dir)."""
+    waves: list
+    pack: object
+    out_paths: object = None
+    clipped: object = None
+
+
+def _output_paths(paths, out_dir):
+    stems = [os.path.splitext(os.path.basename(os.fspath(p)))[0] for p in paths]
+    seen = {}
+    for p, s in zip(paths, stems):
+        if s in seen:
+            raise ValueError("%s and %s would both be written to %s.wav" % (seen[s], p, s))
+        seen[s] = p
+    return [os.path.join(os.fspath(out_dir), s + ".wav") for s in stems]
+
+
+def _write_cropped(out_paths, waves, out, utt, lengths, groups, rate, encoding):
+    """wavio.write_wav_many over the stitched waveforms cropped to `lengths`: straight from the packed output buffer when the
+    decoder left one."""
+    from .wavio import write_wav_many
+    os.makedirs(os.path.dirname(out_paths[0]) or ".", exist_ok=True)
+    rows = (out, utt.out_start, lengths) if out is not None else [w[..., :n] for w, n in zip(waves, lengths)]
+    return write_wav_many(out_paths, rows, rate, encoding, groups)
+
+
+def super_resolve_files(model, paths, out_dir=None, channels: str = "all", encoding: str = "PCM_F32", batch_size: int = 64,
+                        gen_overlap=None, noise=None, generator=None) -> FilesResult:
+    """From WAV files to WAV files: wavio.read_wav_many (one decode launch, the DC moments from the same pass), super_resolve_many's
+    front end and generator batches over the packed buffer it leaves, and wavio.write_wav_many (one encode launch) -- no
+    per-file launch anywhere.  channels "all": every channel of a file is a row of its own and all of them end up in ONE output
+    file; "first": channel 0 only (what the reference's datasets keep).  Every output is cropped to the row's final front-end
+    length (its length at hr_sampling_rate) and written to <out_dir>/<stem>.wav at hr_sampling_rate as `encoding` ("PCM_F32",
+    "PCM_S16", "PCM_S24": see write_wav_many); two inputs with one stem are a ValueError.  out_dir None: nothing is written."""
+    from .resample import front_end_many
+    from .wavio import read_wav_many
+    paths = [os.fspath(p) for p in paths]
+    out_paths = _output_paths(paths, out_dir) if out_dir is not None else None
+    dev = next(model.netG.parameters()).device
+    pack = read_wav_many(paths, dev, channels, with_moments=True)
+    packed, _, plan = front_end_many(pack, pack.rates, _front_end_kwargs(model, batch_size, gen_overlap), noise=noise,
+                                     generator=generator, device=dev, raw_moments=pack.moments)
+    utt = plan.utterances
+    waves, out = _run_packed(model, packed, utt, with_buffer=True)
+    lengths = [min(n, t) for n, t in zip(plan.final_lengths, utt.out_length)]
+    res = FilesResult([w[..., :n] for w, n in zip(waves, lengths)], pack)
+    if out_paths is not None:
+        groups = [[] for _ in paths]
+        for r, f in enumerate(pack.file):
+            groups[f].append(r)
+        res.out_paths = out_paths
+        res.clipped = _write_cropped(out_paths, waves, out, utt, lengths, groups, int(model.opt.hr_sampling_rate), encoding)
+    return res
+
+
+def evaluate_files(model, paths, metric_path=None, batch_size: int = 64, gen_overlap=None, noise=None, generator=None,
+                   out_dir=None, encoding: str = "PCM_F32"):
+    """evaluate_many over WAV files: channel 0 of every file (read_audio's waveform), each of which must be at hr_sampling_rate
+    (evaluate_many's rule).  -> (waveforms, scores) as evaluate_many; metric_path: its `MSE,SNR_SR,LSD` lines.  out_dir: the
+    waveforms are written as well, as super_resolve_files(channels="first") writes them."""
+    from .wavio import read_wav_many
+    paths = [os.fspath(p) for p in paths]
+    out_paths = _output_paths(paths, out_dir) if out_dir is not None else None
+    pack = read_wav_many(paths, next(model.netG.parameters()).device, "first", with_moments=True)
+    waves, scores = evaluate_many(model, pack, pack.rates, batch_size, gen_overlap, noise, generator, metric_path,
+                                  raw_moments=pack.moments)
+    if out_paths is not None:
+        # (every file is at hr_sampling_rate: the final front-end length is the file's own)
+        lengths = [min(n, w.shape[-1]) for n, w in zip(pack.lengths, waves)]
+        clipped = _write_cropped(out_paths, waves, None, None, lengths, None, int(model.opt.hr_sampling_rate), encoding)
+        return waves, scores, clipped
+    return waves, scores
+
+
+def input_files(path) -> List[str]:
+    """AudioDataset.get_files (data/audio_dataset.py:84-100): a directory is walked for .wav files (the reference's test admits
+    every name; .mp3 and .flac are out of scope here), a .wav file is itself, anything else is a CSV whose entries are paths
+    relative to its own directory."""
+    import csv
+    path = os.fspath(path)
+    if os.path.isdir(path):
+        files = []
+        for root, _, names in os.walk(path, topdown=False):
+            files += [os.path.join(root, n) for n in sorted(names) if os.path.splitext(n)[1].lower() == ".wav"]
+        return files
+    if os.path.splitext(path)[1].lower() == ".wav":
+        return [path]
+    root = os.path.split(path)[0]
+    with open(path, "r") as f:
+        return [os.path.join(root, item) for row in csv.reader(f) for item in row]
+
+
+def main(argv=None) -> int:
+    """python -m mdctgan_amd.generate_audio --input FILE|DIR|CSV --output_dir DIR [--channels first|all]
+    [--out_encoding PCM_F32|PCM_S16|PCM_S24] [--metrics] plus the model's flags (the checkpoint: --load_pretrain DIR
+    --which_epoch LABEL, through load_network).  --metrics scores channel 0 of every file against the file itself and writes
+    <output_dir>/metric.txt."""
+    from .options import TrainOptions
+    from .pix2pixHD_model import create_model
+    options = TrainOptions()
+    opt = options.parse(argv)
+    if not opt.input or not opt.output_dir:
+        options.parser.error("--input and --output_dir are required")
+    files = input_files(opt.input)
+    if not files:
+        options.parser.error("no .wav file under %s" % opt.input)
+    model = create_model(opt)
+    if opt.metrics:
+        os.makedirs(opt.output_dir, exist_ok=True)
+        metric_path = os.path.join(opt.output_dir, "metric.txt")
+        with open(metric_path, "w") as f:
+            f.write("MSE,SNR_SR,LSD\n")
+        _, _, clipped = evaluate_files(model, files, metric_path, batch_size=opt.batchSize, out_dir=opt.output_dir,
+                                       encoding=opt.out_encoding)
+        by_file = clipped
+    else:
+        res = super_resolve_files(model, files, opt.output_dir, opt.channels, opt.out_encoding, batch_size=opt.batchSize)
+        by_file = [0] * len(files)
+        for r, f in enumerate(res.pack.file):
+            by_file[f] += res.clipped[r]
+    for path, n in zip(files, by_file):
+        if n:
+            print("%s: %d samples clipped" % (path, n))
+    print("%d files written to %s" % (len(files), opt.output_dir))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

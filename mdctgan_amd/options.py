@@ -87,6 +87,11 @@ _FLAGS = [
     ("lowpass_aug", dict(type=str, default="")), ("lowpass_order", dict(type=int, default=(2, 10), nargs=2)),
     ("lowpass_ripple", dict(type=float, default=(0.01, 1.0), nargs=2)),
     ("lowpass_cutoff", dict(type=float, default=(0.9, 1.0), nargs=2)),
+    # files in, files out (not in the reference: python -m mdctgan_amd.generate_audio): a .wav file, a directory or a CSV list; where
+    # <stem>.wav goes; which channels are super-resolved; the written sample format; metric.txt against the files themselves
+    ("input", dict(type=str, default="")), ("output_dir", dict(type=str, default="")),
+    ("channels", dict(type=str, default="all", choices=["first", "all"])),
+    ("out_encoding", dict(type=str, default="PCM_F32", choices=["PCM_F32", "PCM_S16", "PCM_S24"])), ("metrics", True),
     # transform
     ("lr_sampling_rate", dict(type=int, default=LR_SAMPLE_RATE)),
     ("hr_sampling_rate", dict(type=int, default=HR_SAMPLE_RATE)),

@@ -288,7 +288,20 @@ def data_options(opt) -> dict:
     return o
 
 
-def front_end_many(raws, rates, opt_or_kwargs, noise=None, generator=None, device=None, keep_raw=False):
+def _prepacked(raws):
+    """front_end_many's `raws` when they are packed already -- a wavio.WavPack (anything with buffer / starts / lengths) or a
+    (buffer, starts, lengths) triple -> (float32 device buffer, starts, lengths); None for a list of waveforms."""
+    if all(hasattr(raws, a) for a in ("buffer", "starts", "lengths")):
+        raws = (raws.buffer, raws.starts, raws.lengths)
+    elif not (isinstance(raws, tuple) and len(raws) == 3 and torch.is_tensor(raws[0]) and not torch.is_tensor(raws[1])):
+        return None
+    buf, starts, lengths = raws
+    if buf.dtype != torch.float32 or not buf.is_cuda or not buf.is_contiguous() or buf.dim() != 1:
+        raise ValueError("front_end_many: a packed raw buffer is a contiguous float32 [total] device tensor")
+    return buf, [int(s) for s in starts], [int(n) for n in lengths]
+
+
+def front_end_many(raws, rates, opt_or_kwargs, noise=None, generator=None, device=None, keep_raw=False, raw_moments=None):
     """AudioTestDataset.read_audio + post_processing (data/audio_dataset.py:141-186) for a list of raw waveforms ([T_u] or
     [1, T_u], on the host or the device) at sampling rates `rates` -> (packed, views, plan): the packed low-rate buffer at
     hr_sampling_rate (float32 [plan.totals[-1]], packed.pack_waves' layout, zeros in the gaps), one [1, T'_u] view of it
@@ -300,15 +313,41 @@ def front_end_many(raws, rates, opt_or_kwargs, noise=None, generator=None, devic
     mg_resample_rows per distinct rate pair and step, and under add_noise two more mg_rows_moments and mg_add_noise_rows --
     whatever the number of utterances.  No host read-back.
     keep_raw: plan.raw keeps the packed raw buffer and the shift in utterance order (see FrontEndPlan; one more element-wise launch
-    when the rates differ); nothing else changes."""
+    when the rates differ); nothing else changes.
+    raws may also be packed already: a wavio.WavPack (rates=None: its own) or a (buffer, starts, lengths) triple over a float32
+    device buffer in packed.aligned_layout's layout -- then there is no packing copy, the buffer is read where it is.
+    raw_moments: float64 [U, 2] on the device, {sum x, sum x^2} of every raw waveform in UTTERANCE order with packed.rows_moments'
+    bits (wavio.read_wav_many(with_moments=True) has them from its decode pass) -- in place of the mg_rows_moments launch.  With a
+    list of waveforms and no raw_moments the launches are what they were."""
     o = data_options(opt_or_kwargs)
-    raws = list(raws)
-    if len(raws) == 0:
+    prepacked = _prepacked(raws)
+    if prepacked is not None:
+        raw_buf, raw_starts, lengths = prepacked
+        if rates is None:
+            rates = getattr(raws, "rates", None)
+        raws = []
+    else:
+        raws = list(raws)
+        lengths = [w.numel() for w in raws]
+    if len(lengths) == 0:
         raise ValueError("no waveforms")
-    if any(w.numel() == 0 for w in raws):
+    if min(lengths) == 0:
         raise ValueError("an empty waveform cannot be resampled")
-    plan = plan_front_end([w.numel() for w in raws], rates, o["hr_sampling_rate"], o["lr_sampling_rate"], o["is_lr_input"],
+    plan = plan_front_end(lengths, rates, o["hr_sampling_rate"], o["lr_sampling_rate"], o["is_lr_input"],
                           o["segment_length"], o["gen_overlap"], o["batch_size"], o["out_segment_length"])
+    if prepacked is not None:
+        if raw_starts != plan.starts[0] or raw_buf.numel() < plan.totals[0]:
+            raise ValueError("front_end_many: a packed raw buffer has packed.aligned_layout's layout over its lengths")
+        if device is None:
+            device = raw_buf.device
+        want = torch.device(device)
+        if want.type != "cuda" or (want.index is not None and want.index != raw_buf.device.index):
+            raise ValueError("front_end_many: the packed raw buffer is on %s, not on %s" % (raw_buf.device, device))
+        device = raw_buf.device
+    U = len(lengths)
+    if raw_moments is not None and (raw_moments.dtype != torch.float64 or tuple(raw_moments.shape) != (U, 2)
+                                    or not raw_moments.is_cuda):
+        raise ValueError("front_end_many: raw_moments is a float64 [%d, 2] device tensor, one row per utterance" % U)
     final = plan.final_lengths
     if o["add_noise"]:
         if min(final) < 2:
@@ -320,16 +359,25 @@ def front_end_many(raws, rates, opt_or_kwargs, noise=None, generator=None, devic
 
     # every table in one copy: the raw windows in group order, the final windows, each group's rows, then where utterance u sits in
     # plan.order
-    U = len(raws)
-    reorder = keep_raw and plan.order != list(range(U))
+    shuffled = plan.order != list(range(U))
+    reorder = keep_raw and shuffled
+    pick = raw_moments is not None and shuffled                     # (the moments arrive in utterance order)
     raw_win, lr_win, *group_rows = upload_tables(
         [window_table(plan.starts[0], plan.lengths[0], plan.order), window_table(plan.starts[-1], final)]
         + [g.rows for step in plan.steps for g in step]
-        + ([np.argsort(np.asarray(plan.order, dtype=np.int64), kind="stable")] if reorder else []), device)
+        + ([np.argsort(np.asarray(plan.order, dtype=np.int64), kind="stable")] if reorder else [])
+        + ([np.asarray(plan.order, dtype=np.int64)] if pick else []), device)
+    order_t = group_rows.pop() if pick else None
     place = group_rows.pop() if reorder else None
 
-    buf = pack_waves(raws, PackedLayout(plan.starts[0], plan.lengths[0], plan.totals[0]), device)
-    mom = rows_moments(buf, raw_win, max(plan.lengths[0]))
+    if prepacked is not None:
+        buf = raw_buf[:plan.totals[0]]
+    else:
+        buf = pack_waves(raws, PackedLayout(plan.starts[0], plan.lengths[0], plan.totals[0]), device)
+    if raw_moments is not None:
+        mom = raw_moments[order_t] if pick else raw_moments
+    else:
+        mom = rows_moments(buf, raw_win, max(plan.lengths[0]))
     shift = (1e-4 - mom[:, 0] / (raw_win[:, 2] - raw_win[:, 1]).double()).float()     # raw += 1e-4 - mean(raw), per utterance
     if keep_raw:
         plan.raw = SimpleNamespace(buffer=buf, shift=shift[place].contiguous() if reorder else shift,

@@ -64,6 +64,14 @@ def pack_corpus(waveforms, rates, device, align: int = 64) -> TrainingCorpus:
     return TrainingCorpus(pack_waves(waveforms, layout, device), layout.starts, lengths, rates)
 
 
+def pack_corpus_files(paths, device) -> TrainingCorpus:
+    """pack_corpus straight from WAV files (wavio.read_wav_many: one copy of the payload bytes, one decode launch): channel 0 of
+    every file -- what seg_pad_audio keeps (:104) -- whole, at the sampling rate its header names.  The crop stays draw_windows'."""
+    from .wavio import read_wav_many
+    pack = read_wav_many(paths, device, channels="first")
+    return TrainingCorpus(pack.buffer, pack.starts, pack.lengths, pack.rates)
+
+
 def crop_window(audio_length: int, fs: int, segment_length: int, hr_rate: int) -> int:
     """data/audio_dataset.py:43: the exclusive upper bound of readaudio's random start frame (<= 0: the whole file is loaded)."""
     return int(audio_length - segment_length * fs / hr_rate)
