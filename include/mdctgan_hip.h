@@ -637,6 +637,32 @@ typedef struct {
 size_t mg_conv_wino_weights_bytes(const mg_conv_geom* g);
 size_t mg_conv_wino_tiles_bytes(const mg_conv_geom* g, int which);
 int mg_conv_wino_prepare(const mg_conv_geom* g, const float* w, float* u, void* stream);
+/* What a caller that holds these images across the passes of a step has to know about a layer, in one query: every field follows
+ * from the geometry and the environment of the moment, as the launches do.  (The struct carries a tag, not a typedef, so that it
+ * can share its name with the function: write `struct mg_conv_traits`.)  MG_ERR_ARG: out is NULL or the geometry is invalid. */
+#define MG_IMAGE_NONE 0       /* mg_conv_wino_weights_bytes(g) == 0: the layer keeps no weight image */
+#define MG_IMAGE_WINO_F32 1   /* U = G w G^T in float32 */
+#define MG_IMAGE_WINO_F16 2   /* ... in float16 (MG_PRECISION_F16_INFER layers on float16 images) */
+#define MG_IMAGE_CAST 3       /* the plain float16 copy of the OHWI weights (the float16 GEMM paths of MG_PRECISION_F16) */
+#define MG_IMAGE_CO1 4        /* the weights of a single-output-channel layer padded to 64 tap rows, float32 */
+struct mg_conv_traits {
+    int weight_image;         /* MG_IMAGE_*: what mg_conv_wino_prepare writes into u */
+    int weight_positions;     /* P of a Winograd image (16, 25 or 36), 0 for the other kinds */
+    int weight_elem;          /* bytes per element of u (0 for MG_IMAGE_NONE) */
+    int images_half;          /* the layer's Winograd images u, v and a handed-over v_next are float16 (MG_IMAGE_WINO_F16) */
+    int tiles;                /* 0: v / md are absent, or Winograd images, which the weight gradient takes only as a pair;
+                               * 1: they are the float16 copies of x / dy, each usable without the other;
+                               * 2: md is the scattered dy of a single-output-channel layer (usable alone; v: its rounded x) */
+    int precast[2];           /* [0]: mg_conv_fwd_w honours MG_TILES_V_FILLED with v = float16(x) written by x's producer;
+                               * [1]: mg_conv_dgrad_w honours MG_TILES_MD_FILLED with md = float16(dy) */
+    int vnext_positions;      /* != 0 where mg_conv_wino_vnext_ok(g): the positions of the family v_next is written for (an image
+                               * is only good for a layer of the same family and element type) */
+    int md_from_norm;         /* mg_conv_wino_md_from_norm_ok(g) */
+    int wgrad_adam;           /* mg_conv_wgrad_adam_ok(g) */
+    int wgrad_checks_finite;  /* mg_conv_wgrad_checks_finite(g) */
+    int wgrad_h16;            /* mg_conv_wgrad_h16_ok(g) */
+};
+int mg_conv_traits(const mg_conv_geom* g, struct mg_conv_traits* out);
 int mg_conv_fwd_w(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int act,
                   void* workspace, size_t workspace_bytes, void* stream, const mg_wino_tiles* tiles);
 /* y_raw = conv(x, w) + bias (mg_conv_fwd_w with no activation) followed by mg_instnorm_fwd(y_raw) -> y = act((y_raw - mean)
@@ -673,7 +699,7 @@ int mg_conv_fwd_instnorm_h(const mg_conv_geom* g, const float* x, const float* w
  * MG_PRECISION_F32_WINO43 layers that run as F(4x4,3x3) have the same pair: on maps of <= 40 tiles (640 pixels) per sample with
  * Co % 32 == 0 the inverse transform and the InstanceNorm are one kernel, mg_conv_wino_vnext_ok(g) != 0, and v_next is the
  * 36 * T * Co float image of a following F(4x4,3x3) layer.  The caller hands an image only to a layer of the family it was written
- * for (the same mg_conv_wino_weights_bytes / (Co * Ci) positions). */
+ * for (the same mg_conv_traits.vnext_positions). */
 int mg_conv_wino_vnext_ok(const mg_conv_geom* g);
 int mg_conv_fwd_instnorm_next(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y_raw, float eps,
                               int act, const float* residual, float* y, float* mean, float* rstd, void* workspace,

@@ -45,6 +45,19 @@ class WinoTiles(C.Structure):
 
 _W = C.POINTER(WinoTiles)
 
+IMAGE_NONE, IMAGE_WINO_F32, IMAGE_WINO_F16, IMAGE_CAST, IMAGE_CO1 = range(5)      # mg_conv_traits.weight_image (MG_IMAGE_*)
+
+
+class ConvTraits(C.Structure):
+    """mg_conv_traits: what mg_conv_traits(g) says about a layer's images and fused side paths."""
+    _fields_ = [("weight_image", C.c_int), ("weight_positions", C.c_int), ("weight_elem", C.c_int), ("images_half", C.c_int),
+                ("tiles", C.c_int), ("precast", C.c_int * 2), ("vnext_positions", C.c_int), ("md_from_norm", C.c_int),
+                ("wgrad_adam", C.c_int), ("wgrad_checks_finite", C.c_int), ("wgrad_h16", C.c_int)]
+
+    def astuple(self):
+        """The fields in order, the precast array as a pair."""
+        return tuple(v if isinstance(v, int) else tuple(v) for v in (getattr(self, n) for n, _ in self._fields_))
+
 
 class LossItem(C.Structure):
     """mg_loss_item: one tensor of a multi-tensor loss call."""
@@ -94,6 +107,7 @@ SIGNATURES = {
     "mg_conv_wino_weights_bytes": (_sz, [_G]),
     "mg_conv_wino_prepare": (_i, [_G, _p, _p, _p]),
     "mg_conv_wino_tiles_bytes": (_sz, [_G, _i]),
+    "mg_conv_traits": (_i, [_G, C.POINTER(ConvTraits)]),
     "mg_conv_fwd_w": (_i, [_G, _p, _p, _p, _p, _i, _p, _sz, _p, _W]),
     "mg_conv_fwd_instnorm_workspace": (_sz, [_G]),
     "mg_conv_wino_md_from_norm_ok": (_i, [_G]),

@@ -231,6 +231,14 @@ inline void h16_launch(const H16Plan& p, bool brc, const HgArgs& a, hipStream_t 
 // MG_NO_HGEMM_SA=1: the round-2..5 kernels (im2col matrix + hgemm_kernel) instead of the weight-streaming form (read per call: the
 // bit-identity test flips it)
 inline bool h16_sa_on() { return getenv("MG_NO_HGEMM_SA") == nullptr; }
+// The forward pass (0) / data gradient (1) of the layer takes that form: the instance mg_conv_plan_name prints, and for the forward
+// pass, whose GEMM gathers its rows from float16(x) itself, what mg_conv_traits reports as precast[0]
+inline bool h16_sa(int pass, const mg_conv_geom* g) {
+    HgArgs a{};
+    a.N = pass == 1 ? g->Ci : g->Co;
+    a.K = g->KH * g->KW * (pass == 1 ? g->Co : g->Ci);
+    return h16_sa_on() && hgemm_sa_ok(a);
+}
 // x16_pre (nullable): float16(x) already written by x's producer (MG_TILES_V_FILLED); defer (nullable): FwdDefer
 int h16_fwd(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y, int act, char* ws,
             hipStream_t st, const void* w16_pre, const void* x16_pre, FwdDefer* defer) {

@@ -48,11 +48,35 @@ ConvRoute conv_route(int pass, const mg_conv_geom* g, bool generic) {
     if (pass == 2) return conv_dma_wgrad_ok(g) ? R_DMA : R_IGEMM;
     return conv_dma_dgrad_ok(g) ? R_DMA : cd_reflect_dgrad_ok(g) ? R_DMA_REFLECT : R_IGEMM;
 }
-// a layer any of whose passes runs on the float16 implicit GEMMs keeps a cached float16 copy of its weights (a Winograd
-// layer keeps float32 U / V / Md images under MG_PRECISION_F16: it must never be handed the float16-sized buffers of this path)
-inline bool conv_dma_h_any(const mg_conv_geom* g) {
-    const ConvRoute d = conv_route(1, g);
-    return conv_dma_half(g) && (conv_route(0, g) == R_DMA || d == R_DMA || d == R_DMA_REFLECT);
+// The images a layer keeps between the passes of a step (mg_wino_tiles), from the routes of its three passes: the kind of the
+// weight image mg_conv_wino_prepare writes (MG_IMAGE_*), its Winograd positions P (0: not a Winograd image) and element size, and
+// the byte sizes of u, v and md.  r: the forward route.  The size queries, mg_conv_wino_prepare and mg_conv_traits are views of it.
+struct ConvImages { ConvRoute r; int kind, P, elem; size_t u, v, md; };
+ConvImages conv_images(const mg_conv_geom* g) {
+    const ConvRoute r = conv_route(0, g);
+    switch (r) {
+    case R_CO1:         // tap GEMM: the weights zero-padded to 64 tap rows; v: the rounded x (autocast), md: Gt (data -> weight gradient)
+        return {r, MG_IMAGE_CO1, 0, 4, (size_t)CO1_TAPS * g->Ci * sizeof(float), co1_xr_bytes(g), co1_zt_bytes(g)};
+    case R_H16:         // the float16 weight copy of the autocast GEMM path (conv_h16.h); no tiles
+        return {r, MG_IMAGE_CAST, 0, 2, h16_weights_bytes(g), 0, 0};
+    case R_WINO: case R_WINO4: case R_WINO42: case R_WINO43: case R_WINOH: {
+        const WinoGeo w = wino_geo(r, g);
+        const size_t e = r == R_WINOH ? 2 : sizeof(float), P = w.f.P;
+        const bool fwd_only = r == R_WINO43 || r == R_WINOH;      // V only: no gradient pass reads an image of the output gradient
+        return {r, r == R_WINOH ? MG_IMAGE_WINO_F16 : MG_IMAGE_WINO_F32, w.f.P, (int)e, P * g->Co * w.Kc * e, P * w.T * w.Kc * e,
+                fwd_only ? 0 : P * w.T * g->Co * e};
+    }
+    default: {
+        // a layer whose forward pass or data gradient runs on the float16 implicit GEMMs (conv_dma.h) keeps a float16 copy of its
+        // weights, and -- where its weight gradient runs there too -- the float16 copies of x (forward -> weight gradient) and of dy
+        // (data gradient -> weight gradient) as its "tiles", so that each tensor is cast once per step.  (A Winograd layer keeps
+        // float32 U / V / Md images under MG_PRECISION_F16: it must never be handed the float16-sized buffers of this path.)
+        const ConvRoute d = conv_route(1, g);
+        const bool fh = r == R_DMA, dh = d == R_DMA || d == R_DMA_REFLECT, wh = conv_route(2, g) == R_DMA;
+        if (!conv_dma_half(g) || !(fh || dh)) return {r, MG_IMAGE_NONE, 0, 0, 0, 0, 0};
+        return {r, MG_IMAGE_CAST, 0, 2, h16_weights_bytes(g), wh && fh ? conv_dma_h_x_bytes(g) : 0, wh && dh ? conv_dma_h_dy_bytes(g) : 0};
+    }
+    }
 }
 
 }  // namespace
@@ -137,10 +161,8 @@ int mg_conv_plan_name(int pass, const mg_conv_geom* g, char* out, int out_len) {
         if (pass == 0) deep = h16_deep(px, g->Co, h16_plan(px, g->Co, Kw, false).splits, false);
         else if (pass == 1) deep = h16_deep((long long)g->B * g->H * g->W, g->Ci, h16_plan((long long)g->B * g->H * g->W, g->Ci, g->KH * g->KW * g->Co, true).splits, true);
         else deep = h16_deep(g->Co, Kw, h16_plan(g->Co, Kw, h16_mp(px), false).splits, false);
-        HgArgs probe{};
-        probe.N = pass == 1 ? g->Ci : g->Co; probe.K = pass == 1 ? g->KH * g->KW * g->Co : Kw;
         if (pass == 2 && h16_wgrad_as(g)) snprintf(out, out_len, "hgemm_as_kernel<%d, false, false>", h16_mp(px) / 64);
-        else if (pass != 2 && h16_sa_on() && hgemm_sa_ok(probe)) snprintf(out, out_len, pass == 1 ? "hgemm_sa_kernel<true, false>" : "hgemm_sa_kernel<false, true>");
+        else if (pass != 2 && h16_sa(pass, g)) snprintf(out, out_len, pass == 1 ? "hgemm_sa_kernel<true, false>" : "hgemm_sa_kernel<false, true>");
         else
         snprintf(out, out_len, pass == 1 ? "hgemm_kernel<128, 128, 4, 2, true, %d>" : "hgemm_kernel<128, 128, 4, 2, false, %d>", deep ? 3 : 2);
         break;
@@ -219,54 +241,24 @@ size_t mg_conv_dgrad_workspace(const mg_conv_geom* g) {
     return base;
 }
 
-size_t mg_conv_wino_weights_bytes(const mg_conv_geom* g) {
-    if (!geom_ok(g)) return 0;
-    switch (const ConvRoute r = conv_route(0, g)) {
-    case R_CO1: return (size_t)CO1_TAPS * g->Ci * sizeof(float);      // tap GEMM: the weights zero-padded to 64 tap rows
-    case R_H16: return h16_weights_bytes(g);                          // the float16 weight copy of the autocast GEMM path (conv_h16.h)
-    case R_WINO: case R_WINO4: case R_WINO42: case R_WINO43: {
-        const WinoGeo w = wino_geo(r, g);
-        return (size_t)w.f.P * g->Co * w.Kc * sizeof(float);
-    }
-    case R_WINOH: return (size_t)16 * g->Co * g->Ci * 2;             // U16
-    default: return conv_dma_h_any(g) ? h16_weights_bytes(g) : 0;     // ... and of the float16 implicit GEMMs (conv_dma.h)
-    }
+size_t mg_conv_wino_weights_bytes(const mg_conv_geom* g) { return geom_ok(g) ? conv_images(g).u : 0; }
+size_t mg_conv_wino_tiles_bytes(const mg_conv_geom* g, int which) {
+    if (!geom_ok(g) || which < 0 || which > 1) return 0;
+    const ConvImages m = conv_images(g);
+    return which == 0 ? m.v : m.md;
 }
 int mg_conv_wino_prepare(const mg_conv_geom* g, const float* w, float* u, void* stream) {
-    if (!mg_conv_wino_weights_bytes(g) || !w || !u || !aligned16(w) || !aligned16(u)) return MG_ERR_ARG;
-    switch (const ConvRoute r = conv_route(0, g)) {
-    case R_CO1: co1_pad_w(g, w, u, (hipStream_t)stream); break;
-    case R_WINO: case R_WINO4: case R_WINO42: case R_WINO43: wino_xform_u(wino_geo(r, g), g, w, u, (hipStream_t)stream); break;
-    case R_WINOH: winoh_xform_u(g, w, (_Float16*)u, (hipStream_t)stream); break;
-    default: return h16_prepare(g, w, u, (hipStream_t)stream);
+    if (!geom_ok(g) || !w || !u || !aligned16(w) || !aligned16(u)) return MG_ERR_ARG;
+    const ConvImages m = conv_images(g);
+    switch (m.kind) {
+    case MG_IMAGE_CO1: co1_pad_w(g, w, u, (hipStream_t)stream); break;
+    case MG_IMAGE_WINO_F32: wino_xform_u(wino_geo(m.r, g), g, w, u, (hipStream_t)stream); break;
+    case MG_IMAGE_WINO_F16: winoh_xform_u(g, w, (_Float16*)u, (hipStream_t)stream); break;
+    case MG_IMAGE_CAST: return h16_prepare(g, w, u, (hipStream_t)stream);
+    default: return MG_ERR_ARG;
     }
     MG_CHECK_LAUNCH();
     return MG_OK;
-}
-
-size_t mg_conv_wino_tiles_bytes(const mg_conv_geom* g, int which) {
-    if (!mg_conv_wino_weights_bytes(g)) return 0;
-    switch (const ConvRoute r = conv_route(0, g)) {
-    case R_H16: return 0;
-    case R_CO1: return which == 1 ? co1_zt_bytes(g) : (which == 0 ? co1_xr_bytes(g) : 0);   // Gt (data gradient -> weight gradient); autocast: the rounded x
-    case R_WINOH: return which == 0 ? (size_t)16 * wino_geo(r, g).T * g->Ci * 2 : 0;      // V16 only
-    case R_WINO43:      // V only: no gradient pass reads an image of the output gradient
-        if (which != 0) return 0;
-        [[fallthrough]];
-    case R_WINO: case R_WINO4: case R_WINO42: {
-        const WinoGeo w = wino_geo(r, g);
-        return which == 0 ? (size_t)w.f.P * w.T * w.Kc * sizeof(float) : which == 1 ? (size_t)w.f.P * w.T * g->Co * sizeof(float) : 0;
-    }
-    default: {
-        // float16 implicit GEMMs: the "tiles" are the float16 copies of x (forward -> weight gradient) and of dy (data
-        // gradient -> weight gradient), so that each tensor is cast once per step
-        const ConvRoute d = conv_route(1, g);
-        if (conv_route(2, g) != R_DMA) return 0;
-        if (which == 0) return r == R_DMA ? conv_dma_h_x_bytes(g) : 0;
-        if (which == 1) return (d == R_DMA || d == R_DMA_REFLECT) ? conv_dma_h_dy_bytes(g) : 0;
-        return 0;
-    }
-    }
 }
 static bool wino_tiles_ok(const mg_conv_geom* g, const mg_wino_tiles* t) {
     if (!t || (!t->u && !t->v && !t->md)) return true;
@@ -335,6 +327,29 @@ static bool wino_vnext_ok(const mg_conv_geom* g) {
     return wino_norm_ok(g) && wino_out_norm_next_ok(g->OH / 2, g->OW / 2, g->Co) && g->Co % 16 == 0;
 }
 int mg_conv_wino_vnext_ok(const mg_conv_geom* g) { return g && wino_vnext_ok(g) ? 1 : 0; }
+
+// Everything a caller that holds a layer's images between passes asks about the layer (include/mdctgan_hip.h), in one answer
+int mg_conv_traits(const mg_conv_geom* g, struct mg_conv_traits* out) {
+    if (!out || !geom_ok(g)) return MG_ERR_ARG;
+    const ConvImages m = conv_images(g);
+    const ConvRoute d = conv_route(1, g);
+    const bool half = prec_h(g);
+    *out = {};
+    out->weight_image = m.kind;
+    out->weight_positions = m.P;
+    out->weight_elem = m.elem;
+    out->images_half = m.kind == MG_IMAGE_WINO_F16;
+    // (a forward-only route is neither: its gradient passes do not exist)
+    out->tiles = m.kind == MG_IMAGE_CO1 ? 2 : (half && conv_route(2, g) == R_DMA) ? 1 : 0;
+    out->precast[0] = half && (m.r == R_DMA || (m.r == R_H16 && h16_sa(0, g)));
+    out->precast[1] = half && (d == R_DMA || d == R_DMA_REFLECT);
+    out->vnext_positions = wino_vnext_ok(g) ? m.P : 0;
+    out->md_from_norm = mg_conv_wino_md_from_norm_ok(g);
+    out->wgrad_adam = mg_conv_wgrad_adam_ok(g);
+    out->wgrad_checks_finite = mg_conv_wgrad_checks_finite(g);
+    out->wgrad_h16 = mg_conv_wgrad_h16_ok(g);
+    return MG_OK;
+}
 
 static int conv_fwd_instnorm_impl(const mg_conv_geom* g, const float* x, const float* w, const float* bias, float* y_raw, float eps,
                                   int act, const float* residual, float* y, float* mean, float* rstd, void* workspace,

@@ -143,11 +143,12 @@ def grad_of(p: torch.nn.Parameter):
     return p.grad
 
 
-def _tag_g16(g, weight, bias, weight_grad):
-    """Remember (before the optimiser lays out its arenas) that this weight's gradient kernel can store float16."""
+def _tag_g16(g, t, weight, bias, weight_grad):
+    """Remember (before the optimiser lays out its arenas) that this weight's gradient kernel can store float16.
+    t: ops.traits(g), here and in the helpers below."""
     if (g.precision == _lib.PRECISION_F16 and weight_grad is True and weight.requires_grad
             and not hasattr(weight, "_mg_g16_ok")):
-        weight._mg_g16_ok = bool(ops.wgrad_h16_ok(g))
+        weight._mg_g16_ok = bool(t.wgrad_h16)
         opt = getattr(weight, "_mg_opt", None)
         if weight._mg_g16_ok and opt is not None:
             opt.adopt_g16(weight)         # the arenas were laid out before this first forward pass (ddp.attach)
@@ -182,16 +183,16 @@ def _zero_grad_bias(bias):
     bias._mg_fresh = False
 
 
-def _producer_flag(weight, g):
+def _producer_flag(weight, t):
     """--fp16: the GradScaler's found_inf slot of the optimiser that owns `weight`, when this layer's weight-gradient kernel
-    checks its own results (ops.wgrad_checks_finite) -- FusedAdam.step then leaves the gradient out of its check pass.  The
+    checks its own results (t.wgrad_checks_finite) -- FusedAdam.step then leaves the gradient out of its check pass.  The
     kernel looks at the gradient AFTER accumulation, so the last writer's check covers the whole buffer; every writer of a
     weight gradient passes through here and restates `_mg_inf_checked`."""
     opt = getattr(weight, "_mg_opt", None)
     if opt is None:
         return None
     flag = opt.producer_flag()
-    if flag is None or not ops.wgrad_checks_finite(g):
+    if flag is None or not t.wgrad_checks_finite:
         return None
     return flag
 
@@ -272,11 +273,11 @@ class fused_adam_scope:
         return False
 
 
-def _fusable(g, weight, weight_grad):
+def _fusable(t, weight, weight_grad):
     """The layer keeps a persistent transformed-weight image that mg_conv_wgrad_adam_w refreshes."""
     opt = getattr(weight, "_mg_opt", None)
     return (opt is not None and weight_grad is True and weight.requires_grad and int(getattr(weight, "_mg_writes", 1)) == 1
-            and opt.can_fuse() and ops.wgrad_adam_ok(g))
+            and opt.can_fuse() and t.wgrad_adam)
 
 
 def _persistent_u(g, weight):
@@ -321,16 +322,16 @@ def _wgrad_fused(ctx_u, g, weight, x, gy, v, md):
     return True
 
 
-def _weight_image(g, weight, weight_grad=None):
+def _weight_image(g, t, weight, weight_grad=None):
     """Weight operand image of a training-step convolution: the Winograd transform / float16 copy made by
     ops.wino_weights, or -- for layers whose image is the plain float16 copy -- the slice of the optimiser's float16
     shadow arena (FusedAdam(half_shadow=True)), which the Adam kernel keeps current."""
-    if weight_grad is not None and _fusable(g, weight, weight_grad):
+    if weight_grad is not None and _fusable(t, weight, weight_grad):
         u = _persistent_u(g, weight)
         if u is not None:
             return u
     h = getattr(weight, "_mg_h", None)
-    if h is not None and ops.weights_are_casts(g):
+    if h is not None and t.weight_image == _lib.IMAGE_CAST:
         if weight._version == weight._mg_h_version:
             return h
         if not torch.cuda.is_current_stream_capturing():       # the parameter was rewritten by a torch op: re-sync
@@ -436,10 +437,11 @@ class _ConvFn(torch.autograd.Function):
             Co, Ci = w.shape[0], w.shape[1]
             assert Ci == x.shape[1]
             g = ops.conv_geom(B, H, W, Ci, Co, KH, KW, stride, pad, reflect, prec)
-            _tag_g16(g, weight, bias, weight_grad)
+            t = ops.traits(g)
+            _tag_g16(g, t, weight, bias, weight_grad)
             # Winograd layers: transform the weights once, reuse the image for the data gradient of this step
             if ctx.needs_input_grad[0]:
-                u = _weight_image(g, weight, weight_grad)
+                u = _weight_image(g, t, weight, weight_grad)
             elif x.is_cuda and not torch.is_grad_enabled():
                 # inference: once per weight version (a captured inference graph reads the images its warm-up made)
                 u = _cached_wino_weights(g, weight, fill=not torch.cuda.is_current_stream_capturing())
@@ -447,7 +449,7 @@ class _ConvFn(torch.autograd.Function):
                 u = None
             # ... and keep B^T x B for the weight gradient (A dy A^T is shared between dgrad and wgrad in backward)
             v, v_filled = None, False
-            x16 = _h16_of(x) if ops.precast_ok(0, g) else None
+            x16 = _h16_of(x) if t.precast[0] else None
             if x16 is not None:                  # x's producer already wrote float16(x): the call skips its cast pass
                 v, v_filled = x16, True
                 H16_STATS["used_fwd"] += 1
@@ -462,15 +464,16 @@ class _ConvFn(torch.autograd.Function):
             assert cin_t == x.shape[1]
             g = ops.conv_geom(B, stride * H, stride * W, cout_t, cin_t, KH, KW, stride, pad, False, prec)
             assert (g.OH, g.OW) == (H, W), "unsupported ConvTranspose2d geometry"
+            t = ops.traits(g)
             # the weight image (Winograd U / float16 copy) serves this call and the backward's data gradient
-            u = _weight_image(g, weight) if (ctx.needs_input_grad[0] and x.is_cuda) else None
-            x16 = _h16_of(x) if ops.precast_ok(1, g) else None       # x plays dy in this call
+            u = _weight_image(g, t, weight) if (ctx.needs_input_grad[0] and x.is_cuda) else None
+            x16 = _h16_of(x) if t.precast[1] else None       # x plays dy in this call
             if x16 is not None:
                 H16_STATS["used_fwd"] += 1
             y = ops.conv_dgrad(g, nhwc_view(x), w, b, act, u=u, md_out=x16, md_filled=x16 is not None)
             ctx.u, ctx.v = u, (x16 if (weight_grad and weight.requires_grad) else None)
         y = nchw_view(y)
-        ctx.g, ctx.cfg = g, cfg[:6]
+        ctx.g, ctx.t, ctx.cfg = g, t, cfg[:6]
         ctx.weight, ctx.bias = weight, bias
         ctx.save_for_backward(x, y if act != ACT_NONE else None)
         return _hang_extra(ctx, y) if act in (ACT_RELU, ACT_LRELU02) else y
@@ -488,7 +491,7 @@ def _conv_backward(ctx, gy, x, y, add=None):
     launch of the library otherwise."""
     stride, pad, reflect, act, transposed, weight_grad = ctx.cfg
     assert add is None or not transposed
-    g, weight, bias = ctx.g, ctx.weight, ctx.bias
+    g, t, weight, bias = ctx.g, ctx.t, ctx.weight, ctx.bias
     gy = to_cl(gy)
     kind = _BackwardPass.kind
     shared = _is_shared(weight_grad)
@@ -503,6 +506,7 @@ def _conv_backward(ctx, gy, x, y, add=None):
         x, gy = x[:rows], gy[:rows]
         y = y[:rows] if y is not None else None
         g = ops.conv_geom(rows, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision)
+        t = ops.traits(g)
     # float16(gy) written by gy's producer (an InstanceNorm backward): only for the whole, untouched tensor
     g16 = _h16_of(gy) if (rows is None and act == ACT_NONE) else None
     if act != ACT_NONE:
@@ -518,10 +522,10 @@ def _conv_backward(ctx, gy, x, y, add=None):
     if want_dx:
         if not transposed:
             u = getattr(ctx, "u", None)
-            if g16 is not None and ops.precast_ok(1, g):
+            if g16 is not None and t.precast[1]:
                 md, md_filled = g16, True
                 H16_STATS["used_bwd"] += 1
-            elif u is not None and want_dw and (getattr(ctx, "v", None) is not None or ops.tiles_are_casts(g)):
+            elif u is not None and want_dw and (getattr(ctx, "v", None) is not None or t.tiles):
                 _, md = ops.wino_tile_buffers(g, gy.device, want_v=False)
             if rows is not None:
                 assert add is None
@@ -529,7 +533,7 @@ def _conv_backward(ctx, gy, x, y, add=None):
                     u = None          # the weight image was made for the stacked batch's plan; half the rows take another path
                 dx = torch.empty_like(x_full)
                 g16r = None
-                if rec16 is not None and act == ACT_NONE and ops.precast_ok(1, g):
+                if rec16 is not None and act == ACT_NONE and t.precast[1]:
                     buf, ptr, ver, r_ = rec16
                     if ptr == gy_full.data_ptr() and ver == gy_full._version and r_ == rows and gy_full.is_contiguous(memory_format=CL):
                         g16r = buf
@@ -541,7 +545,7 @@ def _conv_backward(ctx, gy, x, y, add=None):
             if last_use:
                 ctx.u = None
         else:
-            if g16 is not None and ops.precast_ok(0, g):             # gy plays x in this call
+            if g16 is not None and t.precast[0]:             # gy plays x in this call
                 dx = nchw_view(ops.conv_fwd(g, nhwc_view(gy), w, u=getattr(ctx, "u", None), v_out=g16, v_filled=True))
                 H16_STATS["used_bwd"] += 1
             else:
@@ -551,7 +555,7 @@ def _conv_backward(ctx, gy, x, y, add=None):
                 ctx.u = None
     if want_dw and not transposed and rows is None and (bias is None or not bias.requires_grad or (
             getattr(bias, "_mg_zero_grad", False) and not COMPUTE_DEAD_BIAS_GRADS)):
-        vv = getattr(ctx, "v", None) if (md is not None or ops.tiles_are_casts(g)) else None
+        vv = getattr(ctx, "v", None) if (md is not None or t.tiles) else None
         if _wgrad_fused(u_used, g, weight, nhwc_view(x), nhwc_view(gy), vv, md):
             if bias is not None and bias.requires_grad:
                 _zero_grad_bias(bias)
@@ -567,8 +571,8 @@ def _conv_backward(ctx, gy, x, y, add=None):
             else:
                 bbuf, bacc = grad_buffer(bias)
                 ops.colsum(nhwc_view(gy).reshape(-1, g.Co), bbuf, bacc)
-        flag = _producer_flag(weight, g)
-        if ops.wgrad_h16_ok(g):
+        flag = _producer_flag(weight, t)
+        if t.wgrad_h16:
             ops.conv_wgrad_h16(g, nhwc_view(x), nhwc_view(gy), w16, wacc, found_inf=flag)
             weight._mg_inf_checked = flag is not None
         else:
@@ -599,14 +603,14 @@ def _conv_backward(ctx, gy, x, y, add=None):
                 ops.colsum(nhwc_view(gy).reshape(-1, g.Co), bbuf, bacc)
                 bbuf = None
             # Winograd images come as a pair; the float16 copies of the implicit-GEMM layers are independent
-            v = getattr(ctx, "v", None) if (md is not None or ops.tiles_are_casts(g)) else None
-            flag = _producer_flag(weight, g)
+            v = getattr(ctx, "v", None) if (md is not None or t.tiles) else None
+            flag = _producer_flag(weight, t)
             ops.conv_wgrad(g, nhwc_view(x), nhwc_view(gy), wbuf, bbuf, wacc, v=v, md=md, found_inf=flag)
             weight._mg_inf_checked = flag is not None
             ctx.v = None
         else:
-            flag = _producer_flag(weight, g)
-            half = ops.tiles_are_casts(g) and _lib.is_half(g.precision) and g.Co != 1
+            flag = _producer_flag(weight, t)
+            half = t.tiles == 1             # float16 copies of x / dy, each usable alone
             ops.conv_wgrad(g, nhwc_view(gy), nhwc_view(x), wbuf, None, wacc, found_inf=flag,
                            v=g16 if half else None, md=getattr(ctx, "v", None) if half else None)
             ctx.v = None
@@ -650,18 +654,19 @@ class _ConvInstNormFn(torch.autograd.Function):
         assert w.is_contiguous(memory_format=CL), "conv weights must be channels_last (OHWI) tensors"
         prec = cfg[8] if len(cfg) > 8 else amp.current_precision()       # (read by conv_instnorm(), as the grad mode is)
         g = ops.conv_geom(B, H, W, w.shape[1], w.shape[0], w.shape[2], w.shape[3], 1, pad, reflect, prec)
-        _tag_g16(g, weight, bias, weight_grad)
+        t = ops.traits(g)
+        _tag_g16(g, t, weight, bias, weight_grad)
         if ctx.needs_input_grad[0]:
-            u = _weight_image(g, weight, weight_grad)
+            u = _weight_image(g, t, weight, weight_grad)
         elif x.is_cuda and not torch.is_grad_enabled():
             u = _cached_wino_weights(g, weight, fill=not torch.cuda.is_current_stream_capturing())
         else:
             u = None
         v, v_filled = None, False
-        x16 = _h16_of(x) if ops.precast_ok(0, g) else None
+        x16 = _h16_of(x) if t.precast[0] else None
         # (the key names the family by its positions: under amp.wino43 a layer in front may have written F(4x4,3x3) tiles for a
         # layer that itself runs F(2x2,3x3), or the other way round -- neither reads the other family's image)
-        npos = ops.wino_vnext_positions(g) if (pad == 1 and w.shape[2] == 3 and w.shape[3] == 3) else 0
+        npos = t.vnext_positions if (pad == 1 and w.shape[2] == 3 and w.shape[3] == 3) else 0
         xv = _wino_v_of(x, (B, H, W, w.shape[1], bool(reflect), g.precision, npos)) if npos else None
         if x16 is not None:
             v, v_filled = x16, True
@@ -677,7 +682,7 @@ class _ConvInstNormFn(torch.autograd.Function):
         if next_reflect is not None and npos and os.environ.get("MG_NO_WINO_NEXT", "0") != "1":
             tile = 2 if npos == 16 else 4       # F(2x2,3x3) / F(4x4,3x3) output tiles
             v_next = torch.empty(npos * B * (g.OH // tile) * (g.OW // tile) * g.Co, device=x.device,
-                                 dtype=torch.float16 if ops.wino_images_half(g) else torch.float32)
+                                 dtype=torch.float16 if t.images_half else torch.float32)
         y16 = (torch.empty(B * g.OH * g.OW * g.Co, dtype=torch.float16, device=x.device)
                if _want_h16(B, g.OH * g.OW, g.Co, _lib.is_half(prec)) else None)
         if v_next is not None and v_next.dtype == torch.float16:
@@ -689,7 +694,7 @@ class _ConvInstNormFn(torch.autograd.Function):
                                                      nhwc_view(res) if res is not None else None, eps, u, v, v_filled, y16,
                                                      need_raw=need_raw, v_next=v_next, next_reflect=bool(next_reflect))
         ctx.u, ctx.v = u, (v if (weight_grad and weight.requires_grad) else None)
-        ctx.g, ctx.cfg = g, (1, pad, reflect, ACT_NONE, False, weight_grad)
+        ctx.g, ctx.t, ctx.cfg = g, t, (1, pad, reflect, ACT_NONE, False, weight_grad)
         ctx.weight, ctx.bias, ctx.norm_act = weight, bias, act
         if need_raw:
             ctx.save_for_backward(x, nchw_view(y_raw), mean, rstd)
@@ -710,12 +715,12 @@ class _ConvInstNormFn(torch.autograd.Function):
                 holder.g, dres = dres, None
             elif role == "take":
                 skip_g, holder.g = holder.g, None
-        g, weight, bias = ctx.g, ctx.weight, ctx.bias
+        g, t, weight, bias = ctx.g, ctx.t, ctx.weight, ctx.bias
         weight_grad = ctx.cfg[5]
         dead_bias = bias is None or not bias.requires_grad or (getattr(bias, "_mg_zero_grad", False) and not COMPUTE_DEAD_BIAS_GRADS)
         u, v = getattr(ctx, "u", None), getattr(ctx, "v", None)
         if (ctx.needs_input_grad[0] and weight_grad is True and weight.requires_grad and dead_bias and u is not None
-                and v is not None and ops.wino_md_from_norm_ok(g)):
+                and v is not None and t.md_from_norm):
             # InstanceNorm backward and the A dy A^T transform in one kernel; data and weight gradient start from the images
             _, md = ops.wino_tile_buffers(g, gy.device, want_v=False)
             ops.instnorm_bwd_wino_md(g, nhwc_view(gy), nhwc_view(y_raw), mean, rstd, ctx.norm_act, md)
@@ -733,7 +738,7 @@ class _ConvInstNormFn(torch.autograd.Function):
                 _notify(bias)
             return dx, None, None, dres, None
         d16 = (torch.empty(gy.numel(), dtype=torch.float16, device=gy.device)
-               if (_want_h16(g.B, g.OH * g.OW, g.Co, _lib.is_half(g.precision)) and ops.precast_ok(1, g)) else None)
+               if (_want_h16(g.B, g.OH * g.OW, g.Co, _lib.is_half(g.precision)) and t.precast[1]) else None)
         d_raw = _attach_h16(nchw_view(ops.instnorm_bwd(nhwc_view(gy), nhwc_view(y_raw), mean, rstd, ctx.norm_act, dx16=d16)), d16)
         # the skip connection's gradient joins the data gradient inside its last kernel (no elementwise add launch)
         dx = _conv_backward(ctx, d_raw, x, None, add=nhwc_view(skip_g) if (skip_g is not None and ctx.needs_input_grad[0]) else None)

@@ -2,6 +2,9 @@
 Tensors are float32, contiguous, NHWC, resident in HBM.  No arithmetic happens here."""
 from __future__ import annotations
 
+import ctypes
+from typing import NamedTuple, Tuple
+
 import torch
 
 from . import _lib
@@ -26,7 +29,6 @@ PROFILER = None     # object with .begin(name, flops) / .end(); set by bench.py,
 
 
 def plan_name(pass_id: int, g: ConvGeom) -> str:
-    import ctypes
     buf = ctypes.create_string_buffer(96)
     _lib.check(_lib.load().mg_conv_plan_name(pass_id, g, buf, 96), "mg_conv_plan_name")
     return buf.value.decode()
@@ -70,22 +72,51 @@ def wino_tile_buffers(g: ConvGeom, device, want_v=True, want_md=True):
     return v, md
 
 
+class Traits(NamedTuple):
+    """include/mdctgan_hip.h: struct mg_conv_traits, field for field."""
+    weight_image: int               # _lib.IMAGE_*
+    weight_positions: int
+    weight_elem: int
+    images_half: int
+    tiles: int                      # 0: none, or Winograd images (a pair); 1: float16 copies of x / dy; 2: the scattered dy of a co1 layer
+    precast: Tuple[int, int]
+    vnext_positions: int
+    md_from_norm: int
+    wgrad_adam: int
+    wgrad_checks_finite: int
+    wgrad_h16: int
+
+
+# The environment variables that the library reads on EVERY call where it routes a pass (csrc/conv_igemm.hip: conv_route and the
+# family predicates behind it) or fills mg_conv_traits: the thresholds of the two opt-in inference precisions and of F(4x4,2x2),
+# the weight-streaming switch of the float16 GEMM path (precast[0]), and the forced plan of the LDS-DMA families (it moves tiles
+# and splits, which no trait reads today; the traits follow whatever the launch of the moment would do).  Not listed, because the
+# library latches them once per process: MG_NO_WINOGRAD, MG_NO_WINOGRAD4, MG_NO_WINOGRAD42, MG_HALF_NBUF, MG_NO_BK32.
+ROUTE_ENV = ("MG_WINO43_MIN_C", "MG_INFER_F16_MIN_C", "MG_INFER_F16_MIN_TILES", "MG_WINO42_MIN_WORK", "MG_NO_HGEMM_SA",
+             "MG_FORCE_CONV_DMA")
+_ROUTE_ENV_C = tuple(name.encode() for name in ROUTE_ENV)
+# the C library's getenv: the very values the library reads (os.environ writes through to them), at a fifth of os.environ.get's cost
+_getenv = ctypes.CDLL(None).getenv
+_getenv.restype, _getenv.argtypes = ctypes.c_char_p, [ctypes.c_char_p]
+_TRAITS = {}
+
+
+def traits(g: ConvGeom) -> Traits:
+    """What the library says about the layer's images and fused side paths (one mg_conv_traits call per geometry and environment)."""
+    key = (bytes(g),) + tuple(map(_getenv, _ROUTE_ENV_C))
+    hit = _TRAITS.get(key)
+    if hit is None:
+        c = _lib.ConvTraits()
+        _lib.check(_lib.load().mg_conv_traits(g, c), "mg_conv_traits")
+        hit = _TRAITS[key] = Traits(*c.astuple())
+    return hit
+
+
 def tiles_are_casts(g: ConvGeom) -> bool:
     """True for layers whose v / md "tiles" are usable on their own (Winograd images only work as a pair): the autocast
     layers on the float16 implicit GEMMs (csrc/conv_dma.h: plain float16 copies of x / dy) and the single-output-channel
     tap GEMMs (csrc/conv_co1.h: md = the scattered dy)."""
-    key = (g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision, _route_env(g))
-    hit = _CASTS.get(key)
-    if hit is None:
-        name = plan_name(2, g)
-        half = _lib.is_half(g.precision) and name.startswith("conv_wgrad_dma_kernel") and ", true" in name
-        # ... and the single-output-channel tap GEMMs (csrc/conv_co1.h): md is the scattered dy, there is no v
-        co1 = g.Co == 1 and wino_weights_bytes(g) == 64 * g.Ci * 4
-        hit = _CASTS[key] = half or co1
-    return hit
-
-
-_CASTS = {}
+    return traits(g).tiles != 0
 
 
 TILES_V_FILLED, TILES_MD_FILLED = 1, 2      # include/mdctgan_hip.h: MG_TILES_*_FILLED
@@ -100,16 +131,7 @@ def _tiles(u=None, v=None, md=None, add=None, flags=0):
 def precast_ok(pass_id: int, g: ConvGeom) -> bool:
     """True when this pass of the layer reads its activation operand from a plain float16 copy and honours MG_TILES_V_FILLED
     (pass 0) / MG_TILES_MD_FILLED (pass 1): the HALF instances of the implicit GEMMs (csrc/conv_dma.h)."""
-    if not _lib.is_half(g.precision):
-        return False
-    key = ("pc", pass_id, g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision, _route_env(g))
-    hit = _CASTS.get(key)
-    if hit is None:
-        name = plan_name(pass_id, g)
-        hit = name.startswith(("conv_fwd_dma_kernel", "conv_dgrad_dma_kernel")[pass_id]) and ", true" in name
-        # ... and (round 6) the forward pass of the weight-streaming layers, whose GEMM gathers its rows from float16(x) itself
-        hit = _CASTS[key] = hit or (pass_id == 0 and name.startswith("hgemm_sa_kernel<false, true>"))
-    return hit
+    return bool(traits(g).precast[pass_id])
 
 
 def conv_fwd(g: ConvGeom, x, w, bias=None, act=ACT_NONE, u=None, v_out=None, v_filled=False, out=None):
@@ -130,38 +152,18 @@ def conv_fwd(g: ConvGeom, x, w, bias=None, act=ACT_NONE, u=None, v_out=None, v_f
 def wino_vnext_ok(g: ConvGeom) -> bool:
     """True when conv_fwd_instnorm can also write the next 3x3 layer's Winograd input image (float32 F(2x2,3x3) and F(4x4,3x3),
     F(2x2,3x3) on float16 images; small maps)."""
-    key = ("vn", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision, _route_env(g))
-    hit = _CASTS.get(key)
-    if hit is None:
-        hit = _CASTS[key] = bool(_lib.load().mg_conv_wino_vnext_ok(g))
-    return hit
-
-
-def _route_env(g: ConvGeom):
-    """What the predicates of the two opt-in inference precisions read from the environment per call (a cache key beside the
-    geometry)."""
-    import os
-    if g.precision == _lib.PRECISION_F32_WINO43:
-        return os.environ.get("MG_WINO43_MIN_C")
-    if g.precision == _lib.PRECISION_F16_INFER:
-        return (os.environ.get("MG_INFER_F16_MIN_C"), os.environ.get("MG_INFER_F16_MIN_TILES"))
-    return None
+    return traits(g).vnext_positions != 0
 
 
 def wino_images_half(g: ConvGeom) -> bool:
     """True when the layer's Winograd images (u, v, a hand-over v_next) are float16: the eligible layers of PRECISION_F16_INFER."""
-    return g.precision == _lib.PRECISION_F16_INFER and plan_name(0, g).startswith("winoh_gemm_kernel")
+    return bool(traits(g).images_half)
 
 
 def wino_vnext_positions(g: ConvGeom) -> int:
     """Positions P of the Winograd family of a layer with wino_vnext_ok(g) -- 16: F(2x2,3x3), 36: F(4x4,3x3); 0: no hand-over.
     An input image handed from layer to layer (conv_fwd_instnorm's v_next) is only good for the family it was written for."""
-    key = ("vp", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision, _route_env(g))
-    hit = _CASTS.get(key)
-    if hit is None:
-        elem = 2 if (wino_vnext_ok(g) and wino_images_half(g)) else 4
-        hit = _CASTS[key] = wino_weights_bytes(g) // (elem * g.Co * g.Ci) if wino_vnext_ok(g) else 0
-    return hit
+    return traits(g).vnext_positions
 
 
 def conv_fwd_instnorm(g: ConvGeom, x, w, bias=None, act=ACT_NONE, residual=None, eps=1e-5, u=None, v_out=None, v_filled=False,
@@ -211,11 +213,7 @@ def conv_fwd_instnorm(g: ConvGeom, x, w, bias=None, act=ACT_NONE, residual=None,
 
 def wino_md_from_norm_ok(g: ConvGeom) -> bool:
     """True when instnorm_bwd_wino_md can produce this layer's A dy A^T image (F(2x2,3x3) layer, small map)."""
-    key = ("mdn", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision)
-    hit = _CASTS.get(key)
-    if hit is None:
-        hit = _CASTS[key] = bool(_lib.load().mg_conv_wino_md_from_norm_ok(g))
-    return hit
+    return bool(traits(g).md_from_norm)
 
 
 def instnorm_bwd_wino_md(g: ConvGeom, gy, y_raw, mean, rstd, act, md):
@@ -259,21 +257,13 @@ def conv_wgrad(g: ConvGeom, x, dy, dw, dbias=None, accumulate=False, v=None, md=
 def wgrad_checks_finite(g: ConvGeom) -> bool:
     """True when the layer's weight-gradient kernel can do the GradScaler's inf / nan check on its own results
     (mg_conv_wgrad_chk: the float16 A-stationary GEMM of the small-spatial trunk layers)."""
-    key = ("wf", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision)
-    hit = _CASTS.get(key)
-    if hit is None:
-        hit = _CASTS[key] = bool(_lib.load().mg_conv_wgrad_checks_finite(g))
-    return hit
+    return bool(traits(g).wgrad_checks_finite)
 
 
 def wgrad_h16_ok(g: ConvGeom) -> bool:
     """True when the layer's weight gradient can be STORED as float16 by its own kernel (mg_conv_wgrad_h16: the weight-streaming
     trunk layers under --fp16)."""
-    key = ("wh", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision)
-    hit = _CASTS.get(key)
-    if hit is None:
-        hit = _CASTS[key] = bool(_lib.load().mg_conv_wgrad_h16_ok(g))
-    return hit
+    return bool(traits(g).wgrad_h16)
 
 
 def conv_wgrad_h16(g: ConvGeom, x, dy, dw16, accumulate=False, found_inf=None):
@@ -290,11 +280,7 @@ def conv_wgrad_h16(g: ConvGeom, x, dy, dw16, accumulate=False, found_inf=None):
 
 def wgrad_adam_ok(g: ConvGeom) -> bool:
     """True when the layer's weight gradient can run as mg_conv_wgrad_adam_w (Winograd F(2x2,3x3), float32)."""
-    key = ("wa", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision)
-    hit = _CASTS.get(key)
-    if hit is None:
-        hit = _CASTS[key] = bool(_lib.load().mg_conv_wgrad_adam_ok(g))
-    return hit
+    return bool(traits(g).wgrad_adam)
 
 
 def conv_wgrad_adam(g: ConvGeom, x, dy, w, m, v_mom, u, state, beta1, beta2, eps, grad_scale, v=None, md=None):
@@ -576,13 +562,7 @@ def adam_step_segs(p, g, g16, m, v, p16, segs, nsegs, n_total, nbytes, state, be
 
 def weights_are_casts(g: ConvGeom) -> bool:
     """True when the layer's cached weight image (mg_conv_wino_prepare) is the plain float16 copy of its OHWI weights."""
-    if not _lib.is_half(g.precision):
-        return False
-    key = ("w", g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision, _route_env(g))
-    hit = _CASTS.get(key)
-    if hit is None:
-        hit = _CASTS[key] = wino_weights_bytes(g) == g.Co * g.KH * g.KW * g.Ci * 2
-    return hit
+    return traits(g).weight_image == _lib.IMAGE_CAST
 
 
 # SyncBN (SURVEY 8e opt-in; ddp.enable_sync_batchnorm): when set, the per-slice partial sums of a training-mode BatchNorm
