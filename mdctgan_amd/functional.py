@@ -4,12 +4,13 @@ kernels consume -- so chaining them never copies.  Convolution weights ([Co, Ci,
 [Cin_T, Cout_T, KH, KW]) are channels_last as well, which is exactly the OHWI layout of the C ABI.
 
 Weight / bias gradients are accumulated by the kernels straight into ``param.grad`` (no AccumulateGrad
-add pass, no per-step zero fill): the Function returns None for those inputs.  ``GradSlot`` tracks whether
-a parameter's gradient buffer already holds this step's first contribution.
+add pass, no per-step zero fill): the Function returns None for those inputs.  ``param._mg_fresh`` says whether
+a parameter's gradient buffer still waits for this step's first contribution (grad_buffer, mark_fresh).
 """
 from __future__ import annotations
 
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -70,24 +71,7 @@ def _want_h16(B, HW, C, half=None):
     # (round 6: also every SMALL tensor, <= 2 Mi elements -- 2 more bytes per element in a kernel that sits at the launch floor cost
     # nothing, and the stride-2 / transposed rungs next to the trunk then skip their cast launch)
     return (bool(half) and C % 64 == 0 and (B * HW > 2 * C or B * HW * C <= (1 << 21))
-            and os.environ.get("MG_NO_H16_PRODUCER", "0") != "1")
-
-
-def _attach_h16(t, buf):
-    if buf is not None:
-        t._mg_h16 = (buf, t.data_ptr(), t._version, t.numel())
-        H16_STATS["made"] += 1
-    return t
-
-
-def _h16_of(t):
-    rec = getattr(t, "_mg_h16", None)
-    if rec is None:
-        return None
-    buf, ptr, ver, n = rec
-    if t.data_ptr() != ptr or t._version != ver or t.numel() != n or not t.is_contiguous(memory_format=CL):
-        return None
-    return buf
+            and ops._getenv(b"MG_NO_H16_PRODUCER") != b"1")
 
 
 # ResnetBlock chains conv3x3 -> InstanceNorm -> (ReLU) -> conv3x3 on the trunk's small maps: the fused output-transform + norm kernel
@@ -96,21 +80,32 @@ def _h16_of(t):
 # was made from and the consumer's geometry is the one the producer was told (3x3, stride 1, pad 1, same padding mode).
 WINO_NEXT_STATS = {"made": 0, "used": 0}
 
+# The buffers that ride on the tensor they mirror, (buffer, data_ptr, _version, key) each, and where their producers are counted:
+#   _mg_h16       float16 copy of the whole tensor                                    key: numel(), the default
+#   _mg_h16_rows  float16 copy of the first `rows` samples (pass "G", _InstNormFn)    key: rows
+#   _mg_wino_v    Winograd input image for the convolution behind                     key: the consumer's geometry, family, precision
+_SIDECARS = {"_mg_h16": H16_STATS, "_mg_h16_rows": H16_STATS, "_mg_wino_v": WINO_NEXT_STATS}
 
-def _attach_wino_v(t, v, key):
-    t._mg_wino_v = (v, t.data_ptr(), t._version, key)
-    WINO_NEXT_STATS["made"] += 1
+
+def _attach(t, attr, buf, key=None):
+    """Hang `buf` (None: nothing to hang) on t under one of the _SIDECARS names.  key None: t.numel()."""
+    if buf is not None:
+        setattr(t, attr, (buf, t.data_ptr(), t._version, t.numel() if key is None else key))
+        _SIDECARS[attr]["made"] += 1
     return t
 
 
-def _wino_v_of(t, key):
-    rec = getattr(t, "_mg_wino_v", None)
+def _sidecar(t, attr, key=None):
+    """The buffer _attach hung on t, while t is still the tensor it was made from: same storage address, same version counter, the
+    key the consumer expects (None: t.numel()), channels_last contiguous.  None otherwise."""
+    rec = getattr(t, attr, None)
     if rec is None:
         return None
-    v, ptr, ver, k = rec
-    if t.data_ptr() != ptr or t._version != ver or k != key or not t.is_contiguous(memory_format=CL):
+    buf, ptr, ver, k = rec
+    if (t.data_ptr() != ptr or t._version != ver or k != (t.numel() if key is None else key)
+            or not t.is_contiguous(memory_format=CL)):
         return None
-    return v
+    return buf
 
 
 def grad_buffer(p: torch.nn.Parameter):
@@ -183,6 +178,27 @@ def _zero_grad_bias(bias):
     bias._mg_fresh = False
 
 
+def _feeds_norm(p):
+    """The parameter is a bias whose gradient is identically zero and is not computed (mark_bias_feeds_norm)."""
+    return getattr(p, "_mg_zero_grad", False) and not COMPUTE_DEAD_BIAS_GRADS
+
+
+def _dead_bias(bias):
+    """No kernel has to compute this bias's gradient: there is no bias, it takes no gradient, or it feeds an InstanceNorm."""
+    return bias is None or not bias.requires_grad or _feeds_norm(bias)
+
+
+def _bias_grad(bias):
+    """(buffer, accumulate?) for the bias gradient the caller's kernels have to write, (None, None) where there is nothing to write:
+    a dead bias that takes a gradient gets its exact zero here."""
+    if bias is None or not bias.requires_grad:
+        return None, None
+    if _feeds_norm(bias):
+        _zero_grad_bias(bias)
+        return None, None
+    return grad_buffer(bias)
+
+
 def _producer_flag(weight, t):
     """--fp16: the GradScaler's found_inf slot of the optimiser that owns `weight`, when this layer's weight-gradient kernel
     checks its own results (t.wgrad_checks_finite) -- FusedAdam.step then leaves the gradient out of its check pass.  The
@@ -214,6 +230,14 @@ def remove_grad_ready_hook(fn):
 def _notify(p):
     for fn in _grad_hooks:
         fn(p)
+
+
+def _notify_pair(weight, bias):
+    """A convolution's gradients are in place: the weight's (None: it did not go to the arena), then a bias's that takes one."""
+    if weight is not None:
+        _notify(weight)
+    if bias is not None and bias.requires_grad:
+        _notify(bias)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -290,7 +314,6 @@ def _persistent_u(g, weight):
         u = weight._mg_u_persist = torch.empty(nbytes // 4, dtype=torch.float32, device=weight.device)
         weight._mg_u_ok = None
     if weight._mg_u_ok != weight._version:
-        from . import _lib
         _lib.check(_lib.load().mg_conv_wino_prepare(g, _lib.ptr(weight.detach()), _lib.ptr(u), _lib.stream()), "mg_conv_wino_prepare")
         weight._mg_u_ok = weight._version
     return u
@@ -401,7 +424,8 @@ class ExtraGrad:
 
 def _hang_extra(ctx, out):
     ctx.extra = None
-    if any(ctx.needs_input_grad) and os.environ.get("MG_NO_EXTRA_GRAD", "0") != "1":      # (grad mode reads False inside a forward)
+    # (grad mode reads False inside a forward; the C library's getenv sees what os.environ wrote, at 0.6 instead of 1.4 us per node)
+    if any(ctx.needs_input_grad) and ops._getenv(b"MG_NO_EXTRA_GRAD") != b"1":
         ctx.extra = out._mg_extra = ExtraGrad()
     return out
 
@@ -419,61 +443,79 @@ def _take_extra(ctx, like):
 # ------------------------------------------------------------------------------------------------
 # convolution
 # ------------------------------------------------------------------------------------------------
+# What the public wrappers tell their nodes: ConvCfg from conv2d() / conv_transpose2d() to _ConvFn -- and what _conv_backward reads of
+# either node --, ConvNormCfg from conv_instnorm() to _ConvInstNormFn.  weight_grad: True | False | "D" | "D0" (see backward_pass);
+# skip: None | ("give" | "take", SkipGrad); next_reflect: None | the padding mode of the 3x3 stride-1 pad-1 convolution behind;
+# precision and grad_enabled are read by the wrappers: amp.wino43 / amp.infer_f16 look at the grad mode, which is always off inside a
+# Function's forward.  (Built with _make: the generated __new__ costs twice as much per node.)
+ConvCfg = NamedTuple("ConvCfg", [("stride", int), ("pad", int), ("reflect", bool), ("act", int), ("transposed", bool),
+                                 ("weight_grad", object), ("precision", int)])
+ConvNormCfg = NamedTuple("ConvNormCfg", [("pad", int), ("reflect", bool), ("weight_grad", object), ("act", int), ("eps", float),
+                                         ("skip", object), ("grad_enabled", bool), ("next_reflect", object), ("precision", int)])
+
+
+def _forward_operands(ctx, g, t, x, weight, weight_grad, v_key=None):
+    """(u, v, v_filled) of a convolution's forward call.  u: the weight image -- Winograd layers transform the weights once and
+    reuse the image for the data gradient of this step; under no_grad once per weight version (a captured inference graph reads
+    the images its warm-up made).  v: the input image, kept for the weight gradient (A dy A^T is shared between dgrad and wgrad in
+    backward) -- float16(x) or, under v_key (see _SIDECARS), B^T x B where x's producer wrote one (v_filled: the call skips its
+    cast pass / input transform), a buffer for the call to fill otherwise."""
+    if ctx.needs_input_grad[0]:
+        u = _weight_image(g, t, weight, weight_grad)
+    elif x.is_cuda and not torch.is_grad_enabled():
+        u = _cached_wino_weights(g, weight, fill=not torch.cuda.is_current_stream_capturing())
+    else:
+        u = None
+    x16 = _sidecar(x, "_mg_h16") if t.precast[0] else None
+    xv = _sidecar(x, "_mg_wino_v", v_key) if v_key is not None else None
+    if x16 is not None:
+        H16_STATS["used_fwd"] += 1
+        return u, x16, True
+    if xv is not None:              # this layer's own V, kept for its weight gradient
+        WINO_NEXT_STATS["used"] += 1
+        return u, xv, True
+    if u is not None and weight_grad and weight.requires_grad:
+        return u, ops.wino_tile_buffers(g, x.device, want_md=False)[0], False
+    return u, None, False
+
+
 class _ConvFn(torch.autograd.Function):
     """y = act(conv(x, w) + b); transposed=True runs the data-gradient kernel forward (ConvTranspose2d)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, cfg):
         x = to_cl(x)
-        stride, pad, reflect, act, transposed, weight_grad = cfg[:6]
-        # the precision is read by conv2d() / conv_transpose2d(): amp.wino43 looks at the grad mode, which is always off in here
-        prec = cfg[6] if len(cfg) > 6 else amp.current_precision()
+        stride, act, weight_grad = cfg.stride, cfg.act, cfg.weight_grad
         B, _, H, W = x.shape
         w = weight.detach()
         assert w.is_contiguous(memory_format=CL), "conv weights must be channels_last (OHWI) tensors"
         KH, KW = w.shape[2], w.shape[3]
         b = bias.detach() if bias is not None else None
-        if not transposed:
+        if not cfg.transposed:
             Co, Ci = w.shape[0], w.shape[1]
             assert Ci == x.shape[1]
-            g = ops.conv_geom(B, H, W, Ci, Co, KH, KW, stride, pad, reflect, prec)
+            g = ops.conv_geom(B, H, W, Ci, Co, KH, KW, stride, cfg.pad, cfg.reflect, cfg.precision)
             t = ops.traits(g)
             _tag_g16(g, t, weight, bias, weight_grad)
-            # Winograd layers: transform the weights once, reuse the image for the data gradient of this step
-            if ctx.needs_input_grad[0]:
-                u = _weight_image(g, t, weight, weight_grad)
-            elif x.is_cuda and not torch.is_grad_enabled():
-                # inference: once per weight version (a captured inference graph reads the images its warm-up made)
-                u = _cached_wino_weights(g, weight, fill=not torch.cuda.is_current_stream_capturing())
-            else:
-                u = None
-            # ... and keep B^T x B for the weight gradient (A dy A^T is shared between dgrad and wgrad in backward)
-            v, v_filled = None, False
-            x16 = _h16_of(x) if t.precast[0] else None
-            if x16 is not None:                  # x's producer already wrote float16(x): the call skips its cast pass
-                v, v_filled = x16, True
-                H16_STATS["used_fwd"] += 1
-            elif u is not None and weight_grad and weight.requires_grad:
-                v, _ = ops.wino_tile_buffers(g, x.device, want_md=False)
+            u, v, v_filled = _forward_operands(ctx, g, t, x, weight, weight_grad)
             y = ops.conv_fwd(g, nhwc_view(x), w, b, act, u, v, v_filled)
-            ctx.u, ctx.v = u, (v if (weight_grad and weight.requires_grad) else None)
         else:
             # nn.ConvTranspose2d(k, stride, pad, output_padding = stride - 1): the data gradient of the conv
             # high-res [B, sH, sW, Cout_T] -> low-res [B, H, W, Cin_T]
             cin_t, cout_t = w.shape[0], w.shape[1]
             assert cin_t == x.shape[1]
-            g = ops.conv_geom(B, stride * H, stride * W, cout_t, cin_t, KH, KW, stride, pad, False, prec)
+            g = ops.conv_geom(B, stride * H, stride * W, cout_t, cin_t, KH, KW, stride, cfg.pad, False, cfg.precision)
             assert (g.OH, g.OW) == (H, W), "unsupported ConvTranspose2d geometry"
             t = ops.traits(g)
             # the weight image (Winograd U / float16 copy) serves this call and the backward's data gradient
             u = _weight_image(g, t, weight) if (ctx.needs_input_grad[0] and x.is_cuda) else None
-            x16 = _h16_of(x) if t.precast[1] else None       # x plays dy in this call
-            if x16 is not None:
+            v = _sidecar(x, "_mg_h16") if t.precast[1] else None         # x plays dy in this call
+            if v is not None:
                 H16_STATS["used_fwd"] += 1
-            y = ops.conv_dgrad(g, nhwc_view(x), w, b, act, u=u, md_out=x16, md_filled=x16 is not None)
-            ctx.u, ctx.v = u, (x16 if (weight_grad and weight.requires_grad) else None)
+            y = ops.conv_dgrad(g, nhwc_view(x), w, b, act, u=u, md_out=v, md_filled=v is not None)
         y = nchw_view(y)
-        ctx.g, ctx.t, ctx.cfg = g, t, cfg[:6]
+        ctx.u, ctx.v = u, (v if (weight_grad and weight.requires_grad) else None)
+        ctx.g, ctx.t, ctx.cfg = g, t, cfg
         ctx.weight, ctx.bias = weight, bias
         ctx.save_for_backward(x, y if act != ACT_NONE else None)
         return _hang_extra(ctx, y) if act in (ACT_RELU, ACT_LRELU02) else y
@@ -489,18 +531,16 @@ def _conv_backward(ctx, gy, x, y, add=None):
     add (NHWC view, stride-1 convolutions without live rows only): dx += add inside the data gradient's last kernel where the
     layer's path has one that takes it (mg_wino_tiles.add: Winograd gather, reflection fold, split-K epilogue), by one add
     launch of the library otherwise."""
-    stride, pad, reflect, act, transposed, weight_grad = ctx.cfg
+    act, transposed, weight_grad = ctx.cfg.act, ctx.cfg.transposed, ctx.cfg.weight_grad
     assert add is None or not transposed
-    g, t, weight, bias = ctx.g, ctx.t, ctx.weight, ctx.bias
+    g, t, weight = ctx.g, ctx.t, ctx.weight
     gy = to_cl(gy)
     kind = _BackwardPass.kind
     shared = _is_shared(weight_grad)
-    last_use = not shared or kind != "G"                   # a shared layer is walked again by the D pass
     want_dx = ctx.needs_input_grad[0] and not (weight_grad == "D0" and kind == "D")
     want_dw = bool(weight_grad) and weight.requires_grad and not (shared and kind == "G")
     rows = _live_rows(x) if shared else None
     x_full, gy_full = x, gy
-    rec16 = getattr(gy, "_mg_h16_rows", None) if rows is not None else None
     if rows is not None:                                   # pass "G" over a stacked batch: the fake half only
         assert not transposed and not want_dw
         x, gy = x[:rows], gy[:rows]
@@ -508,130 +548,111 @@ def _conv_backward(ctx, gy, x, y, add=None):
         g = ops.conv_geom(rows, g.H, g.W, g.Ci, g.Co, g.KH, g.KW, g.stride, g.pad, g.reflect, g.precision)
         t = ops.traits(g)
     # float16(gy) written by gy's producer (an InstanceNorm backward): only for the whole, untouched tensor
-    g16 = _h16_of(gy) if (rows is None and act == ACT_NONE) else None
+    g16 = _sidecar(gy, "_mg_h16") if (rows is None and act == ACT_NONE) else None
     if act != ACT_NONE:
         extra = _take_extra(ctx, gy_full)          # the feature-matching loss's gradient of this layer's output (see ExtraGrad)
         if extra is not None and rows is not None:
             extra = extra[:rows]
         gy = nchw_view(ops.act_bwd(nhwc_view(gy), nhwc_view(y), act, dy2=nhwc_view(to_cl(extra)) if extra is not None else None))
-    w = weight.detach()
+    u = ctx.u
     dx = None
-    md = None
-    md_filled = False
-    u_used = getattr(ctx, "u", None)
+    gy_image = g16 if transposed else None                 # what the weight gradient may reuse of gy: see _data_grad
     if want_dx:
-        if not transposed:
-            u = getattr(ctx, "u", None)
-            if g16 is not None and t.precast[1]:
-                md, md_filled = g16, True
-                H16_STATS["used_bwd"] += 1
-            elif u is not None and want_dw and (getattr(ctx, "v", None) is not None or t.tiles):
-                _, md = ops.wino_tile_buffers(g, gy.device, want_v=False)
-            if rows is not None:
-                assert add is None
-                if u is not None and ops.wino_weights_bytes(g) != ops.wino_weights_bytes(ctx.g):
-                    u = None          # the weight image was made for the stacked batch's plan; half the rows take another path
-                dx = torch.empty_like(x_full)
-                g16r = None
-                if rec16 is not None and act == ACT_NONE and t.precast[1]:
-                    buf, ptr, ver, r_ = rec16
-                    if ptr == gy_full.data_ptr() and ver == gy_full._version and r_ == rows and gy_full.is_contiguous(memory_format=CL):
-                        g16r = buf
-                        H16_STATS["used_bwd"] += 1
-                ops.conv_dgrad(g, nhwc_view(gy), w, u=u, out=nhwc_view(dx[:rows]), md_out=g16r, md_filled=g16r is not None)
-            else:
-                dx = nchw_view(ops.conv_dgrad(g, nhwc_view(gy), w, u=u, md_out=md, md_filled=md_filled, add=add))
-                add = None
-            if last_use:
-                ctx.u = None
-        else:
-            if g16 is not None and t.precast[0]:             # gy plays x in this call
-                dx = nchw_view(ops.conv_fwd(g, nhwc_view(gy), w, u=getattr(ctx, "u", None), v_out=g16, v_filled=True))
-                H16_STATS["used_bwd"] += 1
-            else:
-                g16 = None
-                dx = nchw_view(ops.conv_fwd(g, nhwc_view(gy), w, u=getattr(ctx, "u", None)))
-            if last_use:
-                ctx.u = None
-    if want_dw and not transposed and rows is None and (bias is None or not bias.requires_grad or (
-            getattr(bias, "_mg_zero_grad", False) and not COMPUTE_DEAD_BIAS_GRADS)):
-        vv = getattr(ctx, "v", None) if (md is not None or t.tiles) else None
-        if _wgrad_fused(u_used, g, weight, nhwc_view(x), nhwc_view(gy), vv, md):
-            if bias is not None and bias.requires_grad:
-                _zero_grad_bias(bias)
-                _notify(bias)
-            ctx.v = None
-            want_dw = False
-    if want_dw and not transposed and getattr(weight, "_mg_g16", None) is not None:
+        dx, gy_image = _data_grad(ctx, g, t, gy, g16, want_dw, rows, x_full, gy_full, add)
+        if not shared or kind != "G":                      # (a shared layer is walked again by the D pass)
+            ctx.u = None
+    if want_dw:
+        _weight_grad(ctx, g, t, x, gy, u, gy_image)
+    return dx
+
+
+def _data_grad(ctx, g, t, gy, g16, want_dw, rows, x_full, gy_full, add):
+    """(dx, what the weight gradient may reuse of gy).  The second is md -- A dy A^T, or gy's float16 copy (g16: the one gy's
+    producer wrote) -- and for a transposed layer, whose weight gradient takes gy as its x operand, g16 where this call read it."""
+    u, w = ctx.u, ctx.weight.detach()
+    if ctx.cfg.transposed:
+        v = g16 if t.precast[0] else None                # gy plays x in this call
+        if v is not None:
+            H16_STATS["used_bwd"] += 1
+        return nchw_view(ops.conv_fwd(g, nhwc_view(gy), w, u=u, v_out=v, v_filled=v is not None)), v
+    if rows is not None:
+        assert add is None
+        if u is not None and ops.wino_weights_bytes(g) != ops.wino_weights_bytes(ctx.g):
+            u = None          # the weight image was made for the stacked batch's plan; half the rows take another path
+        dx = torch.empty_like(x_full)
+        # the float16 copy of the live rows that an InstanceNorm backward behind wrote (_InstNormFn.backward)
+        g16r = _sidecar(gy_full, "_mg_h16_rows", rows) if (ctx.cfg.act == ACT_NONE and t.precast[1]) else None
+        if g16r is not None:
+            H16_STATS["used_bwd"] += 1
+        ops.conv_dgrad(g, nhwc_view(gy), w, u=u, out=nhwc_view(dx[:rows]), md_out=g16r, md_filled=g16r is not None)
+        return dx, None
+    md = g16 if t.precast[1] else None
+    md_filled = md is not None
+    if md_filled:
+        H16_STATS["used_bwd"] += 1
+    elif u is not None and want_dw and (ctx.v is not None or t.tiles):
+        _, md = ops.wino_tile_buffers(g, gy.device, want_v=False)
+    return nchw_view(ops.conv_dgrad(g, nhwc_view(gy), w, u=u, md_out=md, md_filled=md_filled, add=add)), md
+
+
+def _weight_grad(ctx, g, t, x, gy, u, gy_image):
+    """Weight and bias gradient of the node, by one of three tails: fused with Adam and the next forward's weight transform (see
+    _wgrad_fused), stored as float16, plain float32.  u: the weight image the forward ran on; gy_image: see _data_grad."""
+    weight, bias, transposed = ctx.weight, ctx.bias, ctx.cfg.transposed
+    x, gy, written = nhwc_view(x), nhwc_view(gy), weight
+    # Winograd images come as a pair; the float16 copies of the implicit-GEMM layers are independent
+    v, md = (ctx.v if (gy_image is not None or t.tiles) else None), gy_image
+    if not transposed and _dead_bias(bias) and _wgrad_fused(u, g, weight, x, gy, v, md):
+        _bias_grad(bias)
+        written = None          # (only the bias is announced: the weight's gradient did not go to the arena)
+    elif not transposed and getattr(weight, "_mg_g16", None) is not None:
         # --fp16, FusedAdam GRAD_F16: the kernel stores the gradient as float16 (and runs the GradScaler's check on it)
         w16, wacc = grad_buffer16(weight)
-        if bias is not None and bias.requires_grad:
-            if getattr(bias, "_mg_zero_grad", False) and not COMPUTE_DEAD_BIAS_GRADS:
-                _zero_grad_bias(bias)
-            else:
-                bbuf, bacc = grad_buffer(bias)
-                ops.colsum(nhwc_view(gy).reshape(-1, g.Co), bbuf, bacc)
+        bbuf, bacc = _bias_grad(bias)
+        if bbuf is not None:
+            ops.colsum(gy.reshape(-1, g.Co), bbuf, bacc)
         flag = _producer_flag(weight, t)
         if t.wgrad_h16:
-            ops.conv_wgrad_h16(g, nhwc_view(x), nhwc_view(gy), w16, wacc, found_inf=flag)
+            ops.conv_wgrad_h16(g, x, gy, w16, wacc, found_inf=flag)
             weight._mg_inf_checked = flag is not None
         else:
             # another geometry than the one the arena was laid out for (a batch the float16-storing kernel does not take): the
             # float32 kernel, then one cast into the float16 slot the optimiser reads
             tmp = torch.empty(weight.numel(), dtype=torch.float32, device=gy.device)
-            ops.conv_wgrad(g, nhwc_view(x), nhwc_view(gy), tmp, None, False)
+            ops.conv_wgrad(g, x, gy, tmp, None, False)
             if wacc:
                 w16.add_(tmp)
             else:
                 w16.copy_(tmp)
             weight._mg_inf_checked = False
-        ctx.v = None
-        _notify(weight)
-        if bias is not None and bias.requires_grad:
-            _notify(bias)
-        want_dw = False
-    if want_dw:
+    else:
         wbuf, wacc = grad_buffer(weight)
-        bbuf = bacc = None
-        if bias is not None and bias.requires_grad:
-            if getattr(bias, "_mg_zero_grad", False) and not COMPUTE_DEAD_BIAS_GRADS:
-                _zero_grad_bias(bias)
-            else:
-                bbuf, bacc = grad_buffer(bias)
+        bbuf, bacc = _bias_grad(bias)
+        flag = _producer_flag(weight, t)
         if not transposed:
             if bbuf is not None and bacc != wacc:      # keep one accumulate flag per launch
-                ops.colsum(nhwc_view(gy).reshape(-1, g.Co), bbuf, bacc)
+                ops.colsum(gy.reshape(-1, g.Co), bbuf, bacc)
                 bbuf = None
-            # Winograd images come as a pair; the float16 copies of the implicit-GEMM layers are independent
-            v = getattr(ctx, "v", None) if (md is not None or t.tiles) else None
-            flag = _producer_flag(weight, t)
-            ops.conv_wgrad(g, nhwc_view(x), nhwc_view(gy), wbuf, bbuf, wacc, v=v, md=md, found_inf=flag)
-            weight._mg_inf_checked = flag is not None
-            ctx.v = None
+            ops.conv_wgrad(g, x, gy, wbuf, bbuf, wacc, v=v, md=md, found_inf=flag)
         else:
-            flag = _producer_flag(weight, t)
             half = t.tiles == 1             # float16 copies of x / dy, each usable alone
-            ops.conv_wgrad(g, nhwc_view(gy), nhwc_view(x), wbuf, None, wacc, found_inf=flag,
-                           v=g16 if half else None, md=getattr(ctx, "v", None) if half else None)
-            ctx.v = None
-            weight._mg_inf_checked = flag is not None
+            ops.conv_wgrad(g, gy, x, wbuf, None, wacc, found_inf=flag, v=gy_image if half else None, md=ctx.v if half else None)
             if bbuf is not None:
-                ops.colsum(nhwc_view(gy).reshape(-1, g.Ci), bbuf, bacc)
-        _notify(weight)
-        if bias is not None and bias.requires_grad:
-            _notify(bias)
-    return dx
+                ops.colsum(gy.reshape(-1, g.Ci), bbuf, bacc)
+        weight._mg_inf_checked = flag is not None
+    ctx.v = None
+    _notify_pair(written, bias)
 
 
 def conv2d(x, weight, bias, stride=1, padding=0, reflect=False, act=ACT_NONE, weight_grad=True):
-    return _ConvFn.apply(x, weight, bias, (stride, padding, bool(reflect), act, False, weight_grad, amp.current_precision()))
+    return _ConvFn.apply(x, weight, bias, ConvCfg._make((stride, padding, bool(reflect), act, False, weight_grad, amp.current_precision())))
 
 
 def conv_transpose2d(x, weight, bias, stride=2, padding=1, act=ACT_NONE, weight_grad=True):
     prec = amp.current_precision()
     if prec == _lib.PRECISION_F16_INFER:       # this call IS a data-gradient pass, which that forward-only value does not name
         prec = _lib.PRECISION_F16
-    return _ConvFn.apply(x, weight, bias, (stride, padding, False, act, True, weight_grad, prec))
+    return _ConvFn.apply(x, weight, bias, ConvCfg._make((stride, padding, False, act, True, weight_grad, prec)))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -646,61 +667,46 @@ class _ConvInstNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, cfg):
         x = to_cl(x)
-        pad, reflect, weight_grad, act, eps = cfg[:5]
-        ctx.skip = cfg[5] if len(cfg) > 5 else None      # ("give" | "take", SkipGrad): see SkipGrad
+        pad, reflect, weight_grad, next_reflect = cfg.pad, cfg.reflect, cfg.weight_grad, cfg.next_reflect
+        ctx.skip = cfg.skip                              # ("give" | "take", SkipGrad): see SkipGrad
         res = to_cl(residual) if residual is not None else None
         B, _, H, W = x.shape
         w = weight.detach()
         assert w.is_contiguous(memory_format=CL), "conv weights must be channels_last (OHWI) tensors"
-        prec = cfg[8] if len(cfg) > 8 else amp.current_precision()       # (read by conv_instnorm(), as the grad mode is)
-        g = ops.conv_geom(B, H, W, w.shape[1], w.shape[0], w.shape[2], w.shape[3], 1, pad, reflect, prec)
+        g = ops.conv_geom(B, H, W, w.shape[1], w.shape[0], w.shape[2], w.shape[3], 1, pad, reflect, cfg.precision)
         t = ops.traits(g)
         _tag_g16(g, t, weight, bias, weight_grad)
-        if ctx.needs_input_grad[0]:
-            u = _weight_image(g, t, weight, weight_grad)
-        elif x.is_cuda and not torch.is_grad_enabled():
-            u = _cached_wino_weights(g, weight, fill=not torch.cuda.is_current_stream_capturing())
-        else:
-            u = None
-        v, v_filled = None, False
-        x16 = _h16_of(x) if t.precast[0] else None
-        # (the key names the family by its positions: under amp.wino43 a layer in front may have written F(4x4,3x3) tiles for a
-        # layer that itself runs F(2x2,3x3), or the other way round -- neither reads the other family's image)
+        # x's producer (the trunk layer in front) may have written B^T x B.  (The key names the family by its positions: under
+        # amp.wino43 a layer in front may have written F(4x4,3x3) tiles for a layer that itself runs F(2x2,3x3), or the other way
+        # round -- neither reads the other family's image)
         npos = t.vnext_positions if (pad == 1 and w.shape[2] == 3 and w.shape[3] == 3) else 0
-        xv = _wino_v_of(x, (B, H, W, w.shape[1], bool(reflect), g.precision, npos)) if npos else None
-        if x16 is not None:
-            v, v_filled = x16, True
-            H16_STATS["used_fwd"] += 1
-        elif xv is not None:          # x's producer (the trunk layer in front) wrote B^T x B: this layer's own V, kept for its weight gradient
-            v, v_filled = xv, True
-            WINO_NEXT_STATS["used"] += 1
-        elif u is not None and weight_grad and weight.requires_grad:
-            v, _ = ops.wino_tile_buffers(g, x.device, want_md=False)
-        # ... and this layer writes the NEXT trunk layer's image when told that one follows (cfg[7]: its padding mode)
-        next_reflect = cfg[7] if len(cfg) > 7 else None
+        u, v, v_filled = _forward_operands(ctx, g, t, x, weight, weight_grad,
+                                           (B, H, W, w.shape[1], bool(reflect), g.precision, npos) if npos else None)
+        # ... and this layer writes the NEXT trunk layer's image when told that one follows (next_reflect: its padding mode)
         v_next = None
-        if next_reflect is not None and npos and os.environ.get("MG_NO_WINO_NEXT", "0") != "1":
+        if next_reflect is not None and npos and ops._getenv(b"MG_NO_WINO_NEXT") != b"1":
             tile = 2 if npos == 16 else 4       # F(2x2,3x3) / F(4x4,3x3) output tiles
             v_next = torch.empty(npos * B * (g.OH // tile) * (g.OW // tile) * g.Co, device=x.device,
                                  dtype=torch.float16 if t.images_half else torch.float32)
         y16 = (torch.empty(B * g.OH * g.OW * g.Co, dtype=torch.float16, device=x.device)
-               if _want_h16(B, g.OH * g.OW, g.Co, _lib.is_half(prec)) else None)
+               if _want_h16(B, g.OH * g.OW, g.Co, _lib.is_half(cfg.precision)) else None)
         if v_next is not None and v_next.dtype == torch.float16:
             y16 = None          # the consumer named by next_reflect reads the float16 image, not a float16 copy of y
         # under torch.no_grad() nobody reads the raw convolution output again (grad mode is read by conv_instnorm(): inside a
         # Function's forward it is always off, and needs_input_grad ignores it)
-        need_raw = bool(cfg[6]) and any(ctx.needs_input_grad) if len(cfg) > 6 else any(ctx.needs_input_grad)
-        y, y_raw, mean, rstd = ops.conv_fwd_instnorm(g, nhwc_view(x), w, bias.detach() if bias is not None else None, act,
-                                                     nhwc_view(res) if res is not None else None, eps, u, v, v_filled, y16,
+        need_raw = bool(cfg.grad_enabled) and any(ctx.needs_input_grad)
+        y, y_raw, mean, rstd = ops.conv_fwd_instnorm(g, nhwc_view(x), w, bias.detach() if bias is not None else None, cfg.act,
+                                                     nhwc_view(res) if res is not None else None, cfg.eps, u, v, v_filled, y16,
                                                      need_raw=need_raw, v_next=v_next, next_reflect=bool(next_reflect))
         ctx.u, ctx.v = u, (v if (weight_grad and weight.requires_grad) else None)
-        ctx.g, ctx.t, ctx.cfg = g, t, (1, pad, reflect, ACT_NONE, False, weight_grad)
-        ctx.weight, ctx.bias, ctx.norm_act = weight, bias, act
+        # (the convolution's own backward sees a plain stride-1 layer: the norm and its activation are undone in front of it)
+        ctx.g, ctx.t, ctx.cfg = g, t, ConvCfg._make((1, pad, reflect, ACT_NONE, False, weight_grad, cfg.precision))
+        ctx.weight, ctx.bias, ctx.norm_act = weight, bias, cfg.act
         if need_raw:
             ctx.save_for_backward(x, nchw_view(y_raw), mean, rstd)
-        out = _attach_h16(nchw_view(y), y16)
+        out = _attach(nchw_view(y), "_mg_h16", y16)
         if v_next is not None:
-            _attach_wino_v(out, v_next, (B, g.OH, g.OW, g.Co, bool(next_reflect), g.precision, npos))
+            _attach(out, "_mg_wino_v", v_next, (B, g.OH, g.OW, g.Co, bool(next_reflect), g.precision, npos))
         return out
 
     @staticmethod
@@ -716,32 +722,26 @@ class _ConvInstNormFn(torch.autograd.Function):
             elif role == "take":
                 skip_g, holder.g = holder.g, None
         g, t, weight, bias = ctx.g, ctx.t, ctx.weight, ctx.bias
-        weight_grad = ctx.cfg[5]
-        dead_bias = bias is None or not bias.requires_grad or (getattr(bias, "_mg_zero_grad", False) and not COMPUTE_DEAD_BIAS_GRADS)
-        u, v = getattr(ctx, "u", None), getattr(ctx, "v", None)
-        if (ctx.needs_input_grad[0] and weight_grad is True and weight.requires_grad and dead_bias and u is not None
+        u, v = ctx.u, ctx.v
+        # the skip connection's gradient joins the data gradient inside its last kernel (no elementwise add launch)
+        add = nhwc_view(skip_g) if (skip_g is not None and ctx.needs_input_grad[0]) else None
+        if (ctx.needs_input_grad[0] and ctx.cfg.weight_grad is True and weight.requires_grad and _dead_bias(bias) and u is not None
                 and v is not None and t.md_from_norm):
             # InstanceNorm backward and the A dy A^T transform in one kernel; data and weight gradient start from the images
             _, md = ops.wino_tile_buffers(g, gy.device, want_v=False)
             ops.instnorm_bwd_wino_md(g, nhwc_view(gy), nhwc_view(y_raw), mean, rstd, ctx.norm_act, md)
-            w = weight.detach()
-            dx = nchw_view(ops.conv_dgrad(g, None, w, u=u, md_out=md,
-                                          add=nhwc_view(skip_g) if skip_g is not None else None))
-            if bias is not None and bias.requires_grad:
-                _zero_grad_bias(bias)
+            dx = nchw_view(ops.conv_dgrad(g, None, weight.detach(), u=u, md_out=md, add=add))
+            _bias_grad(bias)
             if not _wgrad_fused(u, g, weight, None, None, v, md):
                 wbuf, wacc = grad_buffer(weight)
                 ops.conv_wgrad(g, None, None, wbuf, None, wacc, v=v, md=md)
             ctx.u = ctx.v = None
-            _notify(weight)
-            if bias is not None and bias.requires_grad:
-                _notify(bias)
+            _notify_pair(weight, bias)          # (the weight as well, fused or not: _weight_grad's fused tail announces the bias only)
             return dx, None, None, dres, None
         d16 = (torch.empty(gy.numel(), dtype=torch.float16, device=gy.device)
                if (_want_h16(g.B, g.OH * g.OW, g.Co, _lib.is_half(g.precision)) and t.precast[1]) else None)
-        d_raw = _attach_h16(nchw_view(ops.instnorm_bwd(nhwc_view(gy), nhwc_view(y_raw), mean, rstd, ctx.norm_act, dx16=d16)), d16)
-        # the skip connection's gradient joins the data gradient inside its last kernel (no elementwise add launch)
-        dx = _conv_backward(ctx, d_raw, x, None, add=nhwc_view(skip_g) if (skip_g is not None and ctx.needs_input_grad[0]) else None)
+        d_raw = _attach(nchw_view(ops.instnorm_bwd(nhwc_view(gy), nhwc_view(y_raw), mean, rstd, ctx.norm_act, dx16=d16)), "_mg_h16", d16)
+        dx = _conv_backward(ctx, d_raw, x, None, add=add)
         if skip_g is not None and dx is None:
             dx = skip_g
         return dx, None, None, dres, None
@@ -763,8 +763,9 @@ def conv_instnorm(x, weight, bias, padding=0, reflect=False, act=ACT_NONE, resid
                   next_reflect=None):
     """act(InstanceNorm2d(affine=False)(conv2d(x, weight, bias, stride 1))) + residual.  skip: ("give" | "take", SkipGrad).
     next_reflect (None | bool): the output feeds another 3x3 stride-1 pad-1 convolution with that padding mode -- where the fused
-    kernel runs it also writes that layer's Winograd input image (see _attach_wino_v)."""
-    cfg = (padding, bool(reflect), weight_grad, act, eps, skip, torch.is_grad_enabled(), next_reflect, amp.current_precision())
+    kernel runs it also writes that layer's Winograd input image (see _SIDECARS: _mg_wino_v)."""
+    cfg = ConvNormCfg._make((padding, bool(reflect), weight_grad, act, eps, skip, torch.is_grad_enabled(), next_reflect,
+                             amp.current_precision()))
     return _ConvInstNormFn.apply(x, weight, bias, residual, cfg)
 
 
@@ -779,7 +780,7 @@ class _InstNormFn(torch.autograd.Function):
         y, mean, rstd = ops.instnorm_fwd(nhwc_view(x), act, nhwc_view(res) if res is not None else None, eps, y16=y16)
         ctx.act, ctx.half = act, half
         ctx.save_for_backward(x, mean, rstd)
-        return _hang_extra(ctx, _attach_h16(nchw_view(y), y16))
+        return _hang_extra(ctx, _attach(nchw_view(y), "_mg_h16", y16))
 
     @staticmethod
     def backward(ctx, gy):
@@ -799,14 +800,12 @@ class _InstNormFn(torch.autograd.Function):
                        if _want_h16(rows, H * W, C, ctx.half) else None)
                 ops.instnorm_bwd(nhwc_view(gy[:rows]), nhwc_view(x[:rows]), mean[:rows], rstd[:rows], ctx.act,
                                  out=nhwc_view(dx[:rows]), dx16=d16, dy2=nhwc_view(extra[:rows]) if extra is not None else None)
-                if d16 is not None:
-                    dx._mg_h16_rows = (d16, dx.data_ptr(), dx._version, rows)
-                    H16_STATS["made"] += 1
+                _attach(dx, "_mg_h16_rows", d16, rows)
             else:
                 B, C, H, W = x.shape
                 d16 = torch.empty(x.numel(), dtype=torch.float16, device=x.device) if _want_h16(B, H * W, C, ctx.half) else None
-                dx = _attach_h16(nchw_view(ops.instnorm_bwd(nhwc_view(gy), nhwc_view(x), mean, rstd, ctx.act, dx16=d16,
-                                                            dy2=nhwc_view(extra) if extra is not None else None)), d16)
+                dx = _attach(nchw_view(ops.instnorm_bwd(nhwc_view(gy), nhwc_view(x), mean, rstd, ctx.act, dx16=d16,
+                                                        dy2=nhwc_view(extra) if extra is not None else None)), "_mg_h16", d16)
         dres = gy if ctx.needs_input_grad[1] else None
         return dx, dres, None, None, None
 
@@ -983,7 +982,6 @@ class _Cat2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, b):
-        from . import _lib
         a, b = to_cl(a), to_cl(b)
         B, Ca, H, W = a.shape
         Cb = b.shape[1]
@@ -996,7 +994,6 @@ class _Cat2Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
         B, Ca, Cb, H, W = ctx.dims
         g = nhwc_view(to_cl(g)).contiguous()
         ga = torch.empty(B, H, W, Ca, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[0] else None
@@ -1227,7 +1224,6 @@ def mse_const_pair_loss(pred, target_first: float, target_second: float):
 class _SigmoidFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        from . import _lib
         x = to_cl(x) if x.dim() == 4 else x.contiguous()
         y = torch.empty_like(x)
         _lib.check(_lib.load().mg_sigmoid_fwd(_lib.ptr(x), _lib.ptr(y), x.numel(), _lib.stream()), "mg_sigmoid_fwd")
@@ -1236,7 +1232,6 @@ class _SigmoidFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from . import _lib
         (y,) = ctx.saved_tensors
         gy = gy.contiguous(memory_format=CL) if gy.dim() == 4 else gy.contiguous()
         dx = torch.empty_like(y)

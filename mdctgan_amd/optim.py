@@ -132,7 +132,7 @@ class FusedAdam(torch.optim.Optimizer):
         instead of being cut at every 2048-element bias (36 -> 1 pieces on configs[2]'s trunk)."""
         p = self._params[i]
         return (self._modes[i] == _lib.GRAD_AUTOCAST and self._modes[i - 1] == _lib.GRAD_F16 and p.dim() == 1
-                and getattr(p, "_mg_zero_grad", False) and not Fh.COMPUTE_DEAD_BIAS_GRADS and getattr(p, "_mg_fresh", True))
+                and Fh._feeds_norm(p) and getattr(p, "_mg_fresh", True))
 
     @torch.no_grad()
     def adopt_g16(self, p):
@@ -229,7 +229,6 @@ class FusedAdam(torch.optim.Optimizer):
         """Weight-side fusion (gradient inverse transform + Adam + next forward transform in the weight-gradient call of the
         Winograd trunk layers) is valid for a single process in float32: no gradient reduction has to see the gradient, no
         GradScaler has to inspect it.  MG_NO_WINO_ADAM_FUSION=1 turns it off."""
-        import os
         return (self._built and not self.half_shadow and self.pre_step_hook is None and self.shard is None
                 and os.environ.get("MG_NO_WINO_ADAM_FUSION", "0") != "1")
 
@@ -238,7 +237,6 @@ class FusedAdam(torch.optim.Optimizer):
         the first GradScaler.step on; single process only -- a reduced gradient can be non-finite on a rank whose own
         contribution was finite, so under data parallelism every rank checks the reduced arena.  MG_NO_PRODUCER_INF_CHECK=1
         turns it off."""
-        import os
         if (self._scaler_flag is None or self.pre_step_hook is not None or self.shard is not None
                 or os.environ.get("MG_NO_PRODUCER_INF_CHECK", "0") == "1"):
             return None
@@ -282,8 +280,7 @@ class FusedAdam(torch.optim.Optimizer):
         self.finish_pending()
         if self.pre_step_hook is not None:
             self.pre_step_hook()
-        from .functional import bump_weight_epoch
-        bump_weight_epoch()                   # parameters change through raw pointers: invalidate cached weight images
+        Fh.bump_weight_epoch()                 # parameters change through raw pointers: invalidate cached weight images
         self._step += 1
         g = self.param_groups[0]
         (b1, b2), eps = g["betas"], g["eps"]

@@ -1,4 +1,4 @@
-"""Which convolution backward calls receive a producer-written float16 copy of their gradient operand (functional._h16_of)?
+"""Which convolution backward calls receive a producer-written float16 copy of their gradient operand (functional._sidecar under "_mg_h16")?
 (diagnostic for the --fp16 hand-over of MG_TILES_V_FILLED / MG_TILES_MD_FILLED; GPU)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -12,11 +12,11 @@ opt = options.make_opt(*options.SPECTRAL_FLAGS, "--lr_sampling_rate", "12000", "
                        "--segment_length", "16128", "--gpu_ids", "0", "--fp16")
 model = create_model(opt)
 orig = Fh._conv_backward
-def spy(ctx, gy, x, y):
+def spy(ctx, gy, x, y, add=None):
     g = ctx.g
-    print("conv_bwd", (g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.stride), "attr", hasattr(gy, "_mg_h16"), "valid", Fh._h16_of(Fh.to_cl(gy)) is not None,
-          "same_obj", Fh.to_cl(gy) is gy, "pc1", ops.precast_ok(1, g), "act", ctx.cfg[3], "transposed", ctx.cfg[4], ops.plan_name(1, g)[:40])
-    return orig(ctx, gy, x, y)
+    print("conv_bwd", (g.B, g.H, g.W, g.Ci, g.Co, g.KH, g.stride), "attr", hasattr(gy, "_mg_h16"), "valid", Fh._sidecar(Fh.to_cl(gy), "_mg_h16") is not None,
+          "same_obj", Fh.to_cl(gy) is gy, "pc1", ops.precast_ok(1, g), "act", ctx.cfg.act, "transposed", ctx.cfg.transposed, ops.plan_name(1, g)[:40])
+    return orig(ctx, gy, x, y, add)
 Fh._conv_backward = spy
 g = torch.Generator().manual_seed(1)
 hr = (0.1 * torch.randn(2, 16128, generator=g)).cuda(); lr = (0.1 * torch.randn(2, 16128, generator=g)).cuda()

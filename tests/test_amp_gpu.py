@@ -426,7 +426,7 @@ def test_filled_tiles_skip_the_cast_and_change_nothing():
 
 
 def test_producer_written_float16_copies_change_nothing(monkeypatch):
-    """The AMP step with the norm kernels writing the next convolution's float16 operand (functional._attach_h16 / _h16_of) ==
+    """The AMP step with the norm kernels writing the next convolution's float16 operand (functional._attach / _sidecar under _mg_h16) ==
     the step with MG_NO_H16_PRODUCER=1, bit for bit, and the hand-over really happens in both directions."""
     from mdctgan_amd import functional as Fh
     from mdctgan_amd import options
